@@ -4,6 +4,11 @@
     python bench.py [--gpus N --steps K --warmup W]            # N > 1: starts its own N ranks (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W                 # ... or is started as one of them
+    python bench.py --full                                     # + fenced-step median, in-step rooflines, CPU baseline
+    python bench.py --dump-outputs DIR                         # + what the last timed step computed, as DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure
+(`ms_per_step_median_fenced`, `roofline` / `roofline_more`, `cpu_baseline`) runs only under --full, after the timed steps.
 
 One "step" = one full training iteration of the reference loop body (cn3d_train_motion_GL.py:224-335) on a
 batch already resident in HBM: view-major reshape -> kNN/radius grouping -> encoder forward -> global + circle
@@ -43,7 +48,13 @@ def parse():
     ap.add_argument("--precision", choices=("f32", "x3", "x3b"), default="f32",
                     help="f32 (default, the headline): fp32-grade bf16x6 contractions; x3: opt-in three-product variant "
                          "(~1e-5 relative per GEMM); x3b: three products in the BACKWARD GEMMs only (features / loss unchanged)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the median of K fenced steps, "
+                         "the in-step kernel rooflines and the CPU baseline (off: set-up, warm-up, timed steps, result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (returned arrays; for the training configs also the model "
+                         "state after it) as DIR/<name>.npy in float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--fps", type=int, default=0, help="1: FPS-reorder the views on the GPU inside the timed step")
     ap.add_argument("--graph", type=int, default=1, help="1: replay the step as HIP graph(s): one graph on a single GPU, graph "
                                                          "segments cut at every collective under data parallelism")
@@ -52,6 +63,8 @@ def parse():
                          "N>1 step executes (as an identity) -- to time that path on a one-GPU box; never the headline")
     ap.add_argument("--cpu-clips", type=int, default=32, help="clips in the bounded CPU-baseline sample (default: the metric's own B = 32)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     dflt = {"motion": (32, 24, 2048), "appearance": (32, 24, 2048), "dense": (8, 32, 4096), "extract": (32, 24, 2048)}[a.config]
     a.B = dflt[0] if a.B is None else a.B
     a.T = dflt[1] if a.T is None else a.T
@@ -341,7 +354,7 @@ def make_extract_step(a, dev, rank):
     def eager(batch, epoch=0):
         with torch.no_grad():
             f = extract_batch(net, batch, opt)
-        return f.sum(), None, None                       # (the bench reads a scalar back at the end, as for the loss)
+        return f.sum(), f, None                          # (the bench reads a scalar back at the end, as for the loss; f: --dump-outputs)
     mode, step = "eager", eager
     if a.graph:
         try:
@@ -387,6 +400,31 @@ def cpu_baseline_dense(a):
     return {"value": round(Bc / t, 3), "unit": "clips/s", "cores": cores, "kind": "port",
             "sample": f"B={Bc} clips x T={a.T} views x N={a.N} pts, D={a.D}: 1 warm-up + 1 timed pass ({t:.2f} s) of "
                       f"oracle.dense forward + losses + backward (no optimiser step)"}
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all (every config's outputs are < 20 MB at its defaults)
+
+
+def dump_outputs(path, named, state=None):
+    """--dump-outputs: `named` {name: tensor} = what the caller of the timed step receives, `state` = the module state
+    the step leaves behind (training configs).  float64 stays float64, everything else is written as float32; integer
+    state (num_batches_tracked) as float64."""
+    import numpy as np
+    import torch
+    arrays = {name: t for name, t in named.items() if t is not None}
+    arrays.update(("state." + k, v) for k, v in (state or {}).items())
+    out, total = {}, 0
+    for name, t in arrays.items():
+        x = t.detach().cpu()
+        x = (x.double() if x.dtype == torch.float64 or not x.is_floating_point() else x.float()).numpy()
+        total += x.nbytes
+        out[name] = x
+    if total > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+    print("bench.py: %d arrays (%.1f MB) written to %s" % (len(out), total / 1e6, path), file=sys.stderr)
 
 
 def main():
@@ -495,49 +533,61 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        loss, _, _ = step(batches[i % 2], epoch=0)
+        res = step(batches[i % 2], epoch=0)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    loss = res[0]
     final_loss = float(loss.item())
-    # SURVEY 8(d) asks for the median of fenced steps: the same K steps again, each bracketed by a device synchronise
-    # (the value above stays the contract's one-sync-per-K mean; at ~4 ms/step the per-step fence costs ~1 %)
-    fenced = []
-    for i in range(a.steps):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step(batches[i % 2], epoch=0)
-        torch.cuda.synchronize()
-        fenced.append(time.perf_counter() - t1)
-    fenced.sort()
-    ms_median_fenced = 1e3 * fenced[len(fenced) // 2]
+    if a.dump_outputs and rank == 0:
+        # before anything under --full steps the model again: these are the last TIMED step's results
+        names = ("feature_sum", "features", None) if a.config == "extract" else ("loss", "loss_c", "loss_circle")
+        net = None if a.config == "extract" else eager_step.netR
+        dump_outputs(a.dump_outputs, {n: t for n, t in zip(names, res) if n is not None},
+                     None if net is None else net.state_dict())
 
-    # in-step kernel timing: extra eager steps on EVERY rank (they contain the collectives), reported by rank 0
-    rl_main, rl_more = step_rooflines(a, eager_step, batches)
+    ms_median_fenced = rl_main = rl_more = None
+    if a.full:
+        # SURVEY 8(d) asks for the median of fenced steps: the same K steps again, each bracketed by a device synchronise
+        # (the value above stays the contract's one-sync-per-K mean; at ~4 ms/step the per-step fence costs ~1 %)
+        fenced = []
+        for i in range(a.steps):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step(batches[i % 2], epoch=0)
+            torch.cuda.synchronize()
+            fenced.append(time.perf_counter() - t1)
+        fenced.sort()
+        ms_median_fenced = 1e3 * fenced[len(fenced) // 2]
+        # in-step kernel timing: extra eager steps on EVERY rank (they contain the collectives), reported by rank 0
+        rl_main, rl_more = step_rooflines(a, eager_step, batches)
     out = None
     if rank == 0:
         clips = a.B * world * a.steps / dt
         out = {"metric": _baseline_metric(), "value": round(clips, 2), "unit": "clips/s",
-               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
-               "ms_per_step_median_fenced": round(ms_median_fenced, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-               "dtype_note": dtype_note,
-               "config": {"workload": workload, "global_batch": a.B * world,
-                          "parallelism": f"dp{world}" + (" (REHEARSAL: data-parallel code path on a 1-rank RCCL group)" if a.rehearse_dp else ""),
-                          "launch": mode,
-                          "precision": getattr(a, "precision", "f32")},
-               "final_loss": final_loss}
-        out["roofline"], out["roofline_more"] = rl_main, rl_more
+               "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3)}
+        if a.full:
+            out["ms_per_step_median_fenced"] = round(ms_median_fenced, 3)
+        out.update({
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+            "dtype_note": dtype_note,
+            "config": {"workload": workload, "global_batch": a.B * world,
+                       "parallelism": f"dp{world}" + (" (REHEARSAL: data-parallel code path on a 1-rank RCCL group)" if a.rehearse_dp else ""),
+                       "launch": mode,
+                       "precision": getattr(a, "precision", "f32")},
+            "final_loss": final_loss})
+        if a.full:
+            out["roofline"], out["roofline_more"] = rl_main, rl_more
         if a.config == "dense":
             out["metric"] = ("dense-config contrastive-step clips/sec (BASELINE configs[4]: N=4096 T=32, 3-level set "
                              "abstraction, fp16 MFMA point-MLP)")
         if a.config == "extract":
             out["metric"] = "feature-extraction clips/sec (B=32,T=24,N=2048), eval-mode encoder (SURVEY 8 f-1: extract_motion_feature.py)"
             out.pop("final_loss", None)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_dense(a) if a.config == "dense" else cpu_baseline_extract(a) if a.config == "extract" \
                 else cpu_baseline(a)
     if world > 1:

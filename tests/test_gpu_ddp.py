@@ -189,7 +189,7 @@ def test_bench_gpus_flag_launches_ranks_or_fails_loudly():
     env.pop("WORLD_SIZE", None)
     env.pop("FACL_DIST_BACKEND", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--B", "2", "--T", "4",
-           "--N", "512", "--no-cpu-baseline"]
+           "--N", "512", "--full", "--no-cpu-baseline"]
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode != 0 and "device" in r.stderr

@@ -21,6 +21,20 @@ PRE_BN_BIAS = {"net3DV_1.0.bias", "net3DV_1.3.bias", "net3DV_1.6.bias", "net3DV_
                "net3DV_3.3.bias", "net3DV_3.6.bias", "netR_FC.0.bias"}
 
 
+@pytest.fixture(autouse=True)
+def _conv_without_onednn():
+    """The oracle's fp32 1x1 convolutions through ATen's GEMM path instead of oneDNN.  oneDNN picks its blocking -- and
+    so the summation order -- from the host CPU and the thread count, and train-mode BN over few rows plus max-pool
+    near-ties amplify that: on some hosts the fp32 gradients of c1_d3 then leave the golden's own noise band (0.4 % on
+    net3DV_3.4.bias), on others they stay inside it.  Without oneDNN the fp32 run no longer depends on the host."""
+    prev = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False
+    try:
+        yield
+    finally:
+        torch.backends.mkldnn.enabled = prev
+
+
 @pytest.mark.parametrize("N", [512, 2048])
 @pytest.mark.parametrize("dt", ["float64", "float32"])
 def test_fps_matches_reference(N, dt):

@@ -5,7 +5,7 @@ A=${1:-scratch/lib_prev.so}; N=${2:-3}; K=${3:-}
 for i in $(seq $N); do
   for L in "$A" ""; do
     if [ -n "$L" ]; then export FACL_LIB=$PWD/$L; tag=prev; else unset FACL_LIB; tag=new; fi
-    python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k='$K'

@@ -7,32 +7,32 @@ TAG=$1
 R=$PWD
 O=$R/gpurun_out
 mkdir -p "$O"
-timeout -k 10 300 python bench.py | tail -n 1 > "$O/${TAG}_bench_line.json"
+timeout -k 10 300 python bench.py --full | tail -n 1 > "$O/${TAG}_bench_line.json"
 echo headline done
-timeout -k 10 300 python bench.py --fps 1 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_fps.json"
-timeout -k 10 300 python bench.py --config appearance --D 4 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_appearance.json"
-timeout -k 10 400 python bench.py --config dense | tail -n 1 > "$O/${TAG}_bench_dense.json"
+timeout -k 10 300 python bench.py --full --fps 1 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_fps.json"
+timeout -k 10 300 python bench.py --full --config appearance --D 4 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_appearance.json"
+timeout -k 10 400 python bench.py --full --config dense | tail -n 1 > "$O/${TAG}_bench_dense.json"
 echo dense done
-timeout -k 10 300 python bench.py --precision x3b --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_optin_x3b.json"
-timeout -k 10 300 python bench.py --precision x3 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_optin_x3.json"
-FACL_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --B 16 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_2rank_gloo_rehearsal.json"
-timeout -k 10 300 python bench.py --no-cpu-baseline --rehearse-dp 1 | tail -n 1 > "$O/${TAG}_bench_rehearse_dp.json"
+timeout -k 10 300 python bench.py --full --precision x3b --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_optin_x3b.json"
+timeout -k 10 300 python bench.py --full --precision x3 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_optin_x3.json"
+FACL_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --B 16 --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_2rank_gloo_rehearsal.json"
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --rehearse-dp 1 | tail -n 1 > "$O/${TAG}_bench_rehearse_dp.json"
 # the opt-in full-graph rehearsal may abort inside torch's process-group watchdog: the evidence run goes on, the line
 # of the previous successful run stays
-if FACL_DP_GRAPH=full timeout -k 10 300 python bench.py --no-cpu-baseline --rehearse-dp 1 | tail -n 1 > "$O/${TAG}_fullgraph.tmp"; then
+if FACL_DP_GRAPH=full timeout -k 10 300 python bench.py --full --no-cpu-baseline --rehearse-dp 1 | tail -n 1 > "$O/${TAG}_fullgraph.tmp"; then
   mv "$O/${TAG}_fullgraph.tmp" "$O/${TAG}_bench_rehearse_dp_fullgraph.json"
 else
   echo "full-graph rehearsal FAILED (rc=$?)"; rm -f "$O/${TAG}_fullgraph.tmp"
 fi
-timeout -k 10 300 python bench.py --config extract | tail -n 1 > "$O/${TAG}_bench_extract.json"
-FACL_EVAL_FUSED=0 timeout -k 10 300 python bench.py --config extract --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_extract_unfused.json"
+timeout -k 10 300 python bench.py --full --config extract | tail -n 1 > "$O/${TAG}_bench_extract.json"
+FACL_EVAL_FUSED=0 timeout -k 10 300 python bench.py --full --config extract --no-cpu-baseline | tail -n 1 > "$O/${TAG}_bench_extract_unfused.json"
 timeout -k 10 300 python tools/time_views.py | tail -n 1 > "$O/${TAG}_views.json"
 echo bench lines done
 # `lines` as second argument: only refresh the bench lines (e.g. after profiles/pmc_*.json were regenerated from this build)
 if [ "$2" = "lines" ]; then exit 0; fi
 cd /tmp
 export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$TAG" -o r -- python3 "$R/bench.py" > "$O/prof_${TAG}_bench.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$TAG" -o r -- python3 "$R/bench.py" --full > "$O/prof_${TAG}_bench.log" 2>&1
 echo kernel stats done
 # PMC passes: counters only with --kernel-trace (separate runs; never with other trace domains)
 P="python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph 0"

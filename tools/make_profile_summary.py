@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def d_steps(d):
-    """executed steps of a default run: 3 graph warm-up + W + K timed + K fenced + 8 eager (the capture pass executes nothing)"""
+    """executed steps of a `--full` run: 3 graph warm-up + W + K timed + K fenced + 8 eager (the capture pass executes nothing)"""
     return d["warmup"] + 2 * d["steps"] + 8
 
 
@@ -105,15 +105,15 @@ def main():
     optin_rows = "".join(
         f'| `python bench.py --precision {n.split("_")[-1]}` (OPT-IN arithmetic, not the headline: DESIGN 3.0) | {L[n]["ms_per_step"]} | '
         f'{L[n]["value"]} | `{tag}_{n}.json` |\n' for n in optin)
-    open(os.path.join(pr, f"{tag}_bench_summary.md"), "w").write(f'''# Round {int(tag[1:])}: bench lines and rocprofv3 --kernel-trace --stats of the driver's command `python3 bench.py`
+    open(os.path.join(pr, f"{tag}_bench_summary.md"), "w").write(f'''# Round {int(tag[1:])}: bench lines and rocprofv3 --kernel-trace --stats of `python3 bench.py --full`
 
 MI355X, B=32 T=24 N=2048 D=3.  One profiled run = 1 graph-capture step + 3 graph warm-up steps + 5 warm-up + 20 timed steps
 + 20 fenced steps (HIP-graph replay) + 8 eager steps for the in-step kernel timing of the roofline section + the cpu_baseline leg (CPU only).
 Command (on the GPU box, from /tmp with TMPDIR=/tmp):
-`rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_{tag} -o r -- python3 bench.py`
+`rocprofv3 --kernel-trace --stats --output-format csv -d <output dir>/prof_{tag} -o r -- python3 bench.py --full`
 Raw per-kernel table: `profiles/{tag}_default_cmd_kernel_stats.csv` (the per-step figures below divide by {steps} executed steps).
 
-## bench.py lines of this build, un-profiled (`profiles/{tag}_bench_*.json`; re-run AFTER the PMC tables below were regenerated so that
+## bench.py lines of this build, un-profiled, every command with `--full` (`profiles/{tag}_bench_*.json`; re-run AFTER the PMC tables below were regenerated so that
 ## their `traffic` / `mfma_util_pmc` fields come from this build -- possibly on another box of the pool than the profiled run: box to box the headline varies by ~7 %)
 
 | command | ms/step | clips/s | file |

@@ -47,6 +47,8 @@ def run(default_branch, default_ckpt, args=None):
     netR = netR.to(device).eval()
     if opt.save_path:
         os.makedirs(opt.save_path, exist_ok=True)
+    if opt.synthetic == 0:
+        return run_disk(netR, opt, device)
     gen = torch.Generator(device=device)
     gen.manual_seed(7)
     feats = []
@@ -59,3 +61,32 @@ def run(default_branch, default_ckpt, args=None):
                 for b in range(f.shape[0]):
                     np.save(os.path.join(opt.save_path, 'synthetic_%04d_%03d.npy' % (i, b)), f[b])
     return np.concatenate(feats)
+
+
+def run_disk(netR, opt, device):
+    """--synthetic 0: extract_motion_feature.py:112-214 -- the train split, then the test split, of the clips listed in
+    <data_root>/raw, in order (shuffle=False, drop_last=False: the last batch is ragged); one <v_name>.npy per clip.
+    Returns the (clips, (num_crop+1)*512) features in that order."""
+    from . import dataset as fds
+    from .views import NUM_CROP
+    if (opt.num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM) != (NUM_CROP, 512, 4):
+        raise RuntimeError("--synthetic 0 builds the reference's 10 views of 512 points x 4 channels: "
+                           "use --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
+    if opt.view_rng == 'device':
+        raise RuntimeError("--synthetic 0 draws with --view_rng numpy or philox")
+    index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
+    rng = np.random.RandomState(2000)
+    feats = []
+    with torch.no_grad():
+        for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
+            vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
+            for views, names, _ in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
+                                                   rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch)):
+                B = len(names)
+                clip_major = views.view(opt.num_crop, B, 512, 4).permute(1, 0, 2, 3)
+                f = extract_batch(netR, clip_major, opt, opt.group_radius).cpu().numpy()
+                feats.append(f)
+                if opt.save_path:
+                    for b, n in enumerate(names):
+                        np.save(os.path.join(opt.save_path, n + '.npy'), f[b])
+    return np.concatenate(feats) if feats else np.zeros((0, (opt.num_crop + 1) * 512), np.float32)

@@ -54,12 +54,23 @@ def build_parser(default_branch):
     p.add_argument('--branch_choose', type=str, default=default_branch)
     # NEW
     p.add_argument('--synthetic', type=int, default=1,
-                   help='NEW: 1 = iid U[-0.5,0.5) clouds (no NTU data here); 2 = synthetic RAW clips (the four (rows, 8) clouds the '
+                   help='NEW: 0 = the 3DV clips on disk under --data_root (facl_amd/dataset.py); 1 = iid U[-0.5,0.5) clouds (no NTU data here); 2 = synthetic RAW clips (the four (rows, 8) clouds the '
                         'loader reads per video) through the GPU view construction (facl_amd.views.build_views = the dataset '
                         "class's get_data_train, cn3D_data_set.py:285-350): needs --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
-    p.add_argument('--view_rng', type=str, default='numpy', choices=('numpy', 'device'),
-                   help='NEW (--synthetic 2): numpy = draw the view construction\'s random numbers on the host in the reference\'s '
-                        'NumPy order; device = draw them on the GPU (same distributions, another stream)')
+    p.add_argument('--view_rng', type=str, default='numpy', choices=('numpy', 'device', 'philox'),
+                   help='NEW (--synthetic 0 / 2): numpy = draw the view construction\'s random numbers on the host in the reference\'s '
+                        'NumPy order; device = draw them on the GPU (same distributions, another stream; --synthetic 2 only); '
+                        'philox = counter-based draws on the GPU keyed by (seed, epoch, dataset index of the clip)')
+    p.add_argument('--data_root', type=str, default='../ntu/3DV_ntu60',
+                   help='NEW (--synthetic 0): the dataset root, the literal prefix ../ntu/3DV_ntu60 of the reference\'s paths')
+    p.add_argument('--split', type=str, default='view', choices=('view', 'subject', 'set'),
+                   help='NEW (--synthetic 0): cross-view (the reference\'s literal DATA_CROSS_VIEW=True), cross-subject or cross-set')
+    p.add_argument('--full_train', type=int, default=1,
+                   help='NEW (--split subject): 1 = all training performers (literal full_train=True), 0 = without the validation ones')
+    p.add_argument('--max_steps_per_epoch', type=int, default=0,
+                   help='NEW (--synthetic 0): cap on the steps of an epoch (len(split) // (batchSize * world)); 0 = no cap')
+    p.add_argument('--prefetch', type=int, default=1,
+                   help='NEW (--synthetic 0): 1 = load and draw batch i+1 on a producer thread while step i runs')
     p.add_argument('--num_crop', type=int, default=10, help='NEW: views per clip (literal 10 at :189)')
     p.add_argument('--steps_per_epoch', type=int, default=8, help='NEW: synthetic iterations per epoch')
     p.add_argument('--group_radius', type=float, default=None,
@@ -421,14 +432,41 @@ def run(default_branch, ckpt_pattern, args=None):
     gen.manual_seed(1000 + rank)
     view_rng = np.random.RandomState(2000 + rank)         # --synthetic 2: the generator the view construction draws from
 
+    steps_per_epoch = opt.steps_per_epoch
+    if opt.synthetic == 0:
+        # the reference's loader (cn3d_train_*_GL.py:161-172): NTU_RGBD_new over the listed folder, shuffle + drop_last
+        from . import dataset as fds
+        if (num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM) != (10, 512, 4):
+            raise RuntimeError("--synthetic 0 builds the reference's 10 views of 512 points x 4 channels: "
+                               "use --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
+        if opt.view_rng == 'device':
+            raise RuntimeError("--synthetic 0 draws with --view_rng numpy or philox")
+        index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.TRAIN_LIST_DIR[opt.branch_choose]), opt.dataset)
+        fds.check_same_index_on_all_ranks(index, device)
+        split = index.select(opt.split, full_train=bool(opt.full_train))
+        steps_per_epoch = len(split) // (opt.batchSize * world)
+        if opt.max_steps_per_epoch > 0:
+            steps_per_epoch = min(steps_per_epoch, opt.max_steps_per_epoch)
+        if steps_per_epoch < 1:
+            raise RuntimeError("the split has %d clips: fewer than one batch of %d per rank x %d ranks"
+                               % (len(split), opt.batchSize, world))
+
     run_step = step
     for epoch in range(0, opt.nepoch):
         netR.train()
         for g in optimizer.param_groups:
             g["lr"] = lr_for_epoch(opt.learning_rate, epoch)
         loss_sigma, t0 = 0.0, time.time()
-        for i in range(opt.steps_per_epoch):
-            if opt.synthetic == 2:
+        if opt.synthetic == 0:
+            pos = fds.train_batches(len(split), opt.batchSize, world, rank, opt.manualSeed, epoch)[:steps_per_epoch]
+            disk = fds.DiskBatches(index, opt.data_root, opt.branch_choose, [np.asarray(split)[p] for p in pos],
+                                   opt.view_rng, device, rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch))
+            disk.hold_first = run_step is step and bool(opt.graph) and not (opt.swa_if or opt.cld_if)   # capture on batch 0
+            disk = iter(disk)
+        for i in range(steps_per_epoch):
+            if opt.synthetic == 0:
+                out_points = next(disk)[0]                # (10*B, 512, 4) view-major views of the next batch
+            elif opt.synthetic == 2:
                 # the loop body from the loader's output on (:224-228): raw clips -> the 10 augmented views of every clip,
                 # built on the GPU in one launch, view-major float32 (facl_amd/views.py; draws in the reference's NumPy order)
                 if (num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM) != (10, 512, 4):
@@ -439,12 +477,13 @@ def run(default_branch, ckpt_pattern, args=None):
                 clips = [synthetic_raw_clip(base + b) for b in range(opt.batchSize)]
                 # --view_rng numpy: the reference's NumPy stream (a seed reproduces its views; ~0.2 ms of host draws per clip);
                 # device: the same distributions drawn by a torch generator on the GPU (no per-clip host work)
-                out_points = build_views(clips, view_rng, device, device_rng=gen if opt.view_rng == "device" else None)
+                out_points = build_views(clips, view_rng, device, device_rng=gen if opt.view_rng == "device" else None,
+                                         philox=(2000, epoch, [base + b for b in range(opt.batchSize)])
+                                         if opt.view_rng == "philox" else None)
             elif opt.synthetic == 1:
                 out_points = synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
             else:
-                raise RuntimeError("only --synthetic 1 / 2 are supported: the NTU dataset file pipeline "
-                                   "(cn3D_data_set.py: video lists, .npy loading) is outside this repository's scope")
+                raise RuntimeError("--synthetic must be 0 (the dataset on disk), 1 or 2")
             if run_step is step and opt.graph and not (opt.swa_if or opt.cld_if):
                 try:                                     # capture on the first batch; state restored: same trajectory as eager
                     run_step = GraphedStep(step, out_points, num_crop, restore=True)
@@ -463,7 +502,9 @@ def run(default_branch, ckpt_pattern, args=None):
                 # stop here instead of training on garbage
                 raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
             loss_sigma += lv
-        clips = opt.batchSize * opt.steps_per_epoch * world / (time.time() - t0)
+        if opt.synthetic == 0:
+            disk.close()                                  # stops the producer thread of this epoch
+        clips = opt.batchSize * steps_per_epoch * world / (time.time() - t0)
         logging.info('{} --epoch{} ==Average loss:{}'.format('Valid', epoch, loss_sigma / (i + 1)))
         if rank == 0:
             print('epoch:', epoch, 'loss mode is :', 1, '--loss:', loss_sigma / (i + 1), '| clips/s: %.1f' % clips)

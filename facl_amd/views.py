@@ -77,13 +77,18 @@ def _device_draws(clips, bases, gen, dev):
     return idx.to(torch.int32).contiguous(), noise, cs.contiguous()
 
 
-def build_views(clips, rng=None, device="cuda", device_rng=None):
+def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None):
     """clips: list of (points (P,>=8), key_points, res_points_1, res_points_2) NumPy arrays of one dtype (float32 or
     float64), the arrays `__getitem__` loads for a video.  Returns the (10*B, 512, 4) float32 CUDA tensor = the
     reference's `data1` (view-major rows g*B+b).  `rng`: np.random.RandomState (default: NumPy's global generator,
     like the reference): every draw happens on the host in the reference's order, a seed reproduces its views.
     `device_rng` (a torch.Generator on the device): draw on the device instead -- same distributions, another stream,
-    no per-clip host work."""
+    no per-clip host work.  `philox` = (seed, epoch, clip_ids): counter-based draws on the device (csrc/views_philox.hip):
+    a clip's views depend on (seed, epoch, its dataset index clip_ids[b]) only."""
+    if philox is not None:
+        src, meta, dt = pack_clips(clips, philox[2])
+        dev = torch.device(device)
+        return build_views_philox(torch.from_numpy(src).to(dev), torch.from_numpy(meta).to(dev), dt, philox[0], philox[1])
     rng = np.random if rng is None else rng
     lib = _lib.load_library()
     B = len(clips)
@@ -118,6 +123,68 @@ def build_views(clips, rng=None, device="cuda", device_rng=None):
     _lib.check(fn(_lib.ptr(src), src.shape[0], 8, _lib.ptr(idx), _lib.ptr(noise), _lib.ptr(cs), B, _lib.ptr(out),
                   _lib.stream()), "facl_build_views")
     return out
+
+
+def check_temporal_rows(clip, name):
+    """get_temporal_augment_data (:654-663) draws from the rows whose channel 4 / 7 is non-zero: a clip without any cannot
+    give its temporal views (the reference fails inside np.random.randint(0, 0))."""
+    for t in (4, 7):
+        if not (clip[0][:, t] != 0).any():
+            raise ValueError("clip %s: no row of its point cloud has a non-zero channel %d, so its temporal view cannot be "
+                             "drawn (cn3D_data_set.py:654-663)" % (name, t))
+
+
+def pack_clips(clips, clip_ids, out=None):
+    """The batch's source clouds packed row-wise, (rows, 8) in the clips' one dtype, and the (B, 9) int32 meta of
+    csrc/views_philox.hip (row offsets and counts of the four clouds, dataset index).  Checks what the kernels assume:
+    one float dtype, 2-D (rows >= 1, >= 8 channels) clouds, non-zero temporal rows.  `out`: a (>= rows, 8) array to pack
+    into (a pinned staging buffer); returns (src, meta, dtype) with src a view of it."""
+    dt = clips[0][0].dtype
+    if dt not in (np.float32, np.float64):
+        raise TypeError("source clouds must be float32 or float64")
+    B = len(clips)
+    meta = np.empty((B, 9), dtype=np.int32)
+    off = 0
+    for b, clip in enumerate(clips):
+        if any(a.dtype != dt or a.ndim != 2 or a.shape[1] < 8 or a.shape[0] < 1 for a in clip):
+            raise ValueError("every source cloud must be (rows >= 1, >= 8) of one dtype")
+        check_temporal_rows(clip, clip_ids[b])
+        for k, a in enumerate(clip):
+            meta[b, k], meta[b, 4 + k] = off, a.shape[0]
+            off += a.shape[0]
+        meta[b, 8] = int(clip_ids[b])
+    if off >= 1 << 30:
+        raise ValueError("batch too large: %d source rows" % off)
+    src = np.empty((off, 8), dtype=dt) if out is None else out[:off]
+    for b, clip in enumerate(clips):
+        for k, a in enumerate(clip):
+            src[meta[b, k]:meta[b, k] + a.shape[0]] = a[:, :8]
+    return src, meta, dt
+
+
+def build_views_philox(src, meta, dt, seed, epoch, return_idx=False):
+    """Device half of the philox mode: src (rows, 8) and meta (B, 9) int32 on the device (pack_clips' layout, temporal
+    rows already checked).  Two launches on the current stream: the temporal-row compaction, then the views.
+    Returns the (10*B, 512, 4) float32 views (and, with return_idx, the (B, 10, 512) source rows and the error word)."""
+    lib = _lib.load_library()
+    dev = src.device
+    B, rows = meta.shape[0], src.shape[0]
+    lists = _lib.empty((2, rows), dtype=torch.int32, device=dev)
+    counts = _lib.empty((B, 2), dtype=torch.int32, device=dev)
+    err = torch.zeros((1,), dtype=torch.int32, device=dev)
+    out = _lib.empty((NUM_CROP * B, NUM_POINT, 4), dtype=torch.float32, device=dev)
+    idx = _lib.empty((B, NUM_CROP, NUM_POINT), dtype=torch.int32, device=dev) if return_idx else None
+    _lib.require_cuda(out)
+    f64 = dt == np.float64
+    rt = lib.facl_views_temporal_rows_f64 if f64 else lib.facl_views_temporal_rows_f32
+    _lib.check(rt(_lib.ptr(src), rows, 8, _lib.ptr(meta), B, _lib.ptr(lists), _lib.ptr(counts), _lib.ptr(err),
+                  _lib.stream()), "facl_views_temporal_rows")
+    fn = lib.facl_build_views_philox_f64 if f64 else lib.facl_build_views_philox_f32
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    _lib.check(fn(_lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts),
+                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), B, _lib.ptr(out), _lib.ptr(idx), _lib.stream()),
+               "facl_build_views_philox")
+    return (out, idx, err) if return_idx else out
 
 
 def synthetic_raw_clip(seed, dtype=np.float32, P=900, Kp=300, R1=500, R2=200):

@@ -489,6 +489,26 @@ int facl_build_views_f32(const float* src, int64_t rows, int C, const int32_t* i
 int facl_build_views_f64(const double* src, int64_t rows, int C, const int32_t* idx, const double* noise,
                          const double* cossin, int B, float* out, void* stream);
 
+/* ---- the same views with counter-based draws (--view_rng philox; csrc/views_philox.hip, recipe in its header and in
+ * facl_amd/philox.py): Philox4x32-10 keyed by `seed`, counter (point, draw slot, clip id, epoch) -- a clip's views depend on
+ * (seed, epoch, clip id) only.  Two launches per batch, no host draws:
+ * meta (B,9) int32 per clip: row offsets in src of points, key points, res1, res2; their row counts (>= 1); clip id.
+ * facl_views_temporal_rows_*: list (2,rows) int32 = the rows of each clip's point cloud whose channel 4 (list[0]) /
+ * channel 7 (list[1]) is non-zero, at [base0 + k]; counts (B,2); *err = 1 when a count is zero (err is only raised).
+ * facl_build_views_philox_*: out (10*B,512,4) float32 view-major as facl_build_views_*; a temporal view of a clip with a
+ * zero count is written as zeros (void: the caller must not use the batch when *err != 0).  idx_out (B,10,512) int32 or
+ * NULL: the source row of every point.  rows < 2^30. */
+int facl_views_temporal_rows_f32(const float* src, int64_t rows, int C, const int32_t* meta, int B, int32_t* list,
+                                 int32_t* counts, int32_t* err, void* stream);
+int facl_views_temporal_rows_f64(const double* src, int64_t rows, int C, const int32_t* meta, int B, int32_t* list,
+                                 int32_t* counts, int32_t* err, void* stream);
+int facl_build_views_philox_f32(const float* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
+                                const int32_t* counts, int64_t seed, int epoch, int B, float* out, int32_t* idx_out,
+                                void* stream);
+int facl_build_views_philox_f64(const double* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
+                                const int32_t* counts, int64_t seed, int epoch, int B, float* out, int32_t* idx_out,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 Same update as ``torch.optim.Adam(params, lr, betas, eps)`` with weight_decay = 0, amsgrad = False, maximize = False
 (cn3d_train_motion_GL.py:180: lr 3e-4, betas (0.5, 0.999), eps 1e-6); the step counter and the learning rate live on
 the device, so a captured HIP graph advances its step counter by itself; learning-rate changes reach a replayed graph
-through ``sync_lr()``.  Parameters without a gradient are skipped, like torch's."""
+through ``sync_lr()``.  Parameters without a gradient are skipped, like torch's.  The betas reach the kernels as fp32, so
+``exp_avg_sq`` is torch's with beta2 = fp32(0.999), 1.3e-5 below torch's own; the parameter updates agree to rounding."""
 import ctypes
 
 import torch

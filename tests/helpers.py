@@ -159,3 +159,105 @@ class routing_taps:
         from facl_amd import _lib
         _lib.TAPS = self.prev
         return False
+
+
+# ---- one training step from ANY state (not only the fresh one), in torch fp64 --------------------------------------------
+SA_T_BN = ("net3DV_1.1", "net3DV_1.4", "net3DV_1.7", "net3DV_3.1", "net3DV_3.4", "net3DV_3.7")
+PRE_BN_BIAS = frozenset({"net3DV_1.0.bias", "net3DV_1.3.bias", "net3DV_1.6.bias", "net3DV_3.0.bias", "net3DV_3.3.bias",
+                         "net3DV_3.6.bias", "netR_FC.0.bias"})        # in front of a train-mode BatchNorm: no gradient
+
+
+def snapshot(net, optimizer):
+    """Host-side deep copy of everything a training step reads: parameters, BatchNorm running buffers and
+    num_batches_tracked (net.state_dict() writes the host-side counters into the buffers first), the optimizer's exp_avg /
+    exp_avg_sq / step / lr.  FusedAdam.state_dict() SHARES its moment tensors: they are copied here.
+    s["net"], s["optim"] load into a twin (net.load_state_dict / optimizer.load_state_dict); s["adam"] = {name: state},
+    s["step"], s["lr"]."""
+    import copy
+    import torch
+    net_sd = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}
+    osd = optimizer.state_dict()
+    state = {i: {k: (v.detach().cpu().clone() if torch.is_tensor(v) else v) for k, v in st.items()}
+             for i, st in osd["state"].items()}
+    optim_sd = {"state": state, "param_groups": copy.deepcopy(osd["param_groups"])}
+    names = {id(p): n for n, p in net.named_parameters()}
+    pnames = [names[id(p)] for p in optimizer.param_groups[0]["params"]]
+    steps = {int(st["step"]) for st in state.values() if "step" in st}
+    assert len(steps) <= 1, steps
+    return {"net": net_sd, "optim": optim_sd, "adam": {pnames[i]: st for i, st in state.items()},
+            "step": steps.pop() if steps else 0, "lr": float(optim_sd["param_groups"][0]["lr"])}
+
+
+# facl_amd.optim.FusedAdam passes its betas to the kernels as fp32: its moment updates and bias corrections are torch's with
+# beta2 = fp32(0.999) = 0.99900001287 (1 - beta2 = 0.99998712e-3), so its exp_avg_sq sits 1.3e-5 below torch.optim.Adam's with
+# beta2 = 0.999; the parameter updates agree with torch's to rounding (v and its bias correction carry the same factor).
+FUSED_ADAM_BETAS = (0.5, float(np.float32(0.999)))
+
+
+def adam64(snap, grads, betas=(0.5, 0.999), eps=1e-6):
+    """torch.optim.Adam (cn3d_train_motion_GL.py:180) in fp64, started from the snapshot's parameters, moments, step count
+    and lr, applied to `grads` {name: tensor} (parameters without an entry are skipped, like a None .grad).
+    Returns {name: (param, exp_avg, exp_avg_sq)} after the update, fp64 on the gradients' device."""
+    import torch
+    f64 = torch.float64
+    ps, out = [], {}
+    for n, g in grads.items():
+        dev = g.device
+        p = snap["net"][n].to(dev, f64).clone().requires_grad_(True)
+        p.grad = g.detach().to(f64).reshape(p.shape).clone()
+        ps.append((n, p))
+    opt = torch.optim.Adam([p for _, p in ps], lr=snap["lr"], betas=betas, eps=eps, foreach=False)
+    for n, p in ps:
+        st = snap["adam"].get(n)
+        if st is not None and snap["step"] > 0:
+            opt.state[p] = {"step": torch.tensor(float(snap["step"])), "exp_avg": st["exp_avg"].to(p.device, f64).clone(),
+                            "exp_avg_sq": st["exp_avg_sq"].to(p.device, f64).clone()}
+    opt.step()
+    for n, p in ps:
+        out[n] = (p.detach(), opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])
+    return out
+
+
+def reference_step64(snap, x_rows, centers, G, B, S, K, order, routing, backward=True, momentum=0.1, betas=(0.5, 0.999)):
+    """The reference's training step (cn3d_train_motion_GL.py:224-335, without the SwAV / CLD terms) from the state in
+    `snap` (snapshot()), evaluated in torch fp64 on the grouped rows (x_rows (P,D), centers (M*S,3)):
+      x, xg, loss_c, loss_circle   -- forward with the fp64 max-pools / ReLUs, losses through oracle.loss;
+      running                      -- {key: (running_mean, running_var)} after the step (momentum 0.1, netR_FC.1 twice);
+    and with `backward` (routing = the kernel's max-pool and ReLU decisions, routing_taps()):
+      g64, ties                    -- every parameter gradient, routed through those decisions; ties as in forward64;
+      adam64                       -- adam64(snap, g64, betas): parameters and moments after Adam on the fp64 gradients;
+      g32, x32, xg32, loss_c32, loss_circle32 -- the same routed computation in plain torch fp32 (conditioning yardstick)."""
+    import torch
+    from oracle import loss as OL
+    dev = x_rows.device
+    sd = snap["net"]
+    out = {}
+    with torch.no_grad():
+        x, xg, stats, q, _ = forward64(x_rows, centers, sd, G, S, K, dev)
+        out.update(x=x, xg=xg, loss_c=float(OL.global_contrast(G, xg, x, B)), loss_circle=float(OL.circle_contrast(G, x, B, order)))
+        run = {}
+        for key in SA_T_BN:
+            mean, uvar = stats[key]
+            run[key] = ((1 - momentum) * q[f"{key}.running_mean"] + momentum * mean,
+                        (1 - momentum) * q[f"{key}.running_var"] + momentum * uvar)
+        rm, rv = q["netR_FC.1.running_mean"], q["netR_FC.1.running_var"]
+        for key in ("fc_a", "fc_b"):                                           # view rows first, then the clip rows
+            rm = (1 - momentum) * rm + momentum * stats[key][0]
+            rv = (1 - momentum) * rv + momentum * stats[key][1]
+        run["netR_FC.1"] = (rm, rv)
+        out["running"] = run
+    del stats, q
+    if not backward:
+        return out
+
+    def routed(dtype):
+        x_, xg_, _, q_, ties_ = forward64(x_rows, centers, sd, G, S, K, dev, routing=routing, grad=True, dtype=dtype)
+        lc, lo = OL.global_contrast(G, xg_, x_, B), OL.circle_contrast(G, x_, B, order)
+        (lc + lo).backward()
+        g = {k: q_[k].grad.detach() for k in q_ if q_[k].grad is not None}
+        return g, ties_, x_.detach(), xg_.detach(), float(lc.detach()), float(lo.detach())
+    out["g64"], out["ties"], _, _, _, _ = routed(torch.float64)
+    g32, _, out["x32"], out["xg32"], out["loss_c32"], out["loss_circle32"] = routed(torch.float32)
+    out["g32"] = {k: v.double() for k, v in g32.items()}
+    out["adam64"] = adam64(snap, out["g64"], betas)
+    return out

@@ -20,6 +20,16 @@ PRE_BN_BIAS = {"net3DV_1.0.bias", "net3DV_1.3.bias", "net3DV_1.6.bias", "net3DV_
                "net3DV_3.3.bias", "net3DV_3.6.bias", "netR_FC.0.bias"}
 
 
+@pytest.fixture(autouse=True)
+def _poisoned_scratch():
+    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned): the partial-sum workspace and
+    every output / scratch tensor the host layer allocates are filled with NaN bytes before the launches, so a partial
+    row or output element left unwritten at a ragged shape fails the comparison instead of reading recycled memory."""
+    from facl_amd import _lib
+    with _lib.poisoned():
+        yield
+
+
 def _opt(D, B, N=512):
     return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
                            sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B,

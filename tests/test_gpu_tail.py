@@ -3,10 +3,20 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden
+from helpers import FUSED_ADAM_BETAS, load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+
+@pytest.fixture(autouse=True)
+def _poisoned_scratch():
+    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned): the partial-sum workspace and
+    every output / scratch tensor the host layer allocates are filled with NaN bytes before the launches, so a partial
+    row or output element left unwritten at a ragged shape fails the comparison instead of reading recycled memory."""
+    from facl_amd import _lib
+    with _lib.poisoned():
+        yield
 
 
 @pytest.mark.parametrize("G,B,C", [(10, 4, 1024), (24, 32, 1024), (3, 5, 8), (1, 7, 16)])
@@ -148,20 +158,29 @@ def test_fused_adam_equals_torch_adam():
     shapes = [(1024, 1024), (64, 3, 1, 1), (5,), (2049,), (512, 1024), (7, 11)]
     pa = [torch.randn(s, device=DEV).requires_grad_(True) for s in shapes]
     pb = [p.detach().clone().requires_grad_(True) for p in pa]
+    pc = [p.detach().clone().requires_grad_(True) for p in pa]
     oa = FusedAdam(pa, lr=3e-4, betas=(0.5, 0.999), eps=1e-6)
     ob = torch.optim.Adam(pb, lr=3e-4, betas=(0.5, 0.999), eps=1e-6)
+    # FusedAdam holds its betas in fp32 (FUSED_ADAM_BETAS): its moments are torch's with beta2 = fp32(0.999)
+    oc = torch.optim.Adam(pc, lr=3e-4, betas=FUSED_ADAM_BETAS, eps=1e-6)
     for it in range(6):
         if it == 3:
-            oa.param_groups[0]["lr"] = ob.param_groups[0]["lr"] = 3e-4 * 0.7
-        for i, (a, b) in enumerate(zip(pa, pb)):
+            oa.param_groups[0]["lr"] = ob.param_groups[0]["lr"] = oc.param_groups[0]["lr"] = 3e-4 * 0.7
+        for i, (a, b, c) in enumerate(zip(pa, pb, pc)):
             if i == 2:
-                a.grad = b.grad = None                       # like mapping.weight: no gradient, no update
+                a.grad = b.grad = c.grad = None              # like mapping.weight: no gradient, no update
                 continue
             g = torch.randn_like(a) * (10.0 ** (i - 3))
-            a.grad, b.grad = g.clone(), g.clone()
-        oa.step(); ob.step()
+            a.grad, b.grad, c.grad = g.clone(), g.clone(), g.clone()
+        oa.step(); ob.step(); oc.step()
     for a, b in zip(pa, pb):
         assert float((a.detach() - b.detach()).abs().max()) <= 2e-6 * float(b.detach().abs().max())
+    for i, (a, c) in enumerate(zip(pa, pc)):
+        if i == 2:
+            continue
+        for k in ("exp_avg", "exp_avg_sq"):
+            want = oc.state[c][k]
+            assert float((oa.state[a][k] - want).abs().max()) <= 2e-6 * float(want.abs().max()), (i, k)
     sd = oa.state_dict()
     assert int(sd["state"][0]["step"]) == 6 and set(sd["state"][0]) == {"step", "exp_avg", "exp_avg_sq"}
 

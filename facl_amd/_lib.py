@@ -159,6 +159,20 @@ def check(rc, what):
 
 AMAX_WORDS = 2048          # include/facl_hip.h: FACL_AMAX_WORDS
 
+# include/facl_hip.h: the input widths of grouping and the SA point-MLP, and the D-dependent layer-1 layouts
+SA_D_MIN, SA_D_MAX = 3, 8  # FACL_SA_D_MIN, FACL_SA_D_MAX
+
+
+def sa_l1_cols(D):
+    """FACL_SA_L1_COLS(D): floats per row of the folded layer-1 table (weights, zero padding, the bias in column cols - 4, zeros)
+    and rows of R1 in facl_sa_bwd2's output (x_0..x_{D-1}, then sum dz1, then zeros)."""
+    return 8 if D <= 4 else 12
+
+
+def sa_bwd2_out(D):
+    """FACL_SA_BWD2_OUT(D): doubles of facl_sa_bwd2's output, [dW2 (64,64) | R1 (sa_l1_cols(D), 64)]."""
+    return 64 * 64 + 64 * sa_l1_cols(D)
+
 
 def amax_buffers(n, device, zero=True):
     """(n, AMAX_WORDS) int32: n operand-maximum buffers of the fp16x3 GEMMs (csrc/common.h).  Producers either STORE a bound

@@ -93,6 +93,19 @@ __device__ __forceinline__ constexpr int rowmap(int r, int h) { return (r & 3) +
 #define FACL_UNIT 64
 #define FACL_UNIT_ELEMS 4096
 
+// Layer 1 of the SA point-MLP for D > 4 (include/facl_hip.h, FACL_SA_L1_COLS): a folded-table row of three float4s
+// [w0..w3 | w4..w7 | b 0 0 0] and the lane's x (8 floats, zero past D).  The pre-activation is ONE sequential fp32 FMA chain, bias
+// plus channel 0 first, then channels 1..D-1: the order of the D <= 4 kernels, which the host's routing taps restate (sa_mlp.py).
+template <int D>
+__device__ __forceinline__ float l1_chain(const float4* row, const float (&xv)[8]) {
+    const float4 w0 = row[0], w1 = row[1];
+    const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    float v = fmaf(w[0], xv[0], row[2].x);
+#pragma unroll
+    for (int i = 1; i < D; ++i) v = fmaf(w[i], xv[i], v);
+    return v;
+}
+
 // partial-sum workspace: every wave (or block) of a reducing kernel writes one row of doubles
 #define FACL_WS_ROWS 4096
 // the last bytes of the workspace: ticket counters of the single-launch partial-row reduction (finalize.hip), zero between launches

@@ -231,12 +231,13 @@ __global__ __launch_bounds__(64) void k_sa_bn1_chain(const double* __restrict__ 
         for (int o = 32; o > 0; o >>= 1) bound = fmaxf(bound, __shfl_xor(bound, o, 64));
         if (threadIdx.x < FACL_AMAX_SLOTS) aamax[threadIdx.x * FACL_AMAX_STRIDE] = __float_as_uint(bound);
     }
-    for (int i = 0; i < 4; ++i) tab[c * 8 + i] = i < D ? scale * W1[c * D + i] : 0.0f;
-    tab[c * 8 + 4] = scale * b1[c] + shift;
-    tab[c * 8 + 5] = tab[c * 8 + 6] = tab[c * 8 + 7] = 0.0f;
+    const int L = FACL_SA_L1_COLS(D);                                  // row width (include/facl_hip.h): 8, or 12 for D > 4
+    for (int i = 0; i < L - 4; ++i) tab[c * L + i] = i < D ? scale * W1[c * D + i] : 0.0f;
+    tab[c * L + L - 4] = scale * b1[c] + shift;
+    tab[c * L + L - 3] = tab[c * L + L - 2] = tab[c * L + L - 1] = 0.0f;
 }
 
-// Fold BN1 into the first 1x1 conv: a1 = relu((scale*W1) x + (scale*b1 + shift)); rows of 8 floats.
+// Fold BN1 into the first 1x1 conv: a1 = relu((scale*W1) x + (scale*b1 + shift)); rows of FACL_SA_L1_COLS(D) floats.
 // `xamax` -> `a1amax` (both or neither): with X = max|x| over all coordinates (facl_absmax), |a1_c| <= X sum_i |w'_ci| + |b'_c|:
 // the bound of the layer-1 activation for eval-mode constants (train mode takes BatchNorm's own bound, facl_bn_finalize).
 __global__ void k_l1tab(const float* __restrict__ W1, const float* __restrict__ b1, int D,
@@ -244,18 +245,20 @@ __global__ void k_l1tab(const float* __restrict__ W1, const float* __restrict__ 
                         const unsigned* __restrict__ xamax, unsigned* __restrict__ a1amax) {
     const int c = threadIdx.x;                                          // 64 threads = one wave
     const float s = scale ? scale[c] : 1.0f, t = shift ? shift[c] : 0.0f;
+    const int L = FACL_SA_L1_COLS(D);
     float l1 = 0.f;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < L - 4; ++i) {
         const float w = i < D ? s * W1[c * D + i] : 0.0f;
-        tab[c * 8 + i] = w;
+        tab[c * L + i] = w;
         l1 += fabsf(w);
     }
     const float b = s * b1[c] + t;
-    tab[c * 8 + 4] = b;
-    tab[c * 8 + 5] = tab[c * 8 + 6] = tab[c * 8 + 7] = 0.0f;
+    tab[c * L + L - 4] = b;
+    tab[c * L + L - 3] = tab[c * L + L - 2] = tab[c * L + L - 1] = 0.0f;
     if (a1amax) {
         const float X = __uint_as_float(amax_bits(xamax));
-        float bd = fmaf(l1, X, fabsf(b)) * 1.001f;
+        float bd = fmaf(l1, X, fabsf(b)) * 1.001f;                       // 1.001: covers the fp32 roundings of the sum and of the
+                                                                         // (at most 8-term) layer-1 chain many times over
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) bd = fmaxf(bd, __shfl_xor(bd, o, 64));
         a1amax[c * FACL_AMAX_STRIDE] = __float_as_uint(bd);
@@ -405,7 +408,7 @@ extern "C" int facl_bn_eval_consts(int C, const float* gamma, const float* beta,
 extern "C" int facl_bn1_sums_from_moments(const double* mom, double count, int D, const float* W1, const float* b1,
                                           double* sums, void* stream) {
     if (!mom || !W1 || !b1 || !sums) return FACL_E_NULL;
-    if (D != 3 && D != 4) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX) return FACL_E_SHAPE;
     hipLaunchKernelGGL(k_bn1_sums_from_moments, dim3(1), dim3(64), 0, (hipStream_t)stream, mom, count, D, W1, b1, 64,
                        sums);
     return facl_launch_status();
@@ -415,7 +418,7 @@ extern "C" int facl_sa_bn1_chain(const double* mom, double count, int D, const f
                                  const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                                  double* sums, float* bnc, uint32_t* aamax, float* l1tab, void* stream) {
     if (!mom || !W1 || !b1 || !gamma || !beta || !sums || !bnc || !l1tab) return FACL_E_NULL;
-    if ((D != 3 && D != 4) || count < 1) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || count < 1) return FACL_E_SHAPE;
     hipLaunchKernelGGL(k_sa_bn1_chain, dim3(1), dim3(64), 0, (hipStream_t)stream, mom, count, D, W1, b1, gamma, beta, eps, momentum,
                        running_mean, running_var, sums, bnc, aamax, l1tab);
     return facl_launch_status();
@@ -424,7 +427,7 @@ extern "C" int facl_sa_bn1_chain(const double* mom, double count, int D, const f
 extern "C" int facl_sa_l1tab(const float* W1, const float* b1, int D, const float* scale, const float* shift,
                              float* l1tab, const uint32_t* xamax, uint32_t* a1amax, void* stream) {
     if (!W1 || !b1 || !l1tab || ((xamax == nullptr) != (a1amax == nullptr))) return FACL_E_NULL;
-    if (D != 3 && D != 4) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX) return FACL_E_SHAPE;
     hipLaunchKernelGGL(k_l1tab, dim3(1), dim3(64), 0, (hipStream_t)stream, W1, b1, D, scale, shift, l1tab, xamax, a1amax);
     return facl_launch_status();
 }
@@ -512,7 +515,7 @@ __global__ __launch_bounds__(256) void k_sa_bwd_final(
     r -= 64;
     if (r < 64) {                                               // layer 1, channel c = r
         const int c = r;
-        const double* R1_l = out2 + 4096;                       // (8,64): rows x_d (d<D), then sum dz1
+        const double* R1_l = out2 + 4096;                       // (FACL_SA_L1_COLS(D),64): rows x_d (d<D), then sum dz1
         const double mean = bnc1[c], inv = bnc1[64 + c], sc = bnc1[128 + c];
         const double bmm = (double)b1[c] - mean;
         double wr_l = 0, wr_g = 0;
@@ -583,7 +586,7 @@ extern "C" int facl_sa_bwd_final(const double* out3, const double* sums0_g, cons
     if (!out3 || !sums0_g || !sums0_l || !bnc3 || !W3 || !b3 || !out2 || !sums1_l || !R1_g || !mom_l || !bnc1 || !W1 ||
         !b1 || !dW3 || !dg3 || !dbe3 || !dW2 || !dg2 || !dbe2 || !dW1 || !dg1 || !dbe1)
         return FACL_E_NULL;
-    if ((D != 3 && D != 4) || P < 1) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || P < 1) return FACL_E_SHAPE;
     const int total = 16384 + 256 + 4096 + 64 + 64;
     hipLaunchKernelGGL(k_sa_bwd_final, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out3, sums0_g,
                        sums0_l, bnc3, W3, b3, out2, sums1_l, R1_g, mom_l, bnc1, W1, b1, D, P, dW3, dg3, dbe3, dW2, dg2,

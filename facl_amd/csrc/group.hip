@@ -5,6 +5,9 @@
 // the K-th smallest by an MSB-first radix select on the float bit patterns.
 //
 // Roofline: HBM.  Algorithmic bytes per cloud = N*D*4 (read) + S*K*(4 + 4*D) + S*12 (write).
+// D <= 4 stages the whole cloud in LDS (SoA).  D > 4 (up to FACL_SA_D_MAX) stages only what the selection reads (xyz): channels
+// 3..D-1 are gathered from the cloud in global memory when a group row is written (once per emitted row; the cloud is L2-resident),
+// and the row of 5..8 floats is written with scalar stores (no alignment rule).
 #include "common.h"
 #include <stdlib.h>
 
@@ -39,6 +42,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
     float* ys = xs + N;
     float* zs = ys + N;
     float* cs = zs + N;                       // only when D == 4
+    constexpr int DS = D <= 4 ? D : 3;        // channels staged in LDS
     const int m = blockIdx.y;
     // clipB > 0: the input is the loader's (B, G, N, D) clip-major batch and cloud m = g*B + b is read in place (the
     // permute(1,0,2,3).reshape copy of cn3d_train_motion_GL.py:226 is folded into this address)
@@ -51,9 +55,9 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
             const float4 p = *reinterpret_cast<const float4*>(cloud + (size_t)i * 4);
             xs[i] = p.x; ys[i] = p.y; zs[i] = p.z; cs[i] = p.w;
         } else {
-            xs[i] = cloud[(size_t)i * 3 + 0];
-            ys[i] = cloud[(size_t)i * 3 + 1];
-            zs[i] = cloud[(size_t)i * 3 + 2];
+            xs[i] = cloud[(size_t)i * D + 0];
+            ys[i] = cloud[(size_t)i * D + 1];
+            zs[i] = cloud[(size_t)i * D + 2];
         }
     }
     __syncthreads();
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
         // (more than CAP entries can only be left when the rounds ran out of bits on a mass of exact ties: the full-width tie
         // ranking below handles that)
         if (K <= 256 && below + cand <= CAP) {
-            char* sl = reinterpret_cast<char*>(lds + (size_t)D * N) + SLOT_BYTES * wave;
+            char* sl = reinterpret_cast<char*>(lds + (size_t)DS * N) + SLOT_BYTES * wave;
             uint2* slotp = reinterpret_cast<uint2*>(sl);        // (key, index): one 8-byte store / load per entry
             int E = 0;
             {
@@ -220,7 +224,11 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
                     const float gx = outside ? 0.f : __fsub_rn(px, cx), gy = outside ? 0.f : __fsub_rn(py, cy);
                     const float gz = outside ? 0.f : __fsub_rn(pz, cz);
                     if (D == 4) *reinterpret_cast<float4*>(xt_out + o * 4) = make_float4(gx, gy, gz, cs[id]);
-                    else { xt_out[o * 3 + 0] = gx; xt_out[o * 3 + 1] = gy; xt_out[o * 3 + 2] = gz; }
+                    else {
+                        xt_out[o * D + 0] = gx; xt_out[o * D + 1] = gy; xt_out[o * D + 2] = gz;
+#pragma unroll
+                        for (int ch = 3; ch < D; ++ch) xt_out[o * D + ch] = cloud[(size_t)id * D + ch];   // D > 4: from global
+                    }
                 }
             }
             asm volatile("" ::: "memory");                      // the slot is rewritten by the next centroid
@@ -240,7 +248,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
             // them into CKEYS keys per lane through a small LDS slot and finish the remaining rounds -- typically half
             // of them -- on those registers instead of walking all NPL.  Only prefix / hi / remaining come out of it;
             // the emission below still uses the original registers, so no index bookkeeping is needed.
-            uint32_t* slot = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds + (size_t)D * N) + SLOT_BYTES * wave);
+            uint32_t* slot = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds + (size_t)DS * N) + SLOT_BYTES * wave);
             int base = 0;
 #pragma unroll
             for (int j = 0; j < NPL; ++j) {
@@ -274,7 +282,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
         // prefix-popcount positions; ~K/NPL lanes are active per pass), then ALL K neighbours are gathered, radius-tested
         // (the distance is recomputed from the coordinates the gather reads anyway: same exact arithmetic), centred and
         // stored by K lanes at once -- K/64 full-width store passes per output instead of NPL passes of a few lanes each.
-        uint32_t* eslot = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds + (size_t)D * N) + SLOT_BYTES * wave);      // >= 256 words per wave
+        uint32_t* eslot = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds + (size_t)DS * N) + SLOT_BYTES * wave);      // >= 256 words per wave
         // the direct form of one kept neighbour (index i, output slot pos): radius rule, gather, centre, store
         auto emit = [&](int i, int pos) {
             const float px = xs[i], py = ys[i], pz = zs[i];
@@ -287,7 +295,11 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
                 const float gx = outside ? 0.f : __fsub_rn(px, cx), gy = outside ? 0.f : __fsub_rn(py, cy);
                 const float gz = outside ? 0.f : __fsub_rn(pz, cz);
                 if (D == 4) *reinterpret_cast<float4*>(xt_out + o * 4) = make_float4(gx, gy, gz, cs[id]);
-                else { xt_out[o * 3 + 0] = gx; xt_out[o * 3 + 1] = gy; xt_out[o * 3 + 2] = gz; }
+                else {
+                    xt_out[o * D + 0] = gx; xt_out[o * D + 1] = gy; xt_out[o * D + 2] = gz;
+#pragma unroll
+                    for (int ch = 3; ch < D; ++ch) xt_out[o * D + ch] = cloud[(size_t)id * D + ch];       // D > 4: from global
+                }
             }
         };
         int base = 0;
@@ -337,10 +349,16 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
 template <int D, int NPL>
 int launch_group(const float* points, int M, int N, int S, int K, float r2, int32_t* idx, float* xt, float* yt,
                  int clipB, hipStream_t st) {
-    const size_t lds = (size_t)N * D * sizeof(float) + 4 * SLOT_BYTES;   // cloud (SoA, D arrays) + one compacted-list / emission slot per wave
+    constexpr int DS = D <= 4 ? D : 3;                                   // D > 4: only xyz is staged
+    const size_t lds = (size_t)N * DS * sizeof(float) + 4 * SLOT_BYTES;  // cloud (SoA, DS arrays) + one compacted-list / emission slot per wave
     // centroids per workgroup (A/B knob FACL_GROUP_CPW: 16 = four workgroups stage each cloud, 32 = two, 64 = one)
     static const int cpw = getenv("FACL_GROUP_CPW") ? atoi(getenv("FACL_GROUP_CPW")) : CENTROIDS_PER_WG;
-    if (cpw == 32) {
+    if constexpr (D > 4) {                  // the A/B knob is not instantiated for the wide inputs: default geometry only
+        if (N == 64 * NPL)
+            hipLaunchKernelGGL((k_group<D, NPL, CENTROIDS_PER_WG, true>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
+        else
+            hipLaunchKernelGGL((k_group<D, NPL>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
+    } else if (cpw == 32) {
         hipLaunchKernelGGL((k_group<D, NPL, 32>), dim3((S + 31) / 32, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
     } else if (cpw == 8) {
         hipLaunchKernelGGL((k_group<D, NPL, 8>), dim3((S + 7) / 8, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
@@ -370,13 +388,19 @@ int dispatch_group(const float* points, int M, int N, int S, int K, float r2, in
 static int group_entry(const float* points, int M, int N, int D, int S, int K, float r2, int32_t* idx, float* xt,
                        float* yt, int clipB, void* stream) {
     if (!points) return FACL_E_NULL;
-    if (M < 0 || N < 1 || N > 4096 || S < 1 || S > N || K < 1 || K > N || (D != 3 && D != 4)) return FACL_E_SHAPE;
+    if (M < 0 || N < 1 || N > 4096 || S < 1 || S > N || K < 1 || K > N || D < FACL_SA_D_MIN || D > FACL_SA_D_MAX) return FACL_E_SHAPE;
     if (M > 65535 || clipB < 0 || (clipB > 0 && M % clipB)) return FACL_E_SHAPE;
     if (D == 4 && ((((uintptr_t)points) & 15) || (xt && (((uintptr_t)xt) & 15)))) return FACL_E_ALIGN;
     if (M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    return D == 4 ? dispatch_group<4>(points, M, N, S, K, r2, idx, xt, yt, clipB, st)
-                  : dispatch_group<3>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    switch (D) {
+    case 4: return dispatch_group<4>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    case 3: return dispatch_group<3>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    case 5: return dispatch_group<5>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    case 6: return dispatch_group<6>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    case 7: return dispatch_group<7>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    default: return dispatch_group<8>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    }
 }
 
 extern "C" int facl_group(const float* points, int M, int N, int D, int S, int K, float r2, int32_t* idx,

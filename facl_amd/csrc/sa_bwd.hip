@@ -654,7 +654,9 @@ void k_sa_bwd_w3p(const float* __restrict__ y2f, int nunits, const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// bwd2.  Output row per wave: [ dW2 (64 x 64, [c2][c1]) | R1 (8 x 64, rows: x_0..x_{D-1}, 1, 0..) ] = 4608 doubles
+// bwd2 on the exact-fp32 MFMA (FACL_BWD2_F32=1; the default is k_sa_bwd2_sb, sa_bwd2.hip), D <= 4 only: its per-wave LDS tiles
+// take 160,768 B of the 163,840 a CU has, and the wider layer-1 table and x tile of D > 4 do not fit beside them.
+// Output row per wave: [ dW2 (64 x 64, [c2][c1]) | R1 (8 x 64, rows: x_0..x_{D-1}, 1, 0..) ] = 4608 doubles = FACL_SA_BWD2_OUT(D)
 constexpr int B2_V = 64 * 64 + 8 * 64;
 
 template <int D>
@@ -894,19 +896,21 @@ int facl_sa_bwd2_sb_launch(const float* dz2f, const float* y2f, const float* x, 
                            const float* W2, const float* l1tab, double* ws, int grid, const uint32_t* a1amax, hipStream_t st);   // sa_bwd2.hip
 
 extern "C" int facl_sa_bwd2(const float* dz2f, const float* y2f, const float* x, int64_t nunits, int D,
-                            const float* bw2, const float* W2, const float* l1tab, double* out /* 4608 */, void* ws,
-                            const uint32_t* a1amax, void* stream) {
+                            const float* bw2, const float* W2, const float* l1tab, double* out /* FACL_SA_BWD2_OUT(D) */,
+                            void* ws, const uint32_t* a1amax, void* stream) {
     if (!dz2f || !y2f || !x || !bw2 || !W2 || !l1tab || !out || !ws || !a1amax) return FACL_E_NULL;
-    if ((D != 3 && D != 4) || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     // FACL_BWD2_F32=1 selects the exact-fp32 MFMA kernel (v_mfma_f32_32x32x2_f32) instead of the split-bf16 one
     static const int use_f32 = getenv("FACL_BWD2_F32") ? atoi(getenv("FACL_BWD2_F32")) : 0;
     if (!use_f32) {
+        // partial rows of FACL_SA_BWD2_OUT(D) doubles (4864 for D > 4): at most 512 of them, an eighth of the workspace
         const int grid = (int)(nunits < SA_GRID * 8 ? (nunits + 3) / 4 : 2 * SA_GRID);       // 2 workgroups of 4 waves per CU
         int rc = facl_sa_bwd2_sb_launch(dz2f, y2f, x, (int)nunits, D, bw2, W2, l1tab, (double*)ws, grid, a1amax, st);
         if (rc) return rc;
-        return facl_reduce_rows((const double*)ws, grid, B2_V, out, st);       // one row per workgroup (combined in LDS)
+        return facl_reduce_rows((const double*)ws, grid, FACL_SA_BWD2_OUT(D), out, st);   // one row per workgroup (combined in LDS)
     }
+    if (D > 4) return FACL_E_CONFIG;          // the fp32 kernel does not fit a CU's LDS at D > 4 (above): the split-bf16 one serves
     const int grid = (int)(nunits < SA_GRID * 4 ? (nunits + 3) / 4 : SA_GRID);
     const size_t lds = (1024 + 128 + 64) * sizeof(float4) + 4 * (2 * 64 * TQ + 64 * 8) * sizeof(float);
     static bool attr_done[64] = {};

@@ -20,16 +20,21 @@
 //      accumulator tile as the next MFMA's operand"); the A operand dy2^T [row c2][k = p] comes from the LDS image
 //      through two ds_read_b64_tr_b16 per plane, which deliver exactly that k order.
 // Built with -fno-slp-vectorize (facl_amd/build.py): packed f32 VALU beside MFMAs is an anti-lever on gfx950.
-// Output row per wave: [ dW2 (64 x 64, [c2][c1]) | R1 (8 x 64, rows x_0..x_{D-1}, 1, 0..) ] doubles.
+// Output row per wave: [ dW2 (64 x 64, [c2][c1]) | R1 (FACL_SA_L1_COLS(D) x 64, rows x_0..x_{D-1}, 1, 0..) ] doubles.
+// D > 4 (up to 8): x takes two float4s per position in LDS, staged per HALF unit (the same 1 KiB per wave as D <= 4, so the LDS of a
+// workgroup does not grow), the lane's layer-1 rows three float4s, R1 nine accumulators per c1.
 // Roofline: MFMA bf16 (2.5 PFLOP/s dense; 6 executed FLOPs per algorithmic one); 2 workgroups of 4 waves per CU.
 #include "common.h"
 
 namespace {
 
-constexpr int B2_V = 64 * 64 + 8 * 64;
 constexpr int B2S_PLANE = 2 * 32 * 64;          // bytes of one plane of a wave's half-unit image: [c2 tile][32 p][64 B]
 constexpr int B2S_IMG = 3 * B2S_PLANE;          // 12 KiB per wave
 constexpr int B2S_WAVES = 4;
+// LDS bytes of the launch: W2 planes + bw2 table + x of every wave's unit + the per-wave images
+// (the same for every D: at D > 4 the x tile holds the 32 positions of the current HALF unit, two float4s each -- 1 KiB per wave as
+// at D <= 4 -- so that 2 x 78,848 B still fit a CU's 163,840 and two workgroups stay resident)
+constexpr size_t b2s_lds_bytes() { return (1536 + 64 + B2S_WAVES * 64) * sizeof(float4) + B2S_WAVES * (size_t)B2S_IMG; }
 
 #define WAVE_LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
@@ -68,6 +73,9 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     const float* __restrict__ bw2 /* (4,64): scale2, A, B, mean2 */, const float* __restrict__ W2,
     const float* __restrict__ l1tab_g, double* __restrict__ part, int rev, const unsigned* __restrict__ a1amax) {
     extern __shared__ __attribute__((aligned(16))) float4 lds4[];
+    constexpr int L4 = FACL_SA_L1_COLS(D) / 4;              // float4s per layer-1 table row
+    constexpr int NR = D <= 4 ? 5 : 9;                      // R1 accumulators per c1: x_0..x_{NR-2}, then sum dz1
+    constexpr int B2V = FACL_SA_BWD2_OUT(D);
     uint4* w2p = reinterpret_cast<uint4*>(lds4);            // [(ct1*4 + kk)*3 + plane][lane]: 1536 uint4 = 24 KiB
     float4* tab = lds4 + 1536;                              // 4 x 16 float4
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -76,7 +84,7 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     int seW = 127, seA1 = 127;
     if (H3) { seW = wg_h3_se(W2, 64 * 64, reinterpret_cast<float*>(tab)); seA1 = h3_se_of(a1amax); }
     const float sW2 = pow2_biased(seW), sA1 = pow2_biased(seA1);
-    float4* xs4 = tab + 64 + wave * 64;                     // per wave: x of the unit's 64 positions
+    float4* xs4 = tab + 64 + wave * 64;                     // per wave: x of the unit's 64 positions (D > 4: of the half unit, 2 float4s each)
     char* img = reinterpret_cast<char*>(tab + 64 + B2S_WAVES * 64) + wave * B2S_IMG;
     for (int i = threadIdx.x; i < 512; i += 64 * B2S_WAVES) {
         const int ln = i & 63, kk = (i >> 6) & 3, ct1 = i >> 8;
@@ -104,12 +112,13 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     const int lane = lane_id(), h = lane >> 5, q = lane & 31;
     const int wave_g = blockIdx.x * B2S_WAVES + wave, nwaves = gridDim.x * B2S_WAVES;
     // this lane's two layer-1 rows (c1 = q and 32 + q): loop-invariant
-    float4 w1r[2];
+    float4 w1r[2], w1s[2];                                  // w1s: weights 4..7 (D > 4 only)
     float b1r[2];
 #pragma unroll
     for (int ct1 = 0; ct1 < 2; ++ct1) {
-        w1r[ct1] = reinterpret_cast<const float4*>(l1tab_g)[(32 * ct1 + q) * 2];
-        b1r[ct1] = l1tab_g[(32 * ct1 + q) * 8 + 4];
+        w1r[ct1] = reinterpret_cast<const float4*>(l1tab_g)[(32 * ct1 + q) * L4];
+        if (D > 4) w1s[ct1] = reinterpret_cast<const float4*>(l1tab_g)[(32 * ct1 + q) * L4 + 1];
+        b1r[ct1] = l1tab_g[(32 * ct1 + q) * (4 * L4) + 4 * L4 - 4];
     }
     // transposed-read addresses inside a (plane, c2 tile) sub-image: lane (16-lane group g = lane >> 4, i = lane & 15)
     // supplies row 4*(g>>1) + (i>>2), 16-B chunk 2*(g&1) + ((i&3)>>1), 8-B half (i&1); the rows of a fragment's second
@@ -131,11 +140,11 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     f32x16 dw2[2][2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) dw2[0][0][r] = dw2[0][1][r] = dw2[1][0][r] = dw2[1][1][r] = 0.f;
-    float r1[2][5];
+    float r1[2][NR];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int d = 0; d < 5; ++d) r1[a][d] = 0.f;
+        for (int d = 0; d < NR; ++d) r1[a][d] = 0.f;
     constexpr int PA[6] = FACL_SB_PA, PB[6] = FACL_SB_PB;
 
     // rev: walk the units from the LAST one down.  The pass before this one (k_sa_bwd1) wrote dz2 and read y2 front to back, so
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     if (PREF && wave_g < nunits) load_half(rev ? nunits - 1 - wave_g : wave_g, 0);
     for (int uu = wave_g; uu < nunits; uu += nwaves) {
         const int u = rev ? nunits - 1 - uu : uu;
-        {   // x of the unit -> LDS (one float4 per position)
+        if constexpr (D <= 4) {   // x of the unit -> LDS (one float4 per position)
             const size_t p = (size_t)u * 64 + lane;
             float4 xv;
             if (D == 4) xv = *reinterpret_cast<const float4*>(x + p * 4);
@@ -163,6 +172,15 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
 #pragma unroll 1
         for (int ct = 0; ct < 2; ++ct) {
             if (!PREF) load_half(u, ct);                    // all 16 loads in flight before the first use
+            if constexpr (D > 4) {  // x of the HALF unit -> LDS: lane (q, h) writes channels 4h..4h+3 of position 32 ct + q
+                const float* xp = x + ((size_t)u * 64 + 32 * ct + q) * D + 4 * h;
+                float4 xv;
+                xv.x = xp[0];                               // channel 4h (D >= 5)
+                xv.y = h == 0 || D > 5 ? xp[1] : 0.f;
+                xv.z = h == 0 || D > 6 ? xp[2] : 0.f;
+                xv.w = h == 0 || D > 7 ? xp[3] : 0.f;
+                xs4[2 * q + h] = xv;                        // (the previous half's reads are fenced at the end of its iteration)
+            }
             // ---- 1. dy2 -> 16-bit planes: registers (A operand of da1) + LDS image (transposed A operand of dW2)
             bf16x8 ap[4][3];                                // [k16 block][plane]
             float uns_da = 1.f, uns_dw = 1.f;               // H3: inverse scales of this half unit's da1 / dW2 tiles
@@ -265,6 +283,23 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
             float a1v[2][16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                if constexpr (D > 4) {
+                    const float4 xa = xs4[2 * rowmap(r, h)], xb = xs4[2 * rowmap(r, h) + 1];   // broadcast reads
+                    const float xe[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+                    for (int ct1 = 0; ct1 < 2; ++ct1) {
+                        const float w[8] = {w1r[ct1].x, w1r[ct1].y, w1r[ct1].z, w1r[ct1].w, w1s[ct1].x, w1s[ct1].y, w1s[ct1].z, w1s[ct1].w};
+                        float v = fmaf(w[0], xe[0], b1r[ct1]);          // bias + channel 0, then channels 1..D-1 (common.h, l1_chain)
+#pragma unroll
+                        for (int i = 1; i < D; ++i) v = fmaf(w[i], xe[i], v);
+                        a1v[ct1][r] = fmaxf(v, 0.f);
+                        const float dz = v > 0.f ? (H3 ? da1[ct1][r] * uns_da : da1[ct1][r]) : 0.f;
+#pragma unroll
+                        for (int i = 0; i < D; ++i) r1[ct1][i] = fmaf(xe[i], dz, r1[ct1][i]);
+                        r1[ct1][NR - 1] += dz;
+                    }
+                    continue;
+                }
                 const float4 xv = xs4[32 * ct + rowmap(r, h)];              // 2 addresses per instruction: broadcast
 #pragma unroll
                 for (int ct1 = 0; ct1 < 2; ++ct1) {
@@ -357,11 +392,11 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     // level: 13.6 -> ~4 us)
     __syncthreads();
     double* comb = reinterpret_cast<double*>(tab + 64 + B2S_WAVES * 64);
-    float r1v[2][5];
+    float r1v[2][NR];
 #pragma unroll
     for (int ct1 = 0; ct1 < 2; ++ct1)
 #pragma unroll
-        for (int d = 0; d < 5; ++d) r1v[ct1][d] = r1[ct1][d] + __shfl_xor(r1[ct1][d], 32, 64);   // the two lane halves hold different positions of the same c1
+        for (int d = 0; d < NR; ++d) r1v[ct1][d] = r1[ct1][d] + __shfl_xor(r1[ct1][d], 32, 64);   // the two lane halves hold different positions of the same c1
     for (int w = 0; w < B2S_WAVES; ++w) {
         if (wave == w) {
 #pragma unroll
@@ -377,10 +412,10 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
 #pragma unroll
                 for (int ct1 = 0; ct1 < 2; ++ct1)
 #pragma unroll
-                    for (int d = 0; d < 8; ++d) {
+                    for (int d = 0; d < 4 * L4; ++d) {
                         float o = 0.f;
                         if (d < D) o = r1v[ct1][d];
-                        else if (d == D) o = r1v[ct1][4];
+                        else if (d == D) o = r1v[ct1][NR - 1];
                         double* dd = comb + 64 * 64 + d * 64 + 32 * ct1 + q;
                         *dd = (w == 0 ? 0.0 : *dd) + (double)o;
                     }
@@ -388,8 +423,8 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
         }
         __syncthreads();
     }
-    double* row = part + (size_t)blockIdx.x * B2_V;
-    for (int i = threadIdx.x; i < B2_V; i += 64 * B2S_WAVES) row[i] = comb[i];
+    double* row = part + (size_t)blockIdx.x * B2V;
+    for (int i = threadIdx.x; i < B2V; i += 64 * B2S_WAVES) row[i] = comb[i];
 }
 
 }  // namespace
@@ -397,15 +432,32 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
 // launcher for facl_sa_bwd2 (sa_bwd.hip): `grid` workgroups of B2S_WAVES waves, one partial row per WORKGROUP in `ws`
 int facl_sa_bwd2_sb_launch(const float* dz2f, const float* y2f, const float* x, int nunits, int D, const float* bw2,
                            const float* W2, const float* l1tab, double* ws, int grid, const uint32_t* a1amax, hipStream_t st) {
-    const size_t lds = (1536 + 64 + B2S_WAVES * 64) * sizeof(float4) + B2S_WAVES * (size_t)B2S_IMG;
-    static bool attr_done[64] = {};
-    const void* fns[6] = {(const void*)k_sa_bwd2_sb<4, true>, (const void*)k_sa_bwd2_sb<3, true>, (const void*)k_sa_bwd2_sb<4, false>,
-                          (const void*)k_sa_bwd2_sb<3, false>, (const void*)k_sa_bwd2_sb<4, true, true>, (const void*)k_sa_bwd2_sb<3, true, true>};
-    if (int rc = facl_set_dynamic_lds(attr_done, fns, 6, (int)lds)) return rc;
+    const size_t lds = b2s_lds_bytes();
     static const int rev = getenv("FACL_BWD2_REV") ? atoi(getenv("FACL_BWD2_REV")) : 1;
     static const int h3 = getenv("FACL_BWD_H3") ? atoi(getenv("FACL_BWD_H3")) : 1;     // 0: bf16x6 (A/B)
     const dim3 g(grid), b(64 * B2S_WAVES);
     static const int pref = getenv("FACL_BWD2_PREF") ? atoi(getenv("FACL_BWD2_PREF")) : 0;
+    if (D > 4) {
+        // the wide inputs (5..8 channels): default geometry; the FACL_BWD2_PREF experiment is not instantiated for them
+        static bool attr_wide[64] = {};
+        const void* wf[8] = {(const void*)k_sa_bwd2_sb<5, true>, (const void*)k_sa_bwd2_sb<6, true>, (const void*)k_sa_bwd2_sb<7, true>,
+                             (const void*)k_sa_bwd2_sb<8, true>, (const void*)k_sa_bwd2_sb<5, false>, (const void*)k_sa_bwd2_sb<6, false>,
+                             (const void*)k_sa_bwd2_sb<7, false>, (const void*)k_sa_bwd2_sb<8, false>};
+        if (int rc = facl_set_dynamic_lds(attr_wide, wf, 8, (int)lds)) return rc;
+#define FACL_BWD2_WIDE(DD)                                                                                                          \
+        if (h3) hipLaunchKernelGGL((k_sa_bwd2_sb<DD, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);  \
+        else hipLaunchKernelGGL((k_sa_bwd2_sb<DD, false>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
+        if (D == 5) { FACL_BWD2_WIDE(5) }
+        else if (D == 6) { FACL_BWD2_WIDE(6) }
+        else if (D == 7) { FACL_BWD2_WIDE(7) }
+        else { FACL_BWD2_WIDE(8) }
+#undef FACL_BWD2_WIDE
+        return facl_launch_status();
+    }
+    static bool attr_done[64] = {};
+    const void* fns[6] = {(const void*)k_sa_bwd2_sb<4, true>, (const void*)k_sa_bwd2_sb<3, true>, (const void*)k_sa_bwd2_sb<4, false>,
+                          (const void*)k_sa_bwd2_sb<3, false>, (const void*)k_sa_bwd2_sb<4, true, true>, (const void*)k_sa_bwd2_sb<3, true, true>};
+    if (int rc = facl_set_dynamic_lds(attr_done, fns, 6, (int)lds)) return rc;
     if (h3 && pref) {
         if (D == 4) hipLaunchKernelGGL((k_sa_bwd2_sb<4, true, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
         else hipLaunchKernelGGL((k_sa_bwd2_sb<3, true, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);

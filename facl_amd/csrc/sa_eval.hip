@@ -1,7 +1,7 @@
 // Set-abstraction point-MLP, EVAL mode, as ONE kernel (the feature-extraction path,
 // /root/reference/training_code/extract_motion_feature.py:143-221 runs the encoder under eval(): every BatchNorm is a constant
 // per-channel affine, so nothing has to be known about the whole batch before a position can be finished):
-//     x (12-16 B per position) -> a1 = relu(bn1(W1 x + b1))          VALU, folded table (facl_sa_l1tab)
+//     x (12-32 B per position) -> a1 = relu(bn1(W1 x + b1))          VALU, folded table (facl_sa_l1tab)
 //                              -> y2 = a1 W2^T + b2                   48 MFMAs per unit (fp16x3)
 //                              -> a2 = relu(bn2(y2))                  registers
 //                              -> y3 = a2 W3^T + b3                  192 MFMAs per unit (fp16x3)
@@ -32,6 +32,8 @@ __device__ __forceinline__ float wave_max_nonneg_e(float v) {
 }
 
 constexpr int EV_LDS_BYTES = (4096 + 1024) * 16 + (128 + 16 + 16 + 16) * 16 + 3 * 256 * 4 + 64;
+// D > 4: the layer-1 table rows are three float4s instead of two (include/facl_hip.h, FACL_SA_L1_COLS)
+constexpr int ev_lds_bytes(int D) { return EV_LDS_BYTES + (FACL_SA_L1_COLS(D) / 4 - 2) * 64 * 16; }
 
 template <int D, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict__ x, int nunits, const float* __restrict__ l1tab_g,
@@ -43,8 +45,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
     extern __shared__ __attribute__((aligned(16))) float4 lds4[];
     uint4* w3p = reinterpret_cast<uint4*>(lds4);          // B fragments of sgn3*W3: [(ct3*4 + kk)*2 + plane][lane]   64 KiB
     uint4* w2p = w3p + 4096;                              // A fragments of W2:      [(rt*4 + kk)*2 + plane][lane]    16 KiB
-    float4* l1tab = lds4 + 5120;                          // folded layer 1 (x a1's scale): [c][w0 w1 w2 w3 | b 0 0 0]
-    float4* b2s = l1tab + 128;                            // b2 x (a1 scale)(W2 scale)
+    constexpr int L4 = FACL_SA_L1_COLS(D) / 4, XN = D <= 4 ? 4 : 8;
+    float4* l1tab = lds4 + 5120;                          // folded layer 1 (x a1's scale): [c][w0 w1 w2 w3 | b 0 0 0] (D > 4: 3 float4s)
+    float4* b2s = l1tab + 64 * L4;                        // b2 x (a1 scale)(W2 scale)
     float4* sc2s = b2s + 16;
     float4* sh2s = sc2s + 16;
     float* b3s = reinterpret_cast<float*>(sh2s + 16);     // sgn3 * b3
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
         d[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
         d[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
     }
-    if (threadIdx.x < 128) {
+    if (threadIdx.x < 64 * L4) {
         float4 t = reinterpret_cast<const float4*>(l1tab_g)[threadIdx.x];
         t.x *= sA1; t.y *= sA1; t.z *= sA1; t.w *= sA1;                  // relu(s w.x + s b) = s relu(w.x + b): exact for a power of two
         l1tab[threadIdx.x] = t;
@@ -134,11 +137,14 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
 
     const int lane = lane_id(), h = lane >> 5, q = lane & 31;
     const int wave_g = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + (threadIdx.x >> 6)), nwaves = gridDim.x * WAVES;
-    auto load_x = [&](int u, float (&xv)[2][4]) {
+    auto load_x = [&](int u, float (&xv)[2][XN]) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
             const size_t p = (size_t)u * 64 + 32 * ct + q;
-            if (D == 4) {
+            if constexpr (D > 4) {
+#pragma unroll
+                for (int i = 0; i < XN; ++i) xv[ct][i] = i < D ? x[p * D + i] : 0.f;
+            } else if (D == 4) {
                 const float4 t = *reinterpret_cast<const float4*>(x + p * 4);
                 xv[ct][0] = t.x; xv[ct][1] = t.y; xv[ct][2] = t.z; xv[ct][3] = t.w;
             } else {
@@ -148,19 +154,23 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
     };
     auto upper = [&](unsigned v) { return __builtin_amdgcn_permlane32_swap(v, v, false, false)[1]; };
     constexpr int HA[3] = FACL_H3_PA, HB[3] = FACL_H3_PB;
-    float xn[2][4];
+    float xn[2][XN];
     if (wave_g < nunits) load_x(wave_g, xn);
     for (int u = wave_g; u < nunits; u += nwaves) {
         asm volatile("" ::: "memory");       // LDS tables are re-read per unit instead of living in registers
-        float xv[2][4];
+        float xv[2][XN];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xv[ct][i] = xn[ct][i];
+            for (int i = 0; i < XN; ++i) xv[ct][i] = xn[ct][i];
         load_x(u + nwaves < nunits ? u + nwaves : u, xn);   // unconditional prefetch (see k_sa_fwd3_sb)
         // a NaN / inf coordinate anywhere in the group -> every output of the group is NaN (x - x is +0 for finite x)
         float chk = (xv[0][0] - xv[0][0]) + (xv[0][1] - xv[0][1]) + (xv[0][2] - xv[0][2]) + (xv[0][3] - xv[0][3]);
         chk += (xv[1][0] - xv[1][0]) + (xv[1][1] - xv[1][1]) + (xv[1][2] - xv[1][2]) + (xv[1][3] - xv[1][3]);
+        if constexpr (D > 4) {
+#pragma unroll
+            for (int i = 4; i < D; ++i) chk += (xv[0][i] - xv[0][i]) + (xv[1][i] - xv[1][i]);
+        }
         const float poison = __builtin_amdgcn_ballot_w64(chk != chk) ? __uint_as_float(0x7fc00000u) : 0.f;
 
         // ---- layer 1 (VALU) -> fp16 planes of a1 * sA1 for this lane's two positions, k-slots in the order layer 2's B operand wants
@@ -171,6 +181,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int c = 16 * kk + 8 * h + j;
+                if constexpr (D > 4) {
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) a1[ct][j] = fmaxf(l1_chain<D>(l1tab + c * L4, xv[ct]), 0.f);
+                } else {
                 const float4 w = l1tab[c * 2];
                 const float b = l1tab[c * 2 + 1].x;
 #pragma unroll
@@ -180,6 +194,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
                     v = fmaf(w.z, xv[ct][2], v);
                     if (D == 4) v = fmaf(w.w, xv[ct][3], v);
                     a1[ct][j] = fmaxf(v, 0.f);
+                }
                 }
             }
 #pragma unroll
@@ -288,13 +303,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_eval(const float* __restrict_
 }  // namespace
 
 // pooled (nunits, 256) = net3DV_1 in eval mode (cn3d_model_conbag.py:43-58 under model.eval()).  x (nunits*64, D) grouped rows;
-// l1tab (64,8) from facl_sa_l1tab with the eval-mode constants of BN1; scale2 / shift2 (64) and scale3 / shift3 (256): BN2 / BN3
+// l1tab (64,FACL_SA_L1_COLS(D)) from facl_sa_l1tab with the eval-mode constants of BN1; scale2 / shift2 (64) and scale3 / shift3 (256): BN2 / BN3
 // folded (facl_bn_eval_consts rows 2 and 3); a1amax: the bound of max|a1| facl_sa_l1tab derived from max|x| (facl_absmax).
 extern "C" int facl_sa_eval(const float* x, int64_t nunits, int D, const float* l1tab, const float* W2, const float* b2,
                             const float* scale2, const float* shift2, const float* W3, const float* b3, const float* scale3,
                             const float* shift3, float* pooled, const uint32_t* a1amax, void* stream) {
     if (!x || !l1tab || !W2 || !b2 || !scale2 || !shift2 || !W3 || !b3 || !scale3 || !shift3 || !pooled || !a1amax) return FACL_E_NULL;
-    if ((D != 3 && D != 4) || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     // 12 waves per workgroup = three per SIMD (the kernel needs 145 registers; one workgroup per CU: 86 KiB of LDS):
     // 0.304 ms vs 0.3135 ms with 8 waves at the headline shape, same box, alternating runs (FACL_EVAL_WAVES=8 for the A/B)
@@ -310,14 +325,28 @@ extern "C" int facl_sa_eval(const float* x, int64_t nunits, int D, const float* 
             hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, EV_LDS_BYTES);
             if (e != hipSuccess) return (int)e;
         }
+        const void* wide[8] = {(const void*)k_sa_eval<5, 8>, (const void*)k_sa_eval<6, 8>, (const void*)k_sa_eval<7, 8>, (const void*)k_sa_eval<8, 8>,
+                               (const void*)k_sa_eval<5, 12>, (const void*)k_sa_eval<6, 12>, (const void*)k_sa_eval<7, 12>, (const void*)k_sa_eval<8, 12>};
+        for (int i = 0; i < 8; ++i) {
+            hipError_t e = hipFuncSetAttribute(wide[i], hipFuncAttributeMaxDynamicSharedMemorySize, ev_lds_bytes(8));
+            if (e != hipSuccess) return (int)e;
+        }
         attr_done_dev[dev] = true;
     }
-#define FACL_EVAL_LAUNCH(DD, WW) hipLaunchKernelGGL((k_sa_eval<DD, WW>), dim3(grid), dim3(64 * WW), EV_LDS_BYTES, st, x, (int)nunits, l1tab, W2, \
+#define FACL_EVAL_LAUNCH(DD, WW) hipLaunchKernelGGL((k_sa_eval<DD, WW>), dim3(grid), dim3(64 * WW), ev_lds_bytes(DD), st, x, (int)nunits, l1tab, W2, \
                                                     b2, scale2, shift2, W3, b3, scale3, shift3, pooled, a1amax)
     if (D == 4 && W == 12) FACL_EVAL_LAUNCH(4, 12);
     else if (D == 4) FACL_EVAL_LAUNCH(4, 8);
-    else if (W == 12) FACL_EVAL_LAUNCH(3, 12);
-    else FACL_EVAL_LAUNCH(3, 8);
+    else if (D == 3 && W == 12) FACL_EVAL_LAUNCH(3, 12);
+    else if (D == 3) FACL_EVAL_LAUNCH(3, 8);
+    else if (D == 5 && W == 12) FACL_EVAL_LAUNCH(5, 12);
+    else if (D == 5) FACL_EVAL_LAUNCH(5, 8);
+    else if (D == 6 && W == 12) FACL_EVAL_LAUNCH(6, 12);
+    else if (D == 6) FACL_EVAL_LAUNCH(6, 8);
+    else if (D == 7 && W == 12) FACL_EVAL_LAUNCH(7, 12);
+    else if (D == 7) FACL_EVAL_LAUNCH(7, 8);
+    else if (W == 12) FACL_EVAL_LAUNCH(8, 12);
+    else FACL_EVAL_LAUNCH(8, 8);
 #undef FACL_EVAL_LAUNCH
     return facl_launch_status();
 }

@@ -24,13 +24,17 @@ namespace {
 constexpr int SA_GRID = 256;   // one workgroup per CU; waves grid-stride over the units
 
 // ------------------------------------------------------------------------------------------
+// D > 4: only the upper triangle of sum x x^T is accumulated (D + D(D+1)/2 = 44 instead of 72 fp64 sums per lane at D = 8) and
+// mirrored when the row is written; x_i x_j of two fp32 values is exact in fp64, so the mirror is bit-identical to the full sum.
 template <int D>
 __global__ __launch_bounds__(256) void k_x_moments(const float* __restrict__ x, long long P,
                                                    double* __restrict__ part) {
     constexpr int V = D + D * D;
-    double acc[V];
+    constexpr bool TRI = D > 4;
+    constexpr int VA = TRI ? D + D * (D + 1) / 2 : V;       // accumulators per lane
+    double acc[VA];
 #pragma unroll
-    for (int i = 0; i < V; ++i) acc[i] = 0;
+    for (int i = 0; i < VA; ++i) acc[i] = 0;
     const long long stride = (long long)gridDim.x * blockDim.x;
     auto load = [&](long long p, float (&v)[D]) {
         if (D == 4) {
@@ -42,22 +46,35 @@ __global__ __launch_bounds__(256) void k_x_moments(const float* __restrict__ x, 
         }
     };
     auto add = [&](const float (&v)[D]) {
+        if constexpr (TRI) {
+            int t = D;
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                acc[i] += (double)v[i];
+#pragma unroll
+                for (int j = i; j < D; ++j) acc[t++] += (double)v[i] * (double)v[j];
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             acc[i] += (double)v[i];
 #pragma unroll
             for (int j = 0; j < D; ++j) acc[D + i * D + j] += (double)v[i] * (double)v[j];
         }
+        }
     };
     // eight points' loads in flight per thread (one dependent round trip per point made this a 14 us kernel on 38 MB); the points
     // are added in the same order as before, so the sums are bit-identical
+    // (D > 4: four points in flight -- the per-thread point order, hence every sum, is independent of the batch; eight would cost
+    // occupancy at D >= 7; three at D = 8)
+    constexpr int U = TRI ? (D == 8 ? 3 : 4) : 8;
     long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; p + 7 * stride < P; p += 8 * stride) {
-        float v[8][D];
+    for (; p + (U - 1) * stride < P; p += U * stride) {
+        float v[U][D];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) load(p + u * stride, v[u]);
+        for (int u = 0; u < U; ++u) load(p + u * stride, v[u]);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) add(v[u]);
+        for (int u = 0; u < U; ++u) add(v[u]);
     }
     for (; p < P; p += stride) {
         float v[D];
@@ -65,10 +82,27 @@ __global__ __launch_bounds__(256) void k_x_moments(const float* __restrict__ x, 
         add(v);
     }
     const int wave_g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if constexpr (TRI) {
+        int t = D;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            const double s = wave_sum_f64(acc[i]);
+            if (lane_id() == 0) part[(size_t)wave_g * V + i] = s;
+#pragma unroll
+            for (int j = i; j < D; ++j) {
+                const double sij = wave_sum_f64(acc[t++]);
+                if (lane_id() == 0) {
+                    part[(size_t)wave_g * V + D + i * D + j] = sij;
+                    part[(size_t)wave_g * V + D + j * D + i] = sij;
+                }
+            }
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         const double s = wave_sum_f64(acc[i]);
         if (lane_id() == 0) part[(size_t)wave_g * V + i] = s;
+    }
     }
 }
 
@@ -81,13 +115,14 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2(const float* __restrict__ x,
                                                  const float* __restrict__ b2, float* __restrict__ y2f,
                                                  double* __restrict__ part) {
     __shared__ float4 w2f[2 * 8 * 64];      // A fragments of W2: [rt][s4][lane] -> W2[32rt+q][32h+4s4 .. +3]
-    __shared__ float4 l1tab[64 * 2];        // folded layer 1: [c][w0 w1 w2 w3 | b 0 0 0]
+    constexpr int L4 = FACL_SA_L1_COLS(D) / 4, XN = D <= 4 ? 4 : 8;
+    __shared__ float4 l1tab[64 * L4];       // folded layer 1: [c][w0 w1 w2 w3 | b 0 0 0]  (D > 4: [c][w0..w3 | w4..w7 | b 0 0 0])
     __shared__ float4 b2s[16];
     for (int i = threadIdx.x; i < 1024; i += 256) {
         const int ln = i & 63, s4 = (i >> 6) & 7, rt = i >> 9;
         w2f[i] = *reinterpret_cast<const float4*>(W2 + (32 * rt + (ln & 31)) * 64 + 32 * (ln >> 5) + 4 * s4);
     }
-    if (threadIdx.x < 128) l1tab[threadIdx.x] = reinterpret_cast<const float4*>(l1tab_g)[threadIdx.x];
+    if (threadIdx.x < 64 * L4) l1tab[threadIdx.x] = reinterpret_cast<const float4*>(l1tab_g)[threadIdx.x];
     if (threadIdx.x < 16) b2s[threadIdx.x] = reinterpret_cast<const float4*>(b2)[threadIdx.x];
     __syncthreads();
 
@@ -101,11 +136,14 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2(const float* __restrict__ x,
         for (int r = 0; r < 16; ++r) { ps[rt][r] = 0.f; pq[rt][r] = 0.f; }
 
     // software prefetch: with one wave per SIMD the HBM latency of the next unit's input is otherwise exposed
-    auto load_x = [&](int u, float (&xv)[2][4]) {
+    auto load_x = [&](int u, float (&xv)[2][XN]) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
             const size_t p = (size_t)u * 64 + 32 * ct + q;
-            if (D == 4) {
+            if constexpr (D > 4) {
+#pragma unroll
+                for (int i = 0; i < XN; ++i) xv[ct][i] = i < D ? x[p * D + i] : 0.f;
+            } else if (D == 4) {
                 const float4 t = *reinterpret_cast<const float4*>(x + p * 4);
                 xv[ct][0] = t.x; xv[ct][1] = t.y; xv[ct][2] = t.z; xv[ct][3] = t.w;
             } else {
@@ -113,20 +151,24 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2(const float* __restrict__ x,
             }
         }
     };
-    float xn[2][4];
+    float xn[2][XN];
     if (wave_g < nunits) load_x(wave_g, xn);
     for (int u = wave_g; u < nunits; u += nwaves) {
         asm volatile("" ::: "memory");       // LDS tables are re-read per unit instead of living in registers
-        float xv[2][4];
+        float xv[2][XN];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xv[ct][i] = xn[ct][i];
+            for (int i = 0; i < XN; ++i) xv[ct][i] = xn[ct][i];
         if (u + nwaves < nunits) load_x(u + nwaves, xn);
         // layer 1 on the VALU: this lane's two positions x the 32 channels of its half
         float a1[2][32];
 #pragma unroll
         for (int s = 0; s < 32; ++s) {
+            if constexpr (D > 4) {
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) a1[ct][s] = fmaxf(l1_chain<D>(l1tab + (32 * h + s) * L4, xv[ct]), 0.f);
+            } else {
             const float4 w = l1tab[(32 * h + s) * 2];
             const float b = l1tab[(32 * h + s) * 2 + 1].x;
 #pragma unroll
@@ -136,6 +178,7 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2(const float* __restrict__ x,
                 v = fmaf(w.z, xv[ct][2], v);
                 if (D == 4) v = fmaf(w.w, xv[ct][3], v);
                 a1[ct][s] = fmaxf(v, 0.f);
+            }
             }
         }
         f32x16 acc[2][2];
@@ -214,7 +257,8 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2_sb(const float* __restrict__
                                                        const float* __restrict__ b2, float* __restrict__ y2f,
                                                        double* __restrict__ part, const unsigned* __restrict__ a1amax) {
     __shared__ uint4 w2p[2 * 4 * 3 * 64];   // A fragments of W2, [(rt*4 + kk)*3 + plane][lane]: W2[32rt+r][16kk+8h .. +7]
-    __shared__ float4 l1tab[64 * 2];        // folded layer 1: [c][w0 w1 w2 w3 | b 0 0 0]
+    constexpr int L4 = FACL_SA_L1_COLS(D) / 4, XN = D <= 4 ? 4 : 8;
+    __shared__ float4 l1tab[64 * L4];       // folded layer 1: [c][w0 w1 w2 w3 | b 0 0 0]  (D > 4: [c][w0..w3 | w4..w7 | b 0 0 0])
     __shared__ float4 b2s[16];
     __shared__ float red[16];
     // fp16x3 operand scales (common.h): W2 by the power of two of its own maximum (taken here), a1 by the one of its bound
@@ -243,7 +287,7 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2_sb(const float* __restrict__
         d[64] = make_uint4(mi[0], mi[1], mi[2], mi[3]);
         d[128] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
     }
-    if (threadIdx.x < 128) {
+    if (threadIdx.x < 64 * L4) {
         float4 t = reinterpret_cast<const float4*>(l1tab_g)[threadIdx.x];
         if (H3) { t.x *= sA; t.y *= sA; t.z *= sA; t.w *= sA; }   // relu(s w.x + s b) = s relu(w.x + b) for a power of two s: exact
         l1tab[threadIdx.x] = t;
@@ -260,11 +304,14 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2_sb(const float* __restrict__
 #pragma unroll
         for (int r = 0; r < 16; ++r) { ps[rt][r] = 0.f; pq[rt][r] = 0.f; }
 
-    auto load_x = [&](int u, float (&xv)[2][4]) {
+    auto load_x = [&](int u, float (&xv)[2][XN]) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
             const size_t p = (size_t)u * 64 + 32 * ct + q;
-            if (D == 4) {
+            if constexpr (D > 4) {
+#pragma unroll
+                for (int i = 0; i < XN; ++i) xv[ct][i] = i < D ? x[p * D + i] : 0.f;
+            } else if (D == 4) {
                 const float4 t = *reinterpret_cast<const float4*>(x + p * 4);
                 xv[ct][0] = t.x; xv[ct][1] = t.y; xv[ct][2] = t.z; xv[ct][3] = t.w;
             } else {
@@ -272,15 +319,15 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2_sb(const float* __restrict__
             }
         }
     };
-    float xn[2][4];
+    float xn[2][XN];
     if (wave_g < nunits) load_x(wave_g, xn);
     for (int u = wave_g; u < nunits; u += nwaves) {
         asm volatile("" ::: "memory");       // LDS tables are re-read per unit instead of living in registers
-        float xv[2][4];
+        float xv[2][XN];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xv[ct][i] = xn[ct][i];
+            for (int i = 0; i < XN; ++i) xv[ct][i] = xn[ct][i];
         load_x(u + nwaves < nunits ? u + nwaves : u, xn);   // unconditional: a conditional prefetch is waited for on the spot (see k_sa_fwd3_sb)
         // layer 1 on the VALU for this lane's two positions, straight into the bf16 planes of the B operand
         bf16x8 ap[2][4][3];                  // [position tile][k16 block][plane]
@@ -290,6 +337,10 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2_sb(const float* __restrict__
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int c = 16 * kk + 8 * h + j;
+                if constexpr (D > 4) {
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) a1[ct][j] = fmaxf(l1_chain<D>(l1tab + c * L4, xv[ct]), 0.f);
+                } else {
                 const float4 w = l1tab[c * 2];
                 const float b = l1tab[c * 2 + 1].x;
 #pragma unroll
@@ -299,6 +350,7 @@ __global__ __launch_bounds__(256, 2) void k_sa_fwd2_sb(const float* __restrict__
                     v = fmaf(w.z, xv[ct][2], v);
                     if (D == 4) v = fmaf(w.w, xv[ct][3], v);
                     a1[ct][j] = fmaxf(v, 0.f);
+                }
                 }
             }
 #pragma unroll
@@ -836,11 +888,15 @@ __global__ void k_sa_pool(const float* __restrict__ ymax, long long n4, int C4, 
 
 extern "C" int facl_sa_x_moments(const float* x, int64_t P, int D, double* mom, void* ws, void* stream) {
     if (!x || !mom || !ws) return FACL_E_NULL;
-    if ((D != 3 && D != 4) || P < 1) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || P < 1) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int grid = 512, V = D + D * D;       // 512 blocks x 4 waves = 2048 partial rows
     if (D == 4) hipLaunchKernelGGL((k_x_moments<4>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    else hipLaunchKernelGGL((k_x_moments<3>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
+    else if (D == 3) hipLaunchKernelGGL((k_x_moments<3>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
+    else if (D == 5) hipLaunchKernelGGL((k_x_moments<5>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
+    else if (D == 6) hipLaunchKernelGGL((k_x_moments<6>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
+    else if (D == 7) hipLaunchKernelGGL((k_x_moments<7>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
+    else hipLaunchKernelGGL((k_x_moments<8>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
     int rc = facl_launch_status();
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, grid * 4, V, mom, st);
@@ -850,12 +906,25 @@ extern "C" int facl_sa_x_moments(const float* x, int64_t P, int D, double* mom, 
 extern "C" int facl_sa_fwd2(const float* x, int64_t nunits, int D, const float* l1tab, const float* W2,
                             const float* b2, float* y2f, double* sums2, void* ws, const uint32_t* a1amax, void* stream) {
     if (!x || !l1tab || !W2 || !b2 || !y2f || (sums2 && !ws) || !a1amax) return FACL_E_NULL;
-    if ((D != 3 && D != 4) || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)(nunits < 2 * SA_GRID * 4 ? (nunits + 3) / 4 : 2 * SA_GRID);   // 2 workgroups per CU
     double* part = sums2 ? (double*)ws : nullptr;
     static const int use_f32 = getenv("FACL_SA_F32") ? atoi(getenv("FACL_SA_F32")) : 0;     // exact-fp32 MFMA kernel instead
-    if (use_f32) {
+    if (D > 4) {
+        // the wide inputs (5..8 channels): same kernels, layer-1 table rows of FACL_SA_L1_COLS(D) floats
+#define FACL_FWD2_WIDE(DD)                                                                                                         \
+        if (use_f32) hipLaunchKernelGGL((k_sa_fwd2<DD>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);   \
+        else if (h3w) hipLaunchKernelGGL((k_sa_fwd2_sb<DD, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, \
+                                         part, a1amax);                                                                            \
+        else hipLaunchKernelGGL((k_sa_fwd2_sb<DD, false>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
+        static const int h3w = getenv("FACL_FWD_H3") ? atoi(getenv("FACL_FWD_H3")) : 1;
+        if (D == 5) { FACL_FWD2_WIDE(5) }
+        else if (D == 6) { FACL_FWD2_WIDE(6) }
+        else if (D == 7) { FACL_FWD2_WIDE(7) }
+        else { FACL_FWD2_WIDE(8) }
+#undef FACL_FWD2_WIDE
+    } else if (use_f32) {
         if (D == 4) hipLaunchKernelGGL((k_sa_fwd2<4>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);
         else hipLaunchKernelGGL((k_sa_fwd2<3>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);
     } else {

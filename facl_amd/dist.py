@@ -205,7 +205,9 @@ def make_bn_reduce_fn(group=None):
     oneshot = None
     if os.environ.get("FACL_ONESHOT_SYNCBN", "0") not in ("", "0"):
         from .mailbox import OneShotAllReduce
-        oneshot = OneShotAllReduce(group, n_max=4608)        # the largest SyncBN buffer of the step: B2_V = 4608 doubles
+        # 4608 doubles of capacity; the set-abstraction's SyncBN buffers are the moments (D + D*D <= 72) and R1 (512 doubles,
+        # 768 at INPUT_FEATURE_NUM > 4); a buffer over the capacity goes through the process group (reduce_fn below)
+        oneshot = OneShotAllReduce(group, n_max=4608)
 
     def reduce_fn(t):
         if oneshot is not None and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() <= oneshot.n_max:

@@ -118,8 +118,8 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
     P, D = x_rows.shape
     if P % UNIT:
         raise ValueError("P must be a multiple of 64 (knn_K = 64)")
-    if D not in (3, 4):
-        raise NotImplementedError("INPUT_FEATURE_NUM must be 3 or 4 (got %d)" % D)
+    if not _lib.SA_D_MIN <= D <= _lib.SA_D_MAX:
+        raise NotImplementedError("INPUT_FEATURE_NUM must be in %d..%d (got %d)" % (_lib.SA_D_MIN, _lib.SA_D_MAX, D))
     nunits = P // UNIT
     dev = x_rows.device
     st = _lib.stream()
@@ -129,6 +129,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
     W1 = p["W1"].reshape(64, D)
     W2 = p["W2"].reshape(64, 64)
     W3 = p["W3"].reshape(256, 64)
+    L1C = _lib.sa_l1_cols(D)                       # folded layer-1 table row: weights | bias in column L1C - 4 (include/facl_hip.h)
     ctx = {}
     # fp16x3 operand maxima (csrc/common.h): [0] max|x| (eval), [1] bound of a1, [2] bound of a2, [3] max(pooled)
     # training: [1], [2] are stored by facl_bn_finalize and [3] is zeroed by BN3's finalize call right before facl_sa_pool
@@ -148,7 +149,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         # sums of y1 from the moments -> BatchNorm-1 constants (+ running statistics, + the bound of a1) -> folded layer-1 table:
         # one single-wave launch (facl_sa_bn1_chain; bit-identical to facl_bn1_sums_from_moments + facl_bn_finalize + facl_sa_l1tab)
         bnc1 = _lib.empty((5, 64), dtype=torch.float32, device=dev)
-        l1tab = _lib.empty((64, 8), dtype=torch.float32, device=dev)
+        l1tab = _lib.empty((64, L1C), dtype=torch.float32, device=dev)
         _lib.check(lib.facl_sa_bn1_chain(_lib.ptr(mom), count, D, _lib.ptr(W1), _lib.ptr(p["b1"]), _lib.ptr(p["g1"]), _lib.ptr(p["be1"]),
                                          BN_EPS, BN_MOMENTUM, _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(sums1), _lib.ptr(bnc1),
                                          _lib.ptr(amax[1]), _lib.ptr(l1tab), st), "facl_sa_bn1_chain")
@@ -159,7 +160,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         bnc1 = _bn_eval(64, p["g1"], p["be1"], p["rm1"], p["rv1"])
         xa = amax[0]                                       # eval: the bound of a1 follows from max|x| (facl_sa_l1tab)
         _lib.check(lib.facl_absmax(_lib.ptr(x_rows), x_rows.numel(), _lib.ptr(xa), st), "facl_absmax")
-        l1tab = _lib.empty((64, 8), dtype=torch.float32, device=dev)
+        l1tab = _lib.empty((64, L1C), dtype=torch.float32, device=dev)
         _lib.check(lib.facl_sa_l1tab(_lib.ptr(W1), _lib.ptr(p["b1"]), D, _lib.ptr(bnc1[2]), _lib.ptr(bnc1[3]),
                                      _lib.ptr(l1tab), _lib.ptr(xa), _lib.ptr(amax[1]), st), "facl_sa_l1tab")
     if not training and _EVAL_FUSED and precision in ("f32", "x3b") and _FWD_H3:
@@ -229,7 +230,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
                                 _lib.ptr(amax[3]), st), "facl_sa_pool")
     if _lib.TAPS is not None and K == UNIT:          # tests only: the ReLU decisions of the three layers (tie-proof parity)
         xd, tb = x_rows.double(), l1tab.double()
-        v = (tb[:, 0] * xd[:, :1] + tb[:, 4]).float().double()                # the kernels' sequential fp32 FMA chain
+        v = (tb[:, 0] * xd[:, :1] + tb[:, L1C - 4]).float().double()          # the kernels' sequential fp32 FMA chain
         for i in range(1, D):
             v = (tb[:, i] * xd[:, i:i + 1] + v).float().double()
         _lib.TAPS["relu_sa1"] = v > 0
@@ -298,7 +299,7 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
     # that pass 1 touched last are still in the memory-side cache (FACL_BWD2_REV=0: front to back)
     bw2 = _lib.empty((4, 64), **f32)
     _lib.check(lib.facl_sa_bwd_consts2(ptr(sums1), ptr(bnc2), P, ptr(bw2), st), "facl_sa_bwd_consts2")
-    out2 = _lib.empty(64 * 64 + 8 * 64, **f64)
+    out2 = _lib.empty(_lib.sa_bwd2_out(D), **f64)
     with _lib.timed("facl_sa_bwd2"):
         _lib.check(lib.facl_sa_bwd2(ptr(dz2f), ptr(ctx["y2f"]), ptr(x_rows), nunits, D, ptr(bw2), ptr(W2), ptr(ctx["l1tab"]),
                                     ptr(out2), ptr(ws), ptr(ctx["amax"][1]), st), "facl_sa_bwd2")
@@ -308,7 +309,7 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
         _lib.check(lib.facl_sa_bwd_w3(ptr(ctx["y2f"]), nunits, ptr(bnc2), ptr(coef), ptr(ctx["arg"]), ptr(out3), ptr(ws),
                                       ptr(ctx["amax"][2]), st), "facl_sa_bwd_w3")
 
-    R1_g = out2[4096:]
+    R1_g = out2[4096:]                           # (sa_l1_cols(D), 64): rows x_0..x_{D-1}, sum dz1, zeros
     if reduce_fn is not None:
         R1_g = reduce_fn(R1_g.clone())
 

@@ -58,7 +58,8 @@ int facl_fps_reorder(const float* points, int M, int N, int D, const int32_t* pi
  * 0..S-1; fp32 dist^2 = (dx*dx+dy*dy)+dz*dz; the K nearest are kept; a kept neighbour with
  * dist^2 > r2 (strict) is replaced by the centroid's own row; all D channels are gathered and
  * xyz is centred on the centroid.
- *   points (M,N,D) f32, D in {3,4}
+ *   points (M,N,D) f32, FACL_SA_D_MIN <= D <= FACL_SA_D_MAX (xyz + up to five feature channels); D == 4 needs 16-byte
+ *          aligned points / xt, no other D has an alignment rule
  *   idx    (M,S,K) int32, ascending along K before the radius replacement   (may be NULL)
  *   xt     (M,S,K,D) f32 -- the memory behind the reference's (M,D,S,K) view (may be NULL)
  *   yt     (M,S,3)   f32 -- the memory behind the reference's (M,3,S,1) view (may be NULL)
@@ -92,22 +93,33 @@ int facl_bn_eval_consts(int C, const float* gamma, const float* beta, const floa
 
 /* ---- set-abstraction point-MLP forward (net3DV_1, cn3d_model_conbag.py:43-58 / :162-177) ----
  * x is the grouped input, (P,D) rows = the memory behind the reference's (M,D,S,K) view, P = M*S*K,
- * K = 64 ("unit" = 64 consecutive rows = one group), D in {3,4}.  Weights are the reference's
+ * K = 64 ("unit" = 64 consecutive rows = one group), 3 <= D <= 8 (FACL_SA_D_MIN..FACL_SA_D_MAX).  Weights are the reference's
  * tensors as stored in the checkpoint: W1 (64,D), W2 (64,64), W3 (256,64), row-major (Cout,Cin).
  *   facl_sa_x_moments           x -> mom = [sum_p x (D) | sum_p x x^T (D*D)]  (double)
  *   facl_bn1_sums_from_moments  mom -> sums of y1 = W1 x + b1 (exact: y1 is affine in x)
- *   facl_sa_l1tab               fold BN1 into layer 1: l1tab (64,8) = [scale*W1 | scale*b1+shift | 0]
+ *   facl_sa_l1tab               fold BN1 into layer 1: l1tab (64,FACL_SA_L1_COLS(D)) = [scale*W1 | 0 | scale*b1+shift | 0]
  *   facl_sa_fwd2                x -> y2 = relu(bn1(y1)) W2^T + b2, stored in "fragment layout"
  *                               (nunits*4096 floats, see csrc/common.h); sums2 (64,2) or NULL
  *   facl_sa_fwd3                y2 -> per (group,channel) max_k sgn3*y3 and its argmax k (uint8),
  *                               y3 = relu(bn2(y2)) W3^T + b3; sums3 (256,2) = (sum, sumsq) of y3 or NULL
  *   facl_sa_pool                pooled = relu(|scale3| * ymax + shift3)   (rows,C)
+ *
+ * The D-dependent layer-1 layouts.  FACL_SA_L1_COLS(D) is 8 for D <= 4 and 12 for D > 4:
+ *   l1tab  (64, FACL_SA_L1_COLS(D)) floats per row: the folded weights in columns 0..FACL_SA_L1_COLS(D)-5 (zero for i >= D),
+ *          the folded bias in column FACL_SA_L1_COLS(D) - 4, zeros after it (D <= 4: [w0 w1 w2 w3 | b 0 0 0]);
+ *   R1     the tail of facl_sa_bwd2's output, (FACL_SA_L1_COLS(D), 64) doubles: rows sum_p x_d*dz1 (d < D), then sum_p dz1
+ *          (row D), then zeros; the whole output is FACL_SA_BWD2_OUT(D) doubles (4608 for D <= 4, 4864 for D > 4).
  */
+#define FACL_SA_D_MIN 3
+#define FACL_SA_D_MAX 8
+#define FACL_SA_L1_COLS(D) ((D) <= 4 ? 8 : 12)
+#define FACL_SA_BWD2_OUT(D) (64 * 64 + 64 * FACL_SA_L1_COLS(D))
 int facl_sa_x_moments(const float* x, int64_t P, int D, double* mom, void* ws, void* stream);
 int facl_bn1_sums_from_moments(const double* mom, double count, int D, const float* W1, const float* b1,
                                double* sums, void* stream);
 /* training, the 64-channel first layer: facl_bn1_sums_from_moments + facl_bn_finalize + facl_sa_l1tab in ONE launch (sums (64,2),
- * bnc (5,64), running statistics, the activation bound in aamax, l1tab (64,8)); every output bit-identical to the three calls */
+ * bnc (5,64), running statistics, the activation bound in aamax, l1tab (64,FACL_SA_L1_COLS(D))); every output bit-identical to
+ * the three calls */
 int facl_sa_bn1_chain(const double* mom, double count, int D, const float* W1, const float* b1, const float* gamma,
                       const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                       double* sums, float* bnc, uint32_t* aamax, float* l1tab, void* stream);
@@ -162,8 +174,8 @@ int facl_rows_act_amax(const float* y, int64_t R, int C, const float* scale, con
  *   facl_sa_bwd_w3  y2f, bnc2, coef, arg -> out (20544 doubles) =
  *                   [ sum_g coef*a2[arg] (256,64) | sum_p a2^T a2 (64,64) | sum_p a2 (64) ]
  *   facl_sa_bwd2    dz2f, y2f, x, bw2 (4,64) = [scale2 | A | B | mean2] with dy2 = scale2*dz2 + A + B*(y2-mean2),
- *                   W2, l1tab -> out (4608 doubles) = [ dW2 (64,64) | R1 (8,64) ], R1 rows = sum_p x_d*dz1
- *                   (d < D), then sum_p dz1, then zeros.
+ *                   W2, l1tab -> out (FACL_SA_BWD2_OUT(D) doubles) = [ dW2 (64,64) | R1 (FACL_SA_L1_COLS(D),64) ],
+ *                   R1 rows = sum_p x_d*dz1 (d < D), then sum_p dz1, then zeros.
  */
 int facl_sa_bwd0(const float* dpooled, const float* ymax, int64_t rows, const float* bnc3, float* coef,
                  double* sums, void* ws, void* stream);
@@ -172,7 +184,8 @@ int facl_sa_bwd1(const float* y2f, int64_t nunits, const float* bnc2, const floa
                  void* ws, const uint32_t* a2amax, void* stream);
 int facl_sa_bwd_w3(const float* y2f, int64_t nunits, const float* bnc2, const float* coef,
                    const uint8_t* arg, double* out, void* ws, const uint32_t* a2amax, void* stream);
-/* a1amax / a2amax: the activation bounds the forward passes were given (facl_sa_fwd2 / facl_sa_fwd3_h3) */
+/* a1amax / a2amax: the activation bounds the forward passes were given (facl_sa_fwd2 / facl_sa_fwd3_h3).  facl_sa_bwd2 returns
+ * FACL_E_CONFIG for D > 4 when the exact-fp32 A/B kernel is selected (FACL_BWD2_F32=1): it does not fit a CU's LDS there */
 int facl_sa_bwd2(const float* dz2f, const float* y2f, const float* x, int64_t nunits, int D,
                  const float* bw2, const float* W2, const float* l1tab, double* out, void* ws,
                  const uint32_t* a1amax, void* stream);
@@ -181,7 +194,7 @@ int facl_sa_bwd2(const float* dz2f, const float* y2f, const float* x, int64_t nu
  *   facl_sa_bwd_consts3  sums0 (dbeta3,dgamma3) -> G3 (64,64), h3 (64) for facl_sa_bwd1
  *   facl_sa_bwd_consts2  sums1 (dbeta2,dgamma2) -> bw2 (4,64) for facl_sa_bwd2
  *   facl_sa_bwd_final    all partial sums -> dW3,dgamma3,dbeta3, dW2,dgamma2,dbeta2, dW1,dgamma1,dbeta1
- *                        (R1_g (8,64) = all-reduced tail of facl_sa_bwd2's output, mom_l = local x moments) */
+ *                        (R1_g (FACL_SA_L1_COLS(D),64) = all-reduced tail of facl_sa_bwd2's output, mom_l = local x moments) */
 /* BN backward constants of a row layer (tail): sums (C,2) = (dbeta, dgamma) of THIS rank / after the SyncBN
  * all-reduce -> dbeta (C), dgamma (C) fp32 parameter gradients (local) and kk (2,C) = reduced sums / P */
 int facl_bn_bwd_consts(const double* sums_local, const double* sums_global, int C, double P, float* dbeta,

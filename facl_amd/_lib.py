@@ -120,6 +120,14 @@ SIGNATURES = {
     "facl_mailbox_close": [c_p],
     "facl_mailbox_free": [c_p],
     "facl_mailbox_allreduce": [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p],
+    "facl_gen3dv_frames": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    "facl_gen3dv_voxelise": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_d, c_p, c_p, c_p, c_p, c_p],
+    "facl_gen3dv_volumes": [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_p],
+    "facl_gen3dv_filter": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p],
+    "facl_gen3dv_compact": [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_p],
+    "facl_gen3dv_sample": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "facl_gen3dv_app": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_l, c_p, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_i, c_l, c_d,
+                        c_p, c_p, c_p, c_p, c_p],
 }
 RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes"}
 

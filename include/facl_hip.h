@@ -522,6 +522,55 @@ int facl_build_views_philox_f64(const double* src, int64_t rows, int C, const in
                                 const int32_t* counts, int64_t seed, int epoch, int B, float* out, int32_t* idx_out,
                                 void* stream);
 
+/* ---- 3DV generation: depth frames -> motion, key and appearance clouds (generate_data/generate_NTU.py; csrc/gen3dv.hip,
+ * whose header describes the stages and the layouts) for a batch of B clips.  int32 unless said otherwise:
+ *   frames uint16 (NF,H,W): per clip the first file of its folder, then its chosen frames (at most FACL_GEN3DV_MAX_FRAMES)
+ *   fmeta  (NF,4): clip; index among the clip's chosen frames, -1 for the first file; the frame before it in the motion
+ *          chain (:140-150); offset of its pixel list in pix (exclusive scan of fcount over the chosen frames)
+ *   fbox   (NF,4): rows [60,rhi) and columns [clo,chi) survive load_depth_from_img (:339-351); [3] = frame has a pixel
+ *   fcount (NF): pixels kept;  fext float64 (NF,6): min xyz, max xyz of their back-projection (+-inf when none)
+ *   cmin   float64 (B,3), cgrid (B,4) = nx, ny, nz, voxel offset: the clip's grid (:165-181), voxel (x*ny+y)*nz+z
+ *   occ, mocc uint64 (NV), ZEROED by the caller: bit i = chosen frame i has a point / a motion point in the voxel
+ *   pix    (NP): the kept pixels of every chosen frame, row-major;  wtab (B,5,64): weight of frame i in channel m (:409-438)
+ *   vol    (5,NV) channel planes, key (NV); vol0f, keyf (NV): disca_voxel (:277-296) of channel 0 / of key
+ *   lists  (12*NV): per clip at 12*offset the (m,x,y,z)-ordered hits (5V), the sorted unique voxels (V), and the same two
+ *          under the key mask (:196-201, :212-219), as voxel numbers;  counts (B,4) in that order
+ *   idx    (B,2,2048) rows of the list the reference samples from (hits > 2048: the unique list), or NULL: Philox4x32-10
+ *          keyed by seed, counter (row, slot, crc[b], resolution) -- recipe in csrc/gen3dv.hip; crc uint32 (B)
+ *   out_raw, out_key float64 (B,2048,8); norm float64 (B,14): centres, y_len, c_min[5], c_len[5] (:232-240)
+ *   ameta  (NA,3): frame, clip, slot of an appearance frame; idx (NA,2048) ranks among the frame's kept pixels or NULL;
+ *          out float64 (NA,2048,4) (:61-73, :249-260)
+ *   err    a word of flags, only ever raised: 1 a point outside its grid, 2 pixel list overrun, 4 bad fmeta / ameta row,
+ *          8 an empty list or frame, 16 a drawn index out of range.  Nothing is written out of bounds in any of these cases.
+ * maxF = the largest number of chosen frames of a clip, maxvox = the largest nx*ny*nz.  FACL_E_SHAPE beyond the limits
+ * below (never truncated). */
+#define FACL_GEN3DV_MAX_FRAMES        64           /* chosen frames per clip: one bit each            */
+#define FACL_GEN3DV_MAX_FRAMES_TOTAL  (1 << 16)    /* frames (NF) / appearance frames (NA) per batch  */
+#define FACL_GEN3DV_MAX_PIXELS        (1 << 22)    /* H * W                                           */
+#define FACL_GEN3DV_MAX_CLIPS         4096         /* B                                               */
+#define FACL_GEN3DV_MAX_VOXELS        (1 << 24)    /* nx * ny * nz of one clip                        */
+#define FACL_GEN3DV_MAX_VOXELS_TOTAL  (1 << 27)    /* NV                                              */
+int facl_gen3dv_frames(const uint16_t* frames, int NF, int H, int W, int32_t* fbox, int32_t* fcount, double* fext,
+                       void* stream);
+int facl_gen3dv_voxelise(const uint16_t* frames, int NF, int H, int W, const int32_t* fbox, const int32_t* fmeta,
+                         const double* cmin, const int32_t* cgrid, int B, int maxF, int maxvox, int64_t NV, int64_t NP,
+                         double voxel, uint64_t* occ, uint64_t* mocc, int32_t* pix, int32_t* err, void* stream);
+int facl_gen3dv_volumes(const uint64_t* occ, const uint64_t* mocc, const int32_t* wtab, const int32_t* cgrid, int B,
+                        int maxvox, int64_t NV, int32_t* vol, int32_t* key, void* stream);
+int facl_gen3dv_filter(const int32_t* vol, const int32_t* key, const int32_t* cgrid, int B, int maxvox, int64_t NV,
+                       int th_all, int th_key, int32_t* vol0f, int32_t* keyf, void* stream);
+int facl_gen3dv_compact(const int32_t* vol, const int32_t* vol0f, const int32_t* keyf, const int32_t* cgrid, int B,
+                        int maxvox, int64_t NV, int32_t* lists, int32_t* counts, void* stream);
+int facl_gen3dv_sample(const int32_t* vol, const int32_t* vol0f, const int32_t* lists, const int32_t* counts,
+                       const int32_t* cgrid, int B, int maxvox, int64_t NV, const int32_t* idx, int64_t seed,
+                       int resolution, const uint32_t* crc, double* out_raw, double* out_key, double* norm, int32_t* err,
+                       void* stream);
+int facl_gen3dv_app(const uint16_t* frames, int NF, int H, int W, const int32_t* fmeta, const int32_t* fcount,
+                    const int32_t* pix, int64_t NP, const int32_t* ameta, int NA, const int32_t* idx, int64_t seed,
+                    int resolution, const uint32_t* crc, const double* cmin, const int32_t* cgrid, int B, int maxvox,
+                    int64_t NV, double voxel, const int32_t* vol0f, const double* norm, double* out, int32_t* err,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

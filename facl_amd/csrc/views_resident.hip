@@ -1,0 +1,132 @@
+// The philox views of clips that are RESIDENT in device memory (--resident 1): the whole training split is loaded once
+// into a pool, and a batch is B table positions.  No file is read, nothing is packed and no clip data crosses to the
+// device per step.  The views equal csrc/views_philox.hip's bit for bit: the draw recipe and the per-point arithmetic are
+// the same code (views_philox_point.inc); only the way a drawn position becomes a source row differs.
+//
+// Pool (device memory owned by facl_amd/resident.py):
+//   src    (rows_total, 8) in the dataset's one dtype: the clips back to back, each as its four clouds in pack_clips' order
+//   table  (n_clips, FACL_RESIDENT_REC) int64, one record per clip:
+//            [0..3]  row offset in src of points, key points, res1, res2 (64-bit: an NTU-120 split is over 6e8 rows)
+//            [4..7]  their row counts (>= 1; a clip's rows together < 2^31)
+//            [8]     dataset index of the clip = the philox counter word `cid`
+//            [9]     L = sum of the point-cloud rows of the clips before it: the clip's slot in `lists`
+//            [10,11] number of rows of its point cloud whose channel 4 / channel 7 is non-zero (written by the ingest pass)
+//   lists  (2 * sum of point-cloud rows) int32: for the clip at slot L with P point-cloud rows, lists[2L .. 2L + n4) are
+//          the rows with a non-zero channel 4 and lists[2L + P .. 2L + P + n7) those with a non-zero channel 7, in row
+//          order, RELATIVE to the clip's first row.  They depend on the data only: built once at ingest.
+//   err    (2) int32: [0] flags, only ever raised: 1 = a clip without temporal rows, 2 = a selection outside the table;
+//          [1] = the smallest table position with flag 1 (the caller initialises it to INT32_MAX).
+#include "common.h"
+
+namespace {
+
+#include "views_philox_point.inc"
+
+constexpr int REC = FACL_RESIDENT_REC, RC = 8;      // int64 words per table record; channels per pool row
+
+// ingest: one workgroup per table record first + blockIdx.x
+template <typename S>
+__global__ __launch_bounds__(TR_THREADS) void k_resident_temporal_rows(const S* __restrict__ src,
+                                                                       int64_t* __restrict__ table,
+                                                                       int32_t* __restrict__ lists, int first,
+                                                                       int32_t* __restrict__ err) {
+    __shared__ int wtot[2][TR_THREADS / FACL_WAVE];
+    const int pos = first + (int)blockIdx.x;
+    int64_t* rec = table + (int64_t)pos * REC;
+    const int64_t base = rec[0], L = rec[9];
+    const int P = (int)rec[4];
+    int32_t* l4 = lists + 2 * L;
+    int run4 = 0, run7 = 0;
+    for (int c = 0; c < P; c += TR_THREADS)
+        temporal_rows_pass<S, int32_t>(src + base * RC, RC, P, c, 0, l4, l4 + P, run4, run7, wtot);
+    if (threadIdx.x == 0) {
+        rec[10] = run4;
+        rec[11] = run7;
+        if (run4 == 0 || run7 == 0) {
+            atomicOr(err, 1);
+            atomicMin(err + 1, pos);
+        }
+    }
+}
+
+// block = one (clip of the batch, view); thread = one point.  idx_out (B, 10, 512) int64, optional: the pool row of every point.
+template <typename S>
+__global__ __launch_bounds__(NP) void k_build_views_resident(const S* __restrict__ src, const int64_t* __restrict__ table,
+                                                             const int32_t* __restrict__ lists, int n_clips,
+                                                             const int32_t* __restrict__ sel, int B, int64_t seed,
+                                                             int epoch, float* __restrict__ out,
+                                                             int64_t* __restrict__ idx_out, int32_t* __restrict__ err) {
+    const int b = blockIdx.x / NV, v = blockIdx.x % NV, n = threadIdx.x;
+    float* dst = out + (((size_t)v * B + b) * NP + n) * 4;
+    int64_t* io = idx_out ? idx_out + ((size_t)b * NV + v) * NP + n : nullptr;
+    const int pos = sel[b];
+    if (pos < 0 || pos >= n_clips) {                               // not a clip of the pool: no pool memory is touched
+        if (n == 0 && v == 0) atomicOr(err, 2);
+        view_void(dst);
+        if (io) *io = -1;
+        return;
+    }
+    const int64_t* m = table + (int64_t)pos * REC;
+    const ViewDraw q = view_draw(seed, (uint32_t)m[8], epoch);
+    const int src_of = view_source(v);
+    const uint32_t word = view_row_word(q, v, n);
+    int64_t row;
+    if (v == 6 || v == 7) {
+        const int cnt = (int)m[10 + (v - 6)];
+        if (cnt == 0) {                                            // the ingest raised err for this clip: void views
+            view_void(dst);
+            if (io) *io = -1;
+            return;
+        }
+        row = m[0] + lists[2 * m[9] + (v - 6) * m[4] + draw_row(word, cnt)];
+    } else {
+        row = m[src_of] + draw_row(word, (int)m[4 + src_of]);
+    }
+    if (io) *io = row;
+    view_point<S>(src + row * RC, q, v, n, dst);
+}
+
+}  // namespace
+
+template <typename S>
+static int launch_resident_rows(const S* src, int64_t* table, int32_t* lists, int first, int count, int32_t* err,
+                                void* stream) {
+    if (!src || !table || !lists || !err) return FACL_E_NULL;
+    if (first < 0 || count < 1 || (int64_t)first + count > INT32_MAX) return FACL_E_SHAPE;
+    hipLaunchKernelGGL((k_resident_temporal_rows<S>), dim3(count), dim3(TR_THREADS), 0, (hipStream_t)stream, src, table,
+                       lists, first, err);
+    return facl_launch_status();
+}
+
+template <typename S>
+static int launch_views_resident(const S* src, const int64_t* table, const int32_t* lists, int n_clips, const int32_t* sel,
+                                 int B, int64_t seed, int epoch, float* out, int64_t* idx_out, int32_t* err, void* stream) {
+    if (!src || !table || !lists || !sel || !out || !err) return FACL_E_NULL;
+    if (n_clips < 1 || B < 1 || B > (1 << 20)) return FACL_E_SHAPE;
+    if (reinterpret_cast<uintptr_t>(out) % 16) return FACL_E_ALIGN;
+    hipLaunchKernelGGL((k_build_views_resident<S>), dim3(B * NV), dim3(NP), 0, (hipStream_t)stream, src, table, lists,
+                       n_clips, sel, B, seed, epoch, out, idx_out, err);
+    return facl_launch_status();
+}
+
+extern "C" int facl_resident_temporal_rows_f32(const float* src, int64_t* table, int32_t* lists, int first, int count,
+                                               int32_t* err, void* stream) {
+    return launch_resident_rows<float>(src, table, lists, first, count, err, stream);
+}
+
+extern "C" int facl_resident_temporal_rows_f64(const double* src, int64_t* table, int32_t* lists, int first, int count,
+                                               int32_t* err, void* stream) {
+    return launch_resident_rows<double>(src, table, lists, first, count, err, stream);
+}
+
+extern "C" int facl_build_views_resident_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                             const int32_t* sel, int B, int64_t seed, int epoch, float* out,
+                                             int64_t* idx_out, int32_t* err, void* stream) {
+    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, seed, epoch, out, idx_out, err, stream);
+}
+
+extern "C" int facl_build_views_resident_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                             const int32_t* sel, int B, int64_t seed, int epoch, float* out,
+                                             int64_t* idx_out, int32_t* err, void* stream) {
+    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, seed, epoch, out, idx_out, err, stream);
+}

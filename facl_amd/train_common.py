@@ -71,6 +71,13 @@ def build_parser(default_branch):
                    help='NEW (--synthetic 0): cap on the steps of an epoch (len(split) // (batchSize * world)); 0 = no cap')
     p.add_argument('--prefetch', type=int, default=1,
                    help='NEW (--synthetic 0): 1 = load and draw batch i+1 on a producer thread while step i runs')
+    p.add_argument('--resident', type=int, default=0, choices=(0, 1),
+                   help='NEW (--synthetic 0 --view_rng philox): 1 = load the training split ONCE into device memory and build '
+                        'every batch\'s views there by index (facl_amd/resident.py): no file is read and no clip data is copied '
+                        'after the ingest; the views equal --resident 0\'s bit for bit.  Refuses when the split does not fit')
+    p.add_argument('--resident_max_gb', type=float, default=0.0,
+                   help='NEW (--resident 1): bound on the resident pool in GiB; 0 = automatic (free device memory minus the '
+                        'reserve kept for the training step, facl_amd.resident.STEP_RESERVE_BYTES)')
     p.add_argument('--num_crop', type=int, default=10, help='NEW: views per clip (literal 10 at :189)')
     p.add_argument('--steps_per_epoch', type=int, default=8, help='NEW: synthetic iterations per epoch')
     p.add_argument('--group_radius', type=float, default=None,
@@ -402,9 +409,22 @@ def lr_for_epoch(base_lr, epoch, step_size=4, gamma=0.7):
     return base_lr * gamma ** (epoch // step_size)
 
 
+def check_resident_flags(opt):
+    """--resident 1 needs the clips on disk and the counter-based draws; raises before the device is touched."""
+    if not opt.resident:
+        return
+    if opt.synthetic != 0:
+        raise RuntimeError("--resident 1 keeps the 3DV clips of --data_root in device memory: it needs --synthetic 0 "
+                           "(got --synthetic %d, which reads no clip)" % opt.synthetic)
+    if opt.view_rng != 'philox':
+        raise RuntimeError("--resident 1 needs --view_rng philox: --view_rng %s draws every clip's random numbers on the host "
+                           "per batch, which is the per-batch host work that resident clips remove" % opt.view_rng)
+
+
 def run(default_branch, ckpt_pattern, args=None):
     opt = build_parser(default_branch).parse_args(args)
     print(opt)
+    check_resident_flags(opt)
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)
@@ -450,6 +470,15 @@ def run(default_branch, ckpt_pattern, args=None):
         if steps_per_epoch < 1:
             raise RuntimeError("the split has %d clips: fewer than one batch of %d per rank x %d ranks"
                                % (len(split), opt.batchSize, world))
+        resident = None
+        if opt.resident:
+            # every rank holds the whole split: the permutation is over the whole split, a rank's shard changes every epoch
+            from . import resident as fres
+            t_in = time.time()
+            resident = fres.ResidentClips(index, opt.data_root, opt.branch_choose, split, device, max_gb=opt.resident_max_gb)
+            torch.cuda.synchronize()
+            if rank == 0:
+                print('resident: %d clips, %.3f GB, %.2f s' % (resident.n, resident.bytes['total'] / 1e9, time.time() - t_in))
 
     run_step = step
     for epoch in range(0, opt.nepoch):
@@ -459,6 +488,9 @@ def run(default_branch, ckpt_pattern, args=None):
         loss_sigma, t0 = 0.0, time.time()
         if opt.synthetic == 0:
             pos = fds.train_batches(len(split), opt.batchSize, world, rank, opt.manualSeed, epoch)[:steps_per_epoch]
+        if opt.synthetic == 0 and resident is not None:
+            disk = fres.ResidentBatches(resident, [np.asarray(split)[p] for p in pos], seed=2000, epoch=epoch)
+        elif opt.synthetic == 0:
             disk = fds.DiskBatches(index, opt.data_root, opt.branch_choose, [np.asarray(split)[p] for p in pos],
                                    opt.view_rng, device, rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch))
             disk.hold_first = run_step is step and bool(opt.graph) and not (opt.swa_if or opt.cld_if)   # capture on batch 0

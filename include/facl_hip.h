@@ -522,6 +522,34 @@ int facl_build_views_philox_f64(const double* src, int64_t rows, int C, const in
                                 const int32_t* counts, int64_t seed, int epoch, int B, float* out, int32_t* idx_out,
                                 void* stream);
 
+/* ---- the philox views of clips RESIDENT in device memory (--resident 1; csrc/views_resident.hip, facl_amd/resident.py):
+ * the training split is loaded once into a pool and a batch is B table positions.  The views equal
+ * facl_build_views_philox_*'s bit for bit (one shared implementation of the draws and the arithmetic).
+ *   src    (rows_total,8) in the dataset's dtype: the clips back to back, each as points, key points, res1, res2
+ *   table  int64 (n_clips,FACL_RESIDENT_REC): [0..3] row offsets in src of the four clouds, [4..7] their row counts (>= 1, a
+ *          clip's rows together < 2^31), [8] clip id, [9] L = point-cloud rows of all clips before it, [10],[11] number of
+ *          point-cloud rows with a non-zero channel 4 / 7 (written by facl_resident_temporal_rows_*)
+ *   lists  int32 (2 * point-cloud rows of all clips): for a clip with P point-cloud rows, [2L, 2L+n4) = its rows with a
+ *          non-zero channel 4 and [2L+P, 2L+P+n7) = those with a non-zero channel 7, in row order, relative to table[.][0]
+ *   err    int32 (2): [0] flags, only ever raised: 1 a clip without temporal rows, 2 a selection outside [0,n_clips);
+ *          [1] the smallest table position that raised flag 1 (initialise to INT32_MAX)
+ * facl_resident_temporal_rows_*: the ingest pass over table records [first, first+count), once per clip, not per batch.
+ * facl_build_views_resident_*: sel (B) int32 table positions, any order, repeats allowed; out (10*B,512,4) float32
+ * view-major, 16-byte aligned; idx_out int64 (B,10,512) or NULL: the row of src of every point.  A selection outside the
+ * table raises err, reads nothing of the pool and writes zeros (idx_out: -1) for that clip's ten views; so do the temporal
+ * views of a clip whose count is zero.  All row addressing is 64-bit: rows_total has no 2^31 limit. */
+#define FACL_RESIDENT_REC 12
+int facl_resident_temporal_rows_f32(const float* src, int64_t* table, int32_t* lists, int first, int count, int32_t* err,
+                                    void* stream);
+int facl_resident_temporal_rows_f64(const double* src, int64_t* table, int32_t* lists, int first, int count, int32_t* err,
+                                    void* stream);
+int facl_build_views_resident_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                  const int32_t* sel, int B, int64_t seed, int epoch, float* out, int64_t* idx_out,
+                                  int32_t* err, void* stream);
+int facl_build_views_resident_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                  const int32_t* sel, int B, int64_t seed, int epoch, float* out, int64_t* idx_out,
+                                  int32_t* err, void* stream);
+
 /* ---- 3DV generation: depth frames -> motion, key and appearance clouds (generate_data/generate_NTU.py; csrc/gen3dv.hip,
  * whose header describes the stages and the layouts) for a batch of B clips.  int32 unless said otherwise:
  *   frames uint16 (NF,H,W): per clip the first file of its folder, then its chosen frames (at most FACL_GEN3DV_MAX_FRAMES)

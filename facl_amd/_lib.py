@@ -94,10 +94,14 @@ SIGNATURES = {
     "facl_views_temporal_rows_f64": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "facl_build_views_philox_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
     "facl_build_views_philox_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
+    "facl_build_views_philox_gp_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    "facl_build_views_philox_gp_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
     "facl_resident_temporal_rows_f32": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
     "facl_resident_temporal_rows_f64": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
     "facl_build_views_resident_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
     "facl_build_views_resident_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
+    "facl_build_views_resident_gp_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
+    "facl_build_views_resident_gp_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
     "facl_sa_bwd0": [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p],
     "facl_sa_bwd1": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_sa_bwd_w3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p],

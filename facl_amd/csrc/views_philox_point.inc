@@ -5,8 +5,14 @@
 // array; everything a view's VALUES depend on lives here, once, so the two paths cannot drift apart (their views are
 // required to be equal bit for bit).  Include inside an anonymous namespace, after common.h.  The recipe is written out
 // in the header of views_philox.hip and restated in NumPy by facl_amd/philox.py.
+//
+// G views of P points per clip (both run-time arguments): view v is of KIND k = v % 10 (the reference's ten views) in
+// ROUND r = v / 10; every draw slot of round r is the kind's slot + 32 * r, the point index n runs over 0..P-1.
 
-constexpr int NV = 10, NP = 512;          // views, points per view
+constexpr int KINDS = 10;                 // the reference's ten views = the kinds of a round
+constexpr int ROUND_SLOTS = 32;           // counter slots per round (26 in use: rows 0..2, jitter 3..23, angles 24, 25)
+constexpr int CHUNK = 512;                // points per workgroup at most (the reference's cloud: one workgroup per view)
+constexpr int G_MAX = 64, P_MIN = 64, P_MAX = 4096;
 constexpr int TR_THREADS = 256;           // temporal-row compaction: 4 waves, 256 rows per pass
 
 struct u32x4 { uint32_t w[4]; };
@@ -41,23 +47,44 @@ __device__ __forceinline__ ViewDraw view_draw(int64_t seed, uint32_t cid, int ep
     return {(uint32_t)(s & 0xffffffffu), (uint32_t)(s >> 32), cid, (uint32_t)epoch};
 }
 
-// source cloud of each view: points 0,0 | key 1,1 | points 0,0 | temporal lists (of cloud 0) | res1 2 | res2 3
-__device__ __forceinline__ int view_source(int v) { return v < 2 ? 0 : (v < 4 ? 1 : (v < 8 ? 0 : v - 6)); }
+// the domain of (G, P): 1..64 views; 64..4096 points in whole waves (the upper bound is the grouping limit)
+static inline bool views_gp_ok(int G, int P) {
+    return G >= 1 && G <= G_MAX && P >= P_MIN && P <= P_MAX && P % FACL_WAVE == 0;
+}
 
-// the 32-bit word that picks the source row of point n of view v: draw_row(word, count) in [0, count)
-__device__ __forceinline__ uint32_t view_row_word(const ViewDraw& q, int v, int n) {
-    const u32x4 rw = philox4x32_10((uint32_t)n, (uint32_t)(v >> 2), q.cid, q.epoch, q.k0, q.k1);
-    return rw.w[v & 3];
+// launch geometry: workgroups of (clip, view, chunk of up to 512 points), `threads` points each
+struct ViewGrid { int threads, chunks; };
+static inline ViewGrid view_grid(int P) {
+    const int threads = P < CHUNK ? P : CHUNK;
+    return {threads, (P + threads - 1) / threads};
+}
+
+// where a workgroup stands: clip b of the batch, view v = kind k of round `round`, point n (n >= P: nothing to do)
+struct ViewAt { int b, v, k, slot0, n; };
+
+__device__ __forceinline__ ViewAt view_at(int G, int chunks) {
+    const int c = (int)blockIdx.x % chunks, bv = (int)blockIdx.x / chunks;
+    const int v = bv % G;
+    return {bv / G, v, v % KINDS, ROUND_SLOTS * (v / KINDS), c * (int)blockDim.x + (int)threadIdx.x};
+}
+
+// source cloud of each kind: points 0,0 | key 1,1 | points 0,0 | temporal lists (of cloud 0) | res1 2 | res2 3
+__device__ __forceinline__ int view_source(int k) { return k < 2 ? 0 : (k < 4 ? 1 : (k < 8 ? 0 : k - 6)); }
+
+// the 32-bit word that picks the source row of point n of a view of kind k: draw_row(word, count) in [0, count)
+__device__ __forceinline__ uint32_t view_row_word(const ViewDraw& q, int k, int slot0, int n) {
+    const u32x4 rw = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + (k >> 2)), q.cid, q.epoch, q.k0, q.k1);
+    return rw.w[k & 3];
 }
 
 __device__ __forceinline__ void view_void(float* dst) {    // a view that cannot be drawn: zeros
     *reinterpret_cast<float4*>(dst) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// point n of view v from its source row r (>= 8 channels): jitter in fp64 written back in the source dtype, mirror /
-// rotation on float32, channel select; one float4 store to dst
+// point n of a view of kind v (slots from slot0 = 32 * round) from its source row r (>= 8 channels): jitter in fp64
+// written back in the source dtype, mirror / rotation on float32, channel select; one float4 store to dst
 template <typename S>
-__device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDraw& q, int v, int n,
+__device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDraw& q, int v, int slot0, int n,
                                            float* __restrict__ dst) {
     const uint32_t cid = q.cid, epoch = q.epoch, k0 = q.k0, k1 = q.k1;
     const int c3 = v == 6 ? 4 : (v == 7 ? 7 : 3);
@@ -66,7 +93,7 @@ __device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDr
     float o[4];
     o[3] = (float)w;
     auto z = [&](int slot, int d) -> double {                  // standard normal of jitter slot `slot`, coordinate d
-        const u32x4 p = philox4x32_10((uint32_t)n, (uint32_t)(3 + 3 * slot + d), cid, epoch, k0, k1);
+        const u32x4 p = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + 3 + 3 * slot + d), cid, epoch, k0, k1);
         const double u1 = ((double)p.w[0] + 1.0) * 0x1p-32, u2 = (double)p.w[1] * 0x1p-32;
         return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
     };
@@ -86,7 +113,7 @@ __device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDr
         o[0] = (float)x[0]; o[1] = (float)x[1]; o[2] = (float)x[2];
     } else if (v == 4 || v == 5) {                           // jitter, then rotate_trans (:734-749)
         jitter_into_src(v == 4 ? 5 : 6);
-        const u32x4 p = philox4x32_10(0u, (uint32_t)(24 + (v - 4)), cid, epoch, k0, k1);
+        const u32x4 p = philox4x32_10(0u, (uint32_t)(slot0 + 24 + (v - 4)), cid, epoch, k0, k1);
         const double u = ((double)(p.w[0] >> 5) * 67108864.0 + (double)(p.w[1] >> 6)) * 0x1p-53;
         const double angle = (u - 0.5) * 3.141592653589793 * 0.8;
         const double c = cos(angle), s = sin(angle);

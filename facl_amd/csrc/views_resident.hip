@@ -1,7 +1,8 @@
 // The philox views of clips that are RESIDENT in device memory (--resident 1): the whole training split is loaded once
 // into a pool, and a batch is B table positions.  No file is read, nothing is packed and no clip data crosses to the
 // device per step.  The views equal csrc/views_philox.hip's bit for bit: the draw recipe and the per-point arithmetic are
-// the same code (views_philox_point.inc); only the way a drawn position becomes a source row differs.
+// the same code (views_philox_point.inc); only the way a drawn position becomes a source row differs.  G views of P
+// points per clip, by the recipe in the header of views_philox.hip (kind v % 10, round v / 10, slots + 32 * round).
 //
 // Pool (device memory owned by facl_amd/resident.py):
 //   src    (rows_total, 8) in the dataset's one dtype: the clips back to back, each as its four clouds in pack_clips' order
@@ -49,41 +50,44 @@ __global__ __launch_bounds__(TR_THREADS) void k_resident_temporal_rows(const S* 
     }
 }
 
-// block = one (clip of the batch, view); thread = one point.  idx_out (B, 10, 512) int64, optional: the pool row of every point.
+// workgroup = one (clip of the batch, view, chunk of up to 512 points); thread = one point.  idx_out (B, G, P) int64,
+// optional: the pool row of every point.
 template <typename S>
-__global__ __launch_bounds__(NP) void k_build_views_resident(const S* __restrict__ src, const int64_t* __restrict__ table,
-                                                             const int32_t* __restrict__ lists, int n_clips,
-                                                             const int32_t* __restrict__ sel, int B, int64_t seed,
-                                                             int epoch, float* __restrict__ out,
-                                                             int64_t* __restrict__ idx_out, int32_t* __restrict__ err) {
-    const int b = blockIdx.x / NV, v = blockIdx.x % NV, n = threadIdx.x;
-    float* dst = out + (((size_t)v * B + b) * NP + n) * 4;
-    int64_t* io = idx_out ? idx_out + ((size_t)b * NV + v) * NP + n : nullptr;
+__global__ __launch_bounds__(CHUNK) void k_build_views_resident(const S* __restrict__ src, const int64_t* __restrict__ table,
+                                                                const int32_t* __restrict__ lists, int n_clips,
+                                                                const int32_t* __restrict__ sel, int B, int G, int P,
+                                                                int chunks, int64_t seed, int epoch, float* __restrict__ out,
+                                                                int64_t* __restrict__ idx_out, int32_t* __restrict__ err) {
+    const ViewAt at = view_at(G, chunks);
+    const int b = at.b, k = at.k, n = at.n;
+    if (n >= P) return;                                            // the ragged last chunk of a view
+    float* dst = out + (((size_t)at.v * B + b) * P + n) * 4;
+    int64_t* io = idx_out ? idx_out + ((size_t)b * G + at.v) * P + n : nullptr;
     const int pos = sel[b];
     if (pos < 0 || pos >= n_clips) {                               // not a clip of the pool: no pool memory is touched
-        if (n == 0 && v == 0) atomicOr(err, 2);
+        if (n == 0 && at.v == 0) atomicOr(err, 2);
         view_void(dst);
         if (io) *io = -1;
         return;
     }
     const int64_t* m = table + (int64_t)pos * REC;
     const ViewDraw q = view_draw(seed, (uint32_t)m[8], epoch);
-    const int src_of = view_source(v);
-    const uint32_t word = view_row_word(q, v, n);
+    const int src_of = view_source(k);
+    const uint32_t word = view_row_word(q, k, at.slot0, n);
     int64_t row;
-    if (v == 6 || v == 7) {
-        const int cnt = (int)m[10 + (v - 6)];
+    if (k == 6 || k == 7) {
+        const int cnt = (int)m[10 + (k - 6)];
         if (cnt == 0) {                                            // the ingest raised err for this clip: void views
             view_void(dst);
             if (io) *io = -1;
             return;
         }
-        row = m[0] + lists[2 * m[9] + (v - 6) * m[4] + draw_row(word, cnt)];
+        row = m[0] + lists[2 * m[9] + (k - 6) * m[4] + draw_row(word, cnt)];
     } else {
         row = m[src_of] + draw_row(word, (int)m[4 + src_of]);
     }
     if (io) *io = row;
-    view_point<S>(src + row * RC, q, v, n, dst);
+    view_point<S>(src + row * RC, q, k, at.slot0, n, dst);
 }
 
 }  // namespace
@@ -100,12 +104,14 @@ static int launch_resident_rows(const S* src, int64_t* table, int32_t* lists, in
 
 template <typename S>
 static int launch_views_resident(const S* src, const int64_t* table, const int32_t* lists, int n_clips, const int32_t* sel,
-                                 int B, int64_t seed, int epoch, float* out, int64_t* idx_out, int32_t* err, void* stream) {
+                                 int B, int G, int P, int64_t seed, int epoch, float* out, int64_t* idx_out, int32_t* err,
+                                 void* stream) {
     if (!src || !table || !lists || !sel || !out || !err) return FACL_E_NULL;
-    if (n_clips < 1 || B < 1 || B > (1 << 20)) return FACL_E_SHAPE;
+    if (n_clips < 1 || B < 1 || B > (1 << 20) || !views_gp_ok(G, P)) return FACL_E_SHAPE;
     if (reinterpret_cast<uintptr_t>(out) % 16) return FACL_E_ALIGN;
-    hipLaunchKernelGGL((k_build_views_resident<S>), dim3(B * NV), dim3(NP), 0, (hipStream_t)stream, src, table, lists,
-                       n_clips, sel, B, seed, epoch, out, idx_out, err);
+    const ViewGrid g = view_grid(P);
+    hipLaunchKernelGGL((k_build_views_resident<S>), dim3((unsigned)B * G * g.chunks), dim3(g.threads), 0, (hipStream_t)stream,
+                       src, table, lists, n_clips, sel, B, G, P, g.chunks, seed, epoch, out, idx_out, err);
     return facl_launch_status();
 }
 
@@ -122,11 +128,23 @@ extern "C" int facl_resident_temporal_rows_f64(const double* src, int64_t* table
 extern "C" int facl_build_views_resident_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
                                              const int32_t* sel, int B, int64_t seed, int epoch, float* out,
                                              int64_t* idx_out, int32_t* err, void* stream) {
-    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, seed, epoch, out, idx_out, err, stream);
+    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, KINDS, CHUNK, seed, epoch, out, idx_out, err, stream);
 }
 
 extern "C" int facl_build_views_resident_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
                                              const int32_t* sel, int B, int64_t seed, int epoch, float* out,
                                              int64_t* idx_out, int32_t* err, void* stream) {
-    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, seed, epoch, out, idx_out, err, stream);
+    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, KINDS, CHUNK, seed, epoch, out, idx_out, err, stream);
+}
+
+extern "C" int facl_build_views_resident_gp_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                                const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                                int64_t* idx_out, int32_t* err, void* stream) {
+    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, stream);
+}
+
+extern "C" int facl_build_views_resident_gp_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                                const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                                int64_t* idx_out, int32_t* err, void* stream) {
+    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, stream);
 }

@@ -173,11 +173,19 @@ class DiskBatches:
     loading would; 'philox': counter-based draws on the device keyed by (seed, epoch, dataset index).  With `prefetch` a
     producer thread loads and draws batch i+1 (np.load, host draws, packing into pinned staging, H2D on a side stream)
     while batch i is consumed; an event orders the copy before the views launch on the compute stream.  Iterating yields
-    ((10*B, 512, 4) float32 views, v_names, labels)."""
+    ((G*B, P, 4) float32 views, v_names, labels); G = `num_crop` views of P = `num_point` points: 10 x 512, the
+    reference's loader, or with 'philox' any size of the kernels' domain (facl_amd/philox.py)."""
 
-    def __init__(self, index, data_root, branch, vids, mode, device, rng=None, seed=0, epoch=0, prefetch=True):
+    def __init__(self, index, data_root, branch, vids, mode, device, rng=None, seed=0, epoch=0, prefetch=True,
+                 num_crop=V.NUM_CROP, num_point=V.NUM_POINT):
         if mode not in ('numpy', 'philox'):
             raise ValueError("disk batches draw with --view_rng numpy or philox")
+        if mode == 'philox':
+            V.check_view_size(num_crop, num_point)
+        elif (num_crop, num_point) != (V.NUM_CROP, V.NUM_POINT):
+            raise ValueError("the reference's NumPy stream defines %d views of %d points only; other sizes need "
+                             "--view_rng philox" % (V.NUM_CROP, V.NUM_POINT))
+        self.num_crop, self.num_point = int(num_crop), int(num_point)
         self.index, self.root, self.branch, self.vids = index, data_root, branch, list(vids)
         self.mode, self.dev, self.rng, self.seed, self.epoch = mode, torch.device(device), rng, seed, epoch
         self.prefetch = prefetch
@@ -226,7 +234,8 @@ class DiskBatches:
         d = s.dev
         B = len(s.names)
         if self.mode == 'philox':
-            return V.build_views_philox(d['src'], d['meta'], s.dt, self.seed, self.epoch)
+            return V.build_views_philox(d['src'], d['meta'], s.dt, self.seed, self.epoch, num_crop=self.num_crop,
+                                        num_point=self.num_point)
         from . import _lib
         lib = _lib.load_library()
         out = _lib.empty((V.NUM_CROP * B, V.NUM_POINT, 4), dtype=torch.float32, device=self.dev)

@@ -66,14 +66,11 @@ def run(default_branch, default_ckpt, args=None):
 def run_disk(netR, opt, device):
     """--synthetic 0: extract_motion_feature.py:112-214 -- the train split, then the test split, of the clips listed in
     <data_root>/raw, in order (shuffle=False, drop_last=False: the last batch is ragged); one <v_name>.npy per clip.
-    Returns the (clips, (num_crop+1)*512) features in that order."""
+    Returns the (clips, (num_crop+1)*512) features in that order.  With --view_rng philox any --num_crop / --SAMPLE_NUM of
+    the view kernels' domain (a vector is (num_crop+1)*512 long whatever SAMPLE_NUM is)."""
     from . import dataset as fds
-    from .views import NUM_CROP
-    if (opt.num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM) != (NUM_CROP, 512, 4):
-        raise RuntimeError("--synthetic 0 builds the reference's 10 views of 512 points x 4 channels: "
-                           "use --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
-    if opt.view_rng == 'device':
-        raise RuntimeError("--synthetic 0 draws with --view_rng numpy or philox")
+    from .train_common import check_view_flags
+    check_view_flags(opt)
     index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
     rng = np.random.RandomState(2000)
     feats = []
@@ -81,9 +78,10 @@ def run_disk(netR, opt, device):
         for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
             vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
             for views, names, _ in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
-                                                   rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch)):
+                                                   rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch),
+                                                   num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM):
                 B = len(names)
-                clip_major = views.view(opt.num_crop, B, 512, 4).permute(1, 0, 2, 3)
+                clip_major = views.view(opt.num_crop, B, opt.SAMPLE_NUM, 4).permute(1, 0, 2, 3)
                 f = extract_batch(netR, clip_major, opt, opt.group_radius).cpu().numpy()
                 feats.append(f)
                 if opt.save_path:

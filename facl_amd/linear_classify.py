@@ -36,7 +36,9 @@ def accuracy(output, target, topk=(1,)):
 
 
 def fit(features, labels, num_class=120, nepoch=20, batch=256, lr=1e-3, shuffle=None, on_epoch=None):
-    """Train the probe on (n, 11264) float32 CUDA features; returns (model, last-epoch train top-1).  `shuffle`: a
+    """Train the probe on (n, 11264) float32 CUDA features; returns (model, last-epoch train top-1).  The layer is sized
+    from the feature length (any multiple of 512), so features extracted at another --num_crop G -- (G+1)*512 per stream,
+    e.g. 25*512 at G = 24 -- are accepted as they are.  `shuffle`: a
     np.random.RandomState -> every epoch runs over a fresh permutation in full batches only (the reference's loader,
     shuffle=True, drop_last=True); `on_epoch(epoch, model)` is called after every epoch."""
     netR = Final_FC(input_dim=512, gost=features.shape[1] // 512, num_class=num_class).to(features.device)

@@ -30,6 +30,16 @@ INT32_MAX = (1 << 31) - 1
 # buffers; the same in every round).  The reserve is twice that.
 STEP_PEAK_BYTES = 1195342848
 STEP_RESERVE_BYTES = 2 * STEP_PEAK_BYTES
+STEP_PEAK_AT = (32, 10, 512)   # the (B, G, P) of that measurement
+
+
+def step_reserve_bytes(B, G=V.NUM_CROP, P=V.NUM_POINT):
+    """The reserve for a step of B clips x G views x P points: STEP_RESERVE_BYTES scaled by the step's points over the
+    measured step's, never below it.  An upper estimate by construction -- most of the step's memory (the grouped rows and
+    the encoder's activations) grows with B * G and not with P -- so the automatic budget errs towards refusing;
+    --resident_max_gb overrides it."""
+    b0, g0, p0 = STEP_PEAK_AT
+    return max(STEP_RESERVE_BYTES, -(-STEP_RESERVE_BYTES * int(B) * int(G) * int(P) // (b0 * g0 * p0)))
 
 
 # ---- header pass and table: pure NumPy ---------------------------------------------------------------------------------------
@@ -127,8 +137,9 @@ def check_budget(need, free, max_gb=0.0, reserve=STEP_RESERVE_BYTES):
         return
     if need > free - reserve:
         raise RuntimeError("--resident 1: the split needs %d bytes (%.3f GiB) of device memory, but %d bytes (%.3f GiB) "
-                           "are free and %d bytes (%.3f GiB) stay reserved for the training step; nothing falls back to "
-                           "batches from disk: train with --resident 0"
+                           "are free and %d bytes (%.3f GiB) stay reserved for the training step (twice the measured peak of "
+                           "a 32 x 10 x 512 step, scaled by this step's clips x views x points); nothing falls back to "
+                           "batches from disk: train with --resident 0 or set --resident_max_gb"
                            % (need, need / gib, free, free / gib, reserve, reserve / gib))
 
 
@@ -247,34 +258,39 @@ class ResidentClips:
         return int(self.err[0].item())
 
 
-def build_views_resident(res, sel, seed, epoch, return_idx=False):
-    """The (10*B, 512, 4) float32 views of the clips at table positions `sel` (device (B,) int32), one launch on the current
-    stream.  With return_idx also the (B, 10, 512) int64 pool rows.  A position outside the table raises the pool's error
-    word and yields zeros for that clip."""
+def build_views_resident(res, sel, seed, epoch, return_idx=False, num_crop=V.NUM_CROP, num_point=V.NUM_POINT):
+    """The (G*B, P, 4) float32 views (G = num_crop views of P = num_point points, facl_amd/philox.py's recipe) of the clips
+    at table positions `sel` (device (B,) int32), one launch on the current stream.  With return_idx also the (B, G, P) int64
+    pool rows.  A position outside the table raises the pool's error word and yields zeros for that clip."""
     import torch
     from . import _lib
+    V.check_view_size(num_crop, num_point)
+    G, P = int(num_crop), int(num_point)
     lib = _lib.load_library()
     B = sel.shape[0]
     if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous():
         raise TypeError("sel must be a contiguous (B,) int32 tensor")
     _lib.require_cuda(sel, res.src)
-    out = _lib.empty((V.NUM_CROP * B, V.NUM_POINT, 4), dtype=torch.float32, device=res.dev)
-    idx = _lib.empty((B, V.NUM_CROP, V.NUM_POINT), dtype=torch.int64, device=res.dev) if return_idx else None
-    fn = lib.facl_build_views_resident_f64 if res.dtype == np.float64 else lib.facl_build_views_resident_f32
+    out = _lib.empty((G * B, P, 4), dtype=torch.float32, device=res.dev)
+    idx = _lib.empty((B, G, P), dtype=torch.int64, device=res.dev) if return_idx else None
+    fn = lib.facl_build_views_resident_gp_f64 if res.dtype == np.float64 else lib.facl_build_views_resident_gp_f32
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.check(fn(_lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B,
+    _lib.check(fn(_lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B, G, P,
                   seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), _lib.ptr(out), _lib.ptr(idx),
-                  _lib.ptr(res.err), _lib.stream()), "facl_build_views_resident")
+                  _lib.ptr(res.err), _lib.stream()), "facl_build_views_resident_gp")
     return (out, idx) if return_idx else out
 
 
 class ResidentBatches:
     """What `DiskBatches(index, ..., vids, 'philox', device, seed=seed, epoch=epoch)` yields, from the resident pool:
-    ((10*B, 512, 4) float32 views, v_names, labels) per entry of `vids` (a list of (B_i,) arrays of dataset indices).  Per
-    batch: one (B,) int32 copy out of a reused pinned buffer and one launch, both on the current stream; no thread."""
+    ((G*B, P, 4) float32 views, v_names, labels) per entry of `vids` (a list of (B_i,) arrays of dataset indices); G =
+    `num_crop`, P = `num_point`, any size of the kernels' domain.  Per batch: one (B,) int32 copy out of a reused pinned
+    buffer and one launch, both on the current stream; no thread."""
 
-    def __init__(self, resident, vids, seed=0, epoch=0):
+    def __init__(self, resident, vids, seed=0, epoch=0, num_crop=V.NUM_CROP, num_point=V.NUM_POINT):
         import torch
+        V.check_view_size(num_crop, num_point)
+        self.num_crop, self.num_point = int(num_crop), int(num_point)
         self.res, self.seed, self.epoch = resident, seed, epoch
         self.vids = [np.asarray(v).reshape(-1) for v in vids]
         bmax = max([len(v) for v in self.vids] + [1])
@@ -302,7 +318,7 @@ class ResidentBatches:
             sel.copy_(self._pin[:B], non_blocking=True)
             self._copied = torch.cuda.Event()
             self._copied.record()
-            views = build_views_resident(res, sel, self.seed, self.epoch)
+            views = build_views_resident(res, sel, self.seed, self.epoch, num_crop=self.num_crop, num_point=self.num_point)
         names = [res.index.v_name(int(v)) for v in vids]
         labels = [res.index.label(int(v)) for v in vids]
         return views, names, labels

@@ -56,11 +56,13 @@ def build_parser(default_branch):
     p.add_argument('--synthetic', type=int, default=1,
                    help='NEW: 0 = the 3DV clips on disk under --data_root (facl_amd/dataset.py); 1 = iid U[-0.5,0.5) clouds (no NTU data here); 2 = synthetic RAW clips (the four (rows, 8) clouds the '
                         'loader reads per video) through the GPU view construction (facl_amd.views.build_views = the dataset '
-                        "class's get_data_train, cn3D_data_set.py:285-350): needs --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
+                        "class's get_data_train, cn3D_data_set.py:285-350).  0 and 2 need --INPUT_FEATURE_NUM 4 and --num_crop 10 --SAMPLE_NUM 512, "
+                        'the reference\'s loader; with --view_rng philox any --num_crop 1..64 and --SAMPLE_NUM 64..4096 (multiples of 64)')
     p.add_argument('--view_rng', type=str, default='numpy', choices=('numpy', 'device', 'philox'),
                    help='NEW (--synthetic 0 / 2): numpy = draw the view construction\'s random numbers on the host in the reference\'s '
                         'NumPy order; device = draw them on the GPU (same distributions, another stream; --synthetic 2 only); '
-                        'philox = counter-based draws on the GPU keyed by (seed, epoch, dataset index of the clip)')
+                        'philox = counter-based draws on the GPU keyed by (seed, epoch, dataset index of the clip); the only stream '
+                        'with views beyond 10 x 512 (view v = kind v %% 10 in round v // 10: facl_amd/philox.py)')
     p.add_argument('--data_root', type=str, default='../ntu/3DV_ntu60',
                    help='NEW (--synthetic 0): the dataset root, the literal prefix ../ntu/3DV_ntu60 of the reference\'s paths')
     p.add_argument('--split', type=str, default='view', choices=('view', 'subject', 'set'),
@@ -409,6 +411,29 @@ def lr_for_epoch(base_lr, epoch, step_size=4, gamma=0.7):
     return base_lr * gamma ** (epoch // step_size)
 
 
+def check_view_flags(opt):
+    """--synthetic 0 / 2 build views from clips: 4 channels; 10 views of 512 points on the reference's streams, any size of
+    the kernels' domain on the counter-based one.  Raises before the device is touched."""
+    if opt.synthetic not in (0, 2):
+        return
+    what = "--synthetic %d" % opt.synthetic
+    if opt.synthetic == 0 and opt.view_rng == 'device':
+        raise RuntimeError("--synthetic 0 draws with --view_rng numpy or philox")
+    if opt.INPUT_FEATURE_NUM != 4:
+        raise RuntimeError("%s builds views of 4 channels: use --INPUT_FEATURE_NUM 4" % what)
+    if opt.view_rng == 'philox':
+        from .views import check_view_size
+        try:
+            check_view_size(opt.num_crop, opt.SAMPLE_NUM)
+        except ValueError as e:
+            raise RuntimeError("%s --view_rng philox: --num_crop 1..64 and --SAMPLE_NUM 64..4096 in multiples of 64 (%s)"
+                               % (what, e)) from None
+    elif (opt.num_crop, opt.SAMPLE_NUM) != (10, 512):
+        raise RuntimeError("%s --view_rng %s: the reference's stream defines 10 views of 512 points only (its loader draws a "
+                           "literal 512, cn3D_data_set.py:24): use --num_crop 10 --SAMPLE_NUM 512, or --view_rng philox, "
+                           "whose counter-based recipe covers other sizes" % (what, opt.view_rng))
+
+
 def check_resident_flags(opt):
     """--resident 1 needs the clips on disk and the counter-based draws; raises before the device is touched."""
     if not opt.resident:
@@ -425,6 +450,7 @@ def run(default_branch, ckpt_pattern, args=None):
     opt = build_parser(default_branch).parse_args(args)
     print(opt)
     check_resident_flags(opt)
+    check_view_flags(opt)
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)
@@ -456,11 +482,6 @@ def run(default_branch, ckpt_pattern, args=None):
     if opt.synthetic == 0:
         # the reference's loader (cn3d_train_*_GL.py:161-172): NTU_RGBD_new over the listed folder, shuffle + drop_last
         from . import dataset as fds
-        if (num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM) != (10, 512, 4):
-            raise RuntimeError("--synthetic 0 builds the reference's 10 views of 512 points x 4 channels: "
-                               "use --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
-        if opt.view_rng == 'device':
-            raise RuntimeError("--synthetic 0 draws with --view_rng numpy or philox")
         index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.TRAIN_LIST_DIR[opt.branch_choose]), opt.dataset)
         fds.check_same_index_on_all_ranks(index, device)
         split = index.select(opt.split, full_train=bool(opt.full_train))
@@ -475,7 +496,8 @@ def run(default_branch, ckpt_pattern, args=None):
             # every rank holds the whole split: the permutation is over the whole split, a rank's shard changes every epoch
             from . import resident as fres
             t_in = time.time()
-            resident = fres.ResidentClips(index, opt.data_root, opt.branch_choose, split, device, max_gb=opt.resident_max_gb)
+            resident = fres.ResidentClips(index, opt.data_root, opt.branch_choose, split, device, max_gb=opt.resident_max_gb,
+                                          reserve=fres.step_reserve_bytes(opt.batchSize, num_crop, opt.SAMPLE_NUM))
             torch.cuda.synchronize()
             if rank == 0:
                 print('resident: %d clips, %.3f GB, %.2f s' % (resident.n, resident.bytes['total'] / 1e9, time.time() - t_in))
@@ -489,21 +511,20 @@ def run(default_branch, ckpt_pattern, args=None):
         if opt.synthetic == 0:
             pos = fds.train_batches(len(split), opt.batchSize, world, rank, opt.manualSeed, epoch)[:steps_per_epoch]
         if opt.synthetic == 0 and resident is not None:
-            disk = fres.ResidentBatches(resident, [np.asarray(split)[p] for p in pos], seed=2000, epoch=epoch)
+            disk = fres.ResidentBatches(resident, [np.asarray(split)[p] for p in pos], seed=2000, epoch=epoch,
+                                        num_crop=num_crop, num_point=opt.SAMPLE_NUM)
         elif opt.synthetic == 0:
             disk = fds.DiskBatches(index, opt.data_root, opt.branch_choose, [np.asarray(split)[p] for p in pos],
-                                   opt.view_rng, device, rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch))
+                                   opt.view_rng, device, rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch),
+                                   num_crop=num_crop, num_point=opt.SAMPLE_NUM)
             disk.hold_first = run_step is step and bool(opt.graph) and not (opt.swa_if or opt.cld_if)   # capture on batch 0
             disk = iter(disk)
         for i in range(steps_per_epoch):
             if opt.synthetic == 0:
-                out_points = next(disk)[0]                # (10*B, 512, 4) view-major views of the next batch
+                out_points = next(disk)[0]                # (G*B, N, 4) view-major views of the next batch
             elif opt.synthetic == 2:
-                # the loop body from the loader's output on (:224-228): raw clips -> the 10 augmented views of every clip,
+                # the loop body from the loader's output on (:224-228): raw clips -> the augmented views of every clip,
                 # built on the GPU in one launch, view-major float32 (facl_amd/views.py; draws in the reference's NumPy order)
-                if (num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM) != (10, 512, 4):
-                    raise RuntimeError("--synthetic 2 builds the reference's 10 views of 512 points x 4 channels: "
-                                       "use --num_crop 10 --SAMPLE_NUM 512 --INPUT_FEATURE_NUM 4")
                 from .views import build_views, synthetic_raw_clip
                 base = ((epoch * opt.steps_per_epoch + i) * world + rank) * opt.batchSize
                 clips = [synthetic_raw_clip(base + b) for b in range(opt.batchSize)]
@@ -511,7 +532,7 @@ def run(default_branch, ckpt_pattern, args=None):
                 # device: the same distributions drawn by a torch generator on the GPU (no per-clip host work)
                 out_points = build_views(clips, view_rng, device, device_rng=gen if opt.view_rng == "device" else None,
                                          philox=(2000, epoch, [base + b for b in range(opt.batchSize)])
-                                         if opt.view_rng == "philox" else None)
+                                         if opt.view_rng == "philox" else None, num_crop=num_crop, num_point=opt.SAMPLE_NUM)
             elif opt.synthetic == 1:
                 out_points = synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
             else:

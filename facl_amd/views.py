@@ -77,18 +77,32 @@ def _device_draws(clips, bases, gen, dev):
     return idx.to(torch.int32).contiguous(), noise, cs.contiguous()
 
 
-def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None):
+def check_view_size(num_crop, num_point):
+    """The domain of the philox kernels (include/facl_hip.h): 1..64 views; 64..4096 points in multiples of 64."""
+    if not (1 <= int(num_crop) <= 64) or not (64 <= int(num_point) <= 4096) or int(num_point) % 64:
+        raise ValueError("philox views: 1 <= num_crop <= 64 and 64 <= num_point <= 4096 in multiples of 64 (got %r, %r)"
+                         % (num_crop, num_point))
+
+
+def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None, num_crop=NUM_CROP, num_point=NUM_POINT):
     """clips: list of (points (P,>=8), key_points, res_points_1, res_points_2) NumPy arrays of one dtype (float32 or
     float64), the arrays `__getitem__` loads for a video.  Returns the (10*B, 512, 4) float32 CUDA tensor = the
     reference's `data1` (view-major rows g*B+b).  `rng`: np.random.RandomState (default: NumPy's global generator,
     like the reference): every draw happens on the host in the reference's order, a seed reproduces its views.
     `device_rng` (a torch.Generator on the device): draw on the device instead -- same distributions, another stream,
     no per-clip host work.  `philox` = (seed, epoch, clip_ids): counter-based draws on the device (csrc/views_philox.hip):
-    a clip's views depend on (seed, epoch, its dataset index clip_ids[b]) only."""
+    a clip's views depend on (seed, epoch, its dataset index clip_ids[b]) only.  `num_crop`, `num_point`: with `philox`
+    any (G, P) of the kernels' domain -> (G*B, P, 4) (the recipe is in facl_amd/philox.py); the other two streams are the
+    reference's and know 10 x 512 only."""
     if philox is not None:
+        check_view_size(num_crop, num_point)
         src, meta, dt = pack_clips(clips, philox[2])
         dev = torch.device(device)
-        return build_views_philox(torch.from_numpy(src).to(dev), torch.from_numpy(meta).to(dev), dt, philox[0], philox[1])
+        return build_views_philox(torch.from_numpy(src).to(dev), torch.from_numpy(meta).to(dev), dt, philox[0], philox[1],
+                                  num_crop=num_crop, num_point=num_point)
+    if (num_crop, num_point) != (NUM_CROP, NUM_POINT):
+        raise ValueError("the reference's stream defines %d views of %d points only; other sizes need the counter-based "
+                         "draws (philox)" % (NUM_CROP, NUM_POINT))
     rng = np.random if rng is None else rng
     lib = _lib.load_library()
     B = len(clips)
@@ -162,28 +176,31 @@ def pack_clips(clips, clip_ids, out=None):
     return src, meta, dt
 
 
-def build_views_philox(src, meta, dt, seed, epoch, return_idx=False):
+def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NUM_CROP, num_point=NUM_POINT):
     """Device half of the philox mode: src (rows, 8) and meta (B, 9) int32 on the device (pack_clips' layout, temporal
     rows already checked).  Two launches on the current stream: the temporal-row compaction, then the views.
-    Returns the (10*B, 512, 4) float32 views (and, with return_idx, the (B, 10, 512) source rows and the error word)."""
+    Returns the (G*B, P, 4) float32 views of G = num_crop views of P = num_point points (and, with return_idx, the
+    (B, G, P) source rows and the error word)."""
+    check_view_size(num_crop, num_point)
+    G, P = int(num_crop), int(num_point)
     lib = _lib.load_library()
     dev = src.device
     B, rows = meta.shape[0], src.shape[0]
     lists = _lib.empty((2, rows), dtype=torch.int32, device=dev)
     counts = _lib.empty((B, 2), dtype=torch.int32, device=dev)
     err = torch.zeros((1,), dtype=torch.int32, device=dev)
-    out = _lib.empty((NUM_CROP * B, NUM_POINT, 4), dtype=torch.float32, device=dev)
-    idx = _lib.empty((B, NUM_CROP, NUM_POINT), dtype=torch.int32, device=dev) if return_idx else None
+    out = _lib.empty((G * B, P, 4), dtype=torch.float32, device=dev)
+    idx = _lib.empty((B, G, P), dtype=torch.int32, device=dev) if return_idx else None
     _lib.require_cuda(out)
     f64 = dt == np.float64
     rt = lib.facl_views_temporal_rows_f64 if f64 else lib.facl_views_temporal_rows_f32
     _lib.check(rt(_lib.ptr(src), rows, 8, _lib.ptr(meta), B, _lib.ptr(lists), _lib.ptr(counts), _lib.ptr(err),
                   _lib.stream()), "facl_views_temporal_rows")
-    fn = lib.facl_build_views_philox_f64 if f64 else lib.facl_build_views_philox_f32
+    fn = lib.facl_build_views_philox_gp_f64 if f64 else lib.facl_build_views_philox_gp_f32
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     _lib.check(fn(_lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts),
-                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), B, _lib.ptr(out), _lib.ptr(idx), _lib.stream()),
-               "facl_build_views_philox")
+                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), B, G, P, _lib.ptr(out), _lib.ptr(idx),
+                  _lib.stream()), "facl_build_views_philox_gp")
     return (out, idx, err) if return_idx else out
 
 

@@ -521,6 +521,21 @@ int facl_build_views_philox_f32(const float* src, int64_t rows, int C, const int
 int facl_build_views_philox_f64(const double* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
                                 const int32_t* counts, int64_t seed, int epoch, int B, float* out, int32_t* idx_out,
                                 void* stream);
+/* facl_build_views_philox_gp_*: G views of P points per clip (the reference has no recipe beyond 10 x 512; an extension of
+ * this stream only).  View v is of kind k = v % 10 (the ten views above) in round r = v / 10 and draws exactly as kind k
+ * does with every counter slot moved by 32*r (a round uses slots 0..25: rows 0..2, jitter 3..23, angles 24, 25); its row
+ * word is word k & 3 of slot (k >> 2) + 32*r; the point index n runs over 0..P-1 in counter word 0.  A view's values do
+ * not depend on G and its first P' points do not depend on P: the block [v < 10, n < 512] of any (G, P) is
+ * facl_build_views_philox_*'s output bit for bit, and that entry IS this one at G = 10, P = 512 (one kernel).
+ * Domain: 1 <= G <= 64; 64 <= P <= 4096 with P % 64 == 0 (the grouping limit); otherwise FACL_E_SHAPE and no launch.
+ * out (G*B,P,4) float32 view-major (row v*B+b), 16-byte aligned; idx_out (B,G,P) int32 or NULL; void views (zeros,
+ * idx_out -1) for the temporal kinds of EVERY round of a clip with a zero count. */
+int facl_build_views_philox_gp_f32(const float* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
+                                   const int32_t* counts, int64_t seed, int epoch, int B, int G, int P, float* out,
+                                   int32_t* idx_out, void* stream);
+int facl_build_views_philox_gp_f64(const double* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
+                                   const int32_t* counts, int64_t seed, int epoch, int B, int G, int P, float* out,
+                                   int32_t* idx_out, void* stream);
 
 /* ---- the philox views of clips RESIDENT in device memory (--resident 1; csrc/views_resident.hip, facl_amd/resident.py):
  * the training split is loaded once into a pool and a batch is B table positions.  The views equal
@@ -549,6 +564,17 @@ int facl_build_views_resident_f32(const float* src, const int64_t* table, const 
 int facl_build_views_resident_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
                                   const int32_t* sel, int B, int64_t seed, int epoch, float* out, int64_t* idx_out,
                                   int32_t* err, void* stream);
+/* facl_build_views_resident_gp_*: G views of P points per clip out of the pool, by facl_build_views_philox_gp_*'s recipe
+ * (kind v % 10, round v / 10, slots + 32*round, n in 0..P-1) and equal to its output bit for bit.  Same domain: 1 <= G <= 64;
+ * 64 <= P <= 4096 with P % 64 == 0; otherwise FACL_E_SHAPE and no launch.  out (G*B,P,4) float32 view-major, 16-byte
+ * aligned; idx_out int64 (B,G,P) or NULL.  A selection outside the table voids all G views of that clip, a zero temporal
+ * count the temporal kinds of every round.  facl_build_views_resident_* is this entry at G = 10, P = 512 (one kernel). */
+int facl_build_views_resident_gp_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                     const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                     int64_t* idx_out, int32_t* err, void* stream);
+int facl_build_views_resident_gp_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                     const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                     int64_t* idx_out, int32_t* err, void* stream);
 
 /* ---- 3DV generation: depth frames -> motion, key and appearance clouds (generate_data/generate_NTU.py; csrc/gen3dv.hip,
  * whose header describes the stages and the layouts) for a batch of B clips.  int32 unless said otherwise:

@@ -136,8 +136,11 @@ SIGNATURES = {
     "facl_gen3dv_sample": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_gen3dv_app": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_l, c_p, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_i, c_l, c_d,
                         c_p, c_p, c_p, c_p, c_p],
+    "facl_knn_ws_bytes": [c_i, c_i, c_i],
+    "facl_knn_topk": [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "facl_knn_vote": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p],
 }
-RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes"}
+RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes"}
 
 
 def lib_path():

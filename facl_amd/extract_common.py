@@ -63,6 +63,30 @@ def run(default_branch, default_ckpt, args=None):
     return np.concatenate(feats)
 
 
+def extract_split(netR, opt, device, index, split, rng, save_path=''):
+    """One split of `run_disk`: the clips `split` (dataset indices) in order, batches of --batchSize with the last one ragged,
+    views drawn from `rng` (--view_rng numpy) or keyed by (2000, 0, dataset index) (philox).  Returns the
+    (clips, (num_crop+1)*512) float32 features as a DEVICE tensor; with `save_path` every clip is also written to
+    <save_path>/<v_name>.npy as its batch completes.  The caller holds torch.no_grad() and has put `netR` in eval()."""
+    from . import dataset as fds
+    vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
+    feats = []
+    for views, names, _ in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
+                                           rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch),
+                                           num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM):
+        B = len(names)
+        clip_major = views.view(opt.num_crop, B, opt.SAMPLE_NUM, 4).permute(1, 0, 2, 3)
+        f = extract_batch(netR, clip_major, opt, opt.group_radius)
+        feats.append(f)
+        if save_path:
+            fh = f.cpu().numpy()
+            for b, n in enumerate(names):
+                np.save(os.path.join(save_path, n + '.npy'), fh[b])
+    if not feats:
+        return torch.zeros((0, (opt.num_crop + 1) * 512), dtype=torch.float32, device=device)
+    return torch.cat(feats)
+
+
 def run_disk(netR, opt, device):
     """--synthetic 0: extract_motion_feature.py:112-214 -- the train split, then the test split, of the clips listed in
     <data_root>/raw, in order (shuffle=False, drop_last=False: the last batch is ragged); one <v_name>.npy per clip.
@@ -76,15 +100,6 @@ def run_disk(netR, opt, device):
     feats = []
     with torch.no_grad():
         for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
-            vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
-            for views, names, _ in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
-                                                   rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch),
-                                                   num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM):
-                B = len(names)
-                clip_major = views.view(opt.num_crop, B, opt.SAMPLE_NUM, 4).permute(1, 0, 2, 3)
-                f = extract_batch(netR, clip_major, opt, opt.group_radius).cpu().numpy()
-                feats.append(f)
-                if opt.save_path:
-                    for b, n in enumerate(names):
-                        np.save(os.path.join(opt.save_path, n + '.npy'), f[b])
+            if len(split):
+                feats.append(extract_split(netR, opt, device, index, split, rng, opt.save_path).cpu().numpy())
     return np.concatenate(feats) if feats else np.zeros((0, (opt.num_crop + 1) * 512), np.float32)

@@ -81,13 +81,16 @@ def evaluate(netR, features, labels, batch=256):
     return 100.0 * hit / max(features.shape[0], 1)
 
 
-def load_split(index, vids, motion_dir, appearance_dir):
-    """dataset_of_lin.py:37-110 LIner_NTU: per clip motion || appearance features from <dir>/<v_name>.npy, label from the name."""
+def load_split(index, vids, motion_dir, appearance_dir=None):
+    """dataset_of_lin.py:37-110 LIner_NTU: per clip motion || appearance features from <dir>/<v_name>.npy, label from the name.
+    One stream alone (either directory None) gives that stream's features as they are."""
+    dirs = [d for d in (motion_dir, appearance_dir) if d]
+    if not dirs:
+        raise ValueError("load_split needs a motion or an appearance feature directory")
     feats, labels = [], []
     for v in vids:
         n = index.v_name(v)
-        feats.append(np.concatenate((np.load(os.path.join(motion_dir, n + '.npy')),
-                                     np.load(os.path.join(appearance_dir, n + '.npy'))), 0))
+        feats.append(np.concatenate([np.load(os.path.join(d, n + '.npy')) for d in dirs], 0))
         labels.append(index.label(v))
     return np.stack(feats).astype(np.float32), np.asarray(labels, dtype=np.int64)
 

@@ -96,6 +96,11 @@ def build_parser(default_branch):
     p.add_argument('--fps_reorder', type=int, default=0,
                    help='NEW: 1 = FPS-reorder every view on the GPU before grouping (cn3D_data_set.py:665-672; the '
                         'reference assumes FPS-ordered clouds but its live loader never calls it)')
+    p.add_argument('--knn_every', type=int, default=0,
+                   help='NEW (--synthetic 0, one rank): after every E-th epoch extract the train and test splits in memory and '
+                        'log the weighted-kNN test top-1 against the train bank (facl_amd/knn_eval.py) as "knn top1"; 0 = off')
+    p.add_argument('--knn_k', type=int, default=20, help='NEW (--knn_every): neighbours per query (1..64)')
+    p.add_argument('--knn_T', type=float, default=0.1, help='NEW (--knn_every): temperature of the exp(s / T) vote')
     return p
 
 
@@ -446,11 +451,61 @@ def check_resident_flags(opt):
                            "per batch, which is the per-batch host work that resident clips remove" % opt.view_rng)
 
 
+def check_knn_flags(opt, world=None):
+    """--knn_every E > 0 needs the clips on disk and one rank (the sharded monitor does not exist); raises before the device
+    is touched (`world` None: the launcher's WORLD_SIZE)."""
+    if opt.knn_every < 0:
+        raise RuntimeError("--knn_every must be >= 0 (got %d)" % opt.knn_every)
+    if not opt.knn_every:
+        return
+    if opt.synthetic != 0:
+        raise RuntimeError("--knn_every %d evaluates the train and test splits of --data_root: it needs --synthetic 0 "
+                           "(got --synthetic %d, which has no labelled clips)" % (opt.knn_every, opt.synthetic))
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    if world > 1:
+        raise RuntimeError("--knn_every %d runs on one rank only (got %d ranks): the sharded monitor is not implemented"
+                           % (opt.knn_every, world))
+    if not 1 <= opt.knn_k <= 64:
+        raise RuntimeError("--knn_k must be in 1..64 (got %d)" % opt.knn_k)
+    if not opt.knn_T > 0:
+        raise RuntimeError("--knn_T must be positive (got %r)" % opt.knn_T)
+
+
+def knn_monitor(netR, opt, device):
+    """Weighted-kNN test top-1 (%) of the model as it stands: both splits of <data_root>/raw extracted in memory exactly as
+    facl_amd.extract_common.run_disk extracts them (eval(), its own view seed 2000 and generator), test against the train
+    bank.  Reads no training RNG stream and, in eval(), updates no running statistic; runs on ordinary eager launches, so
+    its tensors come from the default allocator pool, never from a captured step's.  The model returns to train()."""
+    from . import dataset as fds
+    from .extract_common import extract_split
+    from .knn_eval import knn_top1
+    index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
+    rng = np.random.RandomState(2000)
+    was_training = netR.training
+    netR.eval()
+    try:
+        with torch.no_grad():
+            data = []
+            for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
+                if not len(split):
+                    raise RuntimeError("--knn_every: a split of %s has no clips" % opt.data_root)
+                f = extract_split(netR, opt, device, index, split, rng)
+                y = torch.as_tensor([index.label(v) for v in split], dtype=torch.int64, device=device)
+                data.append((f, y))
+            from . import _lib
+            _lib.join_pending()
+            (ftr, ytr), (fte, yte) = data
+            return knn_top1(fte, yte, ftr, ytr, k=opt.knn_k, T=opt.knn_T)
+    finally:
+        netR.train(was_training)
+
+
 def run(default_branch, ckpt_pattern, args=None):
     opt = build_parser(default_branch).parse_args(args)
     print(opt)
     check_resident_flags(opt)
     check_view_flags(opt)
+    check_knn_flags(opt)
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)
@@ -561,6 +616,11 @@ def run(default_branch, ckpt_pattern, args=None):
         logging.info('{} --epoch{} ==Average loss:{}'.format('Valid', epoch, loss_sigma / (i + 1)))
         if rank == 0:
             print('epoch:', epoch, 'loss mode is :', 1, '--loss:', loss_sigma / (i + 1), '| clips/s: %.1f' % clips)
+        if opt.knn_every and (epoch + 1) % opt.knn_every == 0:
+            top1 = knn_monitor(netR, opt, device)
+            logging.info('{} --epoch{} ==knn top1:{}'.format('Valid', epoch, top1))
+            print('epoch:', epoch, 'knn top1:', top1)
+        if rank == 0:
             if epoch % 5 == 0:
                 torch.save(netR.state_dict(), ckpt_pattern % (opt.save_root_dir, epoch))
     return netR

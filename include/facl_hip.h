@@ -625,6 +625,39 @@ int facl_gen3dv_app(const uint16_t* frames, int NF, int H, int W, const int32_t*
                     int64_t NV, double voxel, const int32_t* vol0f, const double* norm, double* out, int32_t* err,
                     void* stream);
 
+/* ---- weighted k-nearest-neighbour evaluation of frozen features (csrc/knn.hip) -----------------------------
+ * The reference has no counterpart: this is the standard cheap complement of its linear probe (linear_classify/linercls.py),
+ * cosine similarity between L2-normalised feature rows and an exp(s / T)-weighted vote of the k nearest bank rows.
+ *
+ * facl_knn_topk: for every query row the k bank rows of largest cosine similarity.
+ *   q (nq, C) fp32 rows ldq floats apart; x (nb, C) fp32 rows ldx floats apart (the bank)
+ *   self_idx  int32 (nq) or NULL: the bank row that query must not return (-1: none) -- leave-one-out of a split against itself
+ *   top_val   (nq, k) fp32 cosine similarities, non-increasing along a row;  top_idx (nq, k) int32 bank rows
+ *   ws        facl_knn_ws_bytes(nq, nb, k) bytes, 16-byte aligned; contents are scratch
+ * Rows are normalised as F.normalize does (x / max(||x||, 1e-12), the norm taken in fp64) by a row pre-pass whose factors the
+ * GEMM epilogue applies: no normalised copy of either operand is made.  The similarities are an fp16x3 exact-split GEMM
+ * (each row scaled by its own power of two) with fp32 accumulation: fp32-GEMM accuracy.  Equal similarities are ordered by
+ * the lower bank index, and the result is the same bits from run to run: the order (similarity descending, index ascending)
+ * is total, every partial list is the k best under it, and no atomic takes part.  A similarity that is NaN is never
+ * returned; should fewer than k rows remain, the tail of the row is (-inf, -1).
+ * Domain: nq, nb >= 1; 1 <= k <= 64; C a positive multiple of 64; ldq, ldx >= C and multiples of 4; nb - (self_idx ? 1 : 0)
+ * >= k (a non-NULL self_idx counts as set); else FACL_E_SHAPE.  NULL q / x / outputs / ws: FACL_E_NULL.  q, x, ws not
+ * 16-byte aligned: FACL_E_ALIGN.
+ * facl_knn_ws_bytes: 8 (nq + nb) bytes of row factors + 8 nq k splits bytes of partial lists, where splits (1 when the query
+ * tiles alone fill the device, up to nb / 128 for a handful of queries) is fixed by (nq, nb); never O(nq nb).  FACL_E_SHAPE
+ * outside the domain of (nq, nb, k). */
+int64_t facl_knn_ws_bytes(int nq, int nb, int k);
+int facl_knn_topk(const float* q, int nq, int ldq, const float* x, int nb, int ldx, int C, int k, const int32_t* self_idx,
+                  float* top_val, int32_t* top_idx, void* ws, void* stream);
+
+/* facl_knn_vote: scores[i][c] = sum over the neighbours j of query i with labels[top_idx[i][j]] == c of
+ * exp(top_val[i][j] * inv_T), added in the order j = 0..k-1 (no atomics); pred[i] = argmax_c, the lower class on equal scores.
+ *   labels int32 (nb), each in [0, num_class); pred int32 (nq); scores (nq, num_class) fp32 or NULL
+ * A neighbour whose index is outside [0, nb) or whose label is outside [0, num_class) adds nothing.  One launch.
+ * Domain: nq, nb >= 1; 1 <= k <= 64; 1 <= num_class <= 1024; else FACL_E_SHAPE. */
+int facl_knn_vote(const float* top_val, const int32_t* top_idx, const int32_t* labels, int nq, int nb, int k, int num_class,
+                  float inv_T, int32_t* pred, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

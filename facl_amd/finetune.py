@@ -1,0 +1,282 @@
+"""Supervised fine-tuning of the encoder on a classifier head: the third evaluation protocol beside the
+linear probe (``facl_amd.linear_classify``) and the weighted kNN (``facl_amd.knn_eval``), which both freeze the encoder.
+From a pre-trained checkpoint, from scratch (no checkpoint), or on a stratified fraction of the labels (semi-supervised).
+
+    python -m facl_amd.finetune --synthetic 0 --data_root ../ntu/3DV_ntu60 --checkpoint corr_GL_95.pth --label_fraction 0.1
+
+The head is the reference's probe head ``Final_FC`` (linear_classify/fc_model.py:12-25) reading the encoder's stacked
+output in place (facl_amd/cls_head.py, csrc/cls.hip); the step replays as one HIP graph through ``train_common.GraphedStep``."""
+import logging
+import math
+import os
+import random
+import time
+
+import numpy as np
+import torch
+
+from . import cn3d_model_conbag as MODELL
+from .cls_head import ClipClassifier
+from .train_common import (ContrastiveStep, GraphCaptureFailed, GraphedStep, build_parser, check_resident_flags,
+                           check_view_flags, lr_for_epoch, synthetic_batch)
+
+HEAD_PREFIX = "head."
+
+
+class FineTuneNet(MODELL.PointNet_Plus):
+    """PointNet_Plus that owns its ClipClassifier as ``head``: whatever snapshots ``netR.state_dict()`` (GraphedStep) or
+    moves / switches the model covers the head too.  The encoder keeps its 52 keys; the head adds head.fc.weight / head.fc.bias."""
+
+    def __init__(self, opt, num_class, gost=10, **kw):
+        super().__init__(opt, gost=gost, **kw)
+        self.head = ClipClassifier(gost, num_class)
+
+    def encoder_parameters(self):
+        return [p for n, p in self.named_parameters() if not n.startswith(HEAD_PREFIX)]
+
+    def encoder_state_dict(self):
+        """The encoder keys only: loadable by PointNet_Plus, the extraction entries and --checkpoint here."""
+        return {k: v for k, v in self.state_dict().items() if not k.startswith(HEAD_PREFIX)}
+
+    def head_state_dict(self):
+        """fc.weight / fc.bias: loadable by linear_classify.Final_FC."""
+        return self.head.state_dict()
+
+    def load_encoder_state_dict(self, sd):
+        res = self.load_state_dict(sd, strict=False)
+        missing = [k for k in res.missing_keys if not k.startswith(HEAD_PREFIX)]
+        if missing or res.unexpected_keys:
+            raise RuntimeError("the checkpoint is not an encoder state_dict of this model: missing %s, unexpected %s"
+                               % (missing, list(res.unexpected_keys)))
+
+
+class FineTuneStep(ContrastiveStep):
+    """One supervised iteration: grouping (ContrastiveStep.group) -> encoder forward -> head -> cross-entropy -> backward
+    -> FusedAdam, with no host round trip (`run` is what GraphedStep captures).  The labels come from the static int32
+    device tensor ``self.labels`` (batch,), which the caller fills in place before each call; `order` is ignored."""
+
+    def __init__(self, netR, optimizer, opt, num_crop, group_radius=None, fps_reorder=False):
+        super().__init__(netR, optimizer, opt, num_crop, group_radius, fps_reorder)
+        dev = next(netR.parameters()).device
+        self.labels = torch.zeros(opt.batchSize, dtype=torch.int32, device=dev)
+
+    def _encode_and_step(self, xt, yt, B, order):
+        netR, G = self.netR, self.G
+        if B > self.labels.shape[0]:
+            raise RuntimeError("a batch of %d clips, the step holds %d labels" % (B, self.labels.shape[0]))
+        netR.lazy_code = False
+        netR(xt, yt, 1)
+        logits = netR.head(netR._stacked, G, B)
+        loss, stats = netR.head.loss(logits, self.labels[:B])
+        self.optimizer.zero_grad(set_to_none=True)
+        if self._one is None or self._one.device != loss.device:
+            self._one = torch.ones((), dtype=torch.float32, device=loss.device)    # the seed of backward(): no fill launch per step
+        loss.backward(self._one)
+        self.optimizer.step()
+        return loss, logits, stats
+
+
+def label_subset(labels, fraction, seed):
+    """Stratified subset of a labelled split: per class (ascending), the first max(1, ceil(fraction * n_c)) entries of a
+    RandomState(seed) permutation of that class's clips, the clips taken in ascending dataset index.  The permutations do not
+    depend on `fraction`, so with one seed the subset at f1 is contained in the subset at f2 for f1 < f2; fraction = 1 gives
+    the whole split.  Returns the sorted positions into `labels`.  Pure host code."""
+    fraction = float(fraction)
+    if not 0.0 < fraction <= 1.0:
+        raise ValueError("label_fraction must be in (0, 1] (got %r)" % fraction)
+    labels = np.asarray(labels).reshape(-1)
+    rs = np.random.RandomState(seed)
+    keep = []
+    for c in np.unique(labels):
+        idx = np.flatnonzero(labels == c)
+        perm = rs.permutation(len(idx))
+        keep.append(idx[perm[:max(1, int(math.ceil(fraction * len(idx))))]])
+    return np.sort(np.concatenate(keep)) if keep else np.zeros((0,), dtype=np.int64)
+
+
+def finetune_parser():
+    p = build_parser('0')
+    p.description = "Supervised fine-tuning"
+    p.add_argument('--checkpoint', type=str, default='', help='NEW: encoder state_dict to start from; empty = from scratch')
+    p.add_argument('--num_class', type=int, default=0, help='NEW: classes of the head (0 = 60 for ntu60, 120 for ntu120)')
+    p.add_argument('--label_fraction', type=float, default=1.0,
+                   help='NEW: 0 < f <= 1, the stratified fraction of the train split whose labels are used (label_subset)')
+    p.add_argument('--label_seed', type=int, default=0, help='NEW: seed of the per-class permutations of --label_fraction')
+    p.add_argument('--eval_every', type=int, default=1, help='NEW (--synthetic 0): test top-1 after every E-th epoch; 0 = off')
+    return p
+
+
+def check_finetune_flags(opt, world=None):
+    """One rank, labelled clips or synthetic ones; raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    if world > 1:
+        raise RuntimeError("fine-tuning runs on one rank only (got %d ranks): data-parallel fine-tuning is not implemented" % world)
+    if opt.synthetic not in (0, 1):
+        raise RuntimeError("fine-tuning reads the labelled clips of --data_root (--synthetic 0) or synthetic clouds with "
+                           "random labels (--synthetic 1); got --synthetic %d" % opt.synthetic)
+    if not 0.0 < opt.label_fraction <= 1.0:
+        raise RuntimeError("--label_fraction must be in (0, 1] (got %r)" % opt.label_fraction)
+    if opt.eval_every < 0:
+        raise RuntimeError("--eval_every must be >= 0 (got %d)" % opt.eval_every)
+    if opt.knn_every:
+        raise RuntimeError("--knn_every belongs to the pre-training entries; fine-tuning reports its own test top-1 (--eval_every)")
+    if opt.swa_if or opt.cld_if:
+        raise RuntimeError("--swa_if / --cld_if are terms of the contrastive loss: fine-tuning has the cross-entropy only")
+    if not opt.num_class:
+        opt.num_class = 60 if opt.dataset == 'ntu60' else 120
+    if not 2 <= opt.num_class <= 1024 or opt.num_class % 4:
+        raise RuntimeError("--num_class must be a multiple of 4 in 2..1024 (got %d)" % opt.num_class)
+    if not 1 <= opt.num_crop <= 64:
+        raise RuntimeError("--num_crop must be in 1..64 (got %d)" % opt.num_crop)
+
+
+def _raise_bad_labels(bad, num_class, where):
+    raise RuntimeError("%d label(s) of %s lie outside [0, %d): raise --num_class or check --dataset" % (bad, where, num_class))
+
+
+def evaluate(netR, step, opt, device):
+    """Test top-1 (%) of the model as it stands: the test split of <data_root>/raw in eval(), batches from ordered_batches,
+    views as extract_split draws them (view seed 2000, epoch 0, its own generator), hits from the loss kernel's stats[0].
+    The model returns to the mode it was in."""
+    from . import dataset as fds
+    index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
+    split = index.select(opt.split, test=True)
+    if not len(split):
+        raise RuntimeError("--eval_every: the test split of %s has no clips" % opt.data_root)
+    vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
+    rng = np.random.RandomState(2000)
+    was_training = netR.training
+    netR.eval()
+    total = torch.zeros(2, dtype=torch.int64, device=device)
+    try:
+        with torch.no_grad():
+            for views, names, labels in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
+                                                        rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch),
+                                                        num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM):
+                B = len(names)
+                xt, yt = step.group(views if views.dtype == torch.float32 else views.float())
+                netR.lazy_code = False
+                netR(xt, yt, 1)
+                logits = netR.head(netR._stacked, opt.num_crop, B)
+                y = torch.as_tensor(labels, dtype=torch.int32).to(device)
+                total += netR.head.loss(logits, y)[1]
+    finally:
+        netR.train(was_training)
+    hits, bad = (int(v) for v in total.cpu())
+    if bad:
+        _raise_bad_labels(bad, opt.num_class, "the test split")
+    return 100.0 * hits / len(split)
+
+
+def main(args=None):
+    """Returns the last test top-1 (%), or None when no evaluation ran."""
+    opt = finetune_parser().parse_args(args)
+    print(opt)
+    check_finetune_flags(opt)
+    check_resident_flags(opt)
+    check_view_flags(opt)
+    torch.cuda.set_device(opt.main_gpu)
+    device = torch.device("cuda", opt.main_gpu)
+
+    opt.manualSeed = 1
+    random.seed(opt.manualSeed)
+    torch.manual_seed(opt.manualSeed)
+    np.random.seed(opt.manualSeed)
+    os.makedirs(opt.save_root_dir, exist_ok=True)
+    if opt.log_file:
+        logging.basicConfig(format='%(asctime)s %(message)s', datefmt='%Y/%m/%d %H:%M:%S',
+                            filename=opt.log_file, level=logging.INFO)
+    logging.info('======================================================')
+
+    num_crop = opt.num_crop
+    netR = FineTuneNet(opt, opt.num_class, gost=num_crop)
+    if opt.checkpoint:
+        netR.load_encoder_state_dict(torch.load(opt.checkpoint, map_location="cpu", weights_only=True))
+    netR = netR.to(device)
+    netR.precision = opt.precision
+    from .optim import FusedAdam
+    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06)
+    step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder))
+    gen = torch.Generator(device=device)
+    gen.manual_seed(1000)
+    view_rng = np.random.RandomState(2000)
+
+    steps_per_epoch = opt.steps_per_epoch
+    resident = None
+    if opt.synthetic == 0:
+        from . import dataset as fds
+        index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.TRAIN_LIST_DIR[opt.branch_choose]), opt.dataset)
+        split = np.asarray(index.select(opt.split, full_train=bool(opt.full_train)), dtype=np.int64)
+        n_all = len(split)
+        split = split[label_subset([index.label(int(v)) for v in split], opt.label_fraction, opt.label_seed)]
+        print('labelled clips: %d of %d' % (len(split), n_all))
+        steps_per_epoch = len(split) // opt.batchSize
+        if opt.max_steps_per_epoch > 0:
+            steps_per_epoch = min(steps_per_epoch, opt.max_steps_per_epoch)
+        if steps_per_epoch < 1:
+            raise RuntimeError("the labelled subset has %d clips: fewer than one batch of %d" % (len(split), opt.batchSize))
+        if opt.resident:
+            from . import resident as fres
+            resident = fres.ResidentClips(index, opt.data_root, opt.branch_choose, split, device, max_gb=opt.resident_max_gb,
+                                          reserve=fres.step_reserve_bytes(opt.batchSize, num_crop, opt.SAMPLE_NUM))
+
+    run_step, top1 = step, None
+    for epoch in range(0, opt.nepoch):
+        netR.train()
+        for g in optimizer.param_groups:
+            g["lr"] = lr_for_epoch(opt.learning_rate, epoch, step_size=5, gamma=0.7)      # the probe's schedule
+        loss_sigma, hits, t0 = 0.0, 0, time.time()
+        disk = None
+        if opt.synthetic == 0:
+            pos = fds.train_batches(len(split), opt.batchSize, 1, 0, opt.manualSeed, epoch)[:steps_per_epoch]
+            if resident is not None:
+                disk = fres.ResidentBatches(resident, [split[p] for p in pos], seed=2000, epoch=epoch,
+                                            num_crop=num_crop, num_point=opt.SAMPLE_NUM)
+            else:
+                disk = fds.DiskBatches(index, opt.data_root, opt.branch_choose, [split[p] for p in pos], opt.view_rng, device,
+                                       rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch),
+                                       num_crop=num_crop, num_point=opt.SAMPLE_NUM)
+                disk.hold_first = run_step is step and bool(opt.graph)                   # capture on batch 0
+                disk = iter(disk)
+        for i in range(steps_per_epoch):
+            if opt.synthetic == 0:
+                out_points, _, labels = next(disk)
+                labels = torch.as_tensor(labels, dtype=torch.int32)
+            else:
+                out_points = synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
+                labels = torch.randint(0, opt.num_class, (opt.batchSize,), device=device, generator=gen).to(torch.int32)
+            step.labels.copy_(labels)
+            if run_step is step and opt.graph:
+                try:                                     # capture on the first batch; state restored: same trajectory as eager
+                    run_step = GraphedStep(step, out_points, num_crop, restore=True)
+                except GraphCaptureFailed as e:
+                    print("graph capture failed (%s); running eager" % e)
+                    opt.graph = 0
+            loss, _, stats = run_step(out_points, epoch)
+            torch.cuda.synchronize()
+            lv = loss.item()
+            if lv != lv or lv in (float("inf"), float("-inf")):
+                raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
+            h, bad = (int(v) for v in stats.cpu())
+            if bad:
+                _raise_bad_labels(bad, opt.num_class, "the train split")
+            loss_sigma += lv
+            hits += h
+        if disk is not None:
+            disk.close()
+        clips = opt.batchSize * steps_per_epoch / (time.time() - t0)
+        train_top1 = 100.0 * hits / (opt.batchSize * steps_per_epoch)
+        logging.info('{} --epoch{} ==Average loss:{} train top1:{}'.format('Valid', epoch, loss_sigma / steps_per_epoch, train_top1))
+        print('epoch:', epoch, '--loss:', loss_sigma / steps_per_epoch, 'train top1:', train_top1, '| clips/s: %.1f' % clips)
+        if opt.synthetic == 0 and opt.eval_every and (epoch + 1) % opt.eval_every == 0:
+            top1 = evaluate(netR, step, opt, device)
+            logging.info('{} --epoch{} ==test top1:{}'.format('Valid', epoch, top1))
+            print('epoch:', epoch, 'test top1:', top1)
+        if epoch % 5 == 0 or epoch == opt.nepoch - 1:
+            torch.save(netR.encoder_state_dict(), '%s/finetune_enc_%d.pth' % (opt.save_root_dir, epoch))
+            torch.save(netR.head_state_dict(), '%s/finetune_fc_%d.pth' % (opt.save_root_dir, epoch))
+    return top1
+
+
+if __name__ == '__main__':
+    main()

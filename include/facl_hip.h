@@ -658,6 +658,37 @@ int facl_knn_topk(const float* q, int nq, int ldq, const float* x, int nb, int l
 int facl_knn_vote(const float* top_val, const int32_t* top_idx, const int32_t* labels, int nq, int nb, int k, int num_class,
                   float inv_T, int32_t* pred, float* scores, void* stream);
 
+/* ---- classifier head of supervised fine-tuning (csrc/cls.hip) ------------------------------------------------
+ * The probe head of the reference (linear_classify/fc_model.py:12-25, Final_FC: F.normalize(x, dim=1) then Linear) on the
+ * model's own output layout, and the softmax cross-entropy of its logits.  The Linear layer is facl_gemm_fwd / dgrad / wgrad.
+ * No entry synchronises, allocates or uses an atomic: each can be captured in a graph and returns the same bits every run.
+ *
+ * facl_cls_gather_norm_fwd: `stacked` (G*B + B, C) is the FC head's stacked, view-major output: row g*B + b = view g of clip
+ * b, row G*B + b = the clip's global feature.  out (B, (G+1)*C) = the clip-major vector [x_view0 .. x_view(G-1), x_global] of
+ * every clip times inv_norm[b] = 1 / max(||vector||, 1e-12) (F.normalize's clamp; the sum of squares is taken in fp64 in a fixed
+ * order).  The G + 1 rows of a clip are read in place: no permute / cat copy exists.  One workgroup per clip.
+ * facl_cls_gather_norm_bwd: dstacked[g*B + b] = inv_norm[b] * (dout[b][g] - out[b][g] * <dout[b], out[b]>), the dot product in
+ * fp64 in a fixed order; EVERY row of dstacked (G*B + B, C) is written.  dout, out (B, (G+1)*C).
+ * Domain: C a multiple of 64 in 64..1024; 1 <= G <= 64; B >= 1; else FACL_E_SHAPE.  A NULL pointer: FACL_E_NULL.  stacked, out,
+ * dout, dstacked not 16-byte aligned: FACL_E_ALIGN. */
+int facl_cls_gather_norm_fwd(const float* stacked, int G, int B, int C, float* out, float* inv_norm, void* stream);
+int facl_cls_gather_norm_bwd(const float* dout, const float* out, const float* inv_norm, int G, int B, int C, float* dstacked,
+                             void* stream);
+
+/* facl_softmax_ce: mean cross-entropy of R rows of logits (rows ld floats apart, ncls classes) against int32 labels, the row
+ * maximum subtracted and the exponentials summed in fp64.
+ *   loss     (1) fp32: (sum of the row losses) / R
+ *   dlogits  (R, ncls) fp32 contiguous, or NULL: (softmax - onehot) / R
+ *   stats    int32 (2): [0] rows whose argmax equals the label (the lowest class on equal logits), [1] rows whose label lies
+ *            outside [0, ncls): such a row adds no loss, no gradient (its dlogits row is zero) and no hit, and still counts in R
+ *   ws       the partial-sum workspace (facl_ws_bytes(), 8-byte aligned): 12 R bytes of row losses and flags; scratch
+ * One wave per row writes the row's loss and flags to the workspace; a second launch of ONE wave sums them in a fixed order
+ * in fp64, so the mean does not depend on scheduling.
+ * Domain: 2 <= ncls <= 1024; R >= 1 with 12 R bytes inside the workspace; ld >= ncls; else FACL_E_SHAPE.  NULL logits /
+ * labels / loss / stats / ws: FACL_E_NULL. */
+int facl_softmax_ce(const float* logits, int ld, const int32_t* labels, int R, int ncls, float* loss, float* dlogits,
+                    int32_t* stats, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/facl_hip.h"
 
 #define FACL_WAVE 64
@@ -9,6 +10,12 @@
 static inline int facl_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
+}
+
+// integer A/B knob from the environment; call sites keep the value in a `static const int` (read once per process)
+static inline int facl_env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: `done` = one flag per device ordinal (a
@@ -24,6 +31,25 @@ static inline int facl_set_dynamic_lds(bool (&done)[64], const void* const* fns,
     }
     done[dev] = true;
     return 0;
+}
+
+// Launch KERN with `lds` bytes of dynamic LDS; its per-device attribute is set on first use (the flags are per instantiation of
+// this template, i.e. per kernel; a kernel must always be launched with the same `lds`)
+template <auto KERN, class ARGS>
+static inline int facl_launch_dynamic_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const ARGS& args) {
+    static bool attr_done[64] = {};
+    const void* fns[1] = {(const void*)KERN};
+    if (int rc = facl_set_dynamic_lds(attr_done, fns, 1, lds)) return rc;
+    hipLaunchKernelGGL(KERN, grid, block, lds, st, args);
+    return facl_launch_status();
+}
+
+// XCD-aware tile order: workgroup b of a linearised grid of `total` is dispatched to XCD b % 8 (8 XCDs, one L2 each).  Returns
+// the logical tile index such that each XCD works through a CONTIGUOUS range of logical tiles: tiles that share an operand
+// panel then hit the same L2 instead of pulling the panel through the fabric 8 times.
+__device__ __forceinline__ int facl_xcd_tile(int b, int total) {
+    const int per = total >> 3, rem = total & 7, xcd = b & 7, slot = b >> 3;
+    return (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + slot;
 }
 
 // Phase offset between the workgroups that share a CU.  Co-resident workgroups of one launch start together and do identical work,

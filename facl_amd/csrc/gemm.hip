@@ -15,8 +15,14 @@
 // operands staged global -> registers -> LDS as [k][idx] (+4 pad) so that the MFMA fragments are
 // conflict-free ds_read_b32; register prefetch of the next k-tile overlaps the 64 MFMAs of the current one.
 // Roofline: MFMA fp32 (157.3 TFLOP/s); 2*MI*NJ*KK FLOP per call.
+//
+// Split path, device side, once for k_gemm_sb and k_gemm_sbk: SplitOperand<LAY, T, NP, PRO> (raw registers, packed planes, fetch /
+// split / write / fragment read of one operand), fetch_stage (full / partial stage dispatch), mfma_block (piece-product order).
+// Host side, each thing once: GemmArgs (defaults for everything but operands and shape; entries set fields by name),
+// choose_tile (in-workgroup split-K / 128x128 / 64x64, with the rows per statistics partial) for the launcher AND for every
+// entry that must know the choice beforehand, launch<LA, LB, PRO> (precision -> kernel), split_k (chunk rounding, launch,
+// slice sum) for the three split-K weight-gradient entries, facl_sum_slices (also the slice sum of gemm_rs.hip).
 #include "common.h"
-#include <stdlib.h>
 
 int facl_reduce_rows(const double* part, int rows, int V, double* out, hipStream_t st);
 
@@ -28,23 +34,24 @@ constexpr int LDK = BK + 4;      // KC tiles: LDS image [idx][k], row = 36 float
 // IC tiles: LDS image [k][idx], row = NIDX+4 floats (16-B aligned rows).  NIDX = 64*T (T = 32x32 tiles per wave side)
 enum { KC = 0, IC = 1 };
 
+// Entries brace-initialise the operand / shape fields (A .. KK) and set by name what else they use.
 struct GemmArgs {
-    const float* A; int lda;
-    const float* B; int ldb;
-    float* C; int ldc;
-    int MI, NJ, KK;
-    const float* bias;                 // (NJ) or null
-    const float* pscale; const float* pshift;   // (KK) prologue on A, or null
-    const float* xa; const float* xb; int ldxb;  // rank-3 extra term: C += xa[i][0..2] . xb[j][0..2]  (or null)
-    double* part;                      // column statistics partials [(MI/64)][NJ][2], or null
-    int kchunk;                        // split-K: k range per blockIdx.z (wgrad); C then is [z][MI][NJ]
+    const float* A = nullptr; int lda = 0;
+    const float* B = nullptr; int ldb = 0;
+    float* C = nullptr; int ldc = 0;
+    int MI = 0, NJ = 0, KK = 0;
+    const float* bias = nullptr;       // (NJ) or null
+    const float* pscale = nullptr; const float* pshift = nullptr;   // (KK) prologue on A, or null
+    const float* xa = nullptr; const float* xb = nullptr; int ldxb = 0;  // rank-3 extra term: C += xa[i][0..2] . xb[j][0..2]  (or null)
+    double* part = nullptr;            // column statistics partials [(MI/64)][NJ][2], or null
+    int kchunk = 0;                    // k range per blockIdx.z: KK, or a split-K chunk (wgrad; C then is [z][MI][NJ])
     // fused max over each block of 64 consecutive rows (my_max_pool over the S = 64 centroids of a cloud): per
     // (row block, column) max of sgn[j]*C and the FIRST row that attains it; 128x128 tiles only.  Null when unused.
-    const float* sgn; float* smax; int* sarg;
-    int prec;                          // 0: fp32 result (bf16x6 or fp32 MFMA), 1: fp16 inputs, one MFMA product, fp32 accumulate
-    const unsigned* amax;              // NP = 4 (fp16x3 weight gradient): bits of max|A| in hashed slots (common.h), A = dy
-    const unsigned* amax_b;            // NP = 4: bound of max|B| (the activation operand), same format
-    int accum;                         // 1: C += result (gemm_epilogue, vectorised stores only: facl_gemm_wgrad_acc)
+    const float* sgn = nullptr; float* smax = nullptr; int* sarg = nullptr;
+    int prec = 0;                      // 0: fp32 result (bf16x6 or fp32 MFMA), 1: fp16 inputs, one MFMA product, fp32 accumulate
+    const unsigned* amax = nullptr;    // NP = 4 (fp16x3 weight gradient): bits of max|A| in hashed slots (common.h), A = dy
+    const unsigned* amax_b = nullptr;  // NP = 4: bound of max|B| (the activation operand), same format
+    int accum = 0;                     // 1: C += result (gemm_epilogue only, not gemm_epilogue_h: facl_gemm_wgrad_acc)
 };
 
 template <int LAY, int T>
@@ -105,16 +112,12 @@ __device__ __forceinline__ void store_tile(float* __restrict__ T, const float4 (
     }
 }
 
-// XCD-aware tile order: workgroup b of the linearised grid is dispatched to XCD b % 8 (8 XCDs, one L2 each).  Remap so
-// that each XCD works through a CONTIGUOUS range of logical tiles: the column tiles that share an A row-panel (and
-// all tiles of one split-K slice) then hit the same L2 instead of pulling the panel through the fabric 8 times.
+// XCD-aware tile order (common.h: facl_xcd_tile): the column tiles that share an A row-panel (and all tiles of one split-K
+// slice) are consecutive logical tiles, so they hit the same L2.
 struct TileId { int x, y, z; };
 __device__ __forceinline__ TileId xcd_tile() {
     const int nbx = gridDim.x, nby = gridDim.y;
-    const int total = nbx * nby * gridDim.z;
-    const int b = blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z);
-    const int per = total >> 3, rem = total & 7, xcd = b & 7, slot = b >> 3;
-    const int L = (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + slot;
+    const int L = facl_xcd_tile(blockIdx.x + nbx * (blockIdx.y + nby * blockIdx.z), nbx * nby * gridDim.z);
     TileId t;
     t.x = L % nbx; t.y = (L / nbx) % nby; t.z = L / (nbx * nby);
     return t;
@@ -619,14 +622,100 @@ __device__ __forceinline__ void write_tile_kc4(unsigned short* __restrict__ S, c
 }
 
 
+// One operand of the split path, for k_gemm_sb and k_gemm_sbk alike: the raw fp32 registers of the stage being fetched, its
+// packed planes, and the fetch / split / write / fragment-read code of either layout.  PRO = relu(ps * x + pt): over k for a
+// k-contiguous operand (constants read per stage), over the thread's OWN idx for an idx-contiguous one (read once, here).
+template <int LAY, int T, int NP, bool PRO>
+struct SplitOperand {
+    static constexpr int NPL = NP == 4 ? 2 : NP;                        // planes in LDS (fp16x3: two fp16 planes)
+    static constexpr int PLANE = 64 * T * SBROW;                        // one plane (elements)
+    const float* P; int ld, idx0, nidx;
+    const float* ps; const float* pt;
+    float psi = 1.f, pti = 0.f;
+    float4 r4[2 * T];
+    float r8[8 * T];
+    unsigned pk[12 * T];
+    __device__ __forceinline__ SplitOperand(const float* P_, int ld_, int idx0_, int nidx_, const float* ps_, const float* pt_, int tid)
+        : P(P_), ld(ld_), idx0(idx0_), nidx(nidx_), ps(ps_), pt(pt_) {
+        if (PRO && LAY == IC) {
+            int j = idx0 + tid % (64 * T);
+            j = j < nidx ? j : nidx - 1;
+            psi = ps[j]; pti = pt[j];
+        }
+    }
+    template <bool FULL>
+    __device__ __forceinline__ void fetch(int k0, int kend, int tid) {
+        if (LAY == KC) load_tile_kc4<T, FULL>(P, ld, idx0, nidx, k0, kend, r4, tid);
+        else load_tile_ic8<T, FULL>(P, ld, idx0, nidx, k0, kend, r8, tid);
+    }
+    __device__ __forceinline__ float absmax() const {                   // of the fetched stage (the self-scaled form)
+        float m = 0.f;
+        if (LAY == KC) {
+#pragma unroll
+            for (int i = 0; i < 2 * T; ++i) m = fmaxf(fmaxf(m, fmaxf(fabsf(r4[i].x), fabsf(r4[i].y))), fmaxf(fabsf(r4[i].z), fabsf(r4[i].w)));
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8 * T; ++i) m = fmaxf(m, fabsf(r8[i]));
+        }
+        return m;
+    }
+    __device__ __forceinline__ void split(int k0, float sc, int tid) {  // sc: the power-of-two scale of NP = 4
+        if (LAY == KC) split_tile_kc4<PRO, T, NP>(r4, pk, tid, k0, ps, pt, sc);
+        else split_tile_ic8<T, NP, PRO>(r8, pk, psi, pti, sc);
+    }
+    __device__ __forceinline__ void write(unsigned short* S, int tid) const {
+        if (LAY == KC) write_tile_kc4<T, NP>(S, pk, tid);
+        else write_tile_ic8<T, NP>(S, pk, tid);
+    }
+    // the MFMA fragment of plane p: row `row` of the image, k = 16 kk + 8 h ..+7
+    static __device__ __forceinline__ bf16x8 frag(const unsigned short* S, int p, int row, int kk, int h) {
+        return *reinterpret_cast<const bf16x8*>(S + p * PLANE + row * SBROW + 16 * kk + 8 * h);
+    }
+};
+
+// Both operands of stage k0 into their raw registers; a partial last stage (wave-uniform) takes the zero-filling loads.
+template <class OA, class OB>
+__device__ __forceinline__ void fetch_stage(OA& A, OB& B, int k0, int kend, int tid) {
+    if (k0 + BK <= kend) { A.template fetch<true>(k0, kend, tid); B.template fetch<true>(k0, kend, tid); }
+    else { A.template fetch<false>(k0, kend, tid); B.template fetch<false>(k0, kend, tid); }
+}
+
+// Half a stage (k = 16 kk .. 16 kk + 15) of the wave's TM x TN tiles: fragment reads and THE piece-product order.
+template <int NP, int TM, int TN, class OA, class OB>
+__device__ __forceinline__ void mfma_block(const unsigned short* sA, const unsigned short* sB, int kk, int wr, int wc, int q, int h,
+                                           f32x16 (&acc)[TM][TN]) {
+    constexpr int NPL = OA::NPL;
+    bf16x8 af[TM][NPL], bf[TN][NPL];
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) af[a][p] = OA::frag(sA, p, 32 * TM * wr + 32 * a + q, kk, h);
+#pragma unroll
+    for (int b = 0; b < TN; ++b)
+#pragma unroll
+        for (int p = 0; p < NPL; ++p) bf[b][p] = OB::frag(sB, p, 32 * TN * wc + 32 * b + q, kk, h);
+    // smallest terms first.  bf16x6: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi); bf16x3 / fp16x3: (lo,hi) (hi,lo) (hi,hi);
+    // fp16 inputs: ONE product per multiply-add
+    constexpr int PA6[6] = FACL_SB_PA, PB6[6] = FACL_SB_PB, PA3[3] = FACL_SB3_PA, PB3[3] = FACL_SB3_PB, HA[3] = FACL_H3_PA, HB[3] = FACL_H3_PB;
+#pragma unroll
+    for (int t = 0; t < (NP == 3 ? 6 : NP == 1 ? 1 : 3); ++t)
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b) {
+                if constexpr (NP == 4) acc[a][b] = MFMA_F16(__builtin_bit_cast(f16x8h, af[a][HA[t]]), __builtin_bit_cast(f16x8h, bf[b][HB[t]]), acc[a][b]);
+                else if constexpr (NP == 1) acc[a][b] = MFMA_F16(__builtin_bit_cast(f16x8h, af[a][0]), __builtin_bit_cast(f16x8h, bf[b][0]), acc[a][b]);
+                else acc[a][b] = MFMA_BF16(af[a][NP == 3 ? PA6[t] : PA3[t]], bf[b][NP == 3 ? PB6[t] : PB3[t]], acc[a][b]);
+            }
+}
+
 template <int LA, int LB, bool PRO, int TM, int TN, int NP = 3>
 __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void k_gemm_sb(GemmArgs g) {
     constexpr int BM = 64 * TM, BN = 64 * TN;
     constexpr int APL = BM * SBROW, BPL = BN * SBROW;                   // one bf16 plane of each operand (elements)
-    // epilogue staging (floats): the fp16-input instantiation stages one 32-row tile at a time (gemm_epilogue_h) and keeps
+    // epilogue staging (floats): the fp16-input instantiation stages one 32-row tile at a time and keeps
     // only its single operand plane -> 35 KiB of LDS, three workgroups per CU
     constexpr int STG = NP == 1 ? 4 * 32 * (32 * TN + 4) : 4 * (32 * TM) * (32 * TN + 4);
-    constexpr int NPL = NP == 4 ? 2 : NP;                               // planes per operand in LDS (fp16x3: two fp16 planes)
     static_assert(NP != 4 || (LA == IC && LB == IC), "fp16x3 is wired for the weight gradient (both operands idx-contiguous)");
     constexpr int TILE_F = ((NP == 1 ? 1 : NP == 4 ? 2 : 3) * (APL + BPL) * 2 + 3) / 4;   // operand images in floats
     constexpr int SMEM = TILE_F > STG ? TILE_F : STG;
@@ -653,83 +742,15 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void k_gemm_sb(GemmArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-    float4 ra4[2 * TM], rb4[2 * TN];
-    float ra8[8 * TM], rb8[8 * TN];
-    auto fetch = [&](int k0) {
-        if (k0 + BK <= kend) {                                         // wave-uniform
-            if (LA == KC) load_tile_kc4<TM, true>(g.A, g.lda, i0, g.MI, k0, kend, ra4, tid);
-            else load_tile_ic8<TM, true>(g.A, g.lda, i0, g.MI, k0, kend, ra8, tid);
-            if (LB == KC) load_tile_kc4<TN, true>(g.B, g.ldb, j0, g.NJ, k0, kend, rb4, tid);
-            else load_tile_ic8<TN, true>(g.B, g.ldb, j0, g.NJ, k0, kend, rb8, tid);
-        } else {
-            if (LA == KC) load_tile_kc4<TM, false>(g.A, g.lda, i0, g.MI, k0, kend, ra4, tid);
-            else load_tile_ic8<TM, false>(g.A, g.lda, i0, g.MI, k0, kend, ra8, tid);
-            if (LB == KC) load_tile_kc4<TN, false>(g.B, g.ldb, j0, g.NJ, k0, kend, rb4, tid);
-            else load_tile_ic8<TN, false>(g.B, g.ldb, j0, g.NJ, k0, kend, rb8, tid);
-        }
-    };
-    unsigned pka[12 * TM], pkb[12 * TN];
     // PRO: k-contiguous A (forward): prologue over k; idx-contiguous A and B (weight gradient): prologue on B over ITS idx
-    constexpr bool PROB = PRO && LA == IC && LB == IC;
-    float psb = 1.f, ptb = 0.f;
-    if (PROB) {
-        int jb = j0 + tid % (64 * TN);
-        jb = jb < g.NJ ? jb : g.NJ - 1;
-        psb = g.pscale[jb]; ptb = g.pshift[jb];
-    }
-    auto split = [&](int k0) {
-        if (LA == KC) split_tile_kc4<PRO, TM, NP>(ra4, pka, tid, k0, g.pscale, g.pshift);
-        else split_tile_ic8<TM, NP>(ra8, pka, 1.f, 0.f, sca);
-        if (LB == KC) split_tile_kc4<false, TN, NP>(rb4, pkb, tid, k0, nullptr, nullptr);
-        else split_tile_ic8<TN, NP, PROB>(rb8, pkb, psb, ptb, scb);
-    };
-    auto write = [&]() {
-        if (LA == KC) write_tile_kc4<TM, NP>(sA, pka, tid);
-        else write_tile_ic8<TM, NP>(sA, pka, tid);
-        if (LB == KC) write_tile_kc4<TN, NP>(sB, pkb, tid);
-        else write_tile_ic8<TN, NP>(sB, pkb, tid);
-    };
-    auto mfma_block = [&](int kk) {
-        bf16x8 af[TM][NPL], bf[TN][NPL];
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int p = 0; p < NPL; ++p)
-                af[a][p] = *reinterpret_cast<const bf16x8*>(sA + p * APL + (32 * TM * wr + 32 * a + q) * SBROW + 16 * kk + 8 * h);
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int p = 0; p < NPL; ++p)
-                bf[b][p] = *reinterpret_cast<const bf16x8*>(sB + p * BPL + (32 * TN * wc + 32 * b + q) * SBROW + 16 * kk + 8 * h);
-        if constexpr (NP == 4) {                                        // fp16x3: (lo,hi) (hi,lo) (hi,hi)
-            constexpr int HA[3] = FACL_H3_PA, HB[3] = FACL_H3_PB;
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int a = 0; a < TM; ++a)
-#pragma unroll
-                    for (int b = 0; b < TN; ++b)
-                        acc[a][b] = MFMA_F16(__builtin_bit_cast(f16x8h, af[a][HA[t]]), __builtin_bit_cast(f16x8h, bf[b][HB[t]]), acc[a][b]);
-            return;
-        }
-        if constexpr (NP == 1) {                                        // fp16 inputs: ONE product per multiply-add
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[a][0]),
-                                                                       __builtin_bit_cast(f16x8, bf[b][0]), acc[a][b], 0, 0, 0);
-            return;
-        }
-        // smallest terms first: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi)
-        constexpr int PA[6] = FACL_SB_PA, PB[6] = FACL_SB_PB, PA3[3] = FACL_SB3_PA, PB3[3] = FACL_SB3_PB;
-#pragma unroll
-        for (int t = 0; t < (NP == 3 ? 6 : 3); ++t)
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b) acc[a][b] = MFMA_BF16(af[a][NP == 3 ? PA[t] : PA3[t]], bf[b][NP == 3 ? PB[t] : PB3[t]], acc[a][b]);
-    };
+    using OpA = SplitOperand<LA, TM, NP, PRO && LA == KC>;
+    using OpB = SplitOperand<LB, TN, NP, PRO && LA == IC && LB == IC>;
+    OpA opa(g.A, g.lda, i0, g.MI, g.pscale, g.pshift, tid);
+    OpB opb(g.B, g.ldb, j0, g.NJ, g.pscale, g.pshift, tid);
+    auto fetch = [&](int k0) { fetch_stage(opa, opb, k0, kend, tid); };
+    auto split = [&](int k0) { opa.split(k0, sca, tid); opb.split(k0, scb, tid); };
+    auto write = [&]() { opa.write(sA, tid); opb.write(sB, tid); };
+    auto mfma = [&](int kk) { mfma_block<NP, TM, TN, OpA, OpB>(sA, sB, kk, wr, wc, q, h, acc); };
     fetch(kbeg);
     split(kbeg);
     write();
@@ -739,9 +760,9 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void k_gemm_sb(GemmArgs g) {
         const int kn = (k0 + BK < kend) ? k0 + BK : k0;
         fetch(kn);
         __builtin_amdgcn_sched_barrier(0);                             // all loads in flight before the MFMAs
-        mfma_block(0);
+        mfma(0);
         __builtin_amdgcn_sched_barrier(0);
-        mfma_block(1);
+        mfma(1);
         split(kn);                                                     // VALU work for the scheduler to sink into the MFMA shadow
         __syncthreads();                                               // every wave has read this stage
         write();
@@ -794,22 +815,11 @@ __global__ __launch_bounds__(256 * KG, 1) void k_gemm_sbk(GemmArgs g) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
 
-    float4 ra4[2], rb4[2];
-    float ra8[8], rb8[8];
-    auto fetch = [&](int k0) {
-        if (k0 + BK <= kend) {                                         // wave-uniform
-            if (LA == KC) load_tile_kc4<1, true>(g.A, g.lda, i0, g.MI, k0, kend, ra4, tid);
-            else load_tile_ic8<1, true>(g.A, g.lda, i0, g.MI, k0, kend, ra8, tid);
-            if (LB == KC) load_tile_kc4<1, true>(g.B, g.ldb, j0, g.NJ, k0, kend, rb4, tid);
-            else load_tile_ic8<1, true>(g.B, g.ldb, j0, g.NJ, k0, kend, rb8, tid);
-        } else {
-            if (LA == KC) load_tile_kc4<1, false>(g.A, g.lda, i0, g.MI, k0, kend, ra4, tid);
-            else load_tile_ic8<1, false>(g.A, g.lda, i0, g.MI, k0, kend, ra8, tid);
-            if (LB == KC) load_tile_kc4<1, false>(g.B, g.ldb, j0, g.NJ, k0, kend, rb4, tid);
-            else load_tile_ic8<1, false>(g.B, g.ldb, j0, g.NJ, k0, kend, rb8, tid);
-        }
-    };
-    unsigned pka[12], pkb[12];
+    using OpA = SplitOperand<LA, 1, NP, PRO && LA == KC>;
+    using OpB = SplitOperand<LB, 1, NP, PRO && LA == IC && LB == IC>;
+    OpA opa(g.A, g.lda, i0, g.MI, g.pscale, g.pshift, tid);
+    OpB opb(g.B, g.ldb, j0, g.NJ, g.pscale, g.pshift, tid);
+    auto fetch = [&](int k0) { fetch_stage(opa, opb, k0, kend, tid); };
     float* const mxs = smem + MXOFF;
     float uns_nxt = 1.f;                                                // NP = 4: inverse scale of the stage `split` has just prepared
     auto split = [&](int k0) {
@@ -817,22 +827,7 @@ __global__ __launch_bounds__(256 * KG, 1) void k_gemm_sbk(GemmArgs g) {
         if constexpr (NP == 4) {
             // maxima of the group's raw stage tiles: registers -> wave (DPP) -> the group's four waves (LDS, behind a workgroup
             // barrier that ALSO is the one after which the current LDS tile may be overwritten: every wave's MFMA reads are done)
-            float ma = 0.f, mb = 0.f;
-            if (LA == KC) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) ma = fmaxf(fmaxf(ma, fmaxf(fabsf(ra4[i].x), fabsf(ra4[i].y))), fmaxf(fabsf(ra4[i].z), fabsf(ra4[i].w)));
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) ma = fmaxf(ma, fabsf(ra8[i]));
-            }
-            if (LB == KC) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) mb = fmaxf(fmaxf(mb, fmaxf(fabsf(rb4[i].x), fabsf(rb4[i].y))), fmaxf(fabsf(rb4[i].z), fabsf(rb4[i].w)));
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) mb = fmaxf(mb, fabsf(rb8[i]));
-            }
-            ma = facl_wave_max_nonneg(ma); mb = facl_wave_max_nonneg(mb);
+            float ma = facl_wave_max_nonneg(opa.absmax()), mb = facl_wave_max_nonneg(opb.absmax());
             if (lane == 0) { mxs[(grp * 4 + wave) * 2] = ma; mxs[(grp * 4 + wave) * 2 + 1] = mb; }
             __syncthreads();
             const float4 m01 = *reinterpret_cast<const float4*>(mxs + grp * 8), m23 = *reinterpret_cast<const float4*>(mxs + grp * 8 + 4);
@@ -842,39 +837,11 @@ __global__ __launch_bounds__(256 * KG, 1) void k_gemm_sbk(GemmArgs g) {
             sca = pow2_biased(seA); scb = pow2_biased(seB);
             uns_nxt = h3_unscale(seA, seB);
         }
-        if (LA == KC) split_tile_kc4<PRO, 1, NP>(ra4, pka, tid, k0, g.pscale, g.pshift, sca);
-        else split_tile_ic8<1, NP>(ra8, pka, 1.f, 0.f, sca);
-        if (LB == KC) split_tile_kc4<false, 1, NP>(rb4, pkb, tid, k0, nullptr, nullptr, scb);
-        else split_tile_ic8<1, NP>(rb8, pkb, 1.f, 0.f, scb);
+        opa.split(k0, sca, tid); opb.split(k0, scb, tid);
     };
-    auto write = [&]() {
-        if (LA == KC) write_tile_kc4<1, NP>(sA, pka, tid);
-        else write_tile_ic8<1, NP>(sA, pka, tid);
-        if (LB == KC) write_tile_kc4<1, NP>(sB, pkb, tid);
-        else write_tile_ic8<1, NP>(sB, pkb, tid);
-    };
-    f32x16 stg_acc;                                                     // NP = 4: the current stage's partial product (scaled)
-    auto mfma_block = [&](int kk) {
-        bf16x8 af[NPL], bf[NPL];
-#pragma unroll
-        for (int p = 0; p < NPL; ++p) {
-            af[p] = *reinterpret_cast<const bf16x8*>(sA + p * PL + (32 * wr + q) * SBROW + 16 * kk + 8 * h);
-            bf[p] = *reinterpret_cast<const bf16x8*>(sB + p * PL + (32 * wc + q) * SBROW + 16 * kk + 8 * h);
-        }
-        if constexpr (NP == 4) {                                        // smallest terms first: (lo,hi) (hi,lo) (hi,hi)
-            const f16x8h a0 = __builtin_bit_cast(f16x8h, af[0]), a1 = __builtin_bit_cast(f16x8h, af[1]);
-            const f16x8h b0 = __builtin_bit_cast(f16x8h, bf[0]), b1 = __builtin_bit_cast(f16x8h, bf[1]);
-            stg_acc = MFMA_F16(a1, b0, stg_acc); stg_acc = MFMA_F16(a0, b1, stg_acc); stg_acc = MFMA_F16(a0, b0, stg_acc);
-        } else if constexpr (NP == 1) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[0]), __builtin_bit_cast(f16x8, bf[0]),
-                                                               acc[0][0], 0, 0, 0);
-        } else {
-            constexpr int PA[6] = FACL_SB_PA, PB[6] = FACL_SB_PB, PA3[3] = FACL_SB3_PA, PB3[3] = FACL_SB3_PB;
-#pragma unroll
-            for (int t = 0; t < (NP == 3 ? 6 : 3); ++t)
-                acc[0][0] = MFMA_BF16(af[NP == 3 ? PA[t] : PA3[t]], bf[NP == 3 ? PB[t] : PB3[t]], acc[0][0]);
-        }
-    };
+    auto write = [&]() { opa.write(sA, tid); opb.write(sB, tid); };
+    f32x16 stg_acc[1][1];                                               // NP = 4: the current stage's partial product (scaled)
+    auto mfma = [&](int kk) { mfma_block<NP, 1, 1, OpA, OpB>(sA, sB, kk, wr, wc, q, h, NP == 4 ? stg_acc : acc); };
     // stage s of the chunk belongs to group s % KG; a group that runs out of stages re-stages its last one (harmless)
     // and skips the MFMAs, so that every wave reaches every barrier
     auto kof = [&](int it) {
@@ -891,13 +858,13 @@ __global__ __launch_bounds__(256 * KG, 1) void k_gemm_sbk(GemmArgs g) {
         if (grp + KG * it < nst) {                                     // wave-uniform
             if constexpr (NP == 4) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) stg_acc[r] = 0.f;
+                for (int r = 0; r < 16; ++r) stg_acc[0][0][r] = 0.f;
             }
-            mfma_block(0);
-            mfma_block(1);
+            mfma(0);
+            mfma(1);
             if constexpr (NP == 4) {                                    // exact rescale (a power of two), then the ordinary fp32 add
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[0][0][r] = fmaf(stg_acc[r], uns_cur, acc[0][0][r]);
+                for (int r = 0; r < 16; ++r) acc[0][0][r] = fmaf(stg_acc[0][0][r], uns_cur, acc[0][0][r]);
             }
         }
         split(kn);                                                      // (NP = 4: holds the barrier behind the MFMA reads)
@@ -927,18 +894,78 @@ int launch_sbk(const GemmArgs& g, int nz, hipStream_t st) {
     constexpr int TILE_F = (NP == 4 ? 2 : NP) * 2 * 64 * SBROW * 2 / 4, STG = 4 * 32 * 36;
     constexpr int F = SBK_KG * TILE_F > STG + (SBK_KG - 1) * 4096 ? SBK_KG * TILE_F : STG + (SBK_KG - 1) * 4096;
     constexpr int lds = (F + SBK_KG * 8) * 4;                           // + the stage maxima of the self-scaled form
-    static bool attr_done[64] = {};                   // per template instantiation and device ordinal
-    const void* fns[1] = {(const void*)k_gemm_sbk<LA, LB, PRO, NP, SBK_KG>};
-    if (int rc = facl_set_dynamic_lds(attr_done, fns, 1, lds)) return rc;
-    dim3 grid((g.NJ + 63) / 64, (g.MI + 63) / 64, nz);
-    hipLaunchKernelGGL((k_gemm_sbk<LA, LB, PRO, NP, SBK_KG>), grid, dim3(256 * SBK_KG), lds, st, g);
+    const dim3 grid((g.NJ + 63) / 64, (g.MI + 63) / 64, nz);
+    return facl_launch_dynamic_lds<k_gemm_sbk<LA, LB, PRO, NP, SBK_KG>>(grid, dim3(256 * SBK_KG), lds, st, g);
+}
+
+// FACL_GEMM_F32=1 selects the exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32) for fp32-grade results (prec 0) instead of
+// the split-bf16 ones
+bool use_f32_mfma() {
+    static const int use_f32 = facl_env_int("FACL_GEMM_F32", 0);
+    return use_f32 != 0;
+}
+
+// THE tile choice, for the launcher and for every entry that must know it beforehand:
+//   SBK   in-workgroup split-K on 64x64 tiles: one wave of workgroups and enough stages to share out;
+//   T128  128x128 blocks when they already fill the chip;
+//   T64   else 64x64 blocks (4x the workgroups) -- the FC head (M = 768 or 32 rows) would otherwise run on 48 or 8 of the 256 CUs.
+// rows_per_part: output rows behind one row of column-statistics partials (g.part).
+// fills128: the 128x128 blocks alone fill the chip.  With nz >= 256 slices of one small tile SBK holds as well and wins; the
+// fp32-MFMA kernels (FACL_GEMM_F32=1) have no SBK form and go by fills128 alone.
+enum TileFamily { SBK, T128, T64 };
+struct TileChoice { TileFamily family; int rows_per_part; bool fills128; };
+TileChoice choose_tile(const GemmArgs& g, int nz) {
+    static const int nosbk = facl_env_int("FACL_GEMM_NOSBK", 0);
+    const long long t64 = (long long)((g.NJ + 63) / 64) * ((g.MI + 63) / 64) * nz;
+    const bool fills128 = (long long)((g.NJ + 127) / 128) * ((g.MI + 127) / 128) * nz >= 256;
+    if (!nosbk && t64 <= 320 && g.kchunk >= 2 * SBK_KG * BK) return {SBK, 32, fills128};
+    return fills128 ? TileChoice{T128, 64, true} : TileChoice{T64, 32, false};
+}
+
+// the split path (k_gemm_sb / k_gemm_sbk) with NP planes per operand
+template <int LA, int LB, bool PRO, int NP>
+int launch_split(const GemmArgs& g, int nz, const TileChoice& tc, hipStream_t st) {
+    if (tc.family == SBK) return launch_sbk<LA, LB, PRO, NP>(g, nz, st);
+    if (tc.family == T128)
+        hipLaunchKernelGGL((k_gemm_sb<LA, LB, PRO, 2, 2, NP>), dim3((g.NJ + 127) / 128, (g.MI + 127) / 128, nz), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((k_gemm_sb<LA, LB, PRO, 1, 1, NP>), dim3((g.NJ + 63) / 64, (g.MI + 63) / 64, nz), dim3(256), 0, st, g);
     return facl_launch_status();
 }
-// one wave of 64x64 workgroups and enough stages to share out
-static inline bool sbk_fits(const GemmArgs& g, int nz) {
-    static const int off = getenv("FACL_GEMM_NOSBK") ? atoi(getenv("FACL_GEMM_NOSBK")) : 0;
-    const long long t64 = (long long)((g.NJ + 63) / 64) * ((g.MI + 63) / 64) * nz;
-    return !off && t64 <= 320 && g.kchunk >= 2 * SBK_KG * BK;
+
+template <int LA, int LB, bool PRO>
+int launch(const GemmArgs& g, int nz, hipStream_t st, int* rows_per_part) {
+    const TileChoice tc = choose_tile(g, nz);
+    if (rows_per_part) *rows_per_part = tc.rows_per_part;
+    if (g.prec == 1) return launch_split<LA, LB, PRO, 1>(g, nz, tc, st);   // fp16-input MFMA, fp32 accumulation
+    if (g.prec == 2) return launch_split<LA, LB, PRO, 2>(g, nz, tc, st);   // bf16x3 (opt-in)
+    if (!use_f32_mfma()) {
+        // OPT-IN FACL_SBK_H3=1: self-scaled fp16x3 (k_gemm_sbk, NP = 4; not with a prologue).  Measured inside the step: 2.938 vs
+        // 2.946 ms, stand-alone -7..-9 % at K = 1024 -- the split is ~20 % cheaper, not 2.7x: the maximum exchange, the per-stage
+        // rescale and the accumulator reset take back most of what the shorter split gives.  Default: bf16x6.
+        if constexpr (!PRO) {
+            static const int sbk_h3 = facl_env_int("FACL_SBK_H3", 0);
+            if (tc.family == SBK && sbk_h3) return launch_sbk<LA, LB, false, 4>(g, nz, st);
+        }
+        return launch_split<LA, LB, PRO, 3>(g, nz, tc, st);
+    }
+    // LDS-DMA needs 16-byte aligned 4-element pieces: leading dimensions and extents multiples of 4
+    // Measured A/B in one process (49152-row layers): the DMA path wins when BOTH operands are idx-contiguous
+    // (wgrad: 0.431 vs 0.538 ms at 1024x512) and loses a few % when a k-contiguous operand needs the
+    // source-side swizzle (forward 0.564 vs 0.552, dgrad 0.475 vs 0.460) -> used for wgrad only.
+    static const int use_dma = facl_env_int("FACL_GEMM_DMA", 1);
+    const bool dma_ok = use_dma && !PRO && LA == IC && LB == IC && !(g.lda & 3) && !(g.ldb & 3) && !(g.MI & 3) &&
+                        !(g.NJ & 3) && !(((uintptr_t)g.A | (uintptr_t)g.B) & 15);
+    if (rows_per_part) *rows_per_part = tc.fills128 ? 64 : 32;
+    if (tc.fills128) {
+        const dim3 grid((g.NJ + 127) / 128, (g.MI + 127) / 128, nz);
+        if (dma_ok) hipLaunchKernelGGL((k_gemm_dma<LA, LB, 2, 2>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((k_gemm<LA, LB, PRO, 2, 2>), grid, dim3(256), 0, st, g);
+    } else {
+        const dim3 grid((g.NJ + 63) / 64, (g.MI + 63) / 64, nz);
+        if (dma_ok) hipLaunchKernelGGL((k_gemm_dma<LA, LB, 1, 1>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((k_gemm<LA, LB, PRO, 1, 1>), grid, dim3(256), 0, st, g);
+    }
+    return facl_launch_status();
 }
 
 // sum over split-K slices: out[e] = sum_z part[z][e], slices added in order (deterministic); four slice loads in flight
@@ -1002,89 +1029,37 @@ __global__ __launch_bounds__(256) void k_sum_slices_par(const float* __restrict_
     }
 }
 
-static int launch_k_sum_slices(const float* slices, int nz, long long n4, float* dW, hipStream_t st) {
-    static const int par = getenv("FACL_SUM_SLICES_PAR") ? atoi(getenv("FACL_SUM_SLICES_PAR")) : 1;
-    if (par && nz >= 8) {
-        hipLaunchKernelGGL(k_sum_slices_par, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, slices, nz, n4, dW);
+}  // namespace
+
+// out[e] = sum_z slices[z][e] over nz split-K slices of n4 float4s each (used by gemm_rs.hip as well).  par_ok = false
+// pins the serial kernel.
+int facl_sum_slices(const float* slices, int nz, long long n4, float* out, bool par_ok, hipStream_t st) {
+    static const int par = facl_env_int("FACL_SUM_SLICES_PAR", 1);
+    if (par_ok && par && nz >= 8) {
+        hipLaunchKernelGGL(k_sum_slices_par, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, slices, nz, n4, out);
     } else {
         const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-        hipLaunchKernelGGL(k_sum_slices, dim3(grid), dim3(256), 0, st, slices, nz, n4, dW);
+        hipLaunchKernelGGL(k_sum_slices, dim3(grid), dim3(256), 0, st, slices, nz, n4, out);
     }
     return facl_launch_status();
 }
 
-template <int LA, int LB, bool PRO, int NP>
-int launch_sb_np(const GemmArgs& g, int nz, long long big, hipStream_t st, int* rows_per_part) {
-    if (sbk_fits(g, nz)) {
-        if (rows_per_part) *rows_per_part = 32;
-        return launch_sbk<LA, LB, PRO, NP>(g, nz, st);
-    }
-    if (big >= 256) {
-        dim3 grid((g.NJ + 127) / 128, (g.MI + 127) / 128, nz);
-        hipLaunchKernelGGL((k_gemm_sb<LA, LB, PRO, 2, 2, NP>), grid, dim3(256), 0, st, g);
-        if (rows_per_part) *rows_per_part = 64;
-    } else {
-        dim3 grid((g.NJ + 63) / 64, (g.MI + 63) / 64, nz);
-        hipLaunchKernelGGL((k_gemm_sb<LA, LB, PRO, 1, 1, NP>), grid, dim3(256), 0, st, g);
-        if (rows_per_part) *rows_per_part = 32;
-    }
-    return facl_launch_status();
+// Split-K weight gradient: g.KK rows in nz chunks (rounded up to whole stages, nz recomputed), one slice of g.C = `slices` per
+// chunk from the kernel that `launch_kernel(g, nz)` starts (it may refuse with an error code), slices summed into dW.
+template <class LAUNCH>
+static int split_k(GemmArgs g, int nz, float* dW, hipStream_t st, LAUNCH launch_kernel) {
+    g.kchunk = (int)(((long long)g.KK + nz - 1) / nz);
+    g.kchunk = (g.kchunk + BK - 1) / BK * BK;
+    nz = (int)(((long long)g.KK + g.kchunk - 1) / g.kchunk);
+    if (int rc = launch_kernel(g, nz)) return rc;
+    return facl_sum_slices(g.C, nz, (long long)g.MI * g.NJ / 4, dW, true, st);
 }
 
-// tile choice: 128x128 blocks when they already fill the chip, else 64x64 blocks (4x the workgroups) -- the FC head
-// (M = 768 or 32 rows) would otherwise run on 48 or 8 of the 256 CUs
-template <int LA, int LB, bool PRO>
-int launch(const GemmArgs& g, int nz, hipStream_t st, int* rows_per_part) {
-    const long long big = (long long)((g.NJ + 127) / 128) * ((g.MI + 127) / 128) * nz;
-    static const int use_dma = getenv("FACL_GEMM_DMA") ? atoi(getenv("FACL_GEMM_DMA")) : 1;
-    // FACL_GEMM_F32=1 selects the exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32) instead of the split-bf16 ones
-    static const int use_f32 = getenv("FACL_GEMM_F32") ? atoi(getenv("FACL_GEMM_F32")) : 0;
-    if (g.prec == 1) return launch_sb_np<LA, LB, PRO, 1>(g, nz, big, st, rows_per_part);   // fp16-input MFMA, fp32 accumulation
-    if (g.prec == 2) return launch_sb_np<LA, LB, PRO, 2>(g, nz, big, st, rows_per_part);   // bf16x3 (opt-in)
-    if (!use_f32) {
-        if (sbk_fits(g, nz)) {
-            if (rows_per_part) *rows_per_part = 32;
-            // OPT-IN FACL_SBK_H3=1: self-scaled fp16x3 (k_gemm_sbk, NP = 4; not with a prologue).  Measured inside the step: 2.938 vs
-            // 2.946 ms (gpurun_out/r7b_ab.log), stand-alone -7..-9 % at K = 1024 -- the split is ~20 % cheaper, not 2.7x: the maximum
-            // exchange, the per-stage rescale and the accumulator reset take back most of what the shorter split gives.  Default: bf16x6.
-            static const int sbk_h3 = getenv("FACL_SBK_H3") ? atoi(getenv("FACL_SBK_H3")) : 0;
-            if constexpr (!PRO) {
-                if (sbk_h3) return launch_sbk<LA, LB, false, 4>(g, nz, st);
-            }
-            return launch_sbk<LA, LB, PRO, 3>(g, nz, st);
-        }
-        if (big >= 256) {
-            dim3 grid((g.NJ + 127) / 128, (g.MI + 127) / 128, nz);
-            hipLaunchKernelGGL((k_gemm_sb<LA, LB, PRO, 2, 2>), grid, dim3(256), 0, st, g);
-            if (rows_per_part) *rows_per_part = 64;
-        } else {
-            dim3 grid((g.NJ + 63) / 64, (g.MI + 63) / 64, nz);
-            hipLaunchKernelGGL((k_gemm_sb<LA, LB, PRO, 1, 1>), grid, dim3(256), 0, st, g);
-            if (rows_per_part) *rows_per_part = 32;
-        }
-        return facl_launch_status();
-    }
-    // LDS-DMA needs 16-byte aligned 4-element pieces: leading dimensions and extents multiples of 4
-    // Measured A/B in one process (49152-row layers): the DMA path wins when BOTH operands are idx-contiguous
-    // (wgrad: 0.431 vs 0.538 ms at 1024x512) and loses a few % when a k-contiguous operand needs the
-    // source-side swizzle (forward 0.564 vs 0.552, dgrad 0.475 vs 0.460) -> used for wgrad only.
-    const bool dma_ok = use_dma && !PRO && LA == IC && LB == IC && !(g.lda & 3) && !(g.ldb & 3) && !(g.MI & 3) &&
-                        !(g.NJ & 3) && !(((uintptr_t)g.A | (uintptr_t)g.B) & 15);
-    if (big >= 256) {
-        dim3 grid((g.NJ + 127) / 128, (g.MI + 127) / 128, nz);
-        if (dma_ok) hipLaunchKernelGGL((k_gemm_dma<LA, LB, 2, 2>), grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((k_gemm<LA, LB, PRO, 2, 2>), grid, dim3(256), 0, st, g);
-        if (rows_per_part) *rows_per_part = 64;
-    } else {
-        dim3 grid((g.NJ + 63) / 64, (g.MI + 63) / 64, nz);
-        if (dma_ok) hipLaunchKernelGGL((k_gemm_dma<LA, LB, 1, 1>), grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((k_gemm<LA, LB, PRO, 1, 1>), grid, dim3(256), 0, st, g);
-        if (rows_per_part) *rows_per_part = 32;
-    }
-    return facl_launch_status();
+// the statistics partials (one row per rows_per_part output rows, rounded to the workgroup's two wave rows) must fit the workspace
+static bool stats_rows_fit(int64_t M, int N, int rows_per_part, int* prow) {
+    *prow = (int)((M + 2 * rows_per_part - 1) / (2 * rows_per_part)) * 2;
+    return (size_t)*prow * N * 2 * sizeof(double) <= (size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES;
 }
-
-}  // namespace
 
 // y (M,N) = opA(a) W^T + bias (+ centres term), optional BN+ReLU prologue on a, optional column statistics
 static int gemm_fwd_p(const float* a, int64_t M, int K, const float* W, int ldw, int N, const float* bias,
@@ -1094,19 +1069,16 @@ static int gemm_fwd_p(const float* a, int64_t M, int K, const float* W, int ldw,
     if (M < 1 || M > 0x7fffffff || K < 4 || (K & 3) || N < 1 || (ldw & 3)) return FACL_E_SHAPE;
     if ((pscale == nullptr) != (pshift == nullptr) || (centers == nullptr) != (Wc == nullptr)) return FACL_E_NULL;
     hipStream_t st = (hipStream_t)stream;
-    GemmArgs g{a, K, W, ldw, y, N, (int)M, N, K, bias, pscale, pshift, centers, Wc, ldwc,
-               sums ? (double*)ws : nullptr, K, nullptr, nullptr, nullptr, prec};
-    int rpp = 64;
-    if (sums) {                                                        // the statistics partials must fit BEFORE anything is written
-        const long long big = (long long)((N + 127) / 128) * ((M + 127) / 128);
-        const int rpp0 = (big >= 256 && !sbk_fits(g, 1)) ? 64 : 32;
-        const long long prow0 = ((M + 2 * rpp0 - 1) / (2 * rpp0)) * 2;
-        if ((size_t)prow0 * N * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
-    }
+    GemmArgs g{a, K, W, ldw, y, N, (int)M, N, K};
+    g.bias = bias; g.pscale = pscale; g.pshift = pshift;
+    g.xa = centers; g.xb = Wc; g.ldxb = ldwc;
+    g.part = sums ? (double*)ws : nullptr;
+    g.kchunk = K; g.prec = prec;
+    int rpp = 64, prow = 0;
+    if (sums && !stats_rows_fit(M, N, choose_tile(g, 1).rows_per_part, &prow)) return FACL_E_SHAPE;   // BEFORE anything is written
     int rc = pscale ? launch<KC, KC, true>(g, 1, st, &rpp) : launch<KC, KC, false>(g, 1, st, &rpp);
     if (rc || !sums) return rc;
-    const int prow = (int)((M + 2 * rpp - 1) / (2 * rpp)) * 2;
-    if ((size_t)prow * N * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
+    if (!stats_rows_fit(M, N, rpp, &prow)) return FACL_E_SHAPE;
     // rows of the last (partial) tile that no wave wrote hold stale data only if M % 64 != 0 for the last
     // wave-row; such partial rows contribute nothing because those waves stored s = sq = 0.
     return facl_reduce_rows((const double*)ws, prow, 2 * N, sums, st);
@@ -1120,16 +1092,19 @@ static int gemm_fwd_segmax_p(const float* a, int64_t M, int K, const float* W, i
                              void* stream, int prec) {
     if (!a || !W || !y || !sgn || !ymax || !arg || (sums && !ws)) return FACL_E_NULL;
     if (M < 64 || M > 0x7fffffff || (M & 63) || K < 4 || (K & 3) || N < 1 || (ldw & 3)) return FACL_E_SHAPE;
-    if ((long long)((N + 127) / 128) * ((M + 127) / 128) < 256) return FACL_E_CONFIG;    // needs the 128x128 tiles
+    GemmArgs g{a, K, W, ldw, y, N, (int)M, N, K};
+    g.bias = bias;
+    g.part = sums ? (double*)ws : nullptr;
+    g.sgn = sgn; g.smax = ymax; g.sarg = arg;
+    g.kchunk = K; g.prec = prec;
+    const TileChoice tc = choose_tile(g, 1);
+    if (tc.family != T128) return FACL_E_CONFIG;                       // the fused maximum lives in the 128x128 tiles
     hipStream_t st = (hipStream_t)stream;
-    GemmArgs g{a, K, W, ldw, y, N, (int)M, N, K, bias, nullptr, nullptr, nullptr, nullptr, 0,
-               sums ? (double*)ws : nullptr, K, sgn, ymax, arg, prec};
-    int rpp = 64;
-    if (sums && (size_t)(((M + 127) / 128) * 2) * N * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
+    int rpp = 64, prow = 0;
+    if (sums && !stats_rows_fit(M, N, tc.rows_per_part, &prow)) return FACL_E_SHAPE;
     int rc = launch<KC, KC, false>(g, 1, st, &rpp);
     if (rc || !sums) return rc;
-    const int prow = (int)((M + 2 * rpp - 1) / (2 * rpp)) * 2;
-    if ((size_t)prow * N * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
+    if (!stats_rows_fit(M, N, rpp, &prow)) return FACL_E_SHAPE;
     return facl_reduce_rows((const double*)ws, prow, 2 * N, sums, st);
 }
 
@@ -1138,7 +1113,8 @@ static int gemm_dgrad_p(const float* dy, int64_t M, int N, const float* W, int l
                         void* stream, int prec) {
     if (!dy || !W || !da) return FACL_E_NULL;
     if (M < 1 || M > 0x7fffffff || N < 4 || (N & 3) || K < 1) return FACL_E_SHAPE;
-    GemmArgs g{dy, N, W, ldw, da, K, (int)M, K, N, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, N, nullptr, nullptr, nullptr, prec};
+    GemmArgs g{dy, N, W, ldw, da, K, (int)M, K, N};
+    g.kchunk = N; g.prec = prec;
     return launch<KC, IC, false>(g, 1, (hipStream_t)stream, nullptr);
 }
 
@@ -1148,18 +1124,12 @@ static int gemm_wgrad_p(const float* dy, const float* a, int64_t M, int N, int K
     if (!dy || !a || !dW || !slices) return FACL_E_NULL;
     if (M < 1 || M > 0x7fffffff || N < 4 || (N & 3) || K < 4 || (K & 3) || nz < 1 || nz > 1024) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    {   // few rows (the FC head): the workgroup splits the contraction itself and writes dW directly, no slices
-        GemmArgs g1{dy, N, a, lda, dW, K, N, K, (int)M, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, (int)M, nullptr, nullptr, nullptr, prec};
-        if (M <= 8192 && sbk_fits(g1, 1)) return launch<IC, IC, false>(g1, 1, st, nullptr);
-    }
-    int kchunk = (int)((M + nz - 1) / nz);
-    kchunk = (kchunk + BK - 1) / BK * BK;
-    nz = (int)((M + kchunk - 1) / kchunk);
-    GemmArgs g{dy, N, a, lda, slices, K, N, K, (int)M, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, kchunk, nullptr, nullptr, nullptr, prec};
-    int rc = launch<IC, IC, false>(g, nz, st, nullptr);
-    if (rc) return rc;
-    const long long n4 = (long long)N * K / 4;
-    return launch_k_sum_slices(slices, nz, n4, dW, st);
+    GemmArgs g{dy, N, a, lda, dW, K, N, K, (int)M};
+    g.kchunk = (int)M; g.prec = prec;
+    // few rows (the FC head): the workgroup splits the contraction itself and writes dW directly, no slices
+    if (M <= 8192 && choose_tile(g, 1).family == SBK) return launch<IC, IC, false>(g, 1, st, nullptr);
+    g.C = slices;
+    return split_k(g, nz, dW, st, [&](const GemmArgs& gz, int z) { return launch<IC, IC, false>(gz, z, st, nullptr); });
 }
 
 // dW (N,K) = dy^T (N,M) relu(pscale * y + pshift) (M,K): the weight gradient of a layer whose input activation is the
@@ -1170,22 +1140,17 @@ static int gemm_wgrad_pro_p(const float* dy, const float* y, int64_t M, int N, i
                             const float* pshift, float* dW, float* slices, int nz, void* stream, int prec) {
     if (!dy || !y || !pscale || !pshift || !dW || !slices) return FACL_E_NULL;
     if (M < 1 || M > 0x7fffffff || N < 4 || (N & 3) || K < 4 || (K & 3) || nz < 1 || nz > 1024) return FACL_E_SHAPE;
-    static const int use_f32 = getenv("FACL_GEMM_F32") ? atoi(getenv("FACL_GEMM_F32")) : 0;
-    if (use_f32 || prec == 1) return FACL_E_CONFIG;
+    if (use_f32_mfma() || prec == 1) return FACL_E_CONFIG;
     hipStream_t st = (hipStream_t)stream;
-    int kchunk = (int)((M + nz - 1) / nz);
-    kchunk = (kchunk + BK - 1) / BK * BK;
-    nz = (int)((M + kchunk - 1) / kchunk);
-    GemmArgs g{dy, N, y, ldy, slices, K, N, K, (int)M, nullptr, pscale, pshift, nullptr, nullptr, 0, nullptr, kchunk, nullptr, nullptr, nullptr, prec};
-    const long long big = (long long)((K + 127) / 128) * ((N + 127) / 128) * nz;
-    if (big < 256 || sbk_fits(g, nz)) return FACL_E_CONFIG;
-    dim3 grid((K + 127) / 128, (N + 127) / 128, nz);
-    if (prec == 2) hipLaunchKernelGGL((k_gemm_sb<IC, IC, true, 2, 2, 2>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_sb<IC, IC, true, 2, 2, 3>), grid, dim3(256), 0, st, g);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    const long long n4 = (long long)N * K / 4;
-    return launch_k_sum_slices(slices, nz, n4, dW, st);
+    GemmArgs g{dy, N, y, ldy, slices, K, N, K, (int)M};
+    g.pscale = pscale; g.pshift = pshift; g.prec = prec;
+    return split_k(g, nz, dW, st, [&](const GemmArgs& gz, int z) {
+        if (choose_tile(gz, z).family != T128) return (int)FACL_E_CONFIG;
+        const dim3 grid((K + 127) / 128, (N + 127) / 128, z);
+        if (prec == 2) hipLaunchKernelGGL((k_gemm_sb<IC, IC, true, 2, 2, 2>), grid, dim3(256), 0, st, gz);
+        else hipLaunchKernelGGL((k_gemm_sb<IC, IC, true, 2, 2, 3>), grid, dim3(256), 0, st, gz);
+        return facl_launch_status();
+    });
 }
 
 // fp16x3 weight gradient on the 128x128-tile kernel: dW (N,K) = dy^T f(y), f = relu(pscale*y + pshift) per column when pscale
@@ -1197,22 +1162,17 @@ extern "C" int facl_gemm_wgrad_h3(const float* dy, const float* y, int64_t M, in
                                   int nz, void* stream) {
     if (!dy || !y || !amax || !amax_b || !dW || !slices || (pscale == nullptr) != (pshift == nullptr)) return FACL_E_NULL;
     if (M < 1 || M > 0x7fffffff || N < 4 || (N & 3) || K < 4 || (K & 3) || nz < 1 || nz > 1024) return FACL_E_SHAPE;
-    static const int use_f32 = getenv("FACL_GEMM_F32") ? atoi(getenv("FACL_GEMM_F32")) : 0;
-    if (use_f32) return FACL_E_CONFIG;
+    if (use_f32_mfma()) return FACL_E_CONFIG;
     hipStream_t st = (hipStream_t)stream;
-    int kchunk = (int)((M + nz - 1) / nz);
-    kchunk = (kchunk + BK - 1) / BK * BK;
-    nz = (int)((M + kchunk - 1) / kchunk);
-    GemmArgs g{dy, N, y, ldy, slices, K, N, K, (int)M, nullptr, pscale, pshift, nullptr, nullptr, 0, nullptr, kchunk, nullptr, nullptr, nullptr, 0, amax, amax_b};
-    const long long big = (long long)((K + 127) / 128) * ((N + 127) / 128) * nz;
-    if (big < 256 || sbk_fits(g, nz)) return FACL_E_CONFIG;
-    dim3 grid((K + 127) / 128, (N + 127) / 128, nz);
-    if (pscale) hipLaunchKernelGGL((k_gemm_sb<IC, IC, true, 2, 2, 4>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((k_gemm_sb<IC, IC, false, 2, 2, 4>), grid, dim3(256), 0, st, g);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    const long long n4 = (long long)N * K / 4;
-    return launch_k_sum_slices(slices, nz, n4, dW, st);
+    GemmArgs g{dy, N, y, ldy, slices, K, N, K, (int)M};
+    g.pscale = pscale; g.pshift = pshift; g.amax = amax; g.amax_b = amax_b;
+    return split_k(g, nz, dW, st, [&](const GemmArgs& gz, int z) {
+        if (choose_tile(gz, z).family != T128) return (int)FACL_E_CONFIG;
+        const dim3 grid((K + 127) / 128, (N + 127) / 128, z);
+        if (pscale) hipLaunchKernelGGL((k_gemm_sb<IC, IC, true, 2, 2, 4>), grid, dim3(256), 0, st, gz);
+        else hipLaunchKernelGGL((k_gemm_sb<IC, IC, false, 2, 2, 4>), grid, dim3(256), 0, st, gz);
+        return facl_launch_status();
+    });
 }
 
 extern "C" int facl_gemm_wgrad_pro(const float* dy, const float* y, int64_t M, int N, int K, int ldy, const float* pscale,
@@ -1288,8 +1248,8 @@ extern "C" int facl_gemm_wgrad_acc(const float* dy, const float* a, int64_t M, i
                                    void* stream) {
     if (!dy || !a || !dW) return FACL_E_NULL;
     if (M < 1 || M > 8192 || N < 4 || (N & 3) || K < 4 || (K & 3) || prec < 0 || prec > 2) return FACL_E_SHAPE;
-    GemmArgs g1{dy, N, a, lda, dW, K, N, K, (int)M, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, (int)M, nullptr, nullptr, nullptr, prec};
-    g1.accum = 1;
-    if (!sbk_fits(g1, 1)) return FACL_E_CONFIG;
-    return launch<IC, IC, false>(g1, 1, (hipStream_t)stream, nullptr);
+    GemmArgs g{dy, N, a, lda, dW, K, N, K, (int)M};
+    g.kchunk = (int)M; g.prec = prec; g.accum = 1;
+    if (choose_tile(g, 1).family != SBK) return FACL_E_CONFIG;
+    return launch<IC, IC, false>(g, 1, (hipStream_t)stream, nullptr);
 }

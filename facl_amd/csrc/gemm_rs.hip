@@ -19,10 +19,13 @@
 // combined in LDS in fixed order, one fp64 partial row per workgroup), optional my_max_pool over each cloud's 64 rows
 // (two waves per cloud, merged through LDS, first row wins ties), 128-B row segments stored straight from registers.
 // Roofline: bf16 MFMA (2.5 PFLOP/s dense; 6 executed FLOPs per algorithmic one).
+// Host side: rs_launch / facl_gemm_rs_wgrad pick ONE instantiation through rs_launch_k / wg_launch_k, which set the kernel's
+// dynamic-LDS attribute on first use (common.h: facl_launch_dynamic_lds); the weight gradient's slices are summed by
+// facl_sum_slices (gemm.hip).
 #include "common.h"
-#include <stdlib.h>
 
 int facl_reduce_rows(const double* part, int rows, int V, double* out, hipStream_t st);
+int facl_sum_slices(const float* slices, int nz, long long n4, float* out, bool par_ok, hipStream_t st);   // gemm.hip
 extern "C" int64_t facl_ws_bytes(void);
 
 namespace {
@@ -45,25 +48,25 @@ constexpr int RS_KPRO = 512;                      // longest contraction WITH a 
 constexpr int RS_LDS = RS_LDS_W + RS_LDS_A + 2 * RS_KPRO * 4;     // 68 KiB
 
 struct RsArgs {
-    const float* A; int lda; int M; int K;        // K % 32 == 0
-    const uint4* Wp; int NT;                      // planes [k-step][NT column tiles][3][64]; NT = N / 32
-    int N;                                        // output columns, N % 256 == 0
-    const float* bias;                            // (N) or null
-    const float* pscale; const float* pshift;     // (K) prologue relu(scale*a + shift), or null
-    const float* centers;                         // (M,3) or null: k-step K/16 of Wp holds the centre columns
-    float* C; int ldc;
-    double* part;                                 // statistics partial rows [gridDim.y][2N], or null
-    const float* sgn; float* smax; int* sarg;     // my_max_pool over blocks of 64 rows: (M/64, N), or null
+    const float* A = nullptr; int lda = 0; int M = 0; int K = 0;   // K % 32 == 0
+    const uint4* Wp = nullptr; int NT = 0;        // planes [k-step][NT column tiles][3][64]; NT = N / 32
+    int N = 0;                                    // output columns, N % 256 == 0
+    const float* bias = nullptr;                  // (N) or null
+    const float* pscale = nullptr; const float* pshift = nullptr;   // (K) prologue relu(scale*a + shift), or null
+    const float* centers = nullptr;               // (M,3) or null: k-step K/16 of Wp holds the centre columns
+    float* C = nullptr; int ldc = 0;
+    double* part = nullptr;                       // statistics partial rows [gridDim.y][2N], or null
+    const float* sgn = nullptr; float* smax = nullptr; int* sarg = nullptr;   // my_max_pool over blocks of 64 rows: (M/64, N), or null
     // dgrad only: the output IS dL/da of a layer a = relu(bn(y)); with `by` (M,N) = that layer's raw output and `bbnc`
     // (>= 4 x N: mean | invstd | scale | shift) the partial rows hold the BatchNorm-backward sums of the column instead:
     // (sum_r d, sum_r d * yhat), d = C[r] where scale*y + shift > 0 else 0, yhat = (y - mean) * invstd
-    const float* by; const float* bbnc;
-    int h3;                                       // 1: fp16x3 planes / arithmetic, 0: bf16x6
-    const unsigned* amax;                         // h3 only: bits of (a bound of) max|A| in FACL_AMAX_SLOTS slots -> the
+    const float* by = nullptr; const float* bbnc = nullptr;
+    int h3 = 0;                                   // 1: fp16x3 planes / arithmetic, 0: bf16x6
+    const unsigned* amax = nullptr;               // h3 only: bits of (a bound of) max|A| in FACL_AMAX_SLOTS slots -> the
                                                   // power-of-two scale of A (activations: their bound, gradients: max|dy|)
-    const int* wse;                               // h3 only: biased exponent of the weight scale per 32-column tile (k_rs_planes)
-    int phase_ticks;                              // experiment (FACL_RS_PHASE): first-round workgroups in the CU's second slot start this many 100-MHz ticks late
-    int first_round;                              // number of workgroups resident at launch (2 per CU)
+    const int* wse = nullptr;                     // h3 only: biased exponent of the weight scale per 32-column tile (k_rs_planes)
+    int phase_ticks = 0;                          // experiment (FACL_RS_PHASE): first-round workgroups in the CU's second slot start this many 100-MHz ticks late
+    int first_round = 0;                          // number of workgroups resident at launch (2 per CU)
 };
 
 
@@ -184,13 +187,11 @@ __global__ __launch_bounds__(256) void k_rs_planes_multi(RsPlaneJobs jb) {
 }
 
 struct RsTile { int x, y; };
-// XCD-aware order (as gemm.hip: xcd_tile): each XCD walks a contiguous range of (row group, column block) tiles,
+// XCD-aware order (common.h: facl_xcd_tile): each XCD walks a contiguous range of (row group, column block) tiles,
 // column blocks fastest, so the column blocks that re-read one 256-row panel of A hit the same L2.
 __device__ __forceinline__ RsTile rs_tile() {
-    const int nbx = gridDim.x, total = nbx * gridDim.y;
-    const int b = blockIdx.x + nbx * blockIdx.y;
-    const int per = total >> 3, rem = total & 7, xcd = b & 7, slot = b >> 3;
-    const int L = (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + slot;
+    const int nbx = gridDim.x;
+    const int L = facl_xcd_tile(blockIdx.x + nbx * blockIdx.y, nbx * gridDim.y);
     RsTile t;
     t.x = L % nbx; t.y = L / nbx;
     return t;
@@ -638,10 +639,8 @@ __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad_rs(WgArgs g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware order: the K/128 workgroups that read the same dy rows (same n block, same row slice) are consecutive
     // logical tiles, and each XCD (one L2) walks a contiguous range of them (PMC: 1.0 GB fetched per launch without it)
-    const int gx = gridDim.x, gy = gridDim.y, total = gx * gy * gridDim.z;
-    const int bl = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    const int per = total >> 3, rem = total & 7, xcd = bl & 7, slot = bl >> 3;
-    const int L = (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + slot;
+    const int gx = gridDim.x, gy = gridDim.y;
+    const int L = facl_xcd_tile(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
     const int bx = L % gx, by = (L / gx) % gy, bz = L / (gx * gy);
     const int k0 = bx * 128, n0 = by * 512 + wave * 64;
     const int p0 = bz * g.rows_per_slice;
@@ -841,27 +840,12 @@ __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad_rs(WgArgs g) {
         }
 }
 
-// sum over the row slices, in order (deterministic); four slice loads in flight per thread
-__global__ void k_wg_sum_slices(const float* __restrict__ part, int nz, long long n4, float* __restrict__ out) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    const float4* p4 = reinterpret_cast<const float4*>(part);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        float4 s = p4[i];
-        int z = 1;
-        for (; z + 3 < nz; z += 4) {
-            const float4 v0 = p4[(size_t)z * n4 + i], v1 = p4[(size_t)(z + 1) * n4 + i];
-            const float4 v2 = p4[(size_t)(z + 2) * n4 + i], v3 = p4[(size_t)(z + 3) * n4 + i];
-            s.x += v0.x; s.y += v0.y; s.z += v0.z; s.w += v0.w;
-            s.x += v1.x; s.y += v1.y; s.z += v1.z; s.w += v1.w;
-            s.x += v2.x; s.y += v2.y; s.z += v2.z; s.w += v2.w;
-            s.x += v3.x; s.y += v3.y; s.z += v3.z; s.w += v3.w;
-        }
-        for (; z < nz; ++z) {
-            const float4 v = p4[(size_t)z * n4 + i];
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        reinterpret_cast<float4*>(out)[i] = s;
-    }
+// dynamic LDS of k_wgrad_rs: plane ring (48 / 32 KiB) + per-wave staging (WIDE: the dy image, 8.5 KiB per wave; else the 4-KiB
+// epilogue tile)
+template <bool PRO, bool H3, bool WIDE>
+int wg_launch_k(const WgArgs& g, dim3 grid, hipStream_t st) {
+    constexpr int lds = 2 * (2 * 4 * (H3 ? 2 : 3) * 64) * 16 + WG_WAVES * 32 * (WIDE ? WG_TP : 32) * 4;
+    return facl_launch_dynamic_lds<k_wgrad_rs<PRO, H3, WIDE>>(grid, dim3(64 * WG_WAVES), lds, st, g);
 }
 
 constexpr int RS_LDS8 = RS_LDS_W + 8 * RS_ASLOT + 2 * RS_KPRO * 4 + 8 * 6144;     // 132 KiB: one 8-wave workgroup per CU
@@ -871,8 +855,23 @@ constexpr int RS_LDS8 = RS_LDS_W + 8 * RS_ASLOT + 2 * RS_KPRO * 4 + 8 * 6144;   
 // 0.184 ms, dgrad 1024->512 0.187 vs 0.176, step 3.023 vs 3.006 ms; gpurun_out/r5g_ab.log) -- the weight-plane traffic is
 // not what bounds these kernels.  Default: 4 waves, two workgroups per CU.
 int rs_waves(int h3) {
-    static const int w8 = getenv("FACL_RS_W8") ? atoi(getenv("FACL_RS_W8")) : 0;
+    static const int w8 = facl_env_int("FACL_RS_W8", 0);
     return (h3 && w8) ? 8 : RS_WAVES;
+}
+
+template <bool PRO, bool SEG, bool BST, bool H3, int WV>
+int rs_launch_k(const RsArgs& g, hipStream_t st) {
+    const dim3 grid(g.N / 256, (g.M + 32 * WV - 1) / (32 * WV));
+    return facl_launch_dynamic_lds<k_gemm_rs<PRO, SEG, BST, H3, WV>>(grid, dim3(64 * WV), WV == 8 ? RS_LDS8 : RS_LDS, st, g);
+}
+// the BatchNorm-backward statistics (g.by) exclude prologue and segment maximum (dgrad only)
+template <bool H3, int WV>
+int rs_launch_form(const RsArgs& g, hipStream_t st) {
+    if (g.by) return rs_launch_k<false, false, true, H3, WV>(g, st);
+    if (g.pscale && g.smax) return rs_launch_k<true, true, false, H3, WV>(g, st);
+    if (g.pscale) return rs_launch_k<true, false, false, H3, WV>(g, st);
+    if (g.smax) return rs_launch_k<false, true, false, H3, WV>(g, st);
+    return rs_launch_k<false, false, false, H3, WV>(g, st);
 }
 
 int rs_launch(const RsArgs& g0, hipStream_t st) {
@@ -880,59 +879,13 @@ int rs_launch(const RsArgs& g0, hipStream_t st) {
     {   // Phase offset of the CU's second workgroup slot (see the kernel): ticks x k-steps + 500 of the 100-MHz counter, i.e. about
         // half a workgroup's life; only where the launch runs MORE than one round of workgroups (else the wait is pure loss:
         // measured +5..9 % on the 384-workgroup launches).  FACL_RS_PHASE=<ticks per k-step> overrides, 0 = off.
-        static const int per_ks = getenv("FACL_RS_PHASE") ? atoi(getenv("FACL_RS_PHASE")) : 30;
+        static const int per_ks = facl_env_int("FACL_RS_PHASE", 30);
         const long long wgs = (long long)(g.N / 256) * ((g.M + 32 * rs_waves(g.h3) - 1) / (32 * rs_waves(g.h3)));
         g.first_round = 512;
         g.phase_ticks = (per_ks > 0 && wgs > g.first_round && rs_waves(g.h3) == RS_WAVES) ? per_ks * (g.K >> 4) + 500 : 0;
     }
-    // the dynamic-LDS attribute is per device: one flag per device ordinal (a process may drive several devices, and a
-    // forward on the main thread can race a backward on the autograd thread: the worst case sets the attribute twice)
-    static bool attr_done_dev[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    bool& attr_done = attr_done_dev[dev];
-    if (!attr_done) {
-        const void* fns[10] = {(const void*)k_gemm_rs<false, false, true, true>,(const void*)k_gemm_rs<false, false, false>, (const void*)k_gemm_rs<true, false, false>,
-                              (const void*)k_gemm_rs<false, true, false>, (const void*)k_gemm_rs<true, true, false>,
-                              (const void*)k_gemm_rs<false, false, true>,
-                              (const void*)k_gemm_rs<false, false, false, true>, (const void*)k_gemm_rs<true, false, false, true>,
-                              (const void*)k_gemm_rs<false, true, false, true>, (const void*)k_gemm_rs<true, true, false, true>};
-        for (int i = 0; i < 10; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS);
-            if (e != hipSuccess) return (int)e;
-        }
-        const void* fns8[5] = {(const void*)k_gemm_rs<false, false, true, true, 8>, (const void*)k_gemm_rs<false, false, false, true, 8>,
-                               (const void*)k_gemm_rs<true, false, false, true, 8>, (const void*)k_gemm_rs<false, true, false, true, 8>,
-                               (const void*)k_gemm_rs<true, true, false, true, 8>};
-        for (int i = 0; i < 5; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns8[i], hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS8);
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_done = true;
-    }
-    if (rs_waves(g.h3) == 8) {
-        dim3 grid(g.N / 256, (g.M + 255) / 256);
-        const dim3 blk(512);
-        if (g.by) hipLaunchKernelGGL((k_gemm_rs<false, false, true, true, 8>), grid, blk, RS_LDS8, st, g);
-        else if (g.pscale && g.smax) hipLaunchKernelGGL((k_gemm_rs<true, true, false, true, 8>), grid, blk, RS_LDS8, st, g);
-        else if (g.pscale) hipLaunchKernelGGL((k_gemm_rs<true, false, false, true, 8>), grid, blk, RS_LDS8, st, g);
-        else if (g.smax) hipLaunchKernelGGL((k_gemm_rs<false, true, false, true, 8>), grid, blk, RS_LDS8, st, g);
-        else hipLaunchKernelGGL((k_gemm_rs<false, false, false, true, 8>), grid, blk, RS_LDS8, st, g);
-        return facl_launch_status();
-    }
-    dim3 grid(g.N / 256, (g.M + 32 * RS_WAVES - 1) / (32 * RS_WAVES));
-    const dim3 blk(64 * RS_WAVES);
-    if (g.by && g.h3) hipLaunchKernelGGL((k_gemm_rs<false, false, true, true>), grid, blk, RS_LDS, st, g);
-    else if (g.by) hipLaunchKernelGGL((k_gemm_rs<false, false, true>), grid, blk, RS_LDS, st, g);
-    else if (g.h3 && g.pscale && g.smax) hipLaunchKernelGGL((k_gemm_rs<true, true, false, true>), grid, blk, RS_LDS, st, g);
-    else if (g.h3 && g.pscale) hipLaunchKernelGGL((k_gemm_rs<true, false, false, true>), grid, blk, RS_LDS, st, g);
-    else if (g.h3 && g.smax) hipLaunchKernelGGL((k_gemm_rs<false, true, false, true>), grid, blk, RS_LDS, st, g);
-    else if (g.h3) hipLaunchKernelGGL((k_gemm_rs<false, false, false, true>), grid, blk, RS_LDS, st, g);
-    else if (g.pscale && g.smax) hipLaunchKernelGGL((k_gemm_rs<true, true, false>), grid, blk, RS_LDS, st, g);
-    else if (g.pscale) hipLaunchKernelGGL((k_gemm_rs<true, false, false>), grid, blk, RS_LDS, st, g);
-    else if (g.smax) hipLaunchKernelGGL((k_gemm_rs<false, true, false>), grid, blk, RS_LDS, st, g);
-    else hipLaunchKernelGGL((k_gemm_rs<false, false, false>), grid, blk, RS_LDS, st, g);
-    return facl_launch_status();
+    if (rs_waves(g.h3) == 8) return rs_launch_form<true, 8>(g, st);
+    return g.h3 ? rs_launch_form<true, RS_WAVES>(g, st) : rs_launch_form<false, RS_WAVES>(g, st);
 }
 
 }  // namespace
@@ -1021,8 +974,12 @@ extern "C" int facl_gemm_rs_fwd(const float* a, int64_t M, int K, const void* pl
     if (sums && (size_t)prow * N * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int* wse = (const int*)((const char*)planes + rs_planes_only_bytes(N, K, centers ? 1 : 0));
-    RsArgs g{a, K, (int)M, K, (const uint4*)planes, N / 32, N, bias, pscale, pshift, centers, y, N,
-             sums ? (double*)ws : nullptr, sgn, ymax, arg, nullptr, nullptr, half ? 1 : 0, amax_a, wse};
+    RsArgs g{a, K, (int)M, K, (const uint4*)planes, N / 32, N};
+    g.C = y; g.ldc = N;
+    g.bias = bias; g.pscale = pscale; g.pshift = pshift; g.centers = centers;
+    g.part = sums ? (double*)ws : nullptr;
+    g.sgn = sgn; g.smax = ymax; g.sarg = arg;
+    g.h3 = half ? 1 : 0; g.amax = amax_a; g.wse = wse;
     int rc = rs_launch(g, st);
     if (rc || !sums) return rc;
     return facl_reduce_rows((const double*)ws, prow, 2 * N, sums, st);
@@ -1037,8 +994,9 @@ extern "C" int facl_gemm_rs_dgrad(const float* dy, int64_t M, int N, const void*
     if (!facl_gemm_rs_supported(M, N, K)) return FACL_E_SHAPE;
     if (((uintptr_t)dy | (uintptr_t)planes) & 15) return FACL_E_ALIGN;
     const int* wse = (const int*)((const char*)planes + rs_planes_only_bytes(K, N, 0));
-    RsArgs g{dy, N, (int)M, N, (const uint4*)planes, K / 32, K, nullptr, nullptr, nullptr, nullptr, da, K,
-             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, half ? 1 : 0, amax, wse};
+    RsArgs g{dy, N, (int)M, N, (const uint4*)planes, K / 32, K};
+    g.C = da; g.ldc = K;
+    g.h3 = half ? 1 : 0; g.amax = amax; g.wse = wse;
     return rs_launch(g, (hipStream_t)stream);
 }
 
@@ -1057,8 +1015,10 @@ extern "C" int facl_gemm_rs_dgrad_bnstats(const float* dy, int64_t M, int N, con
     if ((size_t)prow * K * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int* wse = (const int*)((const char*)planes + rs_planes_only_bytes(K, N, 0));
-    RsArgs g{dy, N, (int)M, N, (const uint4*)planes, K / 32, K, nullptr, nullptr, nullptr, nullptr, da, K,
-             (double*)ws, nullptr, nullptr, nullptr, y, bnc, half ? 1 : 0, amax, wse};
+    RsArgs g{dy, N, (int)M, N, (const uint4*)planes, K / 32, K};
+    g.C = da; g.ldc = K;
+    g.part = (double*)ws; g.by = y; g.bbnc = bnc;
+    g.h3 = half ? 1 : 0; g.amax = amax; g.wse = wse;
     int rc = rs_launch(g, st);
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, prow, 2 * K, sums, st);
@@ -1096,28 +1056,16 @@ extern "C" int facl_gemm_rs_wgrad(const float* dy, const float* y, int64_t M, in
     rps = (rps + 31) / 32 * 32;
     hipStream_t st = (hipStream_t)stream;
     WgArgs g{dy, y, (int)M, N, K, pscale, pshift, slices, rps, amax, amax_b};
-    dim3 grid(K / 128, N / 512, nz);
-    const dim3 blk(64 * WG_WAVES);
-    // dynamic LDS: plane ring (48 / 32 KiB) + per-wave staging (WIDE: the dy image, 8.5 KiB per wave; else the 4-KiB epilogue tile)
-    static const int wide_env = getenv("FACL_WGRAD_WIDE") ? atoi(getenv("FACL_WGRAD_WIDE")) : 1;  // 0: dword fragment loads (A/B)
+    const dim3 grid(K / 128, N / 512, nz);
+    static const int wide_env = facl_env_int("FACL_WGRAD_WIDE", 1);                                // 0: dword fragment loads (A/B)
     const int wide = wide_env && !(((uintptr_t)dy) & 15);                                          // the 16-byte row loads need an aligned dy
-    const int lds3 = 2 * (2 * 4 * 3 * 64) * 16, lds2 = 2 * (2 * 4 * 2 * 64) * 16;
-    const int stg_n = WG_WAVES * 32 * 32 * 4, stg_w = WG_WAVES * 32 * WG_TP * 4;
-    static bool attr_done[64] = {};
-    const void* fns[6] = {(const void*)k_wgrad_rs<true, true>, (const void*)k_wgrad_rs<true, false>, (const void*)k_wgrad_rs<false, true>,
-                          (const void*)k_wgrad_rs<false, false>, (const void*)k_wgrad_rs<true, true, true>,
-                          (const void*)k_wgrad_rs<false, true, true>};
-    if (int rc0 = facl_set_dynamic_lds(attr_done, fns, 6, lds3 + stg_w)) return rc0;
-    if (pscale && amax && wide) hipLaunchKernelGGL((k_wgrad_rs<true, true, true>), grid, blk, lds2 + stg_w, st, g);
-    else if (amax && wide) hipLaunchKernelGGL((k_wgrad_rs<false, true, true>), grid, blk, lds2 + stg_w, st, g);
-    else if (pscale && amax) hipLaunchKernelGGL((k_wgrad_rs<true, true>), grid, blk, lds2 + stg_n, st, g);
-    else if (pscale) hipLaunchKernelGGL((k_wgrad_rs<true, false>), grid, blk, lds3 + stg_n, st, g);
-    else if (amax) hipLaunchKernelGGL((k_wgrad_rs<false, true>), grid, blk, lds2 + stg_n, st, g);
-    else hipLaunchKernelGGL((k_wgrad_rs<false, false>), grid, blk, lds3 + stg_n, st, g);
-    int rc = facl_launch_status();
+    int rc;
+    if (pscale && amax && wide) rc = wg_launch_k<true, true, true>(g, grid, st);
+    else if (amax && wide) rc = wg_launch_k<false, true, true>(g, grid, st);
+    else if (pscale && amax) rc = wg_launch_k<true, true, false>(g, grid, st);
+    else if (pscale) rc = wg_launch_k<true, false, false>(g, grid, st);
+    else if (amax) rc = wg_launch_k<false, true, false>(g, grid, st);
+    else rc = wg_launch_k<false, false, false>(g, grid, st);
     if (rc) return rc;
-    const long long n4 = (long long)N * K / 4;
-    const int rgrid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_wg_sum_slices, dim3(rgrid), dim3(256), 0, st, slices, nz, n4, dW);
-    return facl_launch_status();
+    return facl_sum_slices(slices, nz, (long long)N * K / 4, dW, false, st);   // the serial form: one fixed order of additions
 }

@@ -352,7 +352,7 @@ int launch_group(const float* points, int M, int N, int S, int K, float r2, int3
     constexpr int DS = D <= 4 ? D : 3;                                   // D > 4: only xyz is staged
     const size_t lds = (size_t)N * DS * sizeof(float) + 4 * SLOT_BYTES;  // cloud (SoA, DS arrays) + one compacted-list / emission slot per wave
     // centroids per workgroup (A/B knob FACL_GROUP_CPW: 16 = four workgroups stage each cloud, 32 = two, 64 = one)
-    static const int cpw = getenv("FACL_GROUP_CPW") ? atoi(getenv("FACL_GROUP_CPW")) : CENTROIDS_PER_WG;
+    static const int cpw = facl_env_int("FACL_GROUP_CPW", CENTROIDS_PER_WG);
     if constexpr (D > 4) {                  // the A/B knob is not instantiated for the wide inputs: default geometry only
         if (N == 64 * NPL)
             hipLaunchKernelGGL((k_group<D, NPL, CENTROIDS_PER_WG, true>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);

@@ -664,7 +664,7 @@ extern "C" int facl_normalize_map(const float* x, int64_t M, int C, const float*
     if (M < 0 || M > 0x7fffffff || C < 16 || (C & 15) || C > 4096 || K < 1 || K > 256) return FACL_E_SHAPE;
     if ((((uintptr_t)x) | ((uintptr_t)Wm) | ((uintptr_t)x_nor)) & 15) return FACL_E_ALIGN;
     if (M == 0) return 0;
-    static const int four = getenv("FACL_NORMMAP4") ? atoi(getenv("FACL_NORMMAP4")) : 1;     // A/B knob
+    static const int four = facl_env_int("FACL_NORMMAP4", 1);     // A/B knob
     if (four && C == 512 && K == 64)
         hipLaunchKernelGGL((k_normalize_map4<16, 2>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (int)M, Wm,
                            x_nor, code);

@@ -869,7 +869,7 @@ extern "C" int facl_sa_bwd_w3(const float* y2f, int64_t nunits, const float* bnc
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)(nunits < SA_GRID * 4 ? (nunits + 3) / 4 : SA_GRID);
     // round 4 (late): two waves per unit (k_sa_bwd_w3p) unless FACL_BWD_W3_PAIR=0 selects the one-wave-per-unit kernel (A/B)
-    static const int pairk = getenv("FACL_BWD_W3_PAIR") ? atoi(getenv("FACL_BWD_W3_PAIR")) : 1;
+    static const int pairk = facl_env_int("FACL_BWD_W3_PAIR", 1);
     if (pairk) {
         const size_t tiles = (size_t)8 * 64 * TP, combs = (size_t)256 * 65 + 64 * 64 + 64;
         const size_t lds = 32 * sizeof(float4) + (tiles > combs ? tiles : combs) * sizeof(float);
@@ -902,7 +902,7 @@ extern "C" int facl_sa_bwd2(const float* dz2f, const float* y2f, const float* x,
     if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     // FACL_BWD2_F32=1 selects the exact-fp32 MFMA kernel (v_mfma_f32_32x32x2_f32) instead of the split-bf16 one
-    static const int use_f32 = getenv("FACL_BWD2_F32") ? atoi(getenv("FACL_BWD2_F32")) : 0;
+    static const int use_f32 = facl_env_int("FACL_BWD2_F32", 0);
     if (!use_f32) {
         // partial rows of FACL_SA_BWD2_OUT(D) doubles (4864 for D > 4): at most 512 of them, an eighth of the workspace
         const int grid = (int)(nunits < SA_GRID * 8 ? (nunits + 3) / 4 : 2 * SA_GRID);       // 2 workgroups of 4 waves per CU

@@ -433,10 +433,10 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
 int facl_sa_bwd2_sb_launch(const float* dz2f, const float* y2f, const float* x, int nunits, int D, const float* bw2,
                            const float* W2, const float* l1tab, double* ws, int grid, const uint32_t* a1amax, hipStream_t st) {
     const size_t lds = b2s_lds_bytes();
-    static const int rev = getenv("FACL_BWD2_REV") ? atoi(getenv("FACL_BWD2_REV")) : 1;
-    static const int h3 = getenv("FACL_BWD_H3") ? atoi(getenv("FACL_BWD_H3")) : 1;     // 0: bf16x6 (A/B)
+    static const int rev = facl_env_int("FACL_BWD2_REV", 1);
+    static const int h3 = facl_env_int("FACL_BWD_H3", 1);     // 0: bf16x6 (A/B)
     const dim3 g(grid), b(64 * B2S_WAVES);
-    static const int pref = getenv("FACL_BWD2_PREF") ? atoi(getenv("FACL_BWD2_PREF")) : 0;
+    static const int pref = facl_env_int("FACL_BWD2_PREF", 0);
     if (D > 4) {
         // the wide inputs (5..8 channels): default geometry; the FACL_BWD2_PREF experiment is not instantiated for them
         static bool attr_wide[64] = {};

@@ -313,7 +313,7 @@ extern "C" int facl_sa_eval(const float* x, int64_t nunits, int D, const float* 
     hipStream_t st = (hipStream_t)stream;
     // 12 waves per workgroup = three per SIMD (the kernel needs 145 registers; one workgroup per CU: 86 KiB of LDS):
     // 0.304 ms vs 0.3135 ms with 8 waves at the headline shape, same box, alternating runs (FACL_EVAL_WAVES=8 for the A/B)
-    static const int waves = getenv("FACL_EVAL_WAVES") ? atoi(getenv("FACL_EVAL_WAVES")) : 12;
+    static const int waves = facl_env_int("FACL_EVAL_WAVES", 12);
     const int W = waves == 8 ? 8 : 12;
     const int grid = (int)(nunits < 256 * W ? (nunits + W - 1) / W : 256);
     static bool attr_done_dev[64] = {};

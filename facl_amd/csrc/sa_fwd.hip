@@ -910,7 +910,7 @@ extern "C" int facl_sa_fwd2(const float* x, int64_t nunits, int D, const float* 
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)(nunits < 2 * SA_GRID * 4 ? (nunits + 3) / 4 : 2 * SA_GRID);   // 2 workgroups per CU
     double* part = sums2 ? (double*)ws : nullptr;
-    static const int use_f32 = getenv("FACL_SA_F32") ? atoi(getenv("FACL_SA_F32")) : 0;     // exact-fp32 MFMA kernel instead
+    static const int use_f32 = facl_env_int("FACL_SA_F32", 0);     // exact-fp32 MFMA kernel instead
     if (D > 4) {
         // the wide inputs (5..8 channels): same kernels, layer-1 table rows of FACL_SA_L1_COLS(D) floats
 #define FACL_FWD2_WIDE(DD)                                                                                                         \
@@ -918,7 +918,7 @@ extern "C" int facl_sa_fwd2(const float* x, int64_t nunits, int D, const float* 
         else if (h3w) hipLaunchKernelGGL((k_sa_fwd2_sb<DD, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, \
                                          part, a1amax);                                                                            \
         else hipLaunchKernelGGL((k_sa_fwd2_sb<DD, false>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
-        static const int h3w = getenv("FACL_FWD_H3") ? atoi(getenv("FACL_FWD_H3")) : 1;
+        static const int h3w = facl_env_int("FACL_FWD_H3", 1);
         if (D == 5) { FACL_FWD2_WIDE(5) }
         else if (D == 6) { FACL_FWD2_WIDE(6) }
         else if (D == 7) { FACL_FWD2_WIDE(7) }
@@ -929,7 +929,7 @@ extern "C" int facl_sa_fwd2(const float* x, int64_t nunits, int D, const float* 
         else hipLaunchKernelGGL((k_sa_fwd2<3>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);
     } else {
         // fp16x3 (two fp16 planes, three products: csrc/common.h) unless FACL_FWD_H3=0 selects bf16x6 (A/B)
-        static const int h3 = getenv("FACL_FWD_H3") ? atoi(getenv("FACL_FWD_H3")) : 1;
+        static const int h3 = facl_env_int("FACL_FWD_H3", 1);
         if (h3) {
             if (D == 4) hipLaunchKernelGGL((k_sa_fwd2_sb<4, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
             else hipLaunchKernelGGL((k_sa_fwd2_sb<3, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
@@ -952,11 +952,11 @@ static int sa_fwd3_p(const float* y2f, int64_t nunits, const float* scale2, cons
     hipStream_t st = (hipStream_t)stream;
     // 12 waves per workgroup (three per SIMD, 160 registers, no register prefetch of the next y2 tile) since round 4: 0.350 vs
     // 0.359 ms at the headline shape, three alternating same-box runs (gpurun_out: FACL_FWD3_W12=0 restores 8 waves + prefetch)
-    static const int w12 = getenv("FACL_FWD3_W12") ? atoi(getenv("FACL_FWD3_W12")) : 1;
+    static const int w12 = facl_env_int("FACL_FWD3_W12", 1);
     const int WV = (w12 && prec == 3) ? 12 : 8;
     const int grid = (int)(nunits < SA_GRID * WV ? (nunits + WV - 1) / WV : SA_GRID);
     // FACL_SA_F32=1 selects the exact-fp32 MFMA kernel (v_mfma_f32_32x32x2_f32) instead of the split-bf16 one
-    static const int env_f32 = getenv("FACL_SA_F32") ? atoi(getenv("FACL_SA_F32")) : 0;
+    static const int env_f32 = facl_env_int("FACL_SA_F32", 0);
     const int use_f32 = env_f32 && prec == 0;
     const size_t lds = use_f32 ? (4096 + 32) * sizeof(float4) + 256 * sizeof(float) + 8 * 512 * sizeof(double2)
                                : (6144 + 32) * sizeof(float4) + 256 * sizeof(float) + WV * 256 * sizeof(double2);

@@ -129,6 +129,66 @@ def test_few_row_gemms_optin_self_scaled_fp16x3_is_fp32_grade():
     assert worst < 3e-6
 
 
+_KNOB_CHILD = r"""
+import sys, torch
+sys.path.insert(0, ".")
+from facl_amd import _lib
+lib = _lib.load_library(); p = _lib.ptr; dev = torch.device("cuda:0")
+from facl_amd.sa_mlp import _Workspace
+ws = _Workspace.get(dev)
+def rel(x, ref): return float((x.double() - ref).abs().max() / ref.abs().max())
+def nans(*shape, dtype=torch.float32): return torch.full(shape, float("nan"), dtype=dtype, device=dev)
+for M, K, N, nz in ((130, 36, 200, 2), (4096, 64, 1024, 3)):
+    g = torch.Generator(device=dev).manual_seed(M + K + N)
+    a = torch.randn(M, K, device=dev, generator=g)
+    W = torch.randn(N, K, device=dev, generator=g) / K ** 0.5
+    b = torch.randn(N, device=dev, generator=g)
+    ps = torch.rand(K, device=dev, generator=g) + 0.5
+    pt = torch.randn(K, device=dev, generator=g) * 0.3
+    cen = torch.randn(M, 3, device=dev, generator=g)
+    Wc = torch.randn(N, 3, device=dev, generator=g)
+    y = nans(M, N); sums = nans(N, 2, dtype=torch.float64)
+    _lib.check(lib.facl_gemm_fwd(p(a), M, K, p(W), K, N, p(b), p(ps), p(pt), p(cen), p(Wc), 3, p(y), p(sums), p(ws), _lib.stream()), "fwd")
+    ref = torch.relu(a.double() * ps.double() + pt.double()) @ W.double().t() + b.double() + cen.double() @ Wc.double().t()
+    print("FIG fwd %d %.3e 2e-6" % (M, rel(y, ref)))
+    cancel = max(1.0, float(ref.abs().sum(0).max() / ref.sum(0).abs().max()))
+    print("FIG sum %d %.3e 1e-5" % (M, rel(sums[:, 0], ref.sum(0)) / cancel))
+    print("FIG sumsq %d %.3e 1e-5" % (M, rel(sums[:, 1], (ref * ref).sum(0))))
+    dy = torch.randn(M, N, device=dev, generator=g)
+    da = nans(M, K)
+    _lib.check(lib.facl_gemm_dgrad(p(dy), M, N, p(W), K, K, p(da), _lib.stream()), "dgrad")
+    print("FIG dgrad %d %.3e 2e-6" % (M, rel(da, dy.double() @ W.double())))
+    dW = nans(N, K); sl = nans(nz * N * K)
+    _lib.check(lib.facl_gemm_wgrad(p(dy), p(a), M, N, K, K, p(dW), p(sl), nz, _lib.stream()), "wgrad")
+    print("FIG wgrad %d %.3e 3e-6" % (M, rel(dW, dy.double().t() @ a.double())))
+"""
+
+
+@pytest.mark.parametrize("knobs", [{"FACL_GEMM_F32": "1"}, {"FACL_GEMM_F32": "1", "FACL_GEMM_DMA": "0"},
+                                   {"FACL_GEMM_NOSBK": "1", "FACL_SUM_SLICES_PAR": "0"}],
+                         ids=["f32", "f32-nodma", "nosbk-serialsum"])
+def test_gemm_entries_under_the_kernel_choice_knobs(knobs):
+    """The kernels behind the A/B knobs -- the fp32-MFMA ones (FACL_GEMM_F32=1: k_gemm, and k_gemm_dma for the weight gradient
+    unless FACL_GEMM_DMA=0) and the split path with the in-workgroup split-K forced off -- against fp64 at the bounds of
+    test_gemm_fwd / _dgrad / _wgrad: forward with prologue, centre term and statistics, dgrad, split-K weight gradient.
+    (130, 36, 200): 64x64 tiles, a partial k-stage, an N that takes the scalar-store tail; (4096, 64, 1024): the first grid
+    that takes the 128x128 tiles in forward and dgrad.  Its weight gradient asks for three row slices whose boundary does not
+    divide M; only the nosbk-serialsum case runs them (64x64 split tiles, serial slice sum).  In the two FACL_GEMM_F32 cases
+    M <= 8192 and the contraction is long enough for the in-workgroup split-K, so facl_gemm_wgrad makes ONE launch, which
+    under that knob lands on the 64x64 fp32 tiles (k_gemm_dma<IC,IC,1,1>, or k_gemm<IC,IC,false,1,1> without DMA): the
+    128x128 fp32 weight-gradient kernels and a split-K under FACL_GEMM_F32 are not reached by these shapes.  The knobs are
+    read once per process: a child process."""
+    import os, subprocess, sys
+    r = subprocess.run([sys.executable, "-c", _KNOB_CHILD], env=dict(os.environ, **knobs), capture_output=True, text=True,
+                       timeout=300, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert r.returncode == 0, r.stderr[-2000:]
+    figs = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("FIG ")]
+    print(figs)
+    assert len(figs) == 10
+    for name, M, err, bound in figs:
+        assert float(err) < float(bound), (name, M, err, bound)          # a NaN fails too
+
+
 @pytest.mark.parametrize("K,N,ctr", [(256, 256, True), (256, 512, False), (512, 1024, False)])
 def test_tail_layers_headline_size_vs_torch_fp64(K, N, ctr):
     """The three net3DV_3 layers at the headline row count (B*T*S = 49,152 centroid rows) through the Python wrappers the

@@ -12,7 +12,7 @@
 // launch.  Under data parallelism the slices are first summed into a (2, C, 2) tensor for the SyncBN all-reduce
 // (facl_fc_bn_stats / facl_fc_bn_bwd_stats with `sums2`), and the finalisation reads that tensor as one slice per segment.
 // All HBM-trivial (800 x 1024 floats): these kernels are launch-latency-bound, which is why there are few of them.
-#include "common.h"
+#include "rows_common.h"
 
 namespace {
 
@@ -28,29 +28,20 @@ __device__ __forceinline__ void fc_slice(int s, int M, int R, int na, int& r0, i
 // column (sum, sumsq) of each slice: block = 64 channel quads x 4 row phases, combined through LDS in phase order
 __global__ __launch_bounds__(256) void k_fc_stats(const float* __restrict__ y, int M, int R, int na, int C4,
                                                   double* __restrict__ part) {
-    __shared__ double red[3][64][8];
     const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
     const int c4 = blockIdx.x * 64 + lane;
+    __shared__ double red[3][64][8];
     int r0, r1, seg;
     fc_slice(blockIdx.y, M, R, na, r0, r1, seg);
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double acc[8] = {};
     if (c4 < C4)
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const float4 v = reinterpret_cast<const float4*>(y)[(size_t)r * C4 + c4];
-            acc[0] += (double)v.x; acc[1] += (double)v.x * (double)v.x;
-            acc[2] += (double)v.y; acc[3] += (double)v.y * (double)v.y;
-            acc[4] += (double)v.z; acc[5] += (double)v.z * (double)v.z;
-            acc[6] += (double)v.w; acc[7] += (double)v.w * (double)v.w;
-        }
-    if (ph > 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[ph - 1][lane][e] = acc[e];
-    }
-    __syncthreads();
-    if (ph == 0 && c4 < C4) {
+        for (int r = r0 + ph; r < r1; r += 4)
+            lane_each<4>([&](int e, float v) { acc[2 * e] += (double)v; acc[2 * e + 1] += (double)v * (double)v; },
+                         reinterpret_cast<const float4*>(y)[(size_t)r * C4 + c4]);
+    if (phase_sum(acc, red, lane, ph, c4 < C4)) {
         double* pr = part + (size_t)blockIdx.y * 8 * C4 + 8 * c4;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) pr[e] = ((acc[e] + red[0][lane][e]) + red[1][lane][e]) + red[2][lane][e];
+        for (int e = 0; e < 8; ++e) pr[e] = acc[e];
     }
 }
 
@@ -65,6 +56,17 @@ __global__ void k_fc_reduce(const double* __restrict__ part, int na, int nb, int
     sums2[V + v] = b;
 }
 
+// Column c's sums over the slice rows of `part` ((C, 2) doubles each) that slice phase ph owns (slices ph, ph + 4, ...): acc = the
+// pair of segment a (slices [0, na)), then of segment b (slices [na, na + nb)).  The caller's block is 64 channels x 4 slice phases
+// and joins the four partial sums with phase_sum: a serial walk over the ~26 slices by one thread per channel was 11 us of pure
+// load latency.
+__device__ __forceinline__ void fc_slice_sums(const double* __restrict__ part, int na, int nb, int C, int c, int ph, double (&acc)[4]) {
+    const int V = 2 * C;
+    if (c >= C) return;
+    for (int t = ph; t < na; t += 4) { acc[0] += part[(size_t)t * V + 2 * c]; acc[1] += part[(size_t)t * V + 2 * c + 1]; }
+    for (int t = na + ph; t < na + nb; t += 4) { acc[2] += part[(size_t)t * V + 2 * c]; acc[3] += part[(size_t)t * V + 2 * c + 1]; }
+}
+
 // Both segments' train-mode BatchNorm constants bnc2 (2, 5, C) = (mean, invstd, scale, shift, sign) from the slice sums,
 // and the module's running statistics updated TWICE, segment a (the view rows, :228) first, segment b (the clip rows,
 // :229) second: the same arithmetic as two facl_bn_finalize calls (the buffers round to fp32 in between).
@@ -72,25 +74,12 @@ __global__ __launch_bounds__(256) void k_fc_finalize(const double* __restrict__ 
                                                      double count_b, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float eps, float momentum, float* __restrict__ running_mean,
                                                      float* __restrict__ running_var, float* __restrict__ bnc2) {
-    // block = 64 channels x 4 slice phases (phase p adds slices p, p + 4, ...; the four partial sums meet in LDS in phase
-    // order): a serial walk over the ~26 slices by one thread per channel was 11 us of pure load latency
-    __shared__ double red[3][64][4];
     const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
-    const int V = 2 * C;
-    double acc[4] = {0, 0, 0, 0};                                  // (sum, sumsq) of segment a, of segment b
-    if (c < C) {
-        for (int t = ph; t < na; t += 4) { acc[0] += part[(size_t)t * V + 2 * c]; acc[1] += part[(size_t)t * V + 2 * c + 1]; }
-        for (int t = na + ph; t < na + nb; t += 4) { acc[2] += part[(size_t)t * V + 2 * c]; acc[3] += part[(size_t)t * V + 2 * c + 1]; }
-    }
-    if (ph > 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[ph - 1][lane][e] = acc[e];
-    }
-    __syncthreads();
-    if (ph != 0 || c >= C) return;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = ((acc[e] + red[0][lane][e]) + red[1][lane][e]) + red[2][lane][e];
+    __shared__ double red[3][64][4];
+    double acc[4] = {};                                            // (sum, sumsq) of segment a, of segment b
+    fc_slice_sums(part, na, nb, C, c, ph, acc);
+    if (!phase_sum(acc, red, lane, ph, c < C)) return;
     const double g = gamma[c], b = beta[c];
     float rm = running_mean ? running_mean[c] : 0.f, rv = running_var ? running_var[c] : 0.f;
 #pragma unroll
@@ -124,48 +113,25 @@ __global__ __launch_bounds__(256) void k_fc_apply(const float* __restrict__ y, i
     const float4 sb = reinterpret_cast<const float4*>(bnc2 + 7 * C)[c4], tb = reinterpret_cast<const float4*>(bnc2 + 8 * C)[c4];
     for (int r = blockIdx.y; r < R; r += gridDim.y) {
         const float4 sc = r < M ? sa : sb, sh = r < M ? ta : tb;
-        const float4 v = reinterpret_cast<const float4*>(y)[(size_t)r * C4 + c4];
-        float4 o;
-        o.x = relu_nan(fmaf(sc.x, v.x, sh.x)); o.y = relu_nan(fmaf(sc.y, v.y, sh.y));
-        o.z = relu_nan(fmaf(sc.z, v.z, sh.z)); o.w = relu_nan(fmaf(sc.w, v.w, sh.w));
-        reinterpret_cast<float4*>(out)[(size_t)r * C4 + c4] = o;
+        reinterpret_cast<float4*>(out)[(size_t)r * C4 + c4] = lane_map<4>(bn_relu, sc, reinterpret_cast<const float4*>(y)[(size_t)r * C4 + c4], sh);
     }
 }
 
-// backward of relu(bn(y)): per slice the sums of dz = dout * [z > 0] and dz * yhat (rows.hip: k_rows_bwd_stats4)
+// backward of relu(bn(y)): per slice the sums of dz = dout * [z > 0] and dz * yhat (k_rows_bwd_stats4 over the slice's rows, with
+// the segment's constants)
 __global__ __launch_bounds__(256) void k_fc_bwd_stats(const float* __restrict__ dout, const float* __restrict__ y, int M, int R,
                                                       int na, int C4, const float* __restrict__ bnc2, double* __restrict__ part) {
-    __shared__ double red[3][64][8];
     const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
     const int c4 = blockIdx.x * 64 + lane;
-    const int C = 4 * C4;
+    __shared__ double red[3][64][8];
     int r0, r1, seg;
     fc_slice(blockIdx.y, M, R, na, r0, r1, seg);
-    const float* bnc = bnc2 + (size_t)seg * 5 * C;
-    double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (c4 < C4) {
-        const float4 mean = reinterpret_cast<const float4*>(bnc)[c4], inv = reinterpret_cast<const float4*>(bnc + C)[c4];
-        const float4 scale = reinterpret_cast<const float4*>(bnc + 2 * C)[c4], shift = reinterpret_cast<const float4*>(bnc + 3 * C)[c4];
-        for (int r = r0 + ph; r < r1; r += 4) {
-            const size_t o = (size_t)r * C4 + c4;
-            const float4 v = reinterpret_cast<const float4*>(y)[o], g = reinterpret_cast<const float4*>(dout)[o];
-            const float d0 = fmaf(scale.x, v.x, shift.x) > 0.f ? g.x : 0.f, d1 = fmaf(scale.y, v.y, shift.y) > 0.f ? g.y : 0.f;
-            const float d2 = fmaf(scale.z, v.z, shift.z) > 0.f ? g.z : 0.f, d3 = fmaf(scale.w, v.w, shift.w) > 0.f ? g.w : 0.f;
-            acc[0] += (double)d0; acc[1] += (double)d0 * (double)((v.x - mean.x) * inv.x);
-            acc[2] += (double)d1; acc[3] += (double)d1 * (double)((v.y - mean.y) * inv.y);
-            acc[4] += (double)d2; acc[5] += (double)d2 * (double)((v.z - mean.z) * inv.z);
-            acc[6] += (double)d3; acc[7] += (double)d3 * (double)((v.w - mean.w) * inv.w);
-        }
-    }
-    if (ph > 0) {
+    double acc[8] = {};
+    if (c4 < C4) bn_bwd_stats_rows<4>(dout, y, C4, c4, bnc2 + (size_t)seg * 20 * C4, r0 + ph, r1, 4, acc);
+    if (phase_sum(acc, red, lane, ph, c4 < C4)) {
+        double* pr = part + (size_t)blockIdx.y * 8 * C4 + 8 * c4;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) red[ph - 1][lane][e] = acc[e];
-    }
-    __syncthreads();
-    if (ph == 0 && c4 < C4) {
-        double* pr = part + (size_t)blockIdx.y * 2 * C + 8 * c4;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pr[e] = ((acc[e] + red[0][lane][e]) + red[1][lane][e]) + red[2][lane][e];
+        for (int e = 0; e < 8; ++e) pr[e] = acc[e];
     }
 }
 
@@ -176,23 +142,13 @@ __global__ __launch_bounds__(256) void k_fc_bwd_consts(const double* __restrict_
                                                        const double* __restrict__ sums_g, int C, double count_a, double count_b,
                                                        float* __restrict__ dbeta, float* __restrict__ dgamma,
                                                        float* __restrict__ kk2) {
-    __shared__ double red[3][64][4];                               // 64 channels x 4 slice phases, as k_fc_finalize
     const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     const int V = 2 * C;
-    double acc[4] = {0, 0, 0, 0};
-    if (c < C) {
-        for (int t = ph; t < na; t += 4) { acc[0] += part[(size_t)t * V + 2 * c]; acc[1] += part[(size_t)t * V + 2 * c + 1]; }
-        for (int t = na + ph; t < na + nb; t += 4) { acc[2] += part[(size_t)t * V + 2 * c]; acc[3] += part[(size_t)t * V + 2 * c + 1]; }
-    }
-    if (ph > 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[ph - 1][lane][e] = acc[e];
-    }
-    __syncthreads();
-    if (ph != 0 || c >= C) return;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[e] = ((acc[e] + red[0][lane][e]) + red[1][lane][e]) + red[2][lane][e];
+    __shared__ double red[3][64][4];
+    double acc[4] = {};                                            // (sum dz, sum dz * yhat) of segment a, of segment b
+    fc_slice_sums(part, na, nb, C, c, ph, acc);
+    if (!phase_sum(acc, red, lane, ph, c < C)) return;
 #pragma unroll
     for (int seg = 0; seg < 2; ++seg) {
         const double g0 = sums_g ? sums_g[(size_t)seg * V + 2 * c] : acc[2 * seg];
@@ -205,32 +161,20 @@ __global__ __launch_bounds__(256) void k_fc_bwd_consts(const double* __restrict_
     dgamma[c] = (float)acc[1] + (float)acc[3];
 }
 
-// dy = scale * (dz - k1 - yhat * k2) with the row's segment constants (rows.hip: k_rows_bwd_apply4)
+// dy = scale * (dz - k1 - yhat * k2) with the row's segment constants (k_rows_bwd_apply4 with both segments' constants resident)
 __global__ __launch_bounds__(256) void k_fc_bwd_apply(const float* __restrict__ dout, const float* __restrict__ y, int M, int R,
                                                       int C4, const float* __restrict__ bnc2, const float* __restrict__ kk2,
                                                       float* __restrict__ dy) {
     const int c4 = blockIdx.x * 256 + threadIdx.x;
     if (c4 >= C4) return;
     const int C = 4 * C4;
-    float4 mean[2], inv[2], scale[2], shift[2], k1[2], k2[2];
-#pragma unroll
-    for (int seg = 0; seg < 2; ++seg) {
-        const float* bnc = bnc2 + (size_t)seg * 5 * C;
-        mean[seg] = reinterpret_cast<const float4*>(bnc)[c4]; inv[seg] = reinterpret_cast<const float4*>(bnc + C)[c4];
-        scale[seg] = reinterpret_cast<const float4*>(bnc + 2 * C)[c4]; shift[seg] = reinterpret_cast<const float4*>(bnc + 3 * C)[c4];
-        k1[seg] = reinterpret_cast<const float4*>(kk2 + (size_t)seg * 2 * C)[c4];
-        k2[seg] = reinterpret_cast<const float4*>(kk2 + (size_t)seg * 2 * C + C)[c4];
-    }
+    const BnLanes<4> q[2] = {bn_lanes<4>(bnc2, C, c4), bn_lanes<4>(bnc2 + 5 * C, C, c4)};
+    const KkLanes<4> k[2] = {kk_lanes<4>(kk2, C, c4), kk_lanes<4>(kk2 + 2 * C, C, c4)};
     for (int r = blockIdx.y; r < R; r += gridDim.y) {
         const int s = r < M ? 0 : 1;
         const size_t o = (size_t)r * C4 + c4;
-        const float4 v = reinterpret_cast<const float4*>(y)[o], g = reinterpret_cast<const float4*>(dout)[o];
-        float4 out;
-        out.x = scale[s].x * ((fmaf(scale[s].x, v.x, shift[s].x) > 0.f ? g.x : 0.f) - k1[s].x - (v.x - mean[s].x) * inv[s].x * k2[s].x);
-        out.y = scale[s].y * ((fmaf(scale[s].y, v.y, shift[s].y) > 0.f ? g.y : 0.f) - k1[s].y - (v.y - mean[s].y) * inv[s].y * k2[s].y);
-        out.z = scale[s].z * ((fmaf(scale[s].z, v.z, shift[s].z) > 0.f ? g.z : 0.f) - k1[s].z - (v.z - mean[s].z) * inv[s].z * k2[s].z);
-        out.w = scale[s].w * ((fmaf(scale[s].w, v.w, shift[s].w) > 0.f ? g.w : 0.f) - k1[s].w - (v.w - mean[s].w) * inv[s].w * k2[s].w);
-        reinterpret_cast<float4*>(dy)[o] = out;
+        reinterpret_cast<float4*>(dy)[o] = lane_map<4>(bn_relu_bwd, reinterpret_cast<const float4*>(dout)[o], reinterpret_cast<const float4*>(y)[o],
+                                                       q[s].mean, q[s].inv, q[s].scale, q[s].shift, k[s].k1, k[s].k2);
     }
 }
 
@@ -298,10 +242,7 @@ __global__ __launch_bounds__(256) void k_viewmax_stack(const float* __restrict__
             const size_t o = ((size_t)g * B + b) * C4 + c4;
             const float4 v = reinterpret_cast<const float4*>(x)[o];
             reinterpret_cast<float4*>(h)[o] = v;
-            if (v.x > best.x || v.x != v.x) { best.x = v.x; bi.x = g; }
-            if (v.y > best.y || v.y != v.y) { best.y = v.y; bi.y = g; }
-            if (v.z > best.z || v.z != v.z) { best.z = v.z; bi.z = g; }
-            if (v.w > best.w || v.w != v.w) { best.w = v.w; bi.w = g; }
+            first_max_wins(best, bi, v, g);
         }
     }
     if (ph) { sb[ph - 1][it] = best; si[ph - 1][it] = bi; }
@@ -312,10 +253,7 @@ __global__ __launch_bounds__(256) void k_viewmax_stack(const float* __restrict__
             const float4 v = sb[t][it];
             const int4 vi = si[t][it];
             if (vi.x < 0) continue;                        // empty phase (fewer than four views per phase quarter)
-            if (v.x > best.x || v.x != v.x) { best.x = v.x; bi.x = vi.x; }
-            if (v.y > best.y || v.y != v.y) { best.y = v.y; bi.y = vi.y; }
-            if (v.z > best.z || v.z != v.z) { best.z = v.z; bi.z = vi.z; }
-            if (v.w > best.w || v.w != v.w) { best.w = v.w; bi.w = vi.w; }
+            first_max_wins(best, bi, v, vi);
         }
         reinterpret_cast<float4*>(h)[((size_t)G * B + b) * C4 + c4] = best;
         reinterpret_cast<int4*>(arg)[i] = bi;
@@ -338,7 +276,7 @@ extern "C" int64_t facl_ws_bytes(void);
 extern "C" int facl_fc_bn_stats(const float* y, int64_t M, int64_t R, int C, double* sums2, void* ws, void* stream) {
     if (!y || !ws) return FACL_E_NULL;
     if (!fc_shape_ok(M, R, C)) return FACL_E_CONFIG;
-    if (((uintptr_t)y) & 15) return FACL_E_ALIGN;
+    if (!aligned16(y)) return FACL_E_ALIGN;
     const int na = fc_na(M), nb = fc_nb(M, R);
     if ((size_t)(na + nb) * 2 * C * sizeof(double) > (size_t)facl_ws_bytes()) return FACL_E_CONFIG;
     hipStream_t st = (hipStream_t)stream;
@@ -357,7 +295,7 @@ extern "C" int facl_fc_bn_apply(const float* y, int64_t M, int64_t R, int C, con
     if (!y || !gamma || !beta || !bnc2 || !a || (!sums2 && !part)) return FACL_E_NULL;
     if (M < 1 || R <= M || R > 0x7fffffff || C < 4 || (C & 3) || count_a < 1 || count_b < 1) return FACL_E_SHAPE;
     if (!sums2 && (nslices_a < 1 || nslices_b < 1)) return FACL_E_SHAPE;
-    if ((((uintptr_t)y) | ((uintptr_t)a) | ((uintptr_t)bnc2)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(y, a, bnc2)) return FACL_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_fc_finalize, dim3((C + 63) / 64), dim3(256), 0, st, sums2 ? sums2 : part, sums2 ? 1 : nslices_a,
                        sums2 ? 1 : nslices_b, C, count_a, count_b, gamma, beta, eps, momentum, running_mean, running_var, bnc2);
@@ -373,7 +311,7 @@ extern "C" int facl_fc_bn_bwd_stats(const float* dact, const float* y, int64_t M
                                     double* sums2, void* ws, void* stream) {
     if (!dact || !y || !bnc2 || !ws) return FACL_E_NULL;
     if (!fc_shape_ok(M, R, C)) return FACL_E_CONFIG;
-    if ((((uintptr_t)y) | ((uintptr_t)dact) | ((uintptr_t)bnc2)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(y, dact, bnc2)) return FACL_E_ALIGN;
     const int na = fc_na(M), nb = fc_nb(M, R);
     if ((size_t)(na + nb) * 2 * C * sizeof(double) > (size_t)facl_ws_bytes()) return FACL_E_CONFIG;
     hipStream_t st = (hipStream_t)stream;
@@ -391,7 +329,7 @@ extern "C" int facl_fc_bn_bwd_apply(const float* dact, const float* y, int64_t M
     if (!dact || !y || !bnc2 || !ws || !dgamma || !dbeta || !kk2 || !dy) return FACL_E_NULL;
     if (!fc_shape_ok(M, R, C)) return FACL_E_CONFIG;
     if (count_a < 1 || count_b < 1) return FACL_E_SHAPE;
-    if ((((uintptr_t)y) | ((uintptr_t)dact) | ((uintptr_t)bnc2) | ((uintptr_t)kk2) | ((uintptr_t)dy)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(y, dact, bnc2, kk2, dy)) return FACL_E_ALIGN;
     const int na = fc_na(M), nb = fc_nb(M, R);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_fc_bwd_consts, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)ws, na, nb, sums2_g, C, count_a,
@@ -406,7 +344,7 @@ extern "C" int facl_fc_bn_bwd_apply(const float* dact, const float* y, int64_t M
 extern "C" int facl_col_sums(const float* x, int64_t R, int C, float* out, void* stream) {
     if (!x || !out) return FACL_E_NULL;
     if (R < 1 || R > 0x7fffffff || C < 4 || (C & 3)) return FACL_E_SHAPE;
-    if ((((uintptr_t)x) | ((uintptr_t)out)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(x, out)) return FACL_E_ALIGN;
     hipLaunchKernelGGL(k_col_sums, dim3((C / 4 + 15) / 16), dim3(1024), 0, (hipStream_t)stream, x, (int)R, C / 4, out);
     return facl_launch_status();
 }
@@ -414,7 +352,7 @@ extern "C" int facl_col_sums(const float* x, int64_t R, int C, float* out, void*
 extern "C" int facl_viewmax_stack(const float* x, int G, int B, int C, float* h, int32_t* arg, void* stream) {
     if (!x || !h || !arg) return FACL_E_NULL;
     if (G < 1 || B < 1 || C < 4 || (C & 3)) return FACL_E_SHAPE;
-    if ((((uintptr_t)x) | ((uintptr_t)h) | ((uintptr_t)arg)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(x, h, arg)) return FACL_E_ALIGN;
     const int n = B * (C / 4);
     hipLaunchKernelGGL(k_viewmax_stack, dim3((n + 63) / 64), dim3(256), 0, (hipStream_t)stream, x, G, B, C / 4, h, arg);
     return facl_launch_status();

@@ -22,7 +22,7 @@
 // Host side: rs_launch / facl_gemm_rs_wgrad pick ONE instantiation through rs_launch_k / wg_launch_k, which set the kernel's
 // dynamic-LDS attribute on first use (common.h: facl_launch_dynamic_lds); the weight gradient's slices are summed by
 // facl_sum_slices (gemm.hip).
-#include "common.h"
+#include "rows_common.h"
 
 int facl_reduce_rows(const double* part, int rows, int V, double* out, hipStream_t st);
 int facl_sum_slices(const float* slices, int nz, long long n4, float* out, bool par_ok, hipStream_t st);   // gemm.hip
@@ -522,9 +522,9 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void k_gemm_rs(RsArgs g) 
             if (row0 + p < g.M) {
                 if (BST) {                                             // four short chains, then pairwise: ~6 eps on 32 rows
                     const float yy = ystg[p * 32 + (((q >> 2) ^ ((p >> 1) & 7)) << 2) + (q & 3)];
-                    const float d = fmaf(bsc, yy, bsh) > 0.f ? v : 0.f;
+                    const float d = bn_relu_dz(bsc, yy, bsh, v);
                     q4[r >> 2] += d;
-                    g4[r >> 2] = fmaf(d, (yy - bmean) * binv, g4[r >> 2]);
+                    g4[r >> 2] = fmaf(d, bn_yhat(yy, bmean, binv), g4[r >> 2]);
                 } else {
                     s += v; sq = fmaf(v, v, sq);
                 }

@@ -3,8 +3,8 @@
 // backward passes.  All HBM-bound streaming kernels (float4 per lane, channels fastest).
 // Algorithmic bytes: stats R*C*4 read; apply 2*R*C*4; segmax R*C*4 read; bwd_stats 2*R*C*4 read;
 // bwd_apply 3*R*C*4; bwd_sparse 2*R*C*4.
-#include "common.h"
-#include <stdlib.h>
+#include "rows_common.h"
+#include <algorithm>
 
 int facl_reduce_rows(const double* part, int rows, int V, double* out, hipStream_t st);
 
@@ -37,14 +37,9 @@ __global__ void k_rows_bn_relu(const float* __restrict__ y, long long n4, int C4
     const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     int c4 = (int)(i0 % C4);
     const int dc = (int)(stride % C4);
-    for (long long i = i0; i < n4; i += stride, c4 = c4 + dc >= C4 ? c4 + dc - C4 : c4 + dc) {
-        const float4 v = reinterpret_cast<const float4*>(y)[i];
-        const float4 sc = reinterpret_cast<const float4*>(scale)[c4], sh = reinterpret_cast<const float4*>(shift)[c4];
-        float4 o;
-        o.x = relu_nan(fmaf(sc.x, v.x, sh.x)); o.y = relu_nan(fmaf(sc.y, v.y, sh.y));
-        o.z = relu_nan(fmaf(sc.z, v.z, sh.z)); o.w = relu_nan(fmaf(sc.w, v.w, sh.w));
-        reinterpret_cast<float4*>(out)[i] = o;
-    }
+    for (long long i = i0; i < n4; i += stride, c4 = c4 + dc >= C4 ? c4 + dc - C4 : c4 + dc)
+        reinterpret_cast<float4*>(out)[i] = lane_map<4>(bn_relu, reinterpret_cast<const float4*>(scale)[c4],
+                                                        reinterpret_cast<const float4*>(y)[i], reinterpret_cast<const float4*>(shift)[c4]);
 }
 
 // ---- x_pre[m,c] = max_s relu(bn(y[m,s,c])) = relu(|scale| * max_s(sgn*y) + shift), first max wins ----
@@ -58,11 +53,8 @@ __global__ __launch_bounds__(256) void k_rows_segmax(const float* __restrict__ y
     const float* base = y + (size_t)m * S * C + c;
     float best = sgn * base[0];
     int bi = 0;
-    for (int s = 1; s < S; ++s) {
-        const float v = sgn * base[(size_t)s * C];
-        if (v > best || v != v) { best = v; bi = s; }                          // a NaN wins and stays (MaxPool2d propagates it)
-    }
-    out[(size_t)m * C + c] = relu_nan(fmaf(fabsf(scale), best, shift));
+    for (int s = 1; s < S; ++s) first_max_wins(best, bi, sgn * base[(size_t)s * C], s);
+    out[(size_t)m * C + c] = bn_relu(fabsf(scale), best, shift);
     arg[(size_t)m * C + c] = bi;
 }
 
@@ -72,16 +64,10 @@ __global__ __launch_bounds__(256) void k_rows_bwd_stats(const float* __restrict_
                                                         double* __restrict__ part) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    const float mean = bnc[c], inv = bnc[C + c], scale = bnc[2 * C + c], shift = bnc[3 * C + c];
-    double s = 0, g = 0;
-    for (int r = blockIdx.y; r < R; r += gridDim.y) {
-        const float v = y[(size_t)r * C + c];
-        const float d = fmaf(scale, v, shift) > 0.f ? dout[(size_t)r * C + c] : 0.f;
-        s += (double)d;
-        g += (double)d * (double)((v - mean) * inv);
-    }
-    part[(size_t)blockIdx.y * 2 * C + 2 * c] = s;
-    part[(size_t)blockIdx.y * 2 * C + 2 * c + 1] = g;
+    double acc[2] = {};
+    bn_bwd_stats_rows<1>(dout, y, C, c, bnc, blockIdx.y, R, gridDim.y, acc);
+    part[(size_t)blockIdx.y * 2 * C + 2 * c] = acc[0];
+    part[(size_t)blockIdx.y * 2 * C + 2 * c + 1] = acc[1];
 }
 
 // the same, 4 channels per lane (C % 4 == 0, 16-byte aligned tensors): block = 64 channel quads x 4 row phases,
@@ -95,53 +81,26 @@ __global__ __launch_bounds__(256) void k_rows_bwd_stats4(const float* __restrict
     const int C = 4 * C4;
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (c4 < C4) {
-        const float4 mean = reinterpret_cast<const float4*>(bnc)[c4], inv = reinterpret_cast<const float4*>(bnc + C)[c4];
-        const float4 scale = reinterpret_cast<const float4*>(bnc + 2 * C)[c4], shift = reinterpret_cast<const float4*>(bnc + 3 * C)[c4];
+        const BnLanes<4> q = bn_lanes<4>(bnc, C, c4);
         for (int r = blockIdx.y * 4 + ph; r < R; r += gridDim.y * 4) {
             const size_t o = (size_t)r * C4 + c4;
             const float4 v = reinterpret_cast<const float4*>(y)[o], g = reinterpret_cast<const float4*>(dout)[o];
-            const float d0 = fmaf(scale.x, v.x, shift.x) > 0.f ? g.x : 0.f, d1 = fmaf(scale.y, v.y, shift.y) > 0.f ? g.y : 0.f;
-            const float d2 = fmaf(scale.z, v.z, shift.z) > 0.f ? g.z : 0.f, d3 = fmaf(scale.w, v.w, shift.w) > 0.f ? g.w : 0.f;
-            acc[0] += (double)d0; acc[1] += (double)d0 * (double)((v.x - mean.x) * inv.x);
-            acc[2] += (double)d1; acc[3] += (double)d1 * (double)((v.y - mean.y) * inv.y);
-            acc[4] += (double)d2; acc[5] += (double)d2 * (double)((v.z - mean.z) * inv.z);
-            acc[6] += (double)d3; acc[7] += (double)d3 * (double)((v.w - mean.w) * inv.w);
+            const float d0 = bn_relu_dz(q.scale.x, v.x, q.shift.x, g.x), d1 = bn_relu_dz(q.scale.y, v.y, q.shift.y, g.y);
+            const float d2 = bn_relu_dz(q.scale.z, v.z, q.shift.z, g.z), d3 = bn_relu_dz(q.scale.w, v.w, q.shift.w, g.w);
+            acc[0] += (double)d0; acc[1] += (double)d0 * (double)bn_yhat(v.x, q.mean.x, q.inv.x);
+            acc[2] += (double)d1; acc[3] += (double)d1 * (double)bn_yhat(v.y, q.mean.y, q.inv.y);
+            acc[4] += (double)d2; acc[5] += (double)d2 * (double)bn_yhat(v.z, q.mean.z, q.inv.z);
+            acc[6] += (double)d3; acc[7] += (double)d3 * (double)bn_yhat(v.w, q.mean.w, q.inv.w);
         }
     }
-    if (ph > 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[ph - 1][lane][e] = acc[e];
-    }
-    __syncthreads();
-    if (ph == 0 && c4 < C4) {
+    if (phase_sum(acc, red, lane, ph, c4 < C4)) {
         double* pr = part + (size_t)blockIdx.y * 2 * C + 8 * c4;       // columns 4c4..4c4+3, (sum, sum*yhat) pairs
 #pragma unroll
-        for (int e = 0; e < 8; ++e) pr[e] = ((acc[e] + red[0][lane][e]) + red[1][lane][e]) + red[2][lane][e];
+        for (int e = 0; e < 8; ++e) pr[e] = acc[e];
     }
 }
 
-// max|.| of the tensor a kernel writes, for the consumers that scale it by a power of two (fp16x3 GEMMs, common.h): the bit
-// pattern of a non-negative float orders like the unsigned integer, NaN above everything (so a NaN gradient stays visible).
-// The maximum lives in FACL_AMAX_SLOTS slots, one 128-byte line each (a workgroup uses slot = its linear id mod the slot
-// count: thousands of atomics on ONE address serialise in the L2 -- measured, the pass doubled in time); the consumer takes
-// the maximum over the slots.  A wave reads its slot when it STARTS and skips the atomic when it cannot raise that value
-// (a stale read only costs a redundant atomic).  Lanes that left early (channel tail) are absent from the exchange.
-__device__ __forceinline__ float abs_max4(float m, const float4& v) {
-    const unsigned a = __float_as_uint(m);
-    unsigned b = __float_as_uint(v.x) & 0x7fffffffu, c = __float_as_uint(v.y) & 0x7fffffffu;
-    unsigned d = __float_as_uint(v.z) & 0x7fffffffu, e = __float_as_uint(v.w) & 0x7fffffffu;
-    b = b > c ? b : c; d = d > e ? d : e; b = b > d ? b : d;
-    return __uint_as_float(a > b ? a : b);
-}
-__device__ __forceinline__ unsigned* abs_max_slot(unsigned* amax) {
-    return amax + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) & (FACL_AMAX_SLOTS - 1)) * FACL_AMAX_STRIDE;
-}
-__device__ __forceinline__ void publish_abs_max(unsigned* slot, unsigned seen, float m) {
-    const unsigned b = __float_as_uint(m);
-    if (b > seen) atomicMax(slot, b);                                   // the compiler folds a wave's lanes into one atomic
-}
-
-// dy = scale * (dz - k1 - yhat*k2),  kk = (2,C): k1 = dbeta/P, k2 = dgamma/P
+// dy = scale * (dz - k1 - yhat*k2),  kk = (2,C): k1 = dbeta/P, k2 = dgamma/P; any C and alignment, any R * C
 __global__ void k_rows_bwd_apply(const float* __restrict__ dout, const float* __restrict__ y, long long n, int C,
                                  const float* __restrict__ bnc, const float* __restrict__ kk,
                                  float* __restrict__ dy) {
@@ -149,12 +108,8 @@ __global__ void k_rows_bwd_apply(const float* __restrict__ dout, const float* __
     const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     int c = (int)(i0 % C);
     const int dc = (int)(stride % C);
-    for (long long i = i0; i < n; i += stride, c = c + dc >= C ? c + dc - C : c + dc) {
-        const float mean = bnc[c], inv = bnc[C + c], scale = bnc[2 * C + c], shift = bnc[3 * C + c];
-        const float v = y[i];
-        const float d = fmaf(scale, v, shift) > 0.f ? dout[i] : 0.f;
-        dy[i] = scale * (d - kk[c] - (v - mean) * inv * kk[C + c]);
-    }
+    for (long long i = i0; i < n; i += stride, c = c + dc >= C ? c + dc - C : c + dc)
+        dy[i] = bn_relu_bwd(dout[i], y[i], bnc[c], bnc[C + c], bnc[2 * C + c], bnc[3 * C + c], kk[c], kk[C + c]);
 }
 
 // the same, 4 channels per lane (C % 4 == 0, 16-byte aligned tensors): one (row, channel-quad) per iteration
@@ -167,18 +122,12 @@ __global__ __launch_bounds__(256) void k_rows_bwd_apply4(const float* __restrict
     float mx = 0.f;
     unsigned* const slot = amax ? abs_max_slot(amax) : nullptr;
     const unsigned seen = amax ? *slot : 0u;
-    const int C = 4 * C4;
-    const float4 mean = reinterpret_cast<const float4*>(bnc)[c4], inv = reinterpret_cast<const float4*>(bnc + C)[c4];
-    const float4 scale = reinterpret_cast<const float4*>(bnc + 2 * C)[c4], shift = reinterpret_cast<const float4*>(bnc + 3 * C)[c4];
-    const float4 k1 = reinterpret_cast<const float4*>(kk)[c4], k2 = reinterpret_cast<const float4*>(kk + C)[c4];
+    const BnLanes<4> q = bn_lanes<4>(bnc, 4 * C4, c4);
+    const KkLanes<4> k = kk_lanes<4>(kk, 4 * C4, c4);
     for (int r = blockIdx.y; r < R; r += gridDim.y) {
         const size_t o = (size_t)r * C4 + c4;
-        const float4 v = reinterpret_cast<const float4*>(y)[o], g = reinterpret_cast<const float4*>(dout)[o];
-        float4 out;
-        out.x = scale.x * ((fmaf(scale.x, v.x, shift.x) > 0.f ? g.x : 0.f) - k1.x - (v.x - mean.x) * inv.x * k2.x);
-        out.y = scale.y * ((fmaf(scale.y, v.y, shift.y) > 0.f ? g.y : 0.f) - k1.y - (v.y - mean.y) * inv.y * k2.y);
-        out.z = scale.z * ((fmaf(scale.z, v.z, shift.z) > 0.f ? g.z : 0.f) - k1.z - (v.z - mean.z) * inv.z * k2.z);
-        out.w = scale.w * ((fmaf(scale.w, v.w, shift.w) > 0.f ? g.w : 0.f) - k1.w - (v.w - mean.w) * inv.w * k2.w);
+        const float4 out = lane_map<4>(bn_relu_bwd, reinterpret_cast<const float4*>(dout)[o], reinterpret_cast<const float4*>(y)[o],
+                                       q.mean, q.inv, q.scale, q.shift, k.k1, k.k2);
         reinterpret_cast<float4*>(dy)[o] = out;
         mx = abs_max4(mx, out);
     }
@@ -200,7 +149,7 @@ __global__ __launch_bounds__(256) void k_segmax_bwd_stats(const float* __restric
         const float d = xpre[o] > 0.f ? dxpre[o] : 0.f;
         const float v = y[((size_t)m * S + arg[o]) * C + c];
         s += (double)d;
-        g += (double)d * (double)((v - mean) * inv);
+        g += (double)d * (double)bn_yhat(v, mean, inv);
     }
     part[(size_t)blockIdx.y * 2 * C + 2 * c] = s;
     part[(size_t)blockIdx.y * 2 * C + 2 * c + 1] = g;
@@ -223,65 +172,41 @@ __global__ __launch_bounds__(256) void k_segmax_bwd_stats_ymax(const float* __re
     for (int m = blockIdx.y; m < Mrows; m += gridDim.y) {
         const size_t o = (size_t)m * C + c;
         const float d = xpre[o] > 0.f ? dxpre[o] : 0.f;
-        const float v = sg * ymax[o];
         s += (double)d;
-        g += (double)d * (double)((v - mean) * inv);
+        g += (double)d * (double)bn_yhat(sg * ymax[o], mean, inv);
     }
     part[(size_t)blockIdx.y * 2 * C + 2 * c] = s;
     part[(size_t)blockIdx.y * 2 * C + 2 * c + 1] = g;
 }
 
+// dense dy of the max over S: W channels per lane (lanes<W>; amax only with W = 4)
+template <int W>
 __global__ __launch_bounds__(256) void k_segmax_bwd_apply(const float* __restrict__ dxpre, const float* __restrict__ xpre,
                                                           const float* __restrict__ y, const int* __restrict__ arg,
-                                                          int S, int C, const float* __restrict__ bnc,
-                                                          const float* __restrict__ kk, float* __restrict__ dy) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
+                                                          int S, int CW, const float* __restrict__ bnc,
+                                                          const float* __restrict__ kk, float* __restrict__ dy,
+                                                          unsigned* __restrict__ amax) {
+    using F = typename lanes<W>::F;
+    const int cw = blockIdx.x * 256 + threadIdx.x;
     const int m = blockIdx.y;
-    if (c >= C) return;
-    const float mean = bnc[c], inv = bnc[C + c], scale = bnc[2 * C + c];
-    const float k1 = kk[c], k2 = kk[C + c];
-    const size_t o = (size_t)m * C + c;
-    const float d = xpre[o] > 0.f ? dxpre[o] : 0.f;
-    const int a = arg[o];
-    const float* yb = y + (size_t)m * S * C + c;
-    float* db = dy + (size_t)m * S * C + c;
-    for (int s = 0; s < S; ++s) {
-        const float v = yb[(size_t)s * C];
-        db[(size_t)s * C] = scale * ((s == a ? d : 0.f) - k1 - (v - mean) * inv * k2);
-    }
-}
-
-// the same, 4 channels per lane (C % 4 == 0, 16-byte aligned tensors)
-__global__ __launch_bounds__(256) void k_segmax_bwd_apply4(const float* __restrict__ dxpre, const float* __restrict__ xpre,
-                                                           const float* __restrict__ y, const int* __restrict__ arg,
-                                                           int S, int C4, const float* __restrict__ bnc,
-                                                           const float* __restrict__ kk, float* __restrict__ dy,
-                                                           unsigned* __restrict__ amax) {
-    const int c4 = blockIdx.x * 256 + threadIdx.x;
-    const int m = blockIdx.y;
-    if (c4 >= C4) return;
+    if (cw >= CW) return;
     float mx = 0.f;
     unsigned* const slot = amax ? abs_max_slot(amax) : nullptr;
     const unsigned seen = amax ? *slot : 0u;
-    const int C = 4 * C4;
-    const float4 mean = reinterpret_cast<const float4*>(bnc)[c4], inv = reinterpret_cast<const float4*>(bnc + C)[c4];
-    const float4 scale = reinterpret_cast<const float4*>(bnc + 2 * C)[c4];
-    const float4 k1 = reinterpret_cast<const float4*>(kk)[c4], k2 = reinterpret_cast<const float4*>(kk + C)[c4];
-    const size_t o = (size_t)m * C4 + c4;
-    const float4 xp = reinterpret_cast<const float4*>(xpre)[o], dx = reinterpret_cast<const float4*>(dxpre)[o];
-    const int4 a = reinterpret_cast<const int4*>(arg)[o];
-    const float4 d = make_float4(xp.x > 0.f ? dx.x : 0.f, xp.y > 0.f ? dx.y : 0.f, xp.z > 0.f ? dx.z : 0.f, xp.w > 0.f ? dx.w : 0.f);
-    const float4* yb = reinterpret_cast<const float4*>(y) + (size_t)m * S * C4 + c4;
-    float4* db = reinterpret_cast<float4*>(dy) + (size_t)m * S * C4 + c4;
+    const BnLanes<W> q = bn_lanes<W>(bnc, W * CW, cw);
+    const KkLanes<W> k = kk_lanes<W>(kk, W * CW, cw);
+    const size_t o = (size_t)m * CW + cw;
+    const F d = lane_map<W>([](float xp, float dx) { return xp > 0.f ? dx : 0.f; }, reinterpret_cast<const F*>(xpre)[o],
+                            reinterpret_cast<const F*>(dxpre)[o]);
+    const typename lanes<W>::I a = reinterpret_cast<const typename lanes<W>::I*>(arg)[o];
+    const F* yb = reinterpret_cast<const F*>(y) + (size_t)m * S * CW + cw;
+    F* db = reinterpret_cast<F*>(dy) + (size_t)m * S * CW + cw;
     for (int s = 0; s < S; ++s) {
-        const float4 v = yb[(size_t)s * C4];
-        float4 out;
-        out.x = scale.x * ((s == a.x ? d.x : 0.f) - k1.x - (v.x - mean.x) * inv.x * k2.x);
-        out.y = scale.y * ((s == a.y ? d.y : 0.f) - k1.y - (v.y - mean.y) * inv.y * k2.y);
-        out.z = scale.z * ((s == a.z ? d.z : 0.f) - k1.z - (v.z - mean.z) * inv.z * k2.z);
-        out.w = scale.w * ((s == a.w ? d.w : 0.f) - k1.w - (v.w - mean.w) * inv.w * k2.w);
-        db[(size_t)s * C4] = out;
-        mx = abs_max4(mx, out);
+        const F out = lane_map<W>([s](int a, float d, float v, float mean, float inv, float scale, float k1, float k2) {
+            return bn_bwd_dy(scale, s == a ? d : 0.f, k1, bn_yhat(v, mean, inv), k2);
+        }, a, d, yb[(size_t)s * CW], q.mean, q.inv, q.scale, k.k1, k.k2);
+        db[(size_t)s * CW] = out;
+        if constexpr (W == 4) mx = abs_max4(mx, out);
     }
     if (amax) publish_abs_max(slot, seen, mx);
 }
@@ -294,29 +219,21 @@ __global__ __launch_bounds__(256) void k_rows_center_wgrad(const float* __restri
     __shared__ double red[3][64][12];
     const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
     const int c4 = blockIdx.x * 64 + lane;
-    double acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double acc[12] = {};
     if (c4 < C4) {
         for (int r = blockIdx.y * 4 + ph; r < R; r += gridDim.y * 4) {
-            const float4 g = reinterpret_cast<const float4*>(dy)[(size_t)r * C4 + c4];
             const float x0 = ctr[(size_t)r * 3], x1 = ctr[(size_t)r * 3 + 1], x2 = ctr[(size_t)r * 3 + 2];
-            const float gv[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc[3 * e] += (double)gv[e] * (double)x0;
-                acc[3 * e + 1] += (double)gv[e] * (double)x1;
-                acc[3 * e + 2] += (double)gv[e] * (double)x2;
-            }
+            lane_each<4>([&](int e, float g) {
+                acc[3 * e] += (double)g * (double)x0;
+                acc[3 * e + 1] += (double)g * (double)x1;
+                acc[3 * e + 2] += (double)g * (double)x2;
+            }, reinterpret_cast<const float4*>(dy)[(size_t)r * C4 + c4]);
         }
     }
-    if (ph > 0) {
-#pragma unroll
-        for (int e = 0; e < 12; ++e) red[ph - 1][lane][e] = acc[e];
-    }
-    __syncthreads();
-    if (ph == 0 && c4 < C4) {
+    if (phase_sum(acc, red, lane, ph, c4 < C4)) {
         double* pr = part + (size_t)blockIdx.y * 12 * C4 + 12 * c4;      // (channel, xyz) row-major: 3*(4c4+e) + j
 #pragma unroll
-        for (int e = 0; e < 12; ++e) pr[e] = ((acc[e] + red[0][lane][e]) + red[1][lane][e]) + red[2][lane][e];
+        for (int e = 0; e < 12; ++e) pr[e] = acc[e];
     }
 }
 
@@ -329,13 +246,7 @@ __global__ __launch_bounds__(256) void k_viewmax_fwd(const float* __restrict__ x
     const int b = i / C4, c4 = i - b * C4;
     float4 best = reinterpret_cast<const float4*>(x)[(size_t)b * C4 + c4];
     int4 bi = make_int4(0, 0, 0, 0);
-    for (int g = 1; g < G; ++g) {
-        const float4 v = reinterpret_cast<const float4*>(x)[((size_t)g * B + b) * C4 + c4];
-        if (v.x > best.x || v.x != v.x) { best.x = v.x; bi.x = g; }
-        if (v.y > best.y || v.y != v.y) { best.y = v.y; bi.y = g; }
-        if (v.z > best.z || v.z != v.z) { best.z = v.z; bi.z = g; }
-        if (v.w > best.w || v.w != v.w) { best.w = v.w; bi.w = g; }
-    }
+    for (int g = 1; g < G; ++g) first_max_wins(best, bi, reinterpret_cast<const float4*>(x)[((size_t)g * B + b) * C4 + c4], g);
     reinterpret_cast<float4*>(out)[i] = best;
     reinterpret_cast<int4*>(arg)[i] = bi;
 }
@@ -487,12 +398,23 @@ __global__ __launch_bounds__(256) void k_viewmax_bwd_add(const float* __restrict
     dx[((size_t)a.w * B + b) * C + col + 3] += d.w;
 }
 
-int rows_grid_y(int R, int C) {
-    int gx = (C + 255) / 256;
-    int gy = ROWS_BLOCKS / gx;
-    if (gy > R) gy = R;
-    if (gy < 1) gy = 1;
-    return gy;
+// grids of the partial-sum kernels, ROWS_BLOCKS workgroups at most: 256 channels x row slices ...
+dim3 rows_grid(int64_t R, int C) {
+    const int gx = (C + 255) / 256;
+    return dim3(gx, (int)std::max<int64_t>(1, std::min<int64_t>(ROWS_BLOCKS / gx, R)));
+}
+// ... or 64 lanes (of CW columns in all) x 4 row phases: no more slices than groups of four rows
+dim3 phase_grid(int64_t R, int CW) {
+    const int gx = (CW + 63) / 64;
+    return dim3(gx, (int)std::max<int64_t>(1, std::min<int64_t>(ROWS_BLOCKS / gx, (R + 3) / 4)));
+}
+
+// launch `kern` (256 threads; it leaves grid.y partial rows of V doubles in ws), then add the rows in order into `out`
+template <class... KA, class... A>
+int launch_partials(void (*kern)(KA...), dim3 grid, int V, double* out, void* ws, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, args...);
+    if (int rc = facl_launch_status()) return rc;
+    return facl_reduce_rows((const double*)ws, (int)grid.y, V, out, st);
 }
 
 }  // namespace
@@ -500,12 +422,7 @@ int rows_grid_y(int R, int C) {
 extern "C" int facl_rows_stats(const float* y, int64_t R, int C, double* sums, void* ws, void* stream) {
     if (!y || !sums || !ws) return FACL_E_NULL;
     if (R < 1 || R > 0x7fffffff || C < 1 || 2 * C > 4608) return FACL_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int gy = rows_grid_y((int)R, C);
-    hipLaunchKernelGGL(k_rows_stats, dim3((C + 255) / 256, gy), dim3(256), 0, st, y, (int)R, C, (double*)ws);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, gy, 2 * C, sums, st);
+    return launch_partials(k_rows_stats, rows_grid(R, C), 2 * C, sums, ws, (hipStream_t)stream, y, (int)R, C, (double*)ws);
 }
 
 extern "C" int facl_rows_bn_relu(const float* y, int64_t R, int C, const float* scale, const float* shift, float* out,
@@ -531,21 +448,9 @@ extern "C" int facl_rows_bwd_stats(const float* dout, const float* y, int64_t R,
                                    void* ws, void* stream) {
     if (!dout || !y || !bnc || !sums || !ws) return FACL_E_NULL;
     if (R < 1 || R > 0x7fffffff || C < 1 || 2 * C > 4608) return FACL_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    int gy = rows_grid_y((int)R, C);
-    if (!(C & 3) && !((((uintptr_t)dout) | ((uintptr_t)y) | ((uintptr_t)bnc)) & 15)) {
-        const int gx = (C / 4 + 63) / 64;
-        gy = ROWS_BLOCKS / gx;
-        if (gy > (R + 3) / 4) gy = (int)((R + 3) / 4);
-        if (gy < 1) gy = 1;
-        hipLaunchKernelGGL(k_rows_bwd_stats4, dim3(gx, gy), dim3(256), 0, st, dout, y, (int)R, C / 4, bnc, (double*)ws);
-    } else {
-        hipLaunchKernelGGL(k_rows_bwd_stats, dim3((C + 255) / 256, gy), dim3(256), 0, st, dout, y, (int)R, C, bnc,
-                           (double*)ws);
-    }
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, gy, 2 * C, sums, st);
+    const bool quads = !(C & 3) && aligned16(dout, y, bnc);
+    return launch_partials(quads ? k_rows_bwd_stats4 : k_rows_bwd_stats, quads ? phase_grid(R, C / 4) : rows_grid(R, C), 2 * C, sums, ws,
+                           (hipStream_t)stream, dout, y, (int)R, quads ? C / 4 : C, bnc, (double*)ws);
 }
 
 extern "C" int facl_rows_bwd_apply(const float* dout, const float* y, int64_t R, int C, const float* bnc,
@@ -560,7 +465,7 @@ extern "C" int facl_rows_bwd_apply_amax(const float* dout, const float* y, int64
                                         const float* kk, float* dy, uint32_t* amax, void* stream) {
     if (!dout || !y || !bnc || !kk || !dy) return FACL_E_NULL;
     if (R < 1 || C < 1) return FACL_E_SHAPE;
-    if (!(C & 3) && R <= 0x7fffffff && !((((uintptr_t)dout) | ((uintptr_t)y) | ((uintptr_t)dy) | ((uintptr_t)bnc) | ((uintptr_t)kk)) & 15)) {
+    if (!(C & 3) && R <= 0x7fffffff && aligned16(dout, y, dy, bnc, kk)) {
         const int gx = (C / 4 + 255) / 256;
         int gy = 4096 / gx;
         if (gy > R) gy = (int)R;
@@ -578,26 +483,16 @@ extern "C" int facl_segmax_bwd_stats(const float* dxpre, const float* xpre, cons
                                      int64_t M, int S, int C, const float* bnc, double* sums, void* ws, void* stream) {
     if (!dxpre || !xpre || !y || !arg || !bnc || !sums || !ws) return FACL_E_NULL;
     if (M < 1 || M > 0x7fffffff || S < 1 || C < 1 || 2 * C > 4608) return FACL_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int gy = rows_grid_y((int)M, C);
-    hipLaunchKernelGGL(k_segmax_bwd_stats, dim3((C + 255) / 256, gy), dim3(256), 0, st, dxpre, xpre, y, arg, (int)M, S,
-                       C, bnc, (double*)ws);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, gy, 2 * C, sums, st);
+    return launch_partials(k_segmax_bwd_stats, rows_grid(M, C), 2 * C, sums, ws, (hipStream_t)stream, dxpre, xpre, y, arg, (int)M, S,
+                           C, bnc, (double*)ws);
 }
 
 extern "C" int facl_segmax_bwd_stats_ymax(const float* dxpre, const float* xpre, const float* ymax, int64_t M, int C,
                                           const float* bnc, double* sums, void* ws, uint32_t* zamax, int zwords, void* stream) {
     if (!dxpre || !xpre || !ymax || !bnc || !sums || !ws) return FACL_E_NULL;
     if (M < 1 || M > 0x7fffffff || C < 1 || 2 * C > 4608 || zwords < 0) return FACL_E_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const int gy = rows_grid_y((int)M, C);
-    hipLaunchKernelGGL(k_segmax_bwd_stats_ymax, dim3((C + 255) / 256, gy), dim3(256), 0, st, dxpre, xpre, ymax, (int)M, C, bnc,
-                       (double*)ws, zamax, zwords);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, gy, 2 * C, sums, st);
+    return launch_partials(k_segmax_bwd_stats_ymax, rows_grid(M, C), 2 * C, sums, ws, (hipStream_t)stream, dxpre, xpre, ymax, (int)M,
+                           C, bnc, (double*)ws, zamax, zwords);
 }
 
 extern "C" int facl_segmax_bwd_apply(const float* dxpre, const float* xpre, const float* y, const int32_t* arg,
@@ -612,15 +507,11 @@ extern "C" int facl_segmax_bwd_apply_amax(const float* dxpre, const float* xpre,
                                           uint32_t* amax, void* stream) {
     if (!dxpre || !xpre || !y || !arg || !bnc || !kk || !dy) return FACL_E_NULL;
     if (M < 1 || M > 65535 || S < 1 || C < 1) return FACL_E_SHAPE;
-    if (!(C & 3) && !((((uintptr_t)dxpre) | ((uintptr_t)xpre) | ((uintptr_t)y) | ((uintptr_t)arg) | ((uintptr_t)dy) |
-                       ((uintptr_t)bnc) | ((uintptr_t)kk)) & 15)) {
-        hipLaunchKernelGGL(k_segmax_bwd_apply4, dim3((C / 4 + 255) / 256, (int)M), dim3(256), 0, (hipStream_t)stream, dxpre,
-                           xpre, y, arg, S, C / 4, bnc, kk, dy, amax);
-        return facl_launch_status();
-    }
-    if (amax) return FACL_E_ALIGN;
-    hipLaunchKernelGGL(k_segmax_bwd_apply, dim3((C + 255) / 256, (int)M), dim3(256), 0, (hipStream_t)stream, dxpre,
-                       xpre, y, arg, S, C, bnc, kk, dy);
+    const bool quads = !(C & 3) && aligned16(dxpre, xpre, y, arg, dy, bnc, kk);
+    if (!quads && amax) return FACL_E_ALIGN;
+    const int CW = quads ? C / 4 : C;
+    hipLaunchKernelGGL(quads ? k_segmax_bwd_apply<4> : k_segmax_bwd_apply<1>, dim3((CW + 255) / 256, (int)M), dim3(256), 0,
+                       (hipStream_t)stream, dxpre, xpre, y, arg, S, CW, bnc, kk, dy, amax);
     return facl_launch_status();
 }
 
@@ -628,22 +519,15 @@ extern "C" int facl_rows_center_wgrad(const float* dy, const float* centers, int
                                       void* stream) {
     if (!dy || !centers || !dWc || !ws) return FACL_E_NULL;
     if (R < 1 || R > 0x7fffffff || C < 4 || (C & 3) || 3 * C > 4608) return FACL_E_SHAPE;
-    if (((uintptr_t)dy) & 15) return FACL_E_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    const int gx = (C / 4 + 63) / 64;
-    int gy = ROWS_BLOCKS / gx;
-    if (gy > (R + 3) / 4) gy = (int)((R + 3) / 4);
-    if (gy < 1) gy = 1;
-    hipLaunchKernelGGL(k_rows_center_wgrad, dim3(gx, gy), dim3(256), 0, st, dy, centers, (int)R, C / 4, (double*)ws);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, gy, 3 * C, dWc, st);
+    if (!aligned16(dy)) return FACL_E_ALIGN;
+    return launch_partials(k_rows_center_wgrad, phase_grid(R, C / 4), 3 * C, dWc, ws, (hipStream_t)stream, dy, centers, (int)R, C / 4,
+                           (double*)ws);
 }
 
 extern "C" int facl_viewmax_fwd(const float* x, int G, int B, int C, float* out, int32_t* arg, void* stream) {
     if (!x || !out || !arg) return FACL_E_NULL;
     if (G < 1 || B < 1 || C < 4 || (C & 3)) return FACL_E_SHAPE;
-    if ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)arg)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(x, out, arg)) return FACL_E_ALIGN;
     const int n = B * (C / 4);
     hipLaunchKernelGGL(k_viewmax_fwd, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, G, B, C / 4, out, arg);
     return facl_launch_status();
@@ -652,7 +536,7 @@ extern "C" int facl_viewmax_fwd(const float* x, int G, int B, int C, float* out,
 extern "C" int facl_viewmax_bwd(const float* dout, const int32_t* arg, int G, int B, int C, float* dx, void* stream) {
     if (!dout || !arg || !dx) return FACL_E_NULL;
     if (G < 1 || B < 1 || C < 4 || (C & 3)) return FACL_E_SHAPE;
-    if ((((uintptr_t)dout) | ((uintptr_t)dx) | ((uintptr_t)arg)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(dout, dx, arg)) return FACL_E_ALIGN;
     const int n = B * (C / 4);
     hipLaunchKernelGGL(k_viewmax_bwd, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dout, arg, G, B, C / 4, dx);
     return facl_launch_status();
@@ -662,7 +546,7 @@ extern "C" int facl_normalize_map(const float* x, int64_t M, int C, const float*
                                   void* stream) {
     if (!x || !Wm || !x_nor || !code) return FACL_E_NULL;
     if (M < 0 || M > 0x7fffffff || C < 16 || (C & 15) || C > 4096 || K < 1 || K > 256) return FACL_E_SHAPE;
-    if ((((uintptr_t)x) | ((uintptr_t)Wm) | ((uintptr_t)x_nor)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(x, Wm, x_nor)) return FACL_E_ALIGN;
     if (M == 0) return 0;
     static const int four = facl_env_int("FACL_NORMMAP4", 1);     // A/B knob
     if (four && C == 512 && K == 64)
@@ -679,7 +563,7 @@ extern "C" int facl_normalize_map(const float* x, int64_t M, int C, const float*
 extern "C" int facl_viewmax_bwd_add(const float* dout, const int32_t* arg, int G, int B, int C, float* dx, void* stream) {
     if (!dout || !arg || !dx) return FACL_E_NULL;
     if (G < 1 || B < 1 || C < 4 || (C & 3)) return FACL_E_SHAPE;
-    if ((((uintptr_t)dout) | ((uintptr_t)arg)) & 15) return FACL_E_ALIGN;
+    if (!aligned16(dout, arg)) return FACL_E_ALIGN;
     const int n = B * (C / 4);
     hipLaunchKernelGGL(k_viewmax_bwd_add, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dout, arg, B, C / 4, dx);
     return facl_launch_status();

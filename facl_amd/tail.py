@@ -5,6 +5,7 @@ fused bias / centre term / BN column statistics, dgrad, split-K wgrad); train-mo
 SyncBN hook), BN+ReLU apply, BN+ReLU+max over the S centroids without materialising the activation, and the
 matching backward passes are the row kernels of csrc/rows.hip.
 """
+import os
 import threading
 
 import torch
@@ -61,6 +62,11 @@ def _fn(lib, name, prec):
     return getattr(lib, name + _SUFFIX[prec])
 
 
+def _env_on(name, default="1"):
+    """A/B switch from the environment: on unless set to 0."""
+    return os.environ.get(name, default) != "0"
+
+
 def gemm_fwd(a, W, bias, want_stats=False, centers=None, Wc=None, prec=None):
     """y = a W^T + bias [+ centers Wc^T] on the hand-written fp32 MFMA GEMM (csrc/gemm.hip); optional fused
     column (sum, sumsq) for the BatchNorm that follows."""
@@ -91,6 +97,28 @@ def gemm_dgrad(dy, W, prec=None):
     return da
 
 
+def _wgrad_slices(M, N, K):
+    """Row slices of the LDS-staged weight gradient: tiles * slices = one resident wave of workgroups (2 per CU)."""
+    tiles = ((N + 127) // 128) * ((K + 127) // 128)
+    return max(1, min((M + 255) // 256, 512 // tiles))
+
+
+def _wgrad_h3(dy, a, bnc, amax, amax_b, dW, slices, nz):
+    """dW = dy^T a (with `bnc`: dy^T relu(bn(a))) in fp16x3 on the LDS-staged kernel.  False (nothing written) when the
+    kernel does not serve the shape (FACL_E_CONFIG): the caller falls through to the bf16x6 kernels."""
+    lib = _lib.load_library()
+    M, N = dy.shape
+    K = a.shape[1]
+    ps, pt = (bnc[2], bnc[3]) if bnc is not None else (None, None)
+    with _lib.timed("facl_gemm_wgrad %dx%dx%d h3" % (M, N, K)):
+        rc = lib.facl_gemm_wgrad_h3(_lib.ptr(dy), _lib.ptr(a), M, N, K, a.stride(0), _lib.ptr(ps), _lib.ptr(pt), _lib.ptr(amax),
+                                    _lib.ptr(amax_b), _lib.ptr(dW), _lib.ptr(slices), nz, _lib.stream())
+    if rc == -4:
+        return False
+    _lib.check(rc, "facl_gemm_wgrad_h3")
+    return True
+
+
 def gemm_wgrad(dy, a, prec=None, amax=None, amax_b=None):
     """dW = dy^T a, contraction over the rows split into slices (deterministic slice-order sum).  `amax` (the device-side
     max|dy| buffer of facl_rows_bwd_apply_amax) + `amax_b` (the bound of max|a| its forward GEMM used): fp16x3 arithmetic
@@ -98,18 +126,12 @@ def gemm_wgrad(dy, a, prec=None, amax=None, amax_b=None):
     lib = _lib.load_library()
     M, N = dy.shape
     K = a.shape[1]
-    tiles = ((N + 127) // 128) * ((K + 127) // 128)
-    nz = max(1, min((M + 255) // 256, 512 // tiles))     # tiles * nz = one resident wave of workgroups (2 per CU)
+    nz = _wgrad_slices(M, N, K)
     dW = _lib.empty((N, K), dtype=torch.float32, device=dy.device)
     slices = _lib.empty(nz * N * K, dtype=torch.float32, device=dy.device)
     prec = current_precision() if prec is None else prec
-    if amax is not None and amax_b is not None and prec == "f32":
-        with _lib.timed("facl_gemm_wgrad %dx%dx%d h3" % (M, N, K)):
-            rc = lib.facl_gemm_wgrad_h3(_lib.ptr(dy), _lib.ptr(a), M, N, K, a.stride(0), None, None, _lib.ptr(amax), _lib.ptr(amax_b),
-                                        _lib.ptr(dW), _lib.ptr(slices), nz, _lib.stream())
-        if rc != -4:
-            _lib.check(rc, "facl_gemm_wgrad_h3")
-            return dW
+    if amax is not None and amax_b is not None and prec == "f32" and _wgrad_h3(dy, a, None, amax, amax_b, dW, slices, nz):
+        return dW
     with _lib.timed("facl_gemm_wgrad %dx%dx%d%s" % (M, N, K, _LABEL[prec])):
         _lib.check(_fn(lib, "facl_gemm_wgrad", prec)(_lib.ptr(dy), _lib.ptr(a), M, N, K, a.stride(0), _lib.ptr(dW), _lib.ptr(slices), nz,
                                        _lib.stream()), "facl_gemm_wgrad")
@@ -133,6 +155,34 @@ def _bn_bwd_consts(sums, C, count, reduce_fn):
     _lib.check(lib.facl_bn_bwd_consts(_lib.ptr(sums), _lib.ptr(sums_g), C, float(count), _lib.ptr(dbeta), _lib.ptr(dgamma),
                                       _lib.ptr(kk), _lib.stream()), "facl_bn_bwd_consts")
     return dbeta, dgamma, kk
+
+
+def _bn_relu_backward(da, y, bnc, count, reduce_fn, ws, sums=None, amax=None):
+    """Backward of relu(bn(y)) over rows: column sums (unless the producer of `da` left them in `sums`) -> constants -> dense
+    dy, which also raises `amax` (or None) to max|dy|.  Returns (dy, dgamma, dbeta); the parameter gradients stay local sums."""
+    lib = _lib.load_library()
+    R, C = y.shape
+    if sums is None:
+        sums = _lib.empty((C, 2), dtype=torch.float64, device=y.device)
+        _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws),
+                                           _lib.stream()), "facl_rows_bwd_stats")
+    dbeta, dgamma, kk = _bn_bwd_consts(sums, C, count, reduce_fn)
+    dy = _lib.empty_like(y)
+    _lib.check(lib.facl_rows_bwd_apply_amax(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy),
+                                            _lib.ptr(amax), _lib.stream()), "facl_rows_bwd_apply_amax")
+    return dy, dgamma, dbeta
+
+
+def _first_layer_wgrad(dy, h, centers, ws, prec, amax=None, amax_b=None):
+    """dW (C, 3 + Cin) of the first per-centroid layer, whose input is torch.cat((centers, h), 1): the GEMM on h, the three
+    centroid-xyz columns as one streaming pass over dy."""
+    lib = _lib.load_library()
+    R, C = dy.shape
+    dWh = gemm_wgrad(dy, h, prec=prec, amax=amax, amax_b=amax_b)
+    dWc = _lib.empty((C, 3), dtype=torch.float64, device=dy.device)
+    _lib.check(lib.facl_rows_center_wgrad(_lib.ptr(dy), _lib.ptr(centers), R, C, _lib.ptr(dWc), _lib.ptr(ws), _lib.stream()),
+               "facl_rows_center_wgrad")
+    return torch.cat((dWc.float(), dWh), dim=1)
 
 
 def _forward_bn_consts(y, bn, training, reduce_fn, ws, sums=None, aamax=None):
@@ -189,24 +239,10 @@ class _LinearBNReLU(torch.autograd.Function):
         bp = backward_precision(ctx.prec)   # the backward GEMMs run in the arithmetic the forward recorded
         if not ctx.training:
             raise RuntimeError("backward through the eval-mode (folded BN) encoder is not supported")
-        lib = _lib.load_library()
         h, W, y, bnc = ctx.saved_tensors
         ws = _Workspace.get(y.device)
-        R, C = y.shape
-        da = da.contiguous()
-        sums = _lib.empty((C, 2), dtype=torch.float64, device=y.device)
-        _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws),
-                                           _lib.stream()), "facl_rows_bwd_stats")
-        dbeta, dgamma, kk = _bn_bwd_consts(sums, C, ctx.count, ctx.reduce_fn)   # parameter gradients stay local sums
-        dy = _lib.empty_like(y)
-        _lib.check(lib.facl_rows_bwd_apply(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy),
-                                           _lib.stream()), "facl_rows_bwd_apply")
-        dW = gemm_wgrad(dy, h, prec=bp)
-        if ctx.centers is not None:                                     # xyz columns (C,3): one streaming pass over dy
-            dWc = _lib.empty((C, 3), dtype=torch.float64, device=y.device)
-            _lib.check(lib.facl_rows_center_wgrad(_lib.ptr(dy), _lib.ptr(ctx.centers), R, C, _lib.ptr(dWc), _lib.ptr(ws),
-                                                  _lib.stream()), "facl_rows_center_wgrad")
-            dW = torch.cat((dWc.float(), dW), dim=1)
+        dy, dgamma, dbeta = _bn_relu_backward(da.contiguous(), y, bnc, ctx.count, ctx.reduce_fn, ws)
+        dW = gemm_wgrad(dy, h, prec=bp) if ctx.centers is None else _first_layer_wgrad(dy, h, ctx.centers, ws, bp)
         dh = gemm_dgrad(dy, ctx.Wh, prec=bp) if ctx.needs_input_grad[0] else None
         # d(bias) is identically zero in front of a train-mode BN: None leaves the parameter untouched
         return dh, dW, None, dgamma, dbeta, None, None, None, None
@@ -309,7 +345,7 @@ class _Linear(torch.autograd.Function):
         return gemm_dgrad(dy, W, prec=bp), gemm_wgrad(dy, h, prec=bp), dy.sum(0)
 
 
-_FC_FUSED = __import__("os").environ.get("FACL_FC_FUSED", "1") != "0"          # A/B switch: 0 = the single-segment kernels of rounds 2-4
+_FC_FUSED = _env_on("FACL_FC_FUSED")        # A/B switch: 0 = the single-segment kernels of rounds 2-4
 
 
 class _FCHead(torch.autograd.Function):
@@ -602,10 +638,10 @@ def rs_planes_multi(jobs, absmax=None):
 
 # Forward arithmetic of the row-streamed GEMMs: fp16x3 (two fp16 planes of pre-scaled operands, three products: the same
 # fp32-GEMM accuracy at half the MFMA work, csrc/common.h) unless FACL_FWD_H3=0 selects bf16x6 (A/B, bit-identity tests)
-FWD_H3 = __import__("os").environ.get("FACL_FWD_H3", "1") != "0"
+FWD_H3 = _env_on("FACL_FWD_H3")
 # Backward arithmetic of the row-streamed dgrad / weight-gradient kernels: fp16x3 with the gradient operand's power-of-two
 # scale taken per launch from max|dy| (a device scalar its producer kernel maintains); FACL_BWD_H3=0: bf16x6
-BWD_H3 = __import__("os").environ.get("FACL_BWD_H3", "1") != "0"
+BWD_H3 = _env_on("FACL_BWD_H3")
 
 
 def _rs_fwd(a, planes, N, bias, pro, centers, want_stats, seg_sgn, ws, half=False, amax_a=None):
@@ -625,7 +661,7 @@ def _rs_fwd(a, planes, N, bias, pro, centers, want_stats, seg_sgn, ws, half=Fals
     return y, sums, ymax, arg
 
 
-_FUSE_BNSTATS = __import__("os").environ.get("FACL_RS_BNSTATS", "1") != "0"      # A/B switch: 0 = separate facl_rows_bwd_stats pass
+_FUSE_BNSTATS = _env_on("FACL_RS_BNSTATS")   # A/B switch: 0 = separate facl_rows_bwd_stats pass
 
 
 def _rs_dgrad(dy, W, prec, planes=None, bn_y=None, bn_c=None, ws=None, amax=None):
@@ -654,7 +690,7 @@ def _rs_dgrad(dy, W, prec, planes=None, bn_y=None, bn_c=None, ws=None, amax=None
     return da, sums
 
 
-_WGRAD_RS = __import__("os").environ.get("FACL_WGRAD_RS", "1") != "0"            # A/B switch
+_WGRAD_RS = _env_on("FACL_WGRAD_RS")         # A/B switch
 
 
 def _wgrad_pro(dy, y, bnc, prec, amax=None, amax_b=None):
@@ -673,16 +709,11 @@ def _wgrad_pro(dy, y, bnc, prec, amax=None, amax_b=None):
                                               _lib.ptr(amax), _lib.ptr(amax_b), _lib.ptr(dW), _lib.ptr(slices), _lib.stream()),
                        "facl_gemm_rs_wgrad")
         return dW
-    tiles = ((N + 127) // 128) * ((K + 127) // 128)
-    nz = max(1, min((M + 255) // 256, 512 // tiles))
+    nz = _wgrad_slices(M, N, K)
     slices = _lib.empty(nz * N * K, dtype=torch.float32, device=dy.device)
-    if amax is not None and prec == "f32":                              # fp16x3 on the LDS-staged kernel (the narrower layers)
-        with _lib.timed("facl_gemm_wgrad %dx%dx%d h3" % (M, N, K)):
-            rc = lib.facl_gemm_wgrad_h3(_lib.ptr(dy), _lib.ptr(y), M, N, K, y.stride(0), _lib.ptr(bnc[2]), _lib.ptr(bnc[3]),
-                                        _lib.ptr(amax), _lib.ptr(amax_b), _lib.ptr(dW), _lib.ptr(slices), nz, _lib.stream())
-        if rc != -4:
-            _lib.check(rc, "facl_gemm_wgrad_h3")
-            return dW
+    # fp16x3 on the LDS-staged kernel (the narrower layers)
+    if amax is not None and prec == "f32" and _wgrad_h3(dy, y, bnc, amax, amax_b, dW, slices, nz):
+        return dW
     fn = lib.facl_gemm_wgrad_pro_x3 if prec == "x3" else lib.facl_gemm_wgrad_pro
     with _lib.timed("facl_gemm_wgrad %dx%dx%d%s" % (M, N, K, _LABEL[prec])):
         rc = fn(_lib.ptr(dy), _lib.ptr(y), M, N, K, y.stride(0), _lib.ptr(bnc[2]), _lib.ptr(bnc[3]), _lib.ptr(dW),
@@ -698,8 +729,7 @@ def _wgrad_pro(dy, y, bnc, prec, amax=None, amax_b=None):
 
 def net3dv3_supported(P, widths, S, prec):
     """True when the three per-centroid layers (cn3d_model_conbag.py:61-77) run on the row-streamed kernels."""
-    import os
-    if os.environ.get("FACL_TAIL_RS", "1") == "0" or prec not in ("f32", "x3b") or S != 64 or P % 64:
+    if not _env_on("FACL_TAIL_RS") or prec not in ("f32", "x3b") or S != 64 or P % 64:
         return False
     lib = _lib.load_library()
     c0, c1, c2, c3 = widths
@@ -799,24 +829,12 @@ class _Net3DV3(torch.autograd.Function):
         # ---- layers 2 and 1: BN backward rows passes, weight gradient with the recomputed activation, dgrad
         grads = []
         for li, (y, bnc, yin, bnc_in, W) in enumerate(((y2, bnc2, y1, bnc1, W2), (y1, bnc1, None, None, W1)), 1):
-            C = y.shape[1]
-            if sums is None:
-                sums = _lib.empty((C, 2), **f64)
-                _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(da), _lib.ptr(y), P, C, _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws), st),
-                           "facl_rows_bwd_stats")
-            dbe, dga, kk = _bn_bwd_consts(sums, C, ctx.count, ctx.reduce_fn)
-            dy = _lib.empty_like(y)
-            _lib.check(lib.facl_rows_bwd_apply_amax(_lib.ptr(da), _lib.ptr(y), P, C, _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy),
-                                                    _lib.ptr(am(li)), st), "facl_rows_bwd_apply")
+            dy, dga, dbe = _bn_relu_backward(da, y, bnc, ctx.count, ctx.reduce_fn, ws, sums, am(li))
             if yin is not None:
                 dW = _wgrad_pro(dy, yin, bnc_in, bp, am(li), a1b)
                 da, sums = _rs_dgrad(dy, W, bp, bpl[1], yin, bnc_in, ws, am(li))
             else:                                                       # first layer: input = pooled | centres
-                dWh = gemm_wgrad(dy, pooled, prec=bp, amax=am(li), amax_b=a0b)
-                dWc = _lib.empty((C, 3), **f64)
-                _lib.check(lib.facl_rows_center_wgrad(_lib.ptr(dy), _lib.ptr(centers), P, C, _lib.ptr(dWc), _lib.ptr(ws), st),
-                           "facl_rows_center_wgrad")
-                dW = torch.cat((dWc.float(), dWh), dim=1)
+                dW = _first_layer_wgrad(dy, pooled, centers, ws, bp, am(li), a0b)
                 da = _rs_dgrad(dy, W[:, 3:], bp, bpl[2], amax=am(li))[0] if ctx.needs_input_grad[0] else None
             grads.append((dW, dga, dbe))
         (dW2, dga2, dbe2), (dW1, dga1, dbe1) = grads

@@ -27,6 +27,23 @@ def rel_err(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
+def bn_consts(K, g):
+    """Random (5, K) BatchNorm constants on the generator's device: mean | invstd | scale | shift | (unused)."""
+    import torch
+    dev = g.device
+    return torch.stack((torch.randn(K, device=dev, generator=g) * 0.1, torch.rand(K, device=dev, generator=g) + 0.5,
+                        torch.randn(K, device=dev, generator=g), torch.randn(K, device=dev, generator=g) * 0.3,
+                        torch.zeros(K, device=dev))).contiguous()
+
+
+def clear_of_the_relu_edge(y, bnc):
+    """Entries whose scale*y + shift is within rounding of 0 would open or close the ReLU depending on fma vs mul+add; the
+    reference expression of the caller is not the kernel's instruction sequence, so move them well inside the open side."""
+    import torch
+    t = bnc[2].double() * y.double() + bnc[3].double()
+    return torch.where(t.abs() < 1e-4, ((1.0 - bnc[3]) / bnc[2]).expand_as(y), y).contiguous()
+
+
 def max_rel_rows(a, b):
     """max over rows of ||a_i-b_i|| / ||b_i|| (features: atol scaled by row norm, SURVEY hard part 4)."""
     a = np.asarray(a, dtype=np.float64)

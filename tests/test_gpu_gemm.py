@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import bn_consts as _bn_consts, clear_of_the_relu_edge as _clear_of_the_relu_edge, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -482,19 +482,6 @@ def test_gemm_rs_fwd_fp16x3_is_fp32_grade(M, K, N, pro, ctr, seg):
         sy = (y * torch.where(sgn < 0, -1.0, 1.0)).view(M // 64, 64, N)
         assert torch.equal(ymax, sy.max(dim=1).values)
         assert torch.equal(arg.long(), (sy == ymax.unsqueeze(1)).float().argmax(dim=1))
-
-
-def _bn_consts(K, g):
-    return torch.stack((torch.randn(K, device=DEV, generator=g) * 0.1, torch.rand(K, device=DEV, generator=g) + 0.5,
-                        torch.randn(K, device=DEV, generator=g), torch.randn(K, device=DEV, generator=g) * 0.3,
-                        torch.zeros(K, device=DEV))).contiguous()                     # mean | invstd | scale | shift | (unused)
-
-
-def _clear_of_the_relu_edge(y, bnc):
-    """Entries whose scale*y + shift is within rounding of 0 would open or close the ReLU depending on fma vs mul+add; the
-    reference expression below is not the kernel's instruction sequence, so move them well inside the open side."""
-    t = bnc[2].double() * y.double() + bnc[3].double()
-    return torch.where(t.abs() < 1e-4, ((1.0 - bnc[3]) / bnc[2]).expand_as(y), y).contiguous()
 
 
 @pytest.mark.parametrize("mag", [1.0, 3e-9, 7e5])

@@ -203,7 +203,7 @@ def _fc_head_reference_fp64(x_pre, G, W1, b1, gamma, beta, W2, b2, rm, rv, momen
     return torch.cat(outs, 0), rm, rv
 
 
-@pytest.mark.parametrize("G,B,Cin,C,dim", [(24, 32, 1024, 1024, 512), (8, 4, 64, 128, 32), (2, 16, 32, 64, 16)])
+@pytest.mark.parametrize("G,B,Cin,C,dim", [(24, 32, 1024, 1024, 512), (8, 4, 64, 128, 32), (2, 16, 32, 64, 16), (16, 2, 32, 68, 16)])
 def test_fc_head_two_segment_batchnorm_vs_two_fp64_calls(G, B, Cin, C, dim):
     """tail.fc_head on the fused two-segment BatchNorm kernels (csrc/fchead.hip: slice statistics -> both finalisations ->
     one apply; backward: slice sums -> constants + gamma / beta gradients of both segments -> one apply; the view maximum

@@ -19,9 +19,14 @@ def is_distributed():
     return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
 
+def env_world_size():
+    """The launcher's WORLD_SIZE (torch.distributed.run); 1 without a launcher."""
+    return int(os.environ.get("WORLD_SIZE", "1"))
+
+
 def init_from_env(backend=None):
     """Initialise the default process group from RANK/WORLD_SIZE/MASTER_* (torch.distributed.run)."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world = env_world_size()
     if world <= 1 or dist.is_initialized():
         return 0, world if dist.is_initialized() else 1
     rank = int(os.environ["RANK"])

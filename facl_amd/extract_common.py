@@ -8,8 +8,7 @@ import numpy as np
 import torch
 
 from . import cn3d_model_conbag as MM
-from .train_common import build_parser, synthetic_batch
-from .utils_my import group_points_3DV, knn_radius_group
+from .train_common import build_parser, check_view_flags, group_views, synthetic_batch
 
 
 def save_single_feature(feature, save_path, name, num_crop=11):
@@ -24,11 +23,7 @@ def extract_batch(netR, out_points, opt, group_radius=None):
     """(B,G,N,D) clips -> (B, (G+1)*512) features, exactly the reference's per-batch body (:171-182)."""
     B, G, N, D = out_points.shape
     data1 = out_points.permute(1, 0, 2, 3).reshape(-1, N, D).float()
-    if group_radius is None and opt.SAMPLE_NUM == 512:
-        xt, yt = group_points_3DV(data1, opt)
-    else:
-        opt.INPUT_FEATURE_NUM = D
-        xt, yt = knn_radius_group(data1, opt.sample_num_level1, opt.knn_K, 0.16 if group_radius is None else group_radius)
+    xt, yt = group_views(data1, opt, group_radius)
     x, _, _, x_global = netR(xt, yt)
     feat = torch.cat((x, x_global), dim=0)
     return feat.reshape(G + 1, B, 512).permute(1, 0, 2).reshape(B, (G + 1) * 512)
@@ -63,17 +58,21 @@ def run(default_branch, default_ckpt, args=None):
     return np.concatenate(feats)
 
 
-def extract_split(netR, opt, device, index, split, rng, save_path=''):
-    """One split of `run_disk`: the clips `split` (dataset indices) in order, batches of --batchSize with the last one ragged,
-    views drawn from `rng` (--view_rng numpy) or keyed by (2000, 0, dataset index) (philox).  Returns the
-    (clips, (num_crop+1)*512) float32 features as a DEVICE tensor; with `save_path` every clip is also written to
-    <save_path>/<v_name>.npy as its batch completes.  The caller holds torch.no_grad() and has put `netR` in eval()."""
+def ordered_views(opt, device, index, split, rng):
+    """The evaluation pass: the clips `split` (dataset indices) in order, batches of --batchSize with the last one ragged, as
+    ((G*B, N, 4) views, v_names, labels); views drawn from `rng` (--view_rng numpy) or keyed by (2000, 0, index) (philox)."""
     from . import dataset as fds
     vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
+    return iter(fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device, rng=rng, seed=2000,
+                                epoch=0, prefetch=bool(opt.prefetch), num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM))
+
+
+def extract_split(netR, opt, device, index, split, rng, save_path=''):
+    """One split of `run_disk`, drawn by `ordered_views`.  Returns the (clips, (num_crop+1)*512) float32 features as a
+    DEVICE tensor; with `save_path` every clip is also written to <save_path>/<v_name>.npy as its batch completes.  The
+    caller holds torch.no_grad() and has put `netR` in eval()."""
     feats = []
-    for views, names, _ in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
-                                           rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch),
-                                           num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM):
+    for views, names, _ in ordered_views(opt, device, index, split, rng):
         B = len(names)
         clip_major = views.view(opt.num_crop, B, opt.SAMPLE_NUM, 4).permute(1, 0, 2, 3)
         f = extract_batch(netR, clip_major, opt, opt.group_radius)
@@ -93,7 +92,6 @@ def run_disk(netR, opt, device):
     Returns the (clips, (num_crop+1)*512) features in that order.  With --view_rng philox any --num_crop / --SAMPLE_NUM of
     the view kernels' domain (a vector is (num_crop+1)*512 long whatever SAMPLE_NUM is)."""
     from . import dataset as fds
-    from .train_common import check_view_flags
     check_view_flags(opt)
     index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
     rng = np.random.RandomState(2000)

@@ -9,16 +9,16 @@ output in place (facl_amd/cls_head.py, csrc/cls.hip); the step replays as one HI
 import logging
 import math
 import os
-import random
-import time
 
 import numpy as np
 import torch
 
 from . import cn3d_model_conbag as MODELL
+from . import dist as fdist
 from .cls_head import ClipClassifier
-from .train_common import (ContrastiveStep, GraphCaptureFailed, GraphedStep, build_parser, check_resident_flags,
-                           check_view_flags, lr_for_epoch, synthetic_batch)
+from .extract_common import ordered_views
+from .train_common import (ContrastiveStep, TrainBatches, build_parser, check_resident_flags, check_view_flags, eval_mode,
+                           setup_run, synthetic_batch, train_epochs)
 
 HEAD_PREFIX = "head."
 
@@ -108,7 +108,7 @@ def finetune_parser():
 
 def check_finetune_flags(opt, world=None):
     """One rank, labelled clips or synthetic ones; raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
-    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    world = fdist.env_world_size() if world is None else world
     if world > 1:
         raise RuntimeError("fine-tuning runs on one rank only (got %d ranks): data-parallel fine-tuning is not implemented" % world)
     if opt.synthetic not in (0, 1):
@@ -135,33 +135,23 @@ def _raise_bad_labels(bad, num_class, where):
 
 
 def evaluate(netR, step, opt, device):
-    """Test top-1 (%) of the model as it stands: the test split of <data_root>/raw in eval(), batches from ordered_batches,
-    views as extract_split draws them (view seed 2000, epoch 0, its own generator), hits from the loss kernel's stats[0].
+    """Test top-1 (%) of the model as it stands: the test split of <data_root>/raw in eval(), batches and views as
+    extract_split draws them (extract_common.ordered_views with its own generator), hits from the loss kernel's stats[0].
     The model returns to the mode it was in."""
     from . import dataset as fds
     index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
     split = index.select(opt.split, test=True)
     if not len(split):
         raise RuntimeError("--eval_every: the test split of %s has no clips" % opt.data_root)
-    vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
-    rng = np.random.RandomState(2000)
-    was_training = netR.training
-    netR.eval()
     total = torch.zeros(2, dtype=torch.int64, device=device)
-    try:
-        with torch.no_grad():
-            for views, names, labels in fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device,
-                                                        rng=rng, seed=2000, epoch=0, prefetch=bool(opt.prefetch),
-                                                        num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM):
-                B = len(names)
-                xt, yt = step.group(views if views.dtype == torch.float32 else views.float())
-                netR.lazy_code = False
-                netR(xt, yt, 1)
-                logits = netR.head(netR._stacked, opt.num_crop, B)
-                y = torch.as_tensor(labels, dtype=torch.int32).to(device)
-                total += netR.head.loss(logits, y)[1]
-    finally:
-        netR.train(was_training)
+    with eval_mode(netR):
+        for views, names, labels in ordered_views(opt, device, index, split, np.random.RandomState(2000)):
+            xt, yt = step.group(views if views.dtype == torch.float32 else views.float())
+            netR.lazy_code = False
+            netR(xt, yt, 1)
+            logits = netR.head(netR._stacked, opt.num_crop, len(names))
+            y = torch.as_tensor(labels, dtype=torch.int32).to(device)
+            total += netR.head.loss(logits, y)[1]
     hits, bad = (int(v) for v in total.cpu())
     if bad:
         _raise_bad_labels(bad, opt.num_class, "the test split")
@@ -177,16 +167,7 @@ def main(args=None):
     check_view_flags(opt)
     torch.cuda.set_device(opt.main_gpu)
     device = torch.device("cuda", opt.main_gpu)
-
-    opt.manualSeed = 1
-    random.seed(opt.manualSeed)
-    torch.manual_seed(opt.manualSeed)
-    np.random.seed(opt.manualSeed)
-    os.makedirs(opt.save_root_dir, exist_ok=True)
-    if opt.log_file:
-        logging.basicConfig(format='%(asctime)s %(message)s', datefmt='%Y/%m/%d %H:%M:%S',
-                            filename=opt.log_file, level=logging.INFO)
-    logging.info('======================================================')
+    setup_run(opt)
 
     num_crop = opt.num_crop
     netR = FineTuneNet(opt, opt.num_class, gost=num_crop)
@@ -199,75 +180,39 @@ def main(args=None):
     step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder))
     gen = torch.Generator(device=device)
     gen.manual_seed(1000)
-    view_rng = np.random.RandomState(2000)
 
-    steps_per_epoch = opt.steps_per_epoch
-    resident = None
-    if opt.synthetic == 0:
-        from . import dataset as fds
-        index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.TRAIN_LIST_DIR[opt.branch_choose]), opt.dataset)
-        split = np.asarray(index.select(opt.split, full_train=bool(opt.full_train)), dtype=np.int64)
-        n_all = len(split)
-        split = split[label_subset([index.label(int(v)) for v in split], opt.label_fraction, opt.label_seed)]
-        print('labelled clips: %d of %d' % (len(split), n_all))
-        steps_per_epoch = len(split) // opt.batchSize
-        if opt.max_steps_per_epoch > 0:
-            steps_per_epoch = min(steps_per_epoch, opt.max_steps_per_epoch)
-        if steps_per_epoch < 1:
-            raise RuntimeError("the labelled subset has %d clips: fewer than one batch of %d" % (len(split), opt.batchSize))
-        if opt.resident:
-            from . import resident as fres
-            resident = fres.ResidentClips(index, opt.data_root, opt.branch_choose, split, device, max_gb=opt.resident_max_gb,
-                                          reserve=fres.step_reserve_bytes(opt.batchSize, num_crop, opt.SAMPLE_NUM))
+    def labelled(index, split):
+        keep = split[label_subset([index.label(int(v)) for v in split], opt.label_fraction, opt.label_seed)]
+        print('labelled clips: %d of %d' % (len(keep), len(split)))
+        return keep
 
-    run_step, top1 = step, None
-    for epoch in range(0, opt.nepoch):
-        netR.train()
-        for g in optimizer.param_groups:
-            g["lr"] = lr_for_epoch(opt.learning_rate, epoch, step_size=5, gamma=0.7)      # the probe's schedule
-        loss_sigma, hits, t0 = 0.0, 0, time.time()
-        disk = None
-        if opt.synthetic == 0:
-            pos = fds.train_batches(len(split), opt.batchSize, 1, 0, opt.manualSeed, epoch)[:steps_per_epoch]
-            if resident is not None:
-                disk = fres.ResidentBatches(resident, [split[p] for p in pos], seed=2000, epoch=epoch,
-                                            num_crop=num_crop, num_point=opt.SAMPLE_NUM)
-            else:
-                disk = fds.DiskBatches(index, opt.data_root, opt.branch_choose, [split[p] for p in pos], opt.view_rng, device,
-                                       rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch),
-                                       num_crop=num_crop, num_point=opt.SAMPLE_NUM)
-                disk.hold_first = run_step is step and bool(opt.graph)                   # capture on batch 0
-                disk = iter(disk)
-        for i in range(steps_per_epoch):
-            if opt.synthetic == 0:
-                out_points, _, labels = next(disk)
-                labels = torch.as_tensor(labels, dtype=torch.int32)
-            else:
-                out_points = synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
-                labels = torch.randint(0, opt.num_class, (opt.batchSize,), device=device, generator=gen).to(torch.int32)
-            step.labels.copy_(labels)
-            if run_step is step and opt.graph:
-                try:                                     # capture on the first batch; state restored: same trajectory as eager
-                    run_step = GraphedStep(step, out_points, num_crop, restore=True)
-                except GraphCaptureFailed as e:
-                    print("graph capture failed (%s); running eager" % e)
-                    opt.graph = 0
-            loss, _, stats = run_step(out_points, epoch)
-            torch.cuda.synchronize()
-            lv = loss.item()
-            if lv != lv or lv in (float("inf"), float("-inf")):
-                raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
-            h, bad = (int(v) for v in stats.cpu())
-            if bad:
-                _raise_bad_labels(bad, opt.num_class, "the train split")
-            loss_sigma += lv
-            hits += h
+    source = TrainBatches(opt, device, 0, 1, subset=labelled, too_few="the labelled subset has %(clips)d clips: fewer than "
+                          "one batch of %(batch)d") if opt.synthetic == 0 else None
+    steps_per_epoch = opt.steps_per_epoch if source is None else source.steps
+    hits, top1 = 0, None
+
+    def next_batch(disk, epoch, i):
         if disk is not None:
-            disk.close()
-        clips = opt.batchSize * steps_per_epoch / (time.time() - t0)
-        train_top1 = 100.0 * hits / (opt.batchSize * steps_per_epoch)
-        logging.info('{} --epoch{} ==Average loss:{} train top1:{}'.format('Valid', epoch, loss_sigma / steps_per_epoch, train_top1))
-        print('epoch:', epoch, '--loss:', loss_sigma / steps_per_epoch, 'train top1:', train_top1, '| clips/s: %.1f' % clips)
+            out_points, _, labels = next(disk)
+            labels = torch.as_tensor(labels, dtype=torch.int32)
+        else:
+            out_points = synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
+            labels = torch.randint(0, opt.num_class, (opt.batchSize,), device=device, generator=gen).to(torch.int32)
+        step.labels.copy_(labels)
+        return out_points
+
+    def after_step(out):
+        nonlocal hits
+        h, bad = (int(v) for v in out[2].cpu())
+        if bad:
+            _raise_bad_labels(bad, opt.num_class, "the train split")
+        hits += h
+
+    def after_epoch(epoch, mean_loss, clips):
+        nonlocal hits, top1
+        train_top1, hits = 100.0 * hits / (opt.batchSize * steps_per_epoch), 0
+        logging.info('{} --epoch{} ==Average loss:{} train top1:{}'.format('Valid', epoch, mean_loss, train_top1))
+        print('epoch:', epoch, '--loss:', mean_loss, 'train top1:', train_top1, '| clips/s: %.1f' % clips)
         if opt.synthetic == 0 and opt.eval_every and (epoch + 1) % opt.eval_every == 0:
             top1 = evaluate(netR, step, opt, device)
             logging.info('{} --epoch{} ==test top1:{}'.format('Valid', epoch, top1))
@@ -275,6 +220,8 @@ def main(args=None):
         if epoch % 5 == 0 or epoch == opt.nepoch - 1:
             torch.save(netR.encoder_state_dict(), '%s/finetune_enc_%d.pth' % (opt.save_root_dir, epoch))
             torch.save(netR.head_state_dict(), '%s/finetune_fc_%d.pth' % (opt.save_root_dir, epoch))
+
+    train_epochs(opt, step, source, world=1, lr_step=5, next_batch=next_batch, after_epoch=after_epoch, after_step=after_step)
     return top1
 
 

@@ -4,7 +4,6 @@ an exp(s / T)-weighted vote over their labels.  The similarity GEMM and the sele
 (csrc/knn.hip: fp16x3 exact split, running top-k per query in the epilogue), so the (queries, bank) similarity matrix is
 never written.  GPU only: there is no CPU path."""
 import argparse
-import os
 
 import torch
 
@@ -117,18 +116,10 @@ def build_parser():
 
 def main(args=None):
     """The test split classified against the train split as bank; prints and returns the top-1 (%)."""
-    from . import dataset as fds
-    from .linear_classify import load_split
+    from .linear_classify import load_splits
     opt = build_parser().parse_args(args)
     print(opt)
-    device = torch.device("cuda", opt.main_gpu)
-    torch.cuda.set_device(device)
-    index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.PROBE_LIST_DIR), opt.dataset)
-    data = []
-    for vids in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
-        f, y = load_split(index, vids, opt.motion_feature_dir, opt.appearance_feature_dir)
-        data.append((torch.from_numpy(f).to(device), torch.from_numpy(y).to(device)))
-    (ftr, ytr), (fte, yte) = data
+    (ftr, ytr), (fte, yte) = load_splits(opt)
     top1 = knn_top1(fte, yte, ftr, ytr, k=opt.k, T=opt.temperature)
     print('knn top1:', top1)
     return top1

@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import tail as _tail
+from .train_common import lr_for_epoch
 
 
 class Final_FC(nn.Module):
@@ -47,7 +48,7 @@ def fit(features, labels, num_class=120, nepoch=20, batch=256, lr=1e-3, shuffle=
     top1 = 0.0
     for epoch in range(nepoch):
         for g in optimizer.param_groups:
-            g["lr"] = lr * 0.7 ** (epoch // 5)                          # StepLR(5, 0.7) stepped with the epoch
+            g["lr"] = lr_for_epoch(lr, epoch, 5, 0.7)                   # StepLR(5, 0.7) stepped with the epoch
         hit, seen = 0.0, 0
         if shuffle is None:
             chunks = [slice(i, i + batch) for i in range(0, features.shape[0], batch)]
@@ -95,6 +96,20 @@ def load_split(index, vids, motion_dir, appearance_dir=None):
     return np.stack(feats).astype(np.float32), np.asarray(labels, dtype=np.int64)
 
 
+def load_splits(opt):
+    """Makes --main_gpu the current device and returns, on it, ((train features, labels), (test features, labels)) of the
+    clips listed in <data_root>/reslution/Resolution60/raw, read from the feature folders of `opt`."""
+    from . import dataset as fds
+    device = torch.device("cuda", opt.main_gpu)
+    torch.cuda.set_device(device)
+    index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.PROBE_LIST_DIR), opt.dataset)
+    data = []
+    for vids in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
+        f, y = load_split(index, vids, opt.motion_feature_dir, opt.appearance_feature_dir)
+        data.append((torch.from_numpy(f).to(device), torch.from_numpy(y).to(device)))
+    return data
+
+
 def main(args=None):
     """linercls.py:27-150: train the probe on the train split, print test top-1 after every epoch from 16 on."""
     from . import dataset as fds
@@ -113,15 +128,8 @@ def main(args=None):
     p.add_argument('--appearance_feature_dir', type=str, required=True, help='NEW: folder of <v_name>.npy appearance features')
     opt = p.parse_args(args)
     print(opt)
-    device = torch.device("cuda", opt.main_gpu)
-    torch.cuda.set_device(device)
+    (ftr, ytr), (fte, yte) = load_splits(opt)
     torch.manual_seed(1)
-    index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.PROBE_LIST_DIR), opt.dataset)
-    data = []
-    for vids in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
-        f, y = load_split(index, vids, opt.motion_feature_dir, opt.appearance_feature_dir)
-        data.append((torch.from_numpy(f).to(device), torch.from_numpy(y).to(device)))
-    (ftr, ytr), (fte, yte) = data
     if ftr.shape[0] < opt.batchSize:
         raise RuntimeError("the train split has %d clips: fewer than one batch of %d" % (ftr.shape[0], opt.batchSize))
     result = {}

@@ -1,6 +1,7 @@
 """Shared body of the two training entries (the reference ships two scripts that differ in three
 lines: default ``branch_choose``, data root and checkpoint file name -- cn3d_train_apperance_GL.py:135,161,341)."""
 import argparse
+import contextlib
 import logging
 import os
 import random
@@ -137,6 +138,15 @@ def appearance_batch(B, G, N, D, device, generator=None):
     return out.float()
 
 
+def group_views(data1, opt, r2=None):
+    """The grouper of training and extraction over view-major (M,N,D) rows (the second path: or a clip-major (B,G,N,D)
+    batch).  `r2` None: the reference's literals, K=64 and r^2=0.06 at N=512 (:230), group_points_3DV_2048's 0.16 otherwise."""
+    if r2 is None and opt.SAMPLE_NUM == 512:
+        return group_points_3DV(data1, opt)
+    opt.INPUT_FEATURE_NUM = data1.shape[-1]
+    return knn_radius_group(data1, opt.sample_num_level1, opt.knn_K, 0.16 if r2 is None else r2)
+
+
 class ContrastiveStep:
     """One training iteration = the loop body of cn3d_train_motion_GL.py:224-335."""
 
@@ -152,12 +162,7 @@ class ContrastiveStep:
         self.grad_sync = fdist.GradSync(list(netR.named_parameters())) if fdist.is_distributed() else None
 
     def group(self, data1):
-        opt = self.opt
-        if self.r2 is None and opt.SAMPLE_NUM == 512:
-            return group_points_3DV(data1, opt)                                   # :230 (K=64, r^2=0.06 literals)
-        r2 = self.r2 if self.r2 is not None else 0.16                             # group_points_3DV_2048's literal
-        opt.INPUT_FEATURE_NUM = data1.shape[-1]
-        return knn_radius_group(data1, opt.sample_num_level1, opt.knn_K, r2)     # (M,N,D) or clip-major (B,G,N,D)
+        return group_views(data1, self.opt, self.r2)
 
     def __call__(self, out_points, epoch=0, order=None):
         netR, G = self.netR, self.G
@@ -173,27 +178,19 @@ class ContrastiveStep:
         """Device-only body (no host round trips): this is what GraphedStep captures into a HIP graph.
         `out_points`: the loader's clip-major (B,G,N,D) batch, or -- 3-dimensional -- the view-major (G*B,N,D) rows that
         facl_amd.views.build_views writes directly (the permute + reshape of :226 already done)."""
-        netR, G = self.netR, self.G
         if out_points.dim() == 3:
-            M_, N, D = out_points.shape
-            B = M_ // G
+            B = out_points.shape[0] // self.G
             data1 = out_points if out_points.dtype == torch.float32 else out_points.float()
-            if self.fps_reorder:
-                from .fps import fps_sample_data
-                data1 = fps_sample_data(data1, self.opt.sample_num_level1,
-                                        start_idx=torch.zeros(data1.shape[0], dtype=torch.int32, device=data1.device))
-            xt, yt = self.group(data1)
-            return self._encode_and_step(xt, yt, B, order)
-        B, G_, N, D = out_points.shape
-        if self.fps_reorder or out_points.dtype != torch.float32 or (self.r2 is None and self.opt.SAMPLE_NUM == 512):
-            data1 = out_points.permute(1, 0, 2, 3).reshape(-1, N, D).float()      # :226-228 (view-major rows)
-            if self.fps_reorder:                                                   # FPS picks first (start index 0)
-                from .fps import fps_sample_data
-                data1 = fps_sample_data(data1, self.opt.sample_num_level1,
-                                        start_idx=torch.zeros(data1.shape[0], dtype=torch.int32, device=data1.device))
-            xt, yt = self.group(data1)
         else:
-            xt, yt = self.group(out_points)        # clip-major batch: the grouping kernel reads view-major in place
+            B, _, N, D = out_points.shape
+            data1 = out_points                     # clip-major batch: the grouping kernel reads view-major in place ...
+            if self.fps_reorder or out_points.dtype != torch.float32 or (self.r2 is None and self.opt.SAMPLE_NUM == 512):
+                data1 = out_points.permute(1, 0, 2, 3).reshape(-1, N, D).float()  # ... or :226-228 (view-major rows)
+        if self.fps_reorder:                                                       # FPS picks first (start index 0)
+            from .fps import fps_sample_data
+            data1 = fps_sample_data(data1, self.opt.sample_num_level1,
+                                    start_idx=torch.zeros(data1.shape[0], dtype=torch.int32, device=data1.device))
+        xt, yt = self.group(data1)
         return self._encode_and_step(xt, yt, B, order)
 
     def _encode_and_step(self, xt, yt, B, order):
@@ -461,7 +458,7 @@ def check_knn_flags(opt, world=None):
     if opt.synthetic != 0:
         raise RuntimeError("--knn_every %d evaluates the train and test splits of --data_root: it needs --synthetic 0 "
                            "(got --synthetic %d, which has no labelled clips)" % (opt.knn_every, opt.synthetic))
-    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else world
+    world = fdist.env_world_size() if world is None else world
     if world > 1:
         raise RuntimeError("--knn_every %d runs on one rank only (got %d ranks): the sharded monitor is not implemented"
                            % (opt.knn_every, world))
@@ -469,6 +466,18 @@ def check_knn_flags(opt, world=None):
         raise RuntimeError("--knn_k must be in 1..64 (got %d)" % opt.knn_k)
     if not opt.knn_T > 0:
         raise RuntimeError("--knn_T must be positive (got %r)" % opt.knn_T)
+
+
+@contextlib.contextmanager
+def eval_mode(netR):
+    """eval() and no_grad() for the block; the model returns to the mode it was in, also when the block raises."""
+    was_training = netR.training
+    netR.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        netR.train(was_training)
 
 
 def knn_monitor(netR, opt, device):
@@ -481,23 +490,131 @@ def knn_monitor(netR, opt, device):
     from .knn_eval import knn_top1
     index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
     rng = np.random.RandomState(2000)
-    was_training = netR.training
-    netR.eval()
+    with eval_mode(netR):
+        data = []
+        for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
+            if not len(split):
+                raise RuntimeError("--knn_every: a split of %s has no clips" % opt.data_root)
+            f = extract_split(netR, opt, device, index, split, rng)
+            y = torch.as_tensor([index.label(v) for v in split], dtype=torch.int64, device=device)
+            data.append((f, y))
+        from . import _lib
+        _lib.join_pending()
+        (ftr, ytr), (fte, yte) = data
+        return knn_top1(fte, yte, ftr, ytr, k=opt.knn_k, T=opt.knn_T)
+
+
+def setup_run(opt):
+    """Seeds (shared across ranks: the circle-loss permutation is the same on all of them), output folder, log file."""
+    opt.manualSeed = 1
+    random.seed(opt.manualSeed)
+    torch.manual_seed(opt.manualSeed)
+    np.random.seed(opt.manualSeed)
+    os.makedirs(opt.save_root_dir, exist_ok=True)
+    if opt.log_file:
+        logging.basicConfig(format='%(asctime)s %(message)s', datefmt='%Y/%m/%d %H:%M:%S',
+                            filename=opt.log_file, level=logging.INFO)
+    logging.info('======================================================')
+
+
+class TrainBatches:
+    """--synthetic 0, the reference's loader (cn3d_train_*_GL.py:161-172: the listed folder, shuffle + drop_last): the training
+    split on disk (--resident 1: ingested here, once) and this rank's batches of every epoch.  `too_few`: the caller's wording
+    of the refusal, a % template over clips / batch / world; `subset(index, split)` narrows the split (fine-tuning's labels)."""
+
+    def __init__(self, opt, device, rank, world, too_few, subset=None, report_ingest=False):
+        from . import dataset as fds
+        self.opt, self.device, self.rank, self.world = opt, device, rank, world
+        self.index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.TRAIN_LIST_DIR[opt.branch_choose]), opt.dataset)
+        fds.check_same_index_on_all_ranks(self.index, device)
+        split = np.asarray(self.index.select(opt.split, full_train=bool(opt.full_train)), dtype=np.int64)
+        self.split = split if subset is None else subset(self.index, split)
+        self.steps = len(self.split) // (opt.batchSize * world)
+        if opt.max_steps_per_epoch > 0:
+            self.steps = min(self.steps, opt.max_steps_per_epoch)
+        if self.steps < 1:
+            raise RuntimeError(too_few % dict(clips=len(self.split), batch=opt.batchSize, world=world))
+        self.view_rng = np.random.RandomState(2000 + rank)    # --view_rng numpy: the generator the views draw from
+        self.resident = None
+        if opt.resident:
+            # every rank holds the whole split: the permutation is over the whole split, a rank's shard changes every epoch
+            from . import resident as fres
+            t_in = time.time()
+            res = self.resident = fres.ResidentClips(
+                self.index, opt.data_root, opt.branch_choose, self.split, device, max_gb=opt.resident_max_gb,
+                reserve=fres.step_reserve_bytes(opt.batchSize, opt.num_crop, opt.SAMPLE_NUM))
+            torch.cuda.synchronize()
+            if report_ingest:
+                print('resident: %d clips, %.3f GB, %.2f s' % (res.n, res.bytes['total'] / 1e9, time.time() - t_in))
+
+    def epoch(self, epoch, hold_first=False):
+        """Iterator over the epoch's ((G*B, N, 4) view-major views, v_names, labels); the caller close()s it (that stops
+        the epoch's producer thread).  `hold_first`: the producer waits after batch 0 (a graph capture runs on it)."""
+        from . import dataset as fds, resident as fres
+        opt = self.opt
+        pos = fds.train_batches(len(self.split), opt.batchSize, self.world, self.rank, opt.manualSeed, epoch)[:self.steps]
+        vids = [self.split[p] for p in pos]
+        if self.resident is not None:
+            return fres.ResidentBatches(self.resident, vids, seed=2000, epoch=epoch,
+                                        num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM)
+        disk = fds.DiskBatches(self.index, opt.data_root, opt.branch_choose, vids, opt.view_rng, self.device,
+                               rng=self.view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch),
+                               num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM)
+        disk.hold_first = hold_first
+        return iter(disk)
+
+
+def wants_graph(opt):
+    """--graph 1 replays the default loss only (swa_if = cld_if = 0); cleared once a capture has failed."""
+    return bool(opt.graph) and not (opt.swa_if or opt.cld_if)
+
+
+def capture_or_eager(step, out_points, opt):
+    """`step` captured on the first batch (state restored: the same trajectory as eager), or `step` itself."""
+    if not wants_graph(opt):
+        return step
     try:
-        with torch.no_grad():
-            data = []
-            for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
-                if not len(split):
-                    raise RuntimeError("--knn_every: a split of %s has no clips" % opt.data_root)
-                f = extract_split(netR, opt, device, index, split, rng)
-                y = torch.as_tensor([index.label(v) for v in split], dtype=torch.int64, device=device)
-                data.append((f, y))
-            from . import _lib
-            _lib.join_pending()
-            (ftr, ytr), (fte, yte) = data
-            return knn_top1(fte, yte, ftr, ytr, k=opt.knn_k, T=opt.knn_T)
-    finally:
-        netR.train(was_training)
+        return GraphedStep(step, out_points, step.G, restore=True)
+    except GraphCaptureFailed as e:
+        # the state is restored and EVERY rank is here (see GraphCaptureFailed): all continue on eager launches.  Anything
+        # else propagates: the rank exits non-zero and the launcher stops the others
+        print("graph capture failed (%s); running eager" % e)
+        opt.graph = 0
+        return step
+
+
+def check_finite_loss(lv, epoch, i):
+    """Inputs / a checkpoint with NaN or inf (the arithmetic itself has no range limit): no training on garbage."""
+    if lv != lv or lv in (float("inf"), float("-inf")):
+        raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
+
+
+def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, after_step=None):
+    """The epoch loop of the training entries under StepLR(`lr_step`, 0.7).  `source`: the TrainBatches of --synthetic 0, else
+    None (--steps_per_epoch steps).  The entries differ in `next_batch(disk, epoch, i)` -> the step's input (`disk`: the epoch's
+    iterator of `source`, or None), `after_step(what the step returned)` and `after_epoch(epoch, mean_loss, clips_per_s)`."""
+    steps = opt.steps_per_epoch if source is None else source.steps
+    run_step = step
+    for epoch in range(0, opt.nepoch):
+        step.netR.train()
+        for g in step.optimizer.param_groups:
+            g["lr"] = lr_for_epoch(opt.learning_rate, epoch, lr_step)
+        loss_sigma, t0 = 0.0, time.time()
+        disk = None if source is None else source.epoch(epoch, hold_first=run_step is step and wants_graph(opt))
+        for i in range(steps):
+            out_points = next_batch(disk, epoch, i)
+            if run_step is step:                         # capture on the first batch
+                run_step = capture_or_eager(step, out_points, opt)
+            out = run_step(out_points, epoch)
+            torch.cuda.synchronize()
+            lv = out[0].item()
+            check_finite_loss(lv, epoch, i)
+            if after_step is not None:
+                after_step(out)
+            loss_sigma += lv
+        if disk is not None:
+            disk.close()
+        after_epoch(epoch, loss_sigma / steps, opt.batchSize * steps * world / (time.time() - t0))
 
 
 def run(default_branch, ckpt_pattern, args=None):
@@ -510,16 +627,7 @@ def run(default_branch, ckpt_pattern, args=None):
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)
     rank, world = fdist.init_from_env()
-
-    opt.manualSeed = 1
-    random.seed(opt.manualSeed)
-    torch.manual_seed(opt.manualSeed)
-    np.random.seed(opt.manualSeed)          # shared circle-loss permutation across ranks
-    os.makedirs(opt.save_root_dir, exist_ok=True)
-    if opt.log_file:
-        logging.basicConfig(format='%(asctime)s %(message)s', datefmt='%Y/%m/%d %H:%M:%S',
-                            filename=opt.log_file, level=logging.INFO)
-    logging.info('======================================================')
+    setup_run(opt)
 
     num_crop = opt.num_crop
     netR = MODELL.PointNet_Plus(opt, gost=num_crop).to(device)
@@ -532,95 +640,37 @@ def run(default_branch, ckpt_pattern, args=None):
     gen = torch.Generator(device=device)
     gen.manual_seed(1000 + rank)
     view_rng = np.random.RandomState(2000 + rank)         # --synthetic 2: the generator the view construction draws from
+    source = TrainBatches(opt, device, rank, world, report_ingest=rank == 0, too_few="the split has %(clips)d clips: fewer "
+                          "than one batch of %(batch)d per rank x %(world)d ranks") if opt.synthetic == 0 else None
 
-    steps_per_epoch = opt.steps_per_epoch
-    if opt.synthetic == 0:
-        # the reference's loader (cn3d_train_*_GL.py:161-172): NTU_RGBD_new over the listed folder, shuffle + drop_last
-        from . import dataset as fds
-        index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.TRAIN_LIST_DIR[opt.branch_choose]), opt.dataset)
-        fds.check_same_index_on_all_ranks(index, device)
-        split = index.select(opt.split, full_train=bool(opt.full_train))
-        steps_per_epoch = len(split) // (opt.batchSize * world)
-        if opt.max_steps_per_epoch > 0:
-            steps_per_epoch = min(steps_per_epoch, opt.max_steps_per_epoch)
-        if steps_per_epoch < 1:
-            raise RuntimeError("the split has %d clips: fewer than one batch of %d per rank x %d ranks"
-                               % (len(split), opt.batchSize, world))
-        resident = None
-        if opt.resident:
-            # every rank holds the whole split: the permutation is over the whole split, a rank's shard changes every epoch
-            from . import resident as fres
-            t_in = time.time()
-            resident = fres.ResidentClips(index, opt.data_root, opt.branch_choose, split, device, max_gb=opt.resident_max_gb,
-                                          reserve=fres.step_reserve_bytes(opt.batchSize, num_crop, opt.SAMPLE_NUM))
-            torch.cuda.synchronize()
-            if rank == 0:
-                print('resident: %d clips, %.3f GB, %.2f s' % (resident.n, resident.bytes['total'] / 1e9, time.time() - t_in))
+    def next_batch(disk, epoch, i):
+        if opt.synthetic == 0:
+            return next(disk)[0]                      # (G*B, N, 4) view-major views of the next batch
+        if opt.synthetic == 2:
+            # the loop body from the loader's output on (:224-228): raw clips -> the augmented views of every clip,
+            # built on the GPU in one launch, view-major float32 (facl_amd/views.py; draws in the reference's NumPy order)
+            from .views import build_views, synthetic_raw_clip
+            base = ((epoch * opt.steps_per_epoch + i) * world + rank) * opt.batchSize
+            clips = [synthetic_raw_clip(base + b) for b in range(opt.batchSize)]
+            # --view_rng numpy: the reference's NumPy stream (a seed reproduces its views; ~0.2 ms of host draws per clip);
+            # device: the same distributions drawn by a torch generator on the GPU (no per-clip host work)
+            return build_views(clips, view_rng, device, device_rng=gen if opt.view_rng == "device" else None,
+                               philox=(2000, epoch, [base + b for b in range(opt.batchSize)])
+                               if opt.view_rng == "philox" else None, num_crop=num_crop, num_point=opt.SAMPLE_NUM)
+        if opt.synthetic == 1:
+            return synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
+        raise RuntimeError("--synthetic must be 0 (the dataset on disk), 1 or 2")
 
-    run_step = step
-    for epoch in range(0, opt.nepoch):
-        netR.train()
-        for g in optimizer.param_groups:
-            g["lr"] = lr_for_epoch(opt.learning_rate, epoch)
-        loss_sigma, t0 = 0.0, time.time()
-        if opt.synthetic == 0:
-            pos = fds.train_batches(len(split), opt.batchSize, world, rank, opt.manualSeed, epoch)[:steps_per_epoch]
-        if opt.synthetic == 0 and resident is not None:
-            disk = fres.ResidentBatches(resident, [np.asarray(split)[p] for p in pos], seed=2000, epoch=epoch,
-                                        num_crop=num_crop, num_point=opt.SAMPLE_NUM)
-        elif opt.synthetic == 0:
-            disk = fds.DiskBatches(index, opt.data_root, opt.branch_choose, [np.asarray(split)[p] for p in pos],
-                                   opt.view_rng, device, rng=view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch),
-                                   num_crop=num_crop, num_point=opt.SAMPLE_NUM)
-            disk.hold_first = run_step is step and bool(opt.graph) and not (opt.swa_if or opt.cld_if)   # capture on batch 0
-            disk = iter(disk)
-        for i in range(steps_per_epoch):
-            if opt.synthetic == 0:
-                out_points = next(disk)[0]                # (G*B, N, 4) view-major views of the next batch
-            elif opt.synthetic == 2:
-                # the loop body from the loader's output on (:224-228): raw clips -> the augmented views of every clip,
-                # built on the GPU in one launch, view-major float32 (facl_amd/views.py; draws in the reference's NumPy order)
-                from .views import build_views, synthetic_raw_clip
-                base = ((epoch * opt.steps_per_epoch + i) * world + rank) * opt.batchSize
-                clips = [synthetic_raw_clip(base + b) for b in range(opt.batchSize)]
-                # --view_rng numpy: the reference's NumPy stream (a seed reproduces its views; ~0.2 ms of host draws per clip);
-                # device: the same distributions drawn by a torch generator on the GPU (no per-clip host work)
-                out_points = build_views(clips, view_rng, device, device_rng=gen if opt.view_rng == "device" else None,
-                                         philox=(2000, epoch, [base + b for b in range(opt.batchSize)])
-                                         if opt.view_rng == "philox" else None, num_crop=num_crop, num_point=opt.SAMPLE_NUM)
-            elif opt.synthetic == 1:
-                out_points = synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
-            else:
-                raise RuntimeError("--synthetic must be 0 (the dataset on disk), 1 or 2")
-            if run_step is step and opt.graph and not (opt.swa_if or opt.cld_if):
-                try:                                     # capture on the first batch; state restored: same trajectory as eager
-                    run_step = GraphedStep(step, out_points, num_crop, restore=True)
-                except GraphCaptureFailed as e:
-                    # training state is back at its pre-capture values and, under data parallelism, EVERY rank is here
-                    # (GraphSegments' votes): all ranks continue together on eager launches.  Anything else raised under
-                    # world > 1 is not agreed on across ranks: it propagates, the rank exits non-zero and the launcher
-                    # stops the others (no rank is left replaying segments against another's eager collectives).
-                    print("graph capture failed (%s); running eager" % e)
-                    opt.graph = 0
-            loss, _, _ = run_step(out_points, epoch)
-            torch.cuda.synchronize()
-            lv = loss.item()
-            if lv != lv or lv in (float("inf"), float("-inf")):
-                # inputs / a checkpoint with NaN or inf (the arithmetic itself has no range limit any more: DESIGN 3.0):
-                # stop here instead of training on garbage
-                raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
-            loss_sigma += lv
-        if opt.synthetic == 0:
-            disk.close()                                  # stops the producer thread of this epoch
-        clips = opt.batchSize * steps_per_epoch * world / (time.time() - t0)
-        logging.info('{} --epoch{} ==Average loss:{}'.format('Valid', epoch, loss_sigma / (i + 1)))
+    def after_epoch(epoch, mean_loss, clips):
+        logging.info('{} --epoch{} ==Average loss:{}'.format('Valid', epoch, mean_loss))
         if rank == 0:
-            print('epoch:', epoch, 'loss mode is :', 1, '--loss:', loss_sigma / (i + 1), '| clips/s: %.1f' % clips)
+            print('epoch:', epoch, 'loss mode is :', 1, '--loss:', mean_loss, '| clips/s: %.1f' % clips)
         if opt.knn_every and (epoch + 1) % opt.knn_every == 0:
             top1 = knn_monitor(netR, opt, device)
             logging.info('{} --epoch{} ==knn top1:{}'.format('Valid', epoch, top1))
             print('epoch:', epoch, 'knn top1:', top1)
-        if rank == 0:
-            if epoch % 5 == 0:
-                torch.save(netR.state_dict(), ckpt_pattern % (opt.save_root_dir, epoch))
+        if rank == 0 and epoch % 5 == 0:
+            torch.save(netR.state_dict(), ckpt_pattern % (opt.save_root_dir, epoch))
+
+    train_epochs(opt, step, source, world, lr_step=4, next_batch=next_batch, after_epoch=after_epoch)
     return netR

@@ -142,6 +142,8 @@ SIGNATURES = {
     "facl_cls_gather_norm_fwd": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     "facl_cls_gather_norm_bwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
     "facl_softmax_ce": [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "facl_cls_probs_acc": [c_p, c_i, c_i, c_i, c_p, c_i, c_p],
+    "facl_cls_topk": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
 }
 RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes"}
 

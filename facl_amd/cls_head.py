@@ -1,7 +1,8 @@
 """Classifier head of supervised fine-tuning: the reference's probe head ``Final_FC``
 (linear_classify/fc_model.py:12-25 -- F.normalize(x, dim=1), then Linear) on the encoder's own stacked, view-major
 output, and the softmax cross-entropy of its logits.  The normalisation and the loss are the kernels of csrc/cls.hip,
-the Linear layer is ``facl_amd.tail.linear`` (the exact-split MFMA GEMMs).  GPU only: there is no CPU path."""
+the class probabilities and top-k lists of prediction those of csrc/predict.hip, the Linear layer is
+``facl_amd.tail.linear`` (the exact-split MFMA GEMMs).  GPU only: there is no CPU path."""
 import torch
 import torch.nn as nn
 
@@ -90,6 +91,51 @@ class _SoftmaxCE(torch.autograd.Function):
 
 def softmax_ce(logits, labels):
     return _SoftmaxCE.apply(logits, labels)
+
+
+def probs_acc(logits, acc=None, first=None):
+    """Softmax of (R, ncls) float32 logits in fp64 (csrc/predict.hip), stored into a new (R, ncls) float64 tensor (`acc` None) or
+    added to `acc` in place: the sum of the class probabilities over test-time draws.  `first` True with an `acc`: stored into
+    it, whatever it held (the first draw into a preallocated tensor).  A row whose maximum is not finite becomes NaN.
+    Returns `acc`."""
+    lib = _lib.load_library()
+    _lib.require_cuda(logits, acc)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError("logits must be a 2-D float32 tensor (got %s %s)" % (tuple(logits.shape), logits.dtype))
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    R, ncls = logits.shape
+    first = acc is None if first is None else bool(first)
+    if acc is None:
+        if not first:
+            raise ValueError("first=False needs the acc to add to")
+        acc = _lib.empty((R, ncls), dtype=torch.float64, device=logits.device)
+    elif acc.dtype != torch.float64 or acc.shape != (R, ncls) or not acc.is_contiguous():
+        raise ValueError("acc must be a contiguous float64 tensor of shape (%d, %d) (got %s %s)" % (R, ncls, tuple(acc.shape), acc.dtype))
+    _lib.check(lib.facl_cls_probs_acc(_lib.ptr(logits), logits.stride(0), R, ncls, _lib.ptr(acc), int(first), _lib.stream()),
+               "facl_cls_probs_acc(R=%d, ncls=%d)" % (R, ncls))
+    return acc
+
+
+def topk(acc, ndraws, k, labels=None):
+    """The k classes of largest `acc` (R, ncls) float64 per row under (value descending, class ascending) -> (top_p (R, k)
+    float32 = acc / ndraws, top_c (R, k) int32, rank (R,) int32 or None without `labels`): rank = the classes that precede the
+    label in that order (0 = a top-1 hit), -1 in a NaN row, -2 for a label outside [0, ncls)."""
+    lib = _lib.load_library()
+    _lib.require_cuda(acc, labels)
+    if acc.dim() != 2 or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise ValueError("acc must be a contiguous 2-D float64 tensor (got %s %s)" % (tuple(acc.shape), acc.dtype))
+    R, ncls = acc.shape
+    if labels is not None and (labels.dtype != torch.int32 or labels.shape != (R,) or not labels.is_contiguous()):
+        raise ValueError("labels must be a contiguous int32 tensor of shape (%d,) (got %s %s)" % (R, tuple(labels.shape), labels.dtype))
+    ndraws, k = int(ndraws), int(k)
+    dev = acc.device
+    top_p = _lib.empty((R, max(k, 0)), dtype=torch.float32, device=dev)
+    top_c = _lib.empty((R, max(k, 0)), dtype=torch.int32, device=dev)
+    rank = _lib.empty((R,), dtype=torch.int32, device=dev) if labels is not None else None
+    _lib.check(lib.facl_cls_topk(_lib.ptr(acc), R, ncls, ndraws, k, _lib.ptr(labels), _lib.ptr(top_p), _lib.ptr(top_c),
+                                 _lib.ptr(rank), _lib.stream()), "facl_cls_topk(R=%d, ncls=%d, ndraws=%d, k=%d)" % (R, ncls, ndraws, k))
+    return top_p, top_c, rank
 
 
 class ClipClassifier(nn.Module):

@@ -58,13 +58,14 @@ def run(default_branch, default_ckpt, args=None):
     return np.concatenate(feats)
 
 
-def ordered_views(opt, device, index, split, rng):
+def ordered_views(opt, device, index, split, rng, epoch=0):
     """The evaluation pass: the clips `split` (dataset indices) in order, batches of --batchSize with the last one ragged, as
-    ((G*B, N, 4) views, v_names, labels); views drawn from `rng` (--view_rng numpy) or keyed by (2000, 0, index) (philox)."""
+    ((G*B, N, 4) views, v_names, labels); views drawn from `rng` (--view_rng numpy) or keyed by (2000, epoch, index) (philox;
+    `epoch` > 0: a further test-time draw of facl_amd.predict)."""
     from . import dataset as fds
     vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
     return iter(fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device, rng=rng, seed=2000,
-                                epoch=0, prefetch=bool(opt.prefetch), num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM))
+                                epoch=epoch, prefetch=bool(opt.prefetch), num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM))
 
 
 def extract_split(netR, opt, device, index, split, rng, save_path=''):

@@ -126,6 +126,8 @@ def main(args=None):
     p.add_argument('--full_train', type=int, default=1, help='NEW (--split subject): 0 = without the validation performers')
     p.add_argument('--motion_feature_dir', type=str, required=True, help='NEW: folder of <v_name>.npy motion features')
     p.add_argument('--appearance_feature_dir', type=str, required=True, help='NEW: folder of <v_name>.npy appearance features')
+    p.add_argument('--save_fc', type=str, default='',
+                   help="NEW: file the probe's state_dict is saved to after the last epoch (facl_amd.predict --head); '' = not saved")
     opt = p.parse_args(args)
     print(opt)
     (ftr, ytr), (fte, yte) = load_splits(opt)
@@ -139,8 +141,10 @@ def main(args=None):
             result["top1"] = evaluate(netR, fte, yte, opt.batchSize)
             print('epoch:', epoch, 'test top1:', result["top1"])
 
-    fit(ftr, ytr, num_class=opt.num_class, nepoch=opt.nepoch, batch=opt.batchSize, lr=opt.learning_rate,
-        shuffle=np.random.RandomState(1), on_epoch=on_epoch)
+    netR, _ = fit(ftr, ytr, num_class=opt.num_class, nepoch=opt.nepoch, batch=opt.batchSize, lr=opt.learning_rate,
+                  shuffle=np.random.RandomState(1), on_epoch=on_epoch)
+    if opt.save_fc:
+        torch.save(netR.state_dict(), opt.save_fc)
     return result.get("top1")
 
 

@@ -689,6 +689,34 @@ int facl_cls_gather_norm_bwd(const float* dout, const float* out, const float* i
 int facl_softmax_ce(const float* logits, int ld, const int32_t* labels, int R, int ncls, float* loss, float* dlogits,
                     int32_t* stats, void* ws, void* stream);
 
+/* ---- prediction with a trained head (csrc/predict.hip) ----------------------------------------------------------
+ * Class probabilities of a head's logits, accumulated over test-time draws of the views in fp64, and the k most probable
+ * classes of every row with the rank of its label.  One wave per row, lanes striding over the classes.  No entry synchronises,
+ * allocates or uses an atomic; each returns the same bits every run.
+ *
+ * facl_cls_probs_acc: p[i][c] = exp(x[i][c] - max_i) / sum_c exp(x[i][c] - max_i) of R rows of logits (rows ld floats apart,
+ * ncls classes); the differences, the exponentials, their sum (lane partial sums, then the xor tree) and the quotient in fp64.
+ *   acc   (R, ncls) fp64 contiguous: first != 0 stores acc[i][c] = p (whatever acc held, NaN included); first == 0 stores
+ *         acc[i][c] + p.  The sum over the draws is then the caller's: draw 0 with first = 1, every later draw with first = 0.
+ * A logit of -inf gives p = 0.  A row whose maximum is not finite -- a NaN logit anywhere in it, a +inf logit, or nothing but
+ * -inf -- makes the whole acc row NaN, and it stays NaN through the later draws.
+ * Domain: 2 <= ncls <= 1024; R >= 1; ld >= ncls; else FACL_E_SHAPE.  NULL logits / acc: FACL_E_NULL.  acc not 8-byte aligned:
+ * FACL_E_ALIGN. */
+int facl_cls_probs_acc(const float* logits, int ld, int R, int ncls, double* acc, int first, void* stream);
+
+/* facl_cls_topk: for every row of acc the k classes of largest acc under the total order (value descending, class ascending).
+ *   top_p   (R, k) fp32: (float)(acc / ndraws), the fp64 quotient rounded once; non-increasing along a row
+ *   top_c   (R, k) int32 classes
+ *   labels  int32 (R) or NULL;  rank int32 (R), required with labels and ignored without them: rank[i] = the number of classes
+ *           that precede labels[i] in that order over ALL ncls classes, so 0 is a top-1 hit and rank < j a top-j hit for any j
+ *           (k plays no part in it); -2 for a label outside [0, ncls)
+ * A row of acc that holds a NaN gives top_c = -1 and top_p = NaN in all its k entries and rank = -1 (whatever its label is).
+ * Lane e of the row's wave ends up with list entry e: k rounds of a wave argmax over the lanes' <= 16 classes each.
+ * Domain: 2 <= ncls <= 1024; R >= 1; 1 <= k <= min(ncls, 64); ndraws >= 1; else FACL_E_SHAPE.  NULL acc / top_p / top_c, or
+ * labels without rank: FACL_E_NULL.  acc not 8-byte aligned: FACL_E_ALIGN. */
+int facl_cls_topk(const double* acc, int R, int ncls, int ndraws, int k, const int32_t* labels, float* top_p, int32_t* top_c,
+                  int32_t* rank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 //                           the xor tree) in fp64 -> the mean and the two counters.
 // Every reduction has a fixed order and no atomic takes part: the same bits every run, whatever the scheduling.
 #include "common.h"
+#include "norm_rows.h"
 #include <limits.h>
 
 extern "C" int64_t facl_ws_bytes(void);
@@ -42,17 +43,14 @@ __global__ __launch_bounds__(CLS_THREADS) void k_cls_gather_norm_fwd(const float
     for (int i = tid; i < n4; i += CLS_THREADS) {
         const int g = i / C4, c4 = i - g * C4;
         const float4 v = reinterpret_cast<const float4*>(stacked + ((size_t)g * B + b) * C)[c4];
-        ss += (double)v.x * v.x; ss += (double)v.y * v.y; ss += (double)v.z * v.z; ss += (double)v.w * v.w;
+        nr_acc_sq(ss, v);
     }
     ss = cls_block_sum(ss, red);
-    const double nrm = sqrt(ss);
-    const float inv = (float)(1.0 / (nrm > 1e-12 ? nrm : 1e-12));                     // F.normalize: x / max(||x||, eps)
+    const float inv = (float)nr_inv_norm(ss);                                         // F.normalize: x / max(||x||, eps)
     float4* o = reinterpret_cast<float4*>(out + (size_t)b * n4 * 4);
     for (int i = tid; i < n4; i += CLS_THREADS) {
         const int g = i / C4, c4 = i - g * C4;
-        float4 v = reinterpret_cast<const float4*>(stacked + ((size_t)g * B + b) * C)[c4];
-        v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
-        o[i] = v;
+        o[i] = nr_scale_f32(reinterpret_cast<const float4*>(stacked + ((size_t)g * B + b) * C)[c4], inv);
     }
     if (tid == 0) inv_norm[b] = inv;
 }
@@ -67,20 +65,13 @@ __global__ __launch_bounds__(CLS_THREADS) void k_cls_gather_norm_bwd(const float
     const float4* o4 = reinterpret_cast<const float4*>(out + (size_t)b * n4 * 4);
     double dot = 0.0;
     for (int i = tid; i < n4; i += CLS_THREADS) {
-        const float4 d = d4[i], o = o4[i];
-        dot += (double)d.x * o.x; dot += (double)d.y * o.y; dot += (double)d.z * o.z; dot += (double)d.w * o.w;
+        nr_acc_dot(dot, d4[i], o4[i]);
     }
     dot = cls_block_sum(dot, red);
     const double inv = (double)inv_norm[b];
     for (int i = tid; i < n4; i += CLS_THREADS) {
         const int g = i / C4, c4 = i - g * C4;
-        const float4 d = d4[i], o = o4[i];
-        float4 r;
-        r.x = (float)(inv * ((double)d.x - (double)o.x * dot));
-        r.y = (float)(inv * ((double)d.y - (double)o.y * dot));
-        r.z = (float)(inv * ((double)d.z - (double)o.z * dot));
-        r.w = (float)(inv * ((double)d.w - (double)o.w * dot));
-        reinterpret_cast<float4*>(dstacked + ((size_t)g * B + b) * C)[c4] = r;
+        reinterpret_cast<float4*>(dstacked + ((size_t)g * B + b) * C)[c4] = nr_project(inv, d4[i], o4[i], dot);
     }
 }
 

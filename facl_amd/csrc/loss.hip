@@ -12,6 +12,7 @@
 // Per clip: loss_n = sum_i (logaddexp(pos, lse) - pos) / B;   dsim follows by the chain rule.
 // HBM-bound (2 reads + 1 write of R*J floats); one workgroup per clip.
 #include "common.h"
+#include "norm_rows.h"
 
 int facl_reduce_rows(const double* part, int rows, int V, double* out, hipStream_t st);
 
@@ -172,6 +173,15 @@ __global__ __launch_bounds__(1024) void k_contrast_reg(const float* __restrict__
 // B..2B-1 the circle loss (anchor blocks order[0..G-2], positive of slot i in block order[i], column order[i+1]*Bk + clip;
 // block order[G-1] is no anchor: its dsim row is zeroed here so that every row of dsim is written exactly once).
 // The anchors gather, the positive-column index tensors and the second similarity GEMM of the two-call form disappear.
+//
+// MASK selects what a same-clip column is inside the log-sum-exp.  MASK_ZERO: the reference's rule above, the column is the
+// value 0 and counts exp(0); since every clip has such a column, the running maximum may start at 0, an element past the end of
+// the cached block may be loaded as 0, and every cached element may be summed.  MASK_EXCLUDE: the column is no member of the
+// sum at all (negatives only), so none of the three holds: the maximum starts at -inf and masked / past-the-end elements are
+// skipped by the maximum and by the sum (Bk >= 2: at least one negative exists).  In both modes the masked columns' dsim is 0
+// and the positives are read before masking.
+constexpr int MASK_ZERO = 0, MASK_EXCLUDE = 1;
+
 struct PairSpec {
     int nA, nS, slot_rows, circle, G, B, Bk, J, myclip, n;
     const long long* order;
@@ -187,6 +197,7 @@ struct PairSpec {
     }
 };
 
+template <int MASK>
 __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restrict__ sim, int G, int B, int Bk, int J,
                                                            const long long* __restrict__ order, int clip_offset,
                                                            float* __restrict__ dsim, double* __restrict__ part) {
@@ -210,7 +221,7 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     int wi = (int)threadIdx.x / J, wj = (int)threadIdx.x - wi * J, wjm = wj % Bk;
     float v[CK];
     unsigned off[CK];
-    float mx = 0.f;                                        // masked entries are 0, there is at least one
+    float mx = MASK == MASK_ZERO ? 0.f : -INFINITY;        // zero: masked entries are 0, there is at least one
 #pragma unroll
     for (int k = 0; k < CK; ++k) {
         const int e = threadIdx.x + k * 1024;
@@ -223,7 +234,7 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
             if (!masked) x = sim[o];
         }
         v[k] = x;
-        mx = fmaxf(mx, x);
+        if (MASK == MASK_ZERO || !(off[k] >> 31)) mx = fmaxf(mx, x);
         wi += di; wj += dj; wjm += djm;
         if (wj >= J) { wj -= J; ++wi; wjm += Bk - Jm; }
         if (wjm >= Bk) wjm -= Bk;
@@ -238,7 +249,7 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     double se = 0;
 #pragma unroll
     for (int k = 0; k < CK; ++k)
-        if ((int)threadIdx.x + k * 1024 < total) se += (double)__expf(v[k] - mx);
+        if (MASK == MASK_ZERO ? (int)threadIdx.x + k * 1024 < total : !(off[k] >> 31)) se += (double)__expf(v[k] - mx);
     se = block_reduce_sum(se, smd);
     const float lse = mx + (float)log(se);
     double loss_t = 0, dlse_t = 0;
@@ -268,6 +279,7 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
 }
 
 // streaming form for shapes the register-cached kernel cannot hold ((G-1)*J > CK*1024 or G > 1024)
+template <int MASK>
 __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__ sim, int G, int B, int Bk, int J,
                                                        const long long* __restrict__ order, int clip_offset,
                                                        float* __restrict__ dsim, double* __restrict__ part) {
@@ -279,16 +291,22 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
     sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
     sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
-    float mx = 0.f;
+    float mx = MASK == MASK_ZERO ? 0.f : -INFINITY;
     for (int i = 0; i < nA; ++i) {
         const float* row = sim + (size_t)(sp.row_block(i) * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256) mx = fmaxf(mx, (j % Bk == myclip) ? 0.f : row[j]);
+        for (int j = threadIdx.x; j < J; j += 256) {
+            if constexpr (MASK == MASK_ZERO) mx = fmaxf(mx, (j % Bk == myclip) ? 0.f : row[j]);
+            else if (j % Bk != myclip) mx = fmaxf(mx, row[j]);
+        }
     }
     mx = block_reduce_max(mx, smf);
     double se = 0;
     for (int i = 0; i < nA; ++i) {
         const float* row = sim + (size_t)(sp.row_block(i) * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256) se += (double)__expf(((j % Bk == myclip) ? 0.f : row[j]) - mx);
+        for (int j = threadIdx.x; j < J; j += 256) {
+            if constexpr (MASK == MASK_ZERO) se += (double)__expf(((j % Bk == myclip) ? 0.f : row[j]) - mx);
+            else if (j % Bk != myclip) se += (double)__expf(row[j] - mx);
+        }
     }
     se = block_reduce_sum(se, smd);
     const float lse = mx + (float)log(se);
@@ -318,6 +336,55 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
         dsim[pp] = (__expf(pos - t) - 1.f) * invB;
     }
     if (threadIdx.x == 0) part[2 * n + sp.circle] = loss * (double)invB;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Row pass in front of the similarity GEMM: n_r = x_r * s / max(||x_r||_2, 1e-12) (NORM) or n_r = x_r * s, with s = 1/sqrt(tau),
+// so that n @ n^T is cos/tau resp. <.,.>/tau and the GEMMs and the loss launch see no temperature.  One wave per row, 16-byte
+// loads; the sum of squares / the dot product in fp64 in the order of norm_rows.h (per lane, then the xor tree); every element
+// is rounded once to fp32.  No LDS, no atomic: the same bits every run.
+constexpr int LR_THREADS = 256, LR_WAVES = LR_THREADS / 64;
+
+template <bool NORM>
+__global__ __launch_bounds__(LR_THREADS) void k_loss_rows_fwd(const float* __restrict__ x, long long R, int C, float s,
+                                                              float* __restrict__ n, float* __restrict__ inv_norm) {
+    const long long row = (long long)blockIdx.x * LR_WAVES + (threadIdx.x >> 6);
+    if (row >= R) return;                                                            // wave-uniform
+    const int lane = lane_id(), C4 = C >> 2;
+    const float4* x4 = reinterpret_cast<const float4*>(x + (size_t)row * C);
+    float4* n4 = reinterpret_cast<float4*>(n + (size_t)row * C);
+    double inv = 1.0;
+    if constexpr (NORM) {
+        double ss = 0.0;
+        for (int c = lane; c < C4; c += 64) nr_acc_sq(ss, x4[c]);
+        inv = nr_inv_norm(wave_sum_f64(ss));
+    }
+    const double sc = (double)s * inv;
+    for (int c = lane; c < C4; c += 64) n4[c] = nr_scale_f64(x4[c], sc);
+    if (lane == 0) inv_norm[row] = (float)inv;
+}
+
+// dx_r = s inv_r (dn_r - xh_r <dn_r, xh_r>) with the unit row xh_r = n_r / s, i.e. nr_project on (dn_r, n_r) with the dot
+// product divided by s^2;  without normalisation dx_r = s dn_r.
+template <bool NORM>
+__global__ __launch_bounds__(LR_THREADS) void k_loss_rows_bwd(const float* __restrict__ dn, const float* __restrict__ n,
+                                                              const float* __restrict__ inv_norm, long long R, int C, float s,
+                                                              float* __restrict__ dx) {
+    const long long row = (long long)blockIdx.x * LR_WAVES + (threadIdx.x >> 6);
+    if (row >= R) return;                                                            // wave-uniform
+    const int lane = lane_id(), C4 = C >> 2;
+    const float4* d4 = reinterpret_cast<const float4*>(dn + (size_t)row * C);
+    float4* o4 = reinterpret_cast<float4*>(dx + (size_t)row * C);
+    if constexpr (NORM) {
+        const float4* n4 = reinterpret_cast<const float4*>(n + (size_t)row * C);
+        double dot = 0.0;
+        for (int c = lane; c < C4; c += 64) nr_acc_dot(dot, d4[c], n4[c]);
+        dot = wave_sum_f64(dot) / ((double)s * (double)s);
+        const double sc = (double)s * (double)inv_norm[row];
+        for (int c = lane; c < C4; c += 64) o4[c] = nr_project(sc, d4[c], n4[c], dot);
+    } else {
+        for (int c = lane; c < C4; c += 64) o4[c] = nr_scale_f64(d4[c], (double)s);
+    }
 }
 
 // dst[r][:] = src[r][:] * (r < R1 ? *g1 : *g2): the chain rule of the two loss values onto the shared d/dsim matrix
@@ -360,19 +427,36 @@ extern "C" int facl_contrast(const float* sim, int R, int J, int B, int Bk, int 
     return facl_reduce_rows((const double*)ws, B, 1, loss, st);
 }
 
+namespace {
+// shape checks and launch of the pair kernels: per-clip partial losses [loss_c, loss_circle] into ws, d/dsim into dsim
+template <int MASK>
+void launch_pair_kernel(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, float* dsim,
+                        void* ws, hipStream_t st) {
+    if ((long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL)
+        hipLaunchKernelGGL(k_contrast_pair_reg<MASK>, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
+                           clip_offset, dsim, (double*)ws);
+    else
+        hipLaunchKernelGGL(k_contrast_pair<MASK>, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
+                           clip_offset, dsim, (double*)ws);
+}
+
+int launch_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, float* dsim,
+                void* ws, hipStream_t st) {
+    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return FACL_E_SHAPE;
+    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
+    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE) return FACL_E_SHAPE;
+    if (mask_mode == MASK_EXCLUDE && Bk < 2) return FACL_E_SHAPE;            // one key clip: no negative exists
+    if (mask_mode == MASK_ZERO) launch_pair_kernel<MASK_ZERO>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
+    else launch_pair_kernel<MASK_EXCLUDE>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
+    return facl_launch_status();
+}
+}  // namespace
+
 extern "C" int facl_contrast_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
                                   float* dsim, double* losses /* [loss_c, loss_circle] */, void* ws, void* stream) {
     if (!sim || !order || !dsim || !losses || !ws) return FACL_E_NULL;
-    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return FACL_E_SHAPE;
-    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
     hipStream_t st = (hipStream_t)stream;
-    if ((long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL)
-        hipLaunchKernelGGL(k_contrast_pair_reg, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws);
-    else
-        hipLaunchKernelGGL(k_contrast_pair, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws);
-    int rc = facl_launch_status();
+    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, MASK_ZERO, dsim, ws, st);
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, B, 2, losses, st);
 }
@@ -395,21 +479,47 @@ __global__ __launch_bounds__(64) void k_loss_finish(const double* __restrict__ p
 }
 }  // namespace
 
-extern "C" int facl_contrast_pair_sum(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
-                                      float* dsim, double* losses, float* losses32, void* ws, void* stream) {
+// facl_contrast_pair_sum with the mask mode of the same-clip columns as an argument (0 = zero, 1 = exclude)
+extern "C" int facl_contrast_pair_sum_mask(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                           int mask_mode, float* dsim, double* losses, float* losses32, void* ws, void* stream) {
     if (!sim || !order || !dsim || !losses || !losses32 || !ws) return FACL_E_NULL;
-    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return FACL_E_SHAPE;
-    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if ((long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL)
-        hipLaunchKernelGGL(k_contrast_pair_reg, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws);
-    else
-        hipLaunchKernelGGL(k_contrast_pair, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws);
-    int rc = facl_launch_status();
+    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, mask_mode, dsim, ws, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)ws, B, losses, losses32);
+    return facl_launch_status();
+}
+
+extern "C" int facl_contrast_pair_sum(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                      float* dsim, double* losses, float* losses32, void* ws, void* stream) {
+    return facl_contrast_pair_sum_mask(sim, G, B, Bk, J, order, clip_offset, MASK_ZERO, dsim, losses, losses32, ws, stream);
+}
+
+namespace {
+inline bool loss_rows_ok(int64_t R, int C, int normalize, float s) {
+    return R >= 1 && (R + LR_WAVES - 1) / LR_WAVES <= 0x7fffffffLL && C >= 4 && C % 4 == 0 && (normalize == 0 || normalize == 1) &&
+           s > 0.f && s <= 3.402823466e38f;
+}
+}  // namespace
+
+extern "C" int facl_loss_rows_fwd(const float* x, int64_t R, int C, int normalize, float s, float* n, float* inv_norm, void* stream) {
+    if (!loss_rows_ok(R, C, normalize, s)) return FACL_E_SHAPE;
+    if (!x || !n || !inv_norm) return FACL_E_NULL;
+    if (((uintptr_t)x | (uintptr_t)n) & 15) return FACL_E_ALIGN;
+    const dim3 grid((unsigned)((R + LR_WAVES - 1) / LR_WAVES));
+    if (normalize) hipLaunchKernelGGL(k_loss_rows_fwd<true>, grid, dim3(LR_THREADS), 0, (hipStream_t)stream, x, (long long)R, C, s, n, inv_norm);
+    else hipLaunchKernelGGL(k_loss_rows_fwd<false>, grid, dim3(LR_THREADS), 0, (hipStream_t)stream, x, (long long)R, C, s, n, inv_norm);
+    return facl_launch_status();
+}
+
+extern "C" int facl_loss_rows_bwd(const float* dn, const float* n, const float* inv_norm, int64_t R, int C, int normalize, float s,
+                                  float* dx, void* stream) {
+    if (!loss_rows_ok(R, C, normalize, s)) return FACL_E_SHAPE;
+    if (!dn || !n || !inv_norm || !dx) return FACL_E_NULL;
+    if (((uintptr_t)dn | (uintptr_t)n | (uintptr_t)dx) & 15) return FACL_E_ALIGN;
+    const dim3 grid((unsigned)((R + LR_WAVES - 1) / LR_WAVES));
+    if (normalize) hipLaunchKernelGGL(k_loss_rows_bwd<true>, grid, dim3(LR_THREADS), 0, (hipStream_t)stream, dn, n, inv_norm, (long long)R, C, s, dx);
+    else hipLaunchKernelGGL(k_loss_rows_bwd<false>, grid, dim3(LR_THREADS), 0, (hipStream_t)stream, dn, n, inv_norm, (long long)R, C, s, dx);
     return facl_launch_status();
 }
 

@@ -122,6 +122,9 @@ def check_finetune_flags(opt, world=None):
         raise RuntimeError("--knn_every belongs to the pre-training entries; fine-tuning reports its own test top-1 (--eval_every)")
     if opt.swa_if or opt.cld_if:
         raise RuntimeError("--swa_if / --cld_if are terms of the contrastive loss: fine-tuning has the cross-entropy only")
+    if opt.loss_normalize or opt.loss_temperature != 1.0 or opt.loss_mask != 'zero':
+        raise RuntimeError("--loss_normalize / --loss_temperature / --loss_mask shape the contrastive loss: fine-tuning has the "
+                           "cross-entropy only")
     if not opt.num_class:
         opt.num_class = 60 if opt.dataset == 'ntu60' else 120
     if not 2 <= opt.num_class <= 1024 or opt.num_class % 4:

@@ -12,7 +12,7 @@ import torch
 
 from . import cn3d_model_conbag as MODELL
 from . import dist as fdist
-from .utils_my import contrastive_losses_stacked, group_points_3DV, knn_radius_group
+from .utils_my import check_loss_mode, contrastive_losses_stacked, group_points_3DV, is_default_loss_mode, knn_radius_group
 
 
 def build_parser(default_branch):
@@ -102,6 +102,14 @@ def build_parser(default_branch):
                         'log the weighted-kNN test top-1 against the train bank (facl_amd/knn_eval.py) as "knn top1"; 0 = off')
     p.add_argument('--knn_k', type=int, default=20, help='NEW (--knn_every): neighbours per query (1..64)')
     p.add_argument('--knn_T', type=float, default=0.1, help='NEW (--knn_every): temperature of the exp(s / T) vote')
+    p.add_argument('--loss_normalize', type=int, default=0, choices=(0, 1),
+                   help='NEW: 1 = L2-normalise every embedding row in front of the global / circle losses (cosine similarity); '
+                        '0 = raw dot products (the reference)')
+    p.add_argument('--loss_temperature', type=float, default=1.0,
+                   help='NEW: the similarities of the global / circle losses are divided by this temperature (reference: 1)')
+    p.add_argument('--loss_mask', type=str, default='zero', choices=('zero', 'exclude'),
+                   help='NEW: same-clip key columns of the global / circle losses: zero = multiplied by 0, they stay in the '
+                        'softmax as exp(0) (the reference); exclude = taken out of the log-sum-exp (negatives only)')
     return p
 
 
@@ -158,6 +166,9 @@ class ContrastiveStep:
         self.r2 = group_radius
         self.fps_reorder = fps_reorder
         self._one = None
+        # loss modes (utils_my.contrastive_losses_stacked); namespaces from before the flags hold the reference's loss
+        self.loss_mode = dict(normalize=bool(getattr(opt, "loss_normalize", 0)),
+                              temperature=float(getattr(opt, "loss_temperature", 1.0)), mask=getattr(opt, "loss_mask", "zero"))
         self.rank = torch.distributed.get_rank() if fdist.is_distributed() else 0
         self.grad_sync = fdist.GradSync(list(netR.named_parameters())) if fdist.is_distributed() else None
 
@@ -198,13 +209,17 @@ class ContrastiveStep:
         # x_nor / code feed the SwAV / CLD terms only: without them F.normalize + mapping run beside the loss block
         netR.lazy_code = not (self.swa_if or self.cld_if) and not fdist.is_distributed()
         x, code, x_nor, x_global = netR(xt, yt, 1)                                 # :234
-        x_keys = fdist.all_gather_view_major(x, G)
+        if fdist.is_distributed() and not is_default_loss_mode(**self.loss_mode):
+            # the loss modes map the rows first: this rank's view rows are normalised / scaled locally, THEN gathered
+            x_keys = lambda n_views: fdist.all_gather_view_major(n_views, G)
+        else:
+            x_keys = fdist.all_gather_view_major(x, G)
         off = self.rank * B
         # global (:265-287) + circle (:290-316) losses: similarity GEMMs + one HIP kernel each (csrc/loss.hip)
         from .tail import precision as _precision
         with _precision(getattr(netR, "precision", "f32")):    # the similarity GEMMs follow the model's arithmetic
             loss_c, loss_circle, loss = contrastive_losses_stacked(G, netR._stacked, order, x_keys=None if x_keys is x else x_keys,
-                                                                   clip_offset=off, with_sum=True)
+                                                                   clip_offset=off, with_sum=True, **self.loss_mode)
         # loss = loss_circle + loss_c (:329; swa, CLD terms are 0 ...): the fp32 sum comes out of the loss launch itself
         if self.swa_if:                                                            # ... unless switched on: :239-263
             from . import swav_cld
@@ -468,6 +483,16 @@ def check_knn_flags(opt, world=None):
         raise RuntimeError("--knn_T must be positive (got %r)" % opt.knn_T)
 
 
+def check_loss_flags(opt, world=None):
+    """--loss_temperature finite and positive; --loss_mask exclude needs a negative, i.e. batch x world >= 2 key clips.  Raises
+    before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    world = fdist.env_world_size() if world is None else world
+    try:
+        check_loss_mode(opt.loss_temperature, opt.loss_mask, opt.batchSize * world)
+    except ValueError as e:
+        raise RuntimeError("--loss_temperature / --loss_mask: %s" % e) from None
+
+
 @contextlib.contextmanager
 def eval_mode(netR):
     """eval() and no_grad() for the block; the model returns to the mode it was in, also when the block raises."""
@@ -623,6 +648,7 @@ def run(default_branch, ckpt_pattern, args=None):
     check_resident_flags(opt)
     check_view_flags(opt)
     check_knn_flags(opt)
+    check_loss_flags(opt)
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)

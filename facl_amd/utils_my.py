@@ -93,52 +93,104 @@ def group_points(points, opt):
 
 
 # ---- contrastive losses (utils_my.py:53-116 = cn3d_train_motion_GL.py:265-316) -------------------
-def _masked_sim(anchors, keys, anchor_clip, key_clip):
+# Loss modes (no counterpart in the reference; the defaults are the reference's loss):
+#   normalize    every embedding row r -> r / max(||r||_2, 1e-12) (F.normalize), x_global rows included: cosine similarity
+#   temperature  similarities are divided by tau; folded into the rows as the factor s = fp32(1 / sqrt(tau))
+#   mask         'zero': same-clip key columns are multiplied by 0 and stay in the softmax as exp(0) (the reference);
+#                'exclude': they are no members of the log-sum-exp at all (negatives only)
+MASK_MODES = {"zero": 0, "exclude": 1}
+
+
+def loss_scale(temperature):
+    """s = fp32(1 / sqrt(tau)), the factor on every embedding row; ValueError unless tau is finite and positive."""
+    t = float(temperature)
+    if not (t > 0.0 and t < float("inf")):
+        raise ValueError("the loss temperature must be finite and positive (got %r)" % (temperature,))
+    s = float(np.float32(1.0 / np.sqrt(t)))
+    if not (s > 0.0 and s < float("inf")):
+        raise ValueError("the loss temperature %r is outside the fp32 range of 1 / sqrt(tau)" % (temperature,))
+    return s
+
+
+def check_loss_mode(temperature, mask, key_clips=None):
+    """The host refusals of the loss modes, before any launch: (s, mask_mode) or ValueError."""
+    s = loss_scale(temperature)
+    if mask not in MASK_MODES:
+        raise ValueError("unknown loss mask %r (one of %s)" % (mask, ", ".join(sorted(MASK_MODES))))
+    if mask == "exclude" and key_clips is not None and key_clips < 2:
+        raise ValueError("mask 'exclude' with one key clip leaves no negative: it needs batch x world >= 2")
+    return s, MASK_MODES[mask]
+
+
+def is_default_loss_mode(normalize, temperature, mask):
+    """True for the reference's loss (no row pass, mask mode zero)."""
+    return not normalize and float(temperature) == 1.0 and mask == "zero"
+
+
+def _loss_rows_torch(x, normalize, temperature):
+    """n = x * s / max(||x||, 1e-12) resp. x * s in x's dtype (the truth of the HIP row pass); x itself at the defaults."""
+    if not normalize and float(temperature) == 1.0:
+        return x
+    s = loss_scale(temperature)
+    return (torch.nn.functional.normalize(x, p=2, dim=1, eps=1e-12) if normalize else x) * s
+
+
+def _masked_sim(anchors, keys, anchor_clip, key_clip, mask="zero"):
     """l_neg = (anchors @ keys^T) * mask, mask = 0 where the key belongs to the anchor's own clip
     (utils_my.py:55-56,71-72).  Same-clip columns are multiplied by 0 -- NOT removed -- so each of them
-    still contributes exp(0) = 1 to the softmax denominator, exactly like the reference."""
+    still contributes exp(0) = 1 to the softmax denominator, exactly like the reference.  mask 'exclude': they become
+    -inf, i.e. they leave the log-sum-exp."""
     sim = anchors @ keys.t()
     same = anchor_clip[:, None] == key_clip[None, :]
-    return torch.where(same, torch.zeros((), dtype=sim.dtype, device=sim.device), sim)
+    fill = 0.0 if mask == "zero" else float("-inf")
+    return torch.where(same, torch.full((), fill, dtype=sim.dtype, device=sim.device), sim)
 
 
 def _clip_ids(G, B, device, offset=0):
     return (torch.arange(B, device=device) + offset).repeat(G)     # row g*B+b -> clip id b
 
 
-def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, clip_offset=0):
+def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, clip_offset=0, normalize=False, temperature=1.0,
+                    mask='zero'):
     """utils_my.py:53-83.  loss_c = sum_g CE([<xg_n, x_{gB+n}> | (xg @ x^T)*mask], 0), CE = mean over B.
     The (G,B,1+GB) logits tensor and its ``repeat`` are never built: every g shares the negatives, so
     CE_g[n] = logaddexp(pos[g,n], LSE_n) - pos[g,n].
 
     Data-parallel form: ``x_keys`` = the all-gathered view-major embeddings (G*B_global rows) and
-    ``clip_offset`` = rank*B_local; anchors stay local (mean over local B, gradients averaged by DDP)."""
+    ``clip_offset`` = rank*B_local; anchors stay local (mean over local B, gradients averaged by DDP).
+
+    ``normalize`` / ``temperature`` / ``mask``: the loss modes above.  The rows of x_global, x and x_keys (the gathered RAW
+    embeddings: normalising a row commutes with gathering it) are mapped first; the rest is unchanged."""
     B, G = x_global.shape[0], num_crop
-    keys = x if x_keys is None else x_keys
+    check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
+    x_global, x = _loss_rows_torch(x_global, normalize, temperature), _loss_rows_torch(x, normalize, temperature)
+    keys = x if x_keys is None else _loss_rows_torch(x_keys, normalize, temperature)
     Bk = keys.shape[0] // G
     a_clip = torch.arange(B, device=x.device) + clip_offset
-    neg = _masked_sim(x_global, keys, a_clip, _clip_ids(G, Bk, x.device))      # (B, G*Bk)
+    neg = _masked_sim(x_global, keys, a_clip, _clip_ids(G, Bk, x.device), mask)      # (B, G*Bk)
     lse = torch.logsumexp(neg, dim=1)
     pos = (x_global.unsqueeze(0) * x.view(G, B, -1)).sum(-1)                   # (G,B)
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
 
-def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=None, clip_offset=0):
+def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=None, clip_offset=0, normalize=False,
+                    temperature=1.0, mask='zero'):
     """utils_my.py:85-116.  ``order`` replaces the reference's np.random.shuffle(arange(num_crop)) (:96-97);
-    when omitted it is drawn from NumPy's global RNG like the reference."""
-    import numpy as np
+    when omitted it is drawn from NumPy's global RNG like the reference.  Loss modes: as in global_contrast."""
     G, B = num_crop, batchSize
+    check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     if order is None:
         order = np.arange(0, G, 1)
         np.random.shuffle(order)
     order = torch.as_tensor(np.asarray(order), device=x.device, dtype=torch.long)
-    keys = x if x_keys is None else x_keys
+    x = _loss_rows_torch(x, normalize, temperature)
+    keys = x if x_keys is None else _loss_rows_torch(x_keys, normalize, temperature)
     Bk = keys.shape[0] // G
     xv = x.view(G, B, -1)
     anchors = xv[order[:-1]]                                                   # (G-1,B,C)
     pos = (anchors * xv[order[1:]]).sum(-1)                                    # (G-1,B)   :100
     a_clip = (torch.arange(B, device=x.device) + clip_offset).repeat(G - 1)
-    neg = _masked_sim(anchors.reshape((G - 1) * B, -1), keys, a_clip, _clip_ids(G, Bk, x.device))
+    neg = _masked_sim(anchors.reshape((G - 1) * B, -1), keys, a_clip, _clip_ids(G, Bk, x.device), mask)
     neg = neg.view(G - 1, B, G * Bk).permute(1, 0, 2).reshape(B, -1)           # all anchors' negatives, shared (:105-109)
     lse = torch.logsumexp(neg, dim=1)
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
@@ -215,7 +267,7 @@ class _ContrastivePair(torch.autograd.Function):
     positive-column index tensors, no index_add (utils_my.py:63-71,100-103 and their autograd)."""
 
     @staticmethod
-    def forward(ctx, stacked, keys, order, G, clip_offset):
+    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0):
         from . import tail as _tail
         from .sa_mlp import _Workspace
         lib = _lib.load_library()
@@ -236,8 +288,9 @@ class _ContrastivePair(torch.autograd.Function):
         out = _lib.empty(2, dtype=torch.float64, device=dev)
         # [loss_c, loss_circle, loss_circle + loss_c] in fp32 from the loss launch's own finishing kernel (no cast / add launches)
         out32 = _lib.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.facl_contrast_pair_sum(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, _lib.ptr(dsim),
-                                              _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_sum")
+        _lib.check(lib.facl_contrast_pair_sum_mask(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, mask_mode,
+                                                   _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
+                   "facl_contrast_pair_sum_mask")
         ctx.save_for_backward(stacked, keys, dsim)
         ctx.GB = G * B
         ctx.set_materialize_grads(False)           # an unused loss output arrives as None, not as a freshly filled zero tensor
@@ -257,7 +310,7 @@ class _ContrastivePair(torch.autograd.Function):
             return g if g_s is None else g + g_s.float()
         g_c, g_o = tot(g_c), tot(g_o)
         if g_c is None and g_o is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         zero = None
         if g_c is None or g_o is None:
             zero = torch.zeros((), dtype=torch.float32, device=dsim.device)
@@ -278,14 +331,52 @@ class _ContrastivePair(torch.autograd.Function):
                 rc = lib.facl_gemm_wgrad_acc(_lib.ptr(ds), _lib.ptr(stacked), M_, N_, K_, stacked.stride(0), _lib.ptr(d_stacked), pc,
                                              _lib.stream())
             if rc == 0:
-                return d_stacked, None, None, None, None
+                return d_stacked, None, None, None, None, None
             if rc != -4:
                 _lib.check(rc, "facl_gemm_wgrad_acc")
         d_keys = _tail.gemm_wgrad(ds, stacked, prec=bp) if ctx.mfma else ds.t() @ stacked
         if ctx.own_keys:
             d_stacked[:ctx.GB] += d_keys
             d_keys = None
-        return d_stacked, d_keys, None, None, None
+        return d_stacked, d_keys, None, None, None, None
+
+
+class _LossRows(torch.autograd.Function):
+    """n = rows * s / max(||row||, 1e-12) (normalize) or rows * s, s = fp32(1 / sqrt(tau)): the row pass in front of
+    _ContrastivePair (csrc/loss.hip: k_loss_rows_fwd / _bwd), one launch each way."""
+
+    @staticmethod
+    def forward(ctx, x, normalize, s):
+        lib = _lib.load_library()
+        _lib.require_cuda(x)
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise TypeError("the loss row pass takes a 2-D float32 matrix")
+        x = x.contiguous()
+        R, C = x.shape
+        n = _lib.empty_like(x)
+        inv = _lib.empty(R, dtype=torch.float32, device=x.device)
+        _lib.check(lib.facl_loss_rows_fwd(_lib.ptr(x), R, C, int(normalize), s, _lib.ptr(n), _lib.ptr(inv), _lib.stream()),
+                   "facl_loss_rows_fwd(R=%d, C=%d)" % (R, C))
+        ctx.save_for_backward(n, inv)
+        ctx.mode = (int(normalize), s)
+        return n
+
+    @staticmethod
+    def backward(ctx, dn):
+        n, inv = ctx.saved_tensors
+        normalize, s = ctx.mode
+        lib = _lib.load_library()
+        dn = dn.contiguous().float()
+        dx = _lib.empty_like(n)
+        R, C = n.shape
+        _lib.check(lib.facl_loss_rows_bwd(_lib.ptr(dn), _lib.ptr(n), _lib.ptr(inv), R, C, normalize, s, _lib.ptr(dx),
+                                          _lib.stream()), "facl_loss_rows_bwd(R=%d, C=%d)" % (R, C))
+        return dx, None, None
+
+
+def loss_rows(x, normalize=False, temperature=1.0):
+    """The loss modes' row map of a (R, C) float32 matrix on the GPU (C % 4 == 0): x * s / max(||x||, 1e-12) or x * s."""
+    return _LossRows.apply(x, bool(normalize), loss_scale(temperature))
 
 
 def _check_order(order, G):
@@ -297,14 +388,35 @@ def _check_order(order, G):
         raise ValueError("order must be a permutation of range(%d), got %r" % (G, o.tolist()))
 
 
-def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offset=0, with_sum=False):
+def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offset=0, with_sum=False, normalize=False,
+                               temperature=1.0, mask='zero'):
     """(loss_c, loss_circle) from the model's stacked output [x ; x_global] (facl_amd.cn3d_model_conbag: ``_stacked``);
-    with_sum: also `loss_circle + loss_c` (fp32, cn3d_train_motion_GL.py:329) as a third output of the same launch."""
+    with_sum: also `loss_circle + loss_c` (fp32, cn3d_train_motion_GL.py:329) as a third output of the same launch.
+
+    ``normalize`` / ``temperature`` / ``mask``: the loss modes (see global_contrast).  At the defaults nothing but today's
+    launches runs.  Otherwise one row pass n = loss_rows(stacked) runs in front and the loss sees n.  ``x_keys`` is the
+    gathered RAW view-major embeddings (they take the row pass too), or -- what the data-parallel step uses, a row pass over
+    the local rows only -- a callable that maps this rank's view rows n[:G*B] to the gathered keys."""
     G = num_crop
+    GB = G * (stacked.shape[0] // (G + 1))
+    if is_default_loss_mode(normalize, temperature, mask):
+        mask_mode = 0
+        if callable(x_keys):
+            x_keys = x_keys(stacked[:GB])
+    else:
+        key_rows = GB if x_keys is None or callable(x_keys) else x_keys.shape[0]
+        s, mask_mode = check_loss_mode(temperature, mask, None if callable(x_keys) else key_rows // G)
+        if normalize or s != 1.0:
+            stacked = _LossRows.apply(stacked, bool(normalize), s)
+            if x_keys is not None and not callable(x_keys):
+                x_keys = _LossRows.apply(x_keys, bool(normalize), s)
+        if callable(x_keys):
+            x_keys = x_keys(stacked[:GB])
+            check_loss_mode(temperature, mask, x_keys.shape[0] // G)
     if not (torch.is_tensor(order) and order.device == stacked.device and order.dtype == torch.long):
         _check_order(order, G)
         order = torch.as_tensor(order, device=stacked.device, dtype=torch.long)
-    out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset)
+    out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode)
     return out if with_sum else out[:2]
 
 

@@ -442,6 +442,21 @@ int facl_contrast_pair(const float* sim, int G, int B, int Bk, int J, const int6
  * instead of a reduction, a cast and an add. */
 int facl_contrast_pair_sum(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
                            float* dsim, double* losses, float* losses32, void* ws, void* stream);
+/* facl_contrast_pair_sum with the treatment of the same-clip key columns as an argument.  mask_mode 0 (zero) = the reference's
+ * rule above: the column is multiplied by 0 and stays in the log-sum-exp as exp(0); facl_contrast_pair_sum is this entry with
+ * mode 0.  mask_mode 1 (exclude): same-clip columns are no members of the log-sum-exp (negatives only); their dsim is 0 and the
+ * positives are still read before masking; needs Bk >= 2 (a negative must exist).  Any other mode: FACL_E_SHAPE. */
+int facl_contrast_pair_sum_mask(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                int mask_mode, float* dsim, double* losses, float* losses32, void* ws, void* stream);
+/* Row pass in front of the similarity GEMM (cosine similarity and temperature of the contrastive losses): x (R,C) ->
+ * n_r = x_r * s / max(||x_r||_2, 1e-12) (normalize = 1: F.normalize's clamp) or n_r = x_r * s (normalize = 0), with s =
+ * 1/sqrt(temperature), so that n @ n^T = cos / temperature resp. <.,.> / temperature.  inv_norm (R) = 1 / max(||x_r||, 1e-12)
+ * (1 with normalize = 0).  Backward: dx_r = s * inv_norm_r * (dn_r - xh_r <dn_r, xh_r>), xh_r = n_r / s, resp. dx_r = s * dn_r;
+ * every row of dx is written.  Sum of squares and dot product in fp64 in a fixed order, one rounding per element, no atomics.
+ * C % 4 == 0, 0 < s < inf, 16-byte aligned matrices. */
+int facl_loss_rows_fwd(const float* x, int64_t R, int C, int normalize, float s, float* n, float* inv_norm, void* stream);
+int facl_loss_rows_bwd(const float* dn, const float* n, const float* inv_norm, int64_t R, int C, int normalize, float s,
+                       float* dx, void* stream);
 /* dst (R,J) = src scaled by *g1 in rows [0,R1) and by *g2 in rows [R1,R): the two upstream gradients (device scalars)
  * of loss_circle / loss_c applied to the shared d/dsim matrix. */
 int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_t R, int J, const float* g1, const float* g2,

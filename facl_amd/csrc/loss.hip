@@ -15,6 +15,7 @@
 #include "norm_rows.h"
 
 int facl_reduce_rows(const double* part, int rows, int V, double* out, hipStream_t st);
+extern "C" int64_t facl_ws_bytes(void);
 
 namespace {
 
@@ -537,5 +538,276 @@ extern "C" int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_
         const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
         hipLaunchKernelGGL((k_scale_rows2<float>), dim3(grid), dim3(256), 0, st, src, dst, n, split, g1, g2);
     }
+    return facl_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The pair loss with a queue of negative keys from earlier steps.  sim_q ((G+1)*B, L) = [x ; x_global] @ queue^T holds, in its
+// first `valid` columns (qstate = {head, valid}, read on the device: a captured step replays while the queue fills), extra
+// negatives of every clip in both losses; they carry no clip identity, so no mask mode touches them.  Columns >= valid are
+// never used (V = 4 loads the vector that straddles `valid` whole, inside the row, and q_load drops its dead lanes, NaN
+// included) and their dsim_q is written as exactly 0.  A clip's block is now nA x (J + valid) values: too large for the
+// register form, and 2B workgroups reading it three times would leave most CUs idle.  The block is therefore spread over
+// workgroups by (row slot, chunk of QC columns) -- slots 0..G-2: circle anchors order[slot], slot G-1: the view that is no
+// anchor (zero gradient row), slot G: the global loss's row; chunks: ceil(J / QC) of sim, then ceil(L / QC) of sim_q -- in
+// two launches:
+//   k_contrast_queue_part   per chunk (max, sum exp(v - max)) of the members of the log-sum-exp, the sum in fp64;
+//   k_contrast_queue_write  every workgroup combines the partials of its clip's block in the same fixed order (the same lse
+//                           bits in all of them, no atomic), evaluates the positives' terms and writes its chunk of dsim /
+//                           dsim_q; the workgroup of (slot 0 | slot G, chunk 0) stores the clip's loss.
+// The chunk is held in registers inside each kernel (QC / QT values per thread); the same-clip column index advances by
+// increments (one division per thread, see k_contrast_pair_reg).  V = 4: 16-byte loads and stores (J % 4 == L % 4 == 0).
+namespace {
+constexpr int QT = 256;                     // threads per workgroup
+constexpr int QC = 2048;                    // columns per chunk
+constexpr int QN = QC / QT;                 // values per thread
+
+struct QUnit {
+    PairSpec sp;
+    int slot, ch, nch, c0, wlen, len;       // chunk: first column, columns written, leading columns that are live (queue: < valid)
+    bool in_sim;                            // a chunk of sim (same-clip mask applies) or of sim_q
+    size_t base;                            // element offset of the chunk in its matrix
+};
+
+__device__ __forceinline__ QUnit q_unit(int G, int B, int Bk, int J, int L, const long long* order, int clip_offset,
+                                        const int* __restrict__ qstate) {
+    QUnit u;
+    const int cJ = (J + QC - 1) / QC;
+    u.nch = cJ + (L + QC - 1) / QC;
+    u.ch = (int)(blockIdx.x % (unsigned)u.nch);
+    const int t = (int)(blockIdx.x / (unsigned)u.nch);
+    u.slot = t % (G + 1);
+    PairSpec& sp = u.sp;
+    sp.n = t / (G + 1);
+    sp.circle = u.slot < G;
+    sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
+    sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
+    const int v = qstate[1];
+    const int valid = v < 0 ? 0 : (v > L ? L : v);         // clamped: a corrupt state cannot address outside sim_q / dsim_q
+    const size_t r = (size_t)(u.slot == G ? G : sp.ord(u.slot)) * B + sp.n;
+    u.in_sim = u.ch < cJ;
+    if (u.in_sim) {
+        u.c0 = u.ch * QC;
+        u.wlen = J - u.c0 < QC ? J - u.c0 : QC;
+        u.len = u.wlen;
+        u.base = r * J + u.c0;
+    } else {
+        u.c0 = (u.ch - cJ) * QC;
+        u.wlen = L - u.c0 < QC ? L - u.c0 : QC;
+        const int live = valid - u.c0;
+        u.len = live < 0 ? 0 : (live > u.wlen ? u.wlen : live);
+        u.base = r * L + u.c0;
+    }
+    return u;
+}
+
+// The chunk's values into registers.  Bit i of `grad`: value i is a live column that is not a same-clip one (it receives a
+// gradient); bit i of `mem`: it is a member of the log-sum-exp (MASK_ZERO: the same-clip columns too, as the value 0).
+template <int MASK, int V>
+__device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__ m, float (&x)[QN], unsigned& mem, unsigned& grad) {
+    const float* src = m + u.base;
+    const int Bk = u.sp.Bk;
+    int jm = 0, step = 0;
+    if (u.in_sim) { jm = (u.c0 + (int)threadIdx.x * V) % Bk; step = ((QT - 1) * V) % Bk; }
+    mem = grad = 0u;
+#pragma unroll
+    for (int k = 0; k < QN / V; ++k) {
+        const int e = (k * QT + (int)threadIdx.x) * V;
+        float v[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) v[c] = 0.f;
+        if (e < u.len) {                                   // V = 4: wlen % 4 == 0, the whole vector lies inside the row
+            if constexpr (V == 4) {
+                const float4 q = *reinterpret_cast<const float4*>(src + e);
+                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+            } else {
+                v[0] = src[e];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+            const bool live = e + c < u.len;
+            const bool masked = u.in_sim && jm == u.sp.myclip;
+            const bool g = live && !masked;
+            x[k * V + c] = g ? v[c] : 0.f;
+            grad |= (unsigned)g << (k * V + c);
+            mem |= (unsigned)(MASK == MASK_ZERO ? live : g) << (k * V + c);
+            if (u.in_sim && ++jm == Bk) jm = 0;
+        }
+        if (u.in_sim) { jm += step; if (jm >= Bk) jm -= Bk; }
+    }
+}
+
+template <int MASK, int V>
+__global__ __launch_bounds__(QT) void k_contrast_queue_part(const float* __restrict__ sim, const float* __restrict__ sim_q, int G,
+                                                            int B, int Bk, int J, int L, const long long* __restrict__ order,
+                                                            int clip_offset, const int* __restrict__ qstate,
+                                                            float* __restrict__ pm, double* __restrict__ ps) {
+    __shared__ float smf[QT / 64];
+    __shared__ double smd[QT / 64];
+    const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
+    if (u.slot == G - 1) return;                           // no anchor: no member of any log-sum-exp
+    float x[QN];
+    unsigned mem, grad;
+    q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);
+    float mx = -INFINITY;                                  // a chunk without a member: (-inf, 0), skipped by the combination
+#pragma unroll
+    for (int i = 0; i < QN; ++i)
+        if ((mem >> i) & 1u) mx = fmaxf(mx, x[i]);
+    mx = block_reduce_max(mx, smf);
+    double se = 0;
+#pragma unroll
+    for (int i = 0; i < QN; ++i)
+        if ((mem >> i) & 1u) se += (double)__expf(x[i] - mx);
+    se = block_reduce_sum(se, smd);
+    if (threadIdx.x == 0) { pm[blockIdx.x] = mx; ps[blockIdx.x] = se; }
+}
+
+template <int MASK, int V>
+__global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __restrict__ sim, const float* __restrict__ sim_q, int G,
+                                                             int B, int Bk, int J, int L, const long long* __restrict__ order,
+                                                             int clip_offset, const int* __restrict__ qstate,
+                                                             const float* __restrict__ pm, const double* __restrict__ ps,
+                                                             float* __restrict__ dsim, float* __restrict__ dsim_q,
+                                                             double* __restrict__ part) {
+    __shared__ float smf[QT / 64];
+    __shared__ double smd[QT / 64];
+    const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
+    const PairSpec& sp = u.sp;
+    float* dst = (u.in_sim ? dsim : dsim_q) + u.base;
+    float x[QN];
+    unsigned mem = 0u, grad = 0u;
+    float lse = 0.f, dlse = 0.f;
+    double loss = 0;
+    const float invB = 1.f / (float)B;
+    if (u.slot != G - 1) {                                 // workgroup-uniform
+        q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);      // requested ahead of the reductions below
+        // the log-sum-exp of the clip's block from its nA * nch chunk partials (circle: slots 0..G-2 are adjacent units)
+        const int np = sp.nA * u.nch;
+        const size_t p0 = ((size_t)sp.n * (G + 1) + (sp.circle ? 0 : G)) * u.nch;
+        float M = -INFINITY;
+        for (int p = threadIdx.x; p < np; p += QT)
+            if (ps[p0 + p] > 0) M = fmaxf(M, pm[p0 + p]);
+        M = block_reduce_max(M, smf);
+        double S = 0;
+        for (int p = threadIdx.x; p < np; p += QT) {
+            const double s = ps[p0 + p];
+            if (s > 0) S += s * exp((double)pm[p0 + p] - (double)M);
+        }
+        S = block_reduce_sum(S, smd);
+        lse = M + (float)log(S);
+        double loss_t = 0, dlse_t = 0;
+        for (int s = threadIdx.x; s < sp.nS; s += QT) {
+            const float pos = sim[sp.pos_index(s)];
+            const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
+            loss_t += (double)(t - pos);
+            dlse_t += (double)(1.f - __expf(pos - t));
+        }
+        loss = block_reduce_sum(loss_t, smd);
+        dlse = (float)block_reduce_sum(dlse_t, smd) * invB;
+    }
+#pragma unroll
+    for (int k = 0; k < QN / V; ++k) {
+        const int e = (k * QT + (int)threadIdx.x) * V;
+        if (e < u.wlen) {
+            float d[V];
+#pragma unroll
+            for (int c = 0; c < V; ++c) d[c] = ((grad >> (k * V + c)) & 1u) ? dlse * __expf(x[k * V + c] - lse) : 0.f;
+            if constexpr (V == 4) *reinterpret_cast<float4*>(dst + e) = make_float4(d[0], d[1], d[2], d[3]);
+            else dst[e] = d[0];
+        }
+    }
+    if (u.slot == G - 1 || !u.in_sim) return;
+    __syncthreads();                                       // the positives overwrite zeros written just above
+    // positives that lie in this chunk: the circle slot's own one, every view's for the global row
+    for (int s = threadIdx.x; s < sp.nS; s += QT) {
+        if (sp.circle && s != u.slot) continue;
+        const int col = (sp.circle ? sp.ord(s + 1) : s) * Bk + sp.myclip;
+        if (col < u.c0 || col >= u.c0 + u.wlen) continue;
+        const size_t pp = sp.pos_index(s);
+        const float pos = sim[pp];
+        const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
+        dsim[pp] = (__expf(pos - t) - 1.f) * invB;
+    }
+    if (u.ch == 0 && (u.slot == 0 || u.slot == G) && threadIdx.x == 0) part[2 * sp.n + sp.circle] = loss * (double)invB;
+}
+
+template <int MASK, int V>
+void launch_queue_kernels(unsigned units, const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
+                          const int64_t* order, int clip_offset, const int32_t* qstate, float* dsim, float* dsim_q, double* part,
+                          double* ps, float* pm, hipStream_t st) {
+    hipLaunchKernelGGL((k_contrast_queue_part<MASK, V>), dim3(units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
+                       (const long long*)order, clip_offset, (const int*)qstate, pm, ps);
+    hipLaunchKernelGGL((k_contrast_queue_write<MASK, V>), dim3(units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
+                       (const long long*)order, clip_offset, (const int*)qstate, (const float*)pm, (const double*)ps, dsim, dsim_q,
+                       part);
+}
+
+// head clamped to a multiple of P below L: a corrupt state cannot address outside the queue
+__device__ __forceinline__ int q_head(const int* qstate, int P, int L) {
+    int h = qstate[0];
+    if (h < 0) h = 0;
+    h -= h % P;
+    return h > L - P ? L - P : h;
+}
+
+__global__ __launch_bounds__(256) void k_queue_push(const float4* __restrict__ rows, long long n4, int P, int C4,
+                                                    float4* __restrict__ queue, int L, const int* __restrict__ qstate) {
+    float4* dst = queue + (size_t)q_head(qstate, P, L) * C4;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) dst[i] = rows[i];
+}
+
+// its own launch, behind the copy in stream order: no workgroup of the copy reads `head` after it has moved
+__global__ __launch_bounds__(64) void k_queue_advance(int* __restrict__ qstate, int P, int L) {
+    if (threadIdx.x == 0) {
+        const int h = q_head(qstate, P, L), v = qstate[1];
+        const int valid = v < 0 ? 0 : (v > L ? L : v);
+        qstate[0] = (h + P) % L;
+        qstate[1] = valid + P > L ? L : valid + P;
+    }
+}
+}  // namespace
+
+extern "C" int facl_contrast_pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
+                                        const int64_t* order, int clip_offset, int mask_mode, const int32_t* qstate, float* dsim,
+                                        float* dsim_q, double* losses, float* losses32, void* ws, void* stream) {
+    if (!sim || !sim_q || !order || !qstate || !dsim || !dsim_q || !losses || !losses32 || !ws) return FACL_E_NULL;
+    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk || L < 1) return FACL_E_SHAPE;
+    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
+    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE) return FACL_E_SHAPE;
+    if (mask_mode == MASK_EXCLUDE && Bk < 2) return FACL_E_SHAPE;            // one key clip: no negative exists in an empty queue
+    if (J > 0x7fffffff - QC || L > 0x7fffffff - QC) return FACL_E_SHAPE;      // the kernels round both up to chunks in int
+    const long long nch = (J + QC - 1) / QC + (L + QC - 1) / QC, units = (long long)(G + 1) * B * nch;
+    if (units > 0x7fffffffLL) return FACL_E_SHAPE;
+    // workspace: [per-clip losses (2B doubles) | chunk sums (units doubles) | chunk maxima (units floats)]
+    if ((size_t)(2 * (long long)B + units) * sizeof(double) + (size_t)units * sizeof(float) >
+        (size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES) return FACL_E_SHAPE;
+    double* part = (double*)ws;
+    double* ps = part + 2 * (size_t)B;
+    float* pm = (float*)(ps + units);
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = J % 4 == 0 && L % 4 == 0 && !(((uintptr_t)sim | (uintptr_t)sim_q | (uintptr_t)dsim | (uintptr_t)dsim_q) & 15);
+#define FACL_QUEUE_LAUNCH(MASK, V) \
+    launch_queue_kernels<MASK, V>((unsigned)units, sim, sim_q, G, B, Bk, J, L, order, clip_offset, qstate, dsim, dsim_q, part, ps, pm, st)
+    if (mask_mode == MASK_ZERO) { if (vec) FACL_QUEUE_LAUNCH(MASK_ZERO, 4); else FACL_QUEUE_LAUNCH(MASK_ZERO, 1); }
+    else { if (vec) FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 4); else FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 1); }
+#undef FACL_QUEUE_LAUNCH
+    int rc = facl_launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)part, B, losses, losses32);
+    return facl_launch_status();
+}
+
+extern "C" int facl_queue_push(const float* rows, int P, int C, float* queue, int L, int32_t* qstate, void* stream) {
+    if (P < 1 || C < 4 || C % 4 || L < 1 || L % P) return FACL_E_SHAPE;
+    if (!rows || !queue || !qstate) return FACL_E_NULL;
+    if (((uintptr_t)rows | (uintptr_t)queue) & 15) return FACL_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const long long n4 = (long long)P * (C / 4);
+    const int grid = (int)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
+    hipLaunchKernelGGL(k_queue_push, dim3(grid), dim3(256), 0, st, (const float4*)rows, n4, P, C / 4, (float4*)queue, L,
+                       (const int*)qstate);
+    hipLaunchKernelGGL(k_queue_advance, dim3(1), dim3(64), 0, st, (int*)qstate, P, L);
     return facl_launch_status();
 }

@@ -110,6 +110,9 @@ def build_parser(default_branch):
     p.add_argument('--loss_mask', type=str, default='zero', choices=('zero', 'exclude'),
                    help='NEW: same-clip key columns of the global / circle losses: zero = multiplied by 0, they stay in the '
                         'softmax as exp(0) (the reference); exclude = taken out of the log-sum-exp (negatives only)')
+    p.add_argument('--neg_queue', type=int, default=0,
+                   help='NEW (one rank): L > 0 = the global / circle losses also see the x_global rows of the last L clips as '
+                        'negatives (a device-side ring buffer, facl_amd/neg_queue.py); a multiple of --batchSize; 0 = off')
     return p
 
 
@@ -169,6 +172,11 @@ class ContrastiveStep:
         # loss modes (utils_my.contrastive_losses_stacked); namespaces from before the flags hold the reference's loss
         self.loss_mode = dict(normalize=bool(getattr(opt, "loss_normalize", 0)),
                               temperature=float(getattr(opt, "loss_temperature", 1.0)), mask=getattr(opt, "loss_mask", "zero"))
+        # cross-batch queue of negative keys (facl_amd/neg_queue.py): created on the first step, pushed at the end of every step
+        self.neg_queue = int(getattr(opt, "neg_queue", 0))
+        self.queue = None
+        if self.neg_queue and fdist.is_distributed():
+            raise RuntimeError("the negative queue runs on one rank only")
         self.rank = torch.distributed.get_rank() if fdist.is_distributed() else 0
         self.grad_sync = fdist.GradSync(list(netR.named_parameters())) if fdist.is_distributed() else None
 
@@ -202,7 +210,10 @@ class ContrastiveStep:
             data1 = fps_sample_data(data1, self.opt.sample_num_level1,
                                     start_idx=torch.zeros(data1.shape[0], dtype=torch.int32, device=data1.device))
         xt, yt = self.group(data1)
-        return self._encode_and_step(xt, yt, B, order)
+        out = self._encode_and_step(xt, yt, B, order)
+        if self.queue is not None:
+            self.queue.push()                      # this step's x_global rows, after the backward has read the queue
+        return out
 
     def _encode_and_step(self, xt, yt, B, order):
         netR, G = self.netR, self.G
@@ -215,11 +226,15 @@ class ContrastiveStep:
         else:
             x_keys = fdist.all_gather_view_major(x, G)
         off = self.rank * B
+        if self.neg_queue and self.queue is None:
+            from .neg_queue import NegativeQueue
+            self.queue = NegativeQueue(self.neg_queue, netR._stacked.shape[1], B, netR._stacked.device)
         # global (:265-287) + circle (:290-316) losses: similarity GEMMs + one HIP kernel each (csrc/loss.hip)
         from .tail import precision as _precision
         with _precision(getattr(netR, "precision", "f32")):    # the similarity GEMMs follow the model's arithmetic
             loss_c, loss_circle, loss = contrastive_losses_stacked(G, netR._stacked, order, x_keys=None if x_keys is x else x_keys,
-                                                                   clip_offset=off, with_sum=True, **self.loss_mode)
+                                                                   clip_offset=off, with_sum=True, **self.loss_mode,
+                                                                   **({} if self.queue is None else {"queue": self.queue}))
         # loss = loss_circle + loss_c (:329; swa, CLD terms are 0 ...): the fp32 sum comes out of the loss launch itself
         if self.swa_if:                                                            # ... unless switched on: :239-263
             from . import swav_cld
@@ -309,10 +324,14 @@ class GraphedStep:
             sd = step.optimizer.state_dict()
             opt = {"state": {i: {k: v.clone() for k, v in st.items()} for i, st in sd["state"].items()},
                    "param_groups": sd["param_groups"]}
-        return net, opt, [(m, m.steps) for m in self._bn_modules()]
+        queue = getattr(step, "queue", None)             # a step class without the attribute (dense.DenseStep) has no queue
+        queue = None if queue is None else queue.snapshot()              # None: no step has run yet, the queue is empty
+        return net, opt, [(m, m.steps) for m in self._bn_modules()], queue
 
     def _restore(self, snap):
-        net, opt, steps = snap
+        net, opt, steps, queue = snap
+        if getattr(self.step, "queue", None) is not None:                # the warm-up steps are real steps: their rows leave the queue again
+            self.step.queue.restore(queue)
         with torch.no_grad():                            # in place: a captured graph holds the addresses of these tensors
             cur = self.step.netR.state_dict()
             for k, v in net.items():
@@ -483,6 +502,22 @@ def check_knn_flags(opt, world=None):
         raise RuntimeError("--knn_T must be positive (got %r)" % opt.knn_T)
 
 
+def check_queue_flags(opt, world=None):
+    """--neg_queue L: L >= 0, a multiple of --batchSize (a push of one batch never wraps inside itself), one rank (a gathered
+    push would add a collective to the step).  Raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    if opt.neg_queue < 0:
+        raise RuntimeError("--neg_queue must be >= 0 (got %d)" % opt.neg_queue)
+    if not opt.neg_queue:
+        return
+    if opt.neg_queue % opt.batchSize:
+        raise RuntimeError("--neg_queue %d must be a multiple of --batchSize %d: every step stores one row per clip, and a "
+                           "push must not wrap inside itself" % (opt.neg_queue, opt.batchSize))
+    world = fdist.env_world_size() if world is None else world
+    if world > 1:
+        raise RuntimeError("--neg_queue %d runs on one rank only (got %d ranks): the gathered queue is not implemented"
+                           % (opt.neg_queue, world))
+
+
 def check_loss_flags(opt, world=None):
     """--loss_temperature finite and positive; --loss_mask exclude needs a negative, i.e. batch x world >= 2 key clips.  Raises
     before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
@@ -649,6 +684,7 @@ def run(default_branch, ckpt_pattern, args=None):
     check_view_flags(opt)
     check_knn_flags(opt)
     check_loss_flags(opt)
+    check_queue_flags(opt)
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)

@@ -146,12 +146,19 @@ def _masked_sim(anchors, keys, anchor_clip, key_clip, mask="zero"):
     return torch.where(same, torch.full((), fill, dtype=sim.dtype, device=sim.device), sim)
 
 
+def _queue_sim(anchors, queue):
+    """anchors @ queue^T for the valid rows of a negative queue (stored as they are: never mapped again); None without rows."""
+    if queue is None or queue.shape[0] == 0:
+        return None
+    return anchors @ queue.to(device=anchors.device, dtype=anchors.dtype).t()
+
+
 def _clip_ids(G, B, device, offset=0):
     return (torch.arange(B, device=device) + offset).repeat(G)     # row g*B+b -> clip id b
 
 
 def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, clip_offset=0, normalize=False, temperature=1.0,
-                    mask='zero'):
+                    mask='zero', queue=None):
     """utils_my.py:53-83.  loss_c = sum_g CE([<xg_n, x_{gB+n}> | (xg @ x^T)*mask], 0), CE = mean over B.
     The (G,B,1+GB) logits tensor and its ``repeat`` are never built: every g shares the negatives, so
     CE_g[n] = logaddexp(pos[g,n], LSE_n) - pos[g,n].
@@ -160,7 +167,10 @@ def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, cli
     ``clip_offset`` = rank*B_local; anchors stay local (mean over local B, gradients averaged by DDP).
 
     ``normalize`` / ``temperature`` / ``mask``: the loss modes above.  The rows of x_global, x and x_keys (the gathered RAW
-    embeddings: normalising a row commutes with gathering it) are mapped first; the rest is unchanged."""
+    embeddings: normalising a row commutes with gathering it) are mapped first; the rest is unchanged.
+
+    ``queue``: the valid rows (Q, C) of a negative queue (facl_amd/neg_queue.py), extra negative columns <xg_n, q_k> of every
+    clip.  They carry no clip identity (no mask touches them) and are used as stored."""
     B, G = x_global.shape[0], num_crop
     check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     x_global, x = _loss_rows_torch(x_global, normalize, temperature), _loss_rows_torch(x, normalize, temperature)
@@ -168,15 +178,19 @@ def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, cli
     Bk = keys.shape[0] // G
     a_clip = torch.arange(B, device=x.device) + clip_offset
     neg = _masked_sim(x_global, keys, a_clip, _clip_ids(G, Bk, x.device), mask)      # (B, G*Bk)
+    neg_q = _queue_sim(x_global, queue)
+    if neg_q is not None:
+        neg = torch.cat((neg, neg_q), dim=1)
     lse = torch.logsumexp(neg, dim=1)
     pos = (x_global.unsqueeze(0) * x.view(G, B, -1)).sum(-1)                   # (G,B)
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
 
 def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=None, clip_offset=0, normalize=False,
-                    temperature=1.0, mask='zero'):
+                    temperature=1.0, mask='zero', queue=None):
     """utils_my.py:85-116.  ``order`` replaces the reference's np.random.shuffle(arange(num_crop)) (:96-97);
-    when omitted it is drawn from NumPy's global RNG like the reference.  Loss modes: as in global_contrast."""
+    when omitted it is drawn from NumPy's global RNG like the reference.  Loss modes and ``queue``: as in global_contrast
+    (the shared negative set of a clip becomes the (G-1) x (J + Q) block)."""
     G, B = num_crop, batchSize
     check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     if order is None:
@@ -192,6 +206,9 @@ def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=N
     a_clip = (torch.arange(B, device=x.device) + clip_offset).repeat(G - 1)
     neg = _masked_sim(anchors.reshape((G - 1) * B, -1), keys, a_clip, _clip_ids(G, Bk, x.device), mask)
     neg = neg.view(G - 1, B, G * Bk).permute(1, 0, 2).reshape(B, -1)           # all anchors' negatives, shared (:105-109)
+    neg_q = _queue_sim(anchors.reshape((G - 1) * B, -1), queue)
+    if neg_q is not None:
+        neg = torch.cat((neg, neg_q.view(G - 1, B, -1).permute(1, 0, 2).reshape(B, -1)), dim=1)
     lse = torch.logsumexp(neg, dim=1)
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
@@ -264,10 +281,14 @@ class _ContrastivePair(torch.autograd.Function):
     sim = stacked @ keys^T on the hand-written MFMA GEMM, ONE loss launch (facl_contrast_pair: both values and
     d/dsim, the circle anchors addressed through ``order`` instead of gathered), and in the backward one dgrad
     (d stacked = dsim @ keys) plus one wgrad (d keys = dsim^T @ stacked).  No library GEMM, no anchors gather, no
-    positive-column index tensors, no index_add (utils_my.py:63-71,100-103 and their autograd)."""
+    positive-column index tensors, no index_add (utils_my.py:63-71,100-103 and their autograd).
+
+    ``queue`` (a facl_amd.neg_queue.NegativeQueue): a second similarity GEMM sim_q = stacked @ queue^T, the loss launch is
+    facl_contrast_pair_queue (the valid queue rows are extra negatives, read on the device), and the backward adds
+    dsim_q @ queue to d stacked.  The queue itself gets no gradient and is not written here."""
 
     @staticmethod
-    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0):
+    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0, queue=None):
         from . import tail as _tail
         from .sa_mlp import _Workspace
         lib = _lib.load_library()
@@ -288,10 +309,25 @@ class _ContrastivePair(torch.autograd.Function):
         out = _lib.empty(2, dtype=torch.float64, device=dev)
         # [loss_c, loss_circle, loss_circle + loss_c] in fp32 from the loss launch's own finishing kernel (no cast / add launches)
         out32 = _lib.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.facl_contrast_pair_sum_mask(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, mask_mode,
-                                                   _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
-                   "facl_contrast_pair_sum_mask")
-        ctx.save_for_backward(stacked, keys, dsim)
+        ctx.queue = queue is not None
+        if queue is None:
+            _lib.check(lib.facl_contrast_pair_sum_mask(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, mask_mode,
+                                                       _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
+                       "facl_contrast_pair_sum_mask")
+            ctx.save_for_backward(stacked, keys, dsim)
+        else:
+            if queue.C != C or queue.buf.device != dev:
+                raise ValueError("the negative queue holds rows of %d floats on %s; the embeddings have %d on %s"
+                                 % (queue.C, queue.buf.device, C, dev))
+            L = queue.L
+            ctx.mfma_q = (L % 4 == 0 and C % 4 == 0)
+            sim_q = _tail.gemm_fwd(stacked, queue.buf, None, prec=ctx.prec)[0] if ctx.mfma_q else stacked @ queue.buf.t()
+            dsim_q = _lib.empty_like(sim_q)
+            _lib.check(lib.facl_contrast_pair_queue(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order), clip_offset,
+                                                    mask_mode, _lib.ptr(queue.state), _lib.ptr(dsim), _lib.ptr(dsim_q),
+                                                    _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
+                       "facl_contrast_pair_queue")
+            ctx.save_for_backward(stacked, keys, dsim, dsim_q, queue.buf)
         ctx.GB = G * B
         ctx.set_materialize_grads(False)           # an unused loss output arrives as None, not as a freshly filled zero tensor
         return out32[0], out32[1], out32[2]
@@ -300,7 +336,7 @@ class _ContrastivePair(torch.autograd.Function):
     def backward(ctx, g_c, g_o, g_s):
         from . import tail as _tail
         bp = _tail.backward_precision(ctx.prec)
-        stacked, keys, dsim = ctx.saved_tensors
+        stacked, keys, dsim = ctx.saved_tensors[:3]
         # upstream gradients of (loss_c, loss_circle, their sum): the training step only uses the sum (no launch here); any
         # other combination is tensor algebra on device scalars
         def tot(g):
@@ -310,7 +346,7 @@ class _ContrastivePair(torch.autograd.Function):
             return g if g_s is None else g + g_s.float()
         g_c, g_o = tot(g_c), tot(g_o)
         if g_c is None and g_o is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         zero = None
         if g_c is None or g_o is None:
             zero = torch.zeros((), dtype=torch.float32, device=dsim.device)
@@ -323,6 +359,12 @@ class _ContrastivePair(torch.autograd.Function):
         _lib.check(lib.facl_scale_rows2(_lib.ptr(dsim), _lib.ptr(ds), ctx.GB, R, J, _lib.ptr(g_o), _lib.ptr(g_c), _lib.stream()),
                    "facl_scale_rows2")
         d_stacked = _tail.gemm_dgrad(ds, keys, prec=bp) if ctx.mfma else ds @ keys
+        if ctx.queue:                              # the queue's columns: d stacked += dsim_q @ queue (the queue gets no gradient)
+            dsim_q, qbuf = ctx.saved_tensors[3:]
+            dq = _lib.empty_like(dsim_q)
+            _lib.check(lib.facl_scale_rows2(_lib.ptr(dsim_q), _lib.ptr(dq), ctx.GB, R, dsim_q.shape[1], _lib.ptr(g_o), _lib.ptr(g_c),
+                                            _lib.stream()), "facl_scale_rows2")
+            d_stacked += _tail.gemm_dgrad(dq, qbuf, prec=bp) if ctx.mfma_q else dq @ qbuf
         if ctx.own_keys and ctx.mfma:
             # d keys = dsim^T @ stacked accumulated straight into the view rows of d stacked (the keys ARE those rows)
             M_, N_, K_ = ds.shape[0], ds.shape[1], stacked.shape[1]
@@ -331,14 +373,14 @@ class _ContrastivePair(torch.autograd.Function):
                 rc = lib.facl_gemm_wgrad_acc(_lib.ptr(ds), _lib.ptr(stacked), M_, N_, K_, stacked.stride(0), _lib.ptr(d_stacked), pc,
                                              _lib.stream())
             if rc == 0:
-                return d_stacked, None, None, None, None, None
+                return d_stacked, None, None, None, None, None, None
             if rc != -4:
                 _lib.check(rc, "facl_gemm_wgrad_acc")
         d_keys = _tail.gemm_wgrad(ds, stacked, prec=bp) if ctx.mfma else ds.t() @ stacked
         if ctx.own_keys:
             d_stacked[:ctx.GB] += d_keys
             d_keys = None
-        return d_stacked, d_keys, None, None, None, None
+        return d_stacked, d_keys, None, None, None, None, None
 
 
 class _LossRows(torch.autograd.Function):
@@ -389,14 +431,18 @@ def _check_order(order, G):
 
 
 def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offset=0, with_sum=False, normalize=False,
-                               temperature=1.0, mask='zero'):
+                               temperature=1.0, mask='zero', queue=None):
     """(loss_c, loss_circle) from the model's stacked output [x ; x_global] (facl_amd.cn3d_model_conbag: ``_stacked``);
     with_sum: also `loss_circle + loss_c` (fp32, cn3d_train_motion_GL.py:329) as a third output of the same launch.
 
     ``normalize`` / ``temperature`` / ``mask``: the loss modes (see global_contrast).  At the defaults nothing but today's
     launches runs.  Otherwise one row pass n = loss_rows(stacked) runs in front and the loss sees n.  ``x_keys`` is the
     gathered RAW view-major embeddings (they take the row pass too), or -- what the data-parallel step uses, a row pass over
-    the local rows only -- a callable that maps this rank's view rows n[:G*B] to the gathered keys."""
+    the local rows only -- a callable that maps this rank's view rows n[:G*B] to the gathered keys.
+
+    ``queue``: a facl_amd.neg_queue.NegativeQueue whose valid rows are extra negatives of every clip (see _ContrastivePair).
+    The step's own key rows for it, n[G*B:] (x_global after the row map, detached), are staged on the queue; the caller
+    pushes them (``queue.push()``) after the backward.  None: today's launches, nothing else."""
     G = num_crop
     GB = G * (stacked.shape[0] // (G + 1))
     if is_default_loss_mode(normalize, temperature, mask):
@@ -416,7 +462,11 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
     if not (torch.is_tensor(order) and order.device == stacked.device and order.dtype == torch.long):
         _check_order(order, G)
         order = torch.as_tensor(order, device=stacked.device, dtype=torch.long)
-    out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode)
+    if queue is None:
+        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode)
+    else:
+        queue.stage(stacked.detach()[GB:])
+        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, queue)
     return out if with_sum else out[:2]
 
 

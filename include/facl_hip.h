@@ -457,6 +457,23 @@ int facl_contrast_pair_sum_mask(const float* sim, int G, int B, int Bk, int J, c
 int facl_loss_rows_fwd(const float* x, int64_t R, int C, int normalize, float s, float* n, float* inv_norm, void* stream);
 int facl_loss_rows_bwd(const float* dn, const float* n, const float* inv_norm, int64_t R, int C, int normalize, float s,
                        float* dx, void* stream);
+/* facl_contrast_pair_sum_mask with a queue of negative keys from earlier steps.  sim_q ((G+1)*B, L) = [x ; x_global] @
+ * queue^T; qstate = {head, valid} (two int32 ON THE DEVICE, read by the kernels: a captured step replays correctly while the
+ * queue fills).  The first `valid` columns of sim_q are extra negative columns of every clip in both losses; they carry no clip
+ * identity, so neither mask mode touches them.  Columns >= valid are never used (they may hold anything, NaN included; with
+ * valid % 4 != 0 the 16-byte load that straddles `valid` fetches up to three of them and drops them) and their dsim_q is
+ * written as exactly 0; a valid outside [0, L] is clamped.  dsim_q ((G+1)*B, L) = d(loss_c + loss_circle)/d sim_q, every
+ * element written; dsim, losses, losses32 as above.  Same bits every run (no atomics).  L >= 1 and the domain of
+ * facl_contrast_pair_sum_mask, else FACL_E_SHAPE; also when (G+1)*B*(ceil(J/2048) + ceil(L/2048)) chunk partials (12 bytes
+ * each) do not fit the workspace. */
+int facl_contrast_pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order,
+                             int clip_offset, int mask_mode, const int32_t* qstate, float* dsim, float* dsim_q, double* losses,
+                             float* losses32, void* ws, void* stream);
+/* Ring buffer of the queue: copies rows (P,C) into the slots [head, head+P) of queue (L,C) and then, in a second launch in
+ * stream order, sets head = (head + P) % L and valid = min(valid + P, L) in qstate (device int32[2]).  L % P == 0, so a push
+ * never wraps inside itself; head is clamped to a multiple of P below L and valid to [0, L] before use.  C % 4 == 0, L % P == 0,
+ * else FACL_E_SHAPE (checked first); a NULL pointer: FACL_E_NULL; rows / queue 16-byte aligned, else FACL_E_ALIGN. */
+int facl_queue_push(const float* rows, int P, int C, float* queue, int L, int32_t* qstate, void* stream);
 /* dst (R,J) = src scaled by *g1 in rows [0,R1) and by *g2 in rows [R1,R): the two upstream gradients (device scalars)
  * of loss_circle / loss_c applied to the shared d/dsim matrix. */
 int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_t R, int J, const float* g1, const float* g2,

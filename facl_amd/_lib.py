@@ -127,6 +127,7 @@ SIGNATURES = {
     "facl_loss_rows_bwd": [c_p, c_p, c_p, c_l, c_i, c_i, c_f, c_p, c_p],
     "facl_contrast_pair_queue": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_queue_push": [c_p, c_i, c_i, c_p, c_i, c_p, c_p],
+    "facl_ema_apply": [c_i, c_p, c_p, c_p, c_f, c_p],
     "facl_mailbox_bytes": [c_i, c_i],
     "facl_mailbox_alloc": [c_l, c_p, c_p],
     "facl_mailbox_open": [c_p, c_p],

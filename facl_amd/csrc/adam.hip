@@ -5,6 +5,9 @@
 // coherent; a HIP graph bakes them at capture time, when the gradient buffers of the captured step are fixed).
 //   facl_adam_prep: step += 1; consts = (lr / (1 - b1^t), 1 / sqrt(1 - b2^t))      -- one thread, device-resident lr / step
 //   facl_adam_apply: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= step_size * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+// and the momentum average of the key encoder that follows it in the step (facl_amd/key_encoder.py; MoCo's
+// _momentum_update_key_encoder: param_k = param_k * m + param_q * (1 - m), parameters only), same table, same chunks:
+//   facl_ema_apply: pk = m pk + (1-m) p
 #include "common.h"
 #include <math.h>
 #include <stdint.h>
@@ -19,6 +22,14 @@ struct FaclAdamTable {
     float* v[FACL_ADAM_MAX_TENSORS];
     int n[FACL_ADAM_MAX_TENSORS];
     int chunk0[FACL_ADAM_MAX_TENSORS + 1];        // first chunk of tensor i (prefix sums of ceil(n / CHUNK))
+    int nt;
+};
+
+struct FaclEmaTable {
+    float* pk[FACL_ADAM_MAX_TENSORS];
+    const float* p[FACL_ADAM_MAX_TENSORS];
+    int n[FACL_ADAM_MAX_TENSORS];
+    int chunk0[FACL_ADAM_MAX_TENSORS + 1];
     int nt;
 };
 
@@ -95,6 +106,46 @@ __global__ __launch_bounds__(256) void k_adam_apply(FaclAdamTable tb, const floa
     }
 }
 
+// pk = m pk + (1-m) p.  Three roundings and the one of 1 - m (the build has -ffp-contract=off); m = 0 copies p and m = 1 leaves pk
+// as it is through the formula itself: 0 * finite = 0, x + 0 = x.
+__global__ __launch_bounds__(256) void k_ema_apply(FaclEmaTable tb, float m) {
+    int lo = 0, hi = tb.nt;
+    const int c = blockIdx.x;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tb.chunk0[mid] <= c) lo = mid; else hi = mid;
+    }
+    const int t = lo, base = (c - tb.chunk0[t]) * FACL_ADAM_CHUNK;
+    const int n = tb.n[t];
+    float* __restrict__ pk = tb.pk[t];
+    const float* __restrict__ p = tb.p[t];
+    const float om = 1.f - m;
+    if (!(n & 3) && !((((uintptr_t)pk) | ((uintptr_t)p)) & 15)) {
+        float4 k4[2], p4[2];
+        int i4[2];
+        const int n4 = n >> 2;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            i4[k] = (base >> 2) + k * 256 + threadIdx.x;
+            if (i4[k] < n4) {
+                k4[k] = reinterpret_cast<const float4*>(pk)[i4[k]]; p4[k] = reinterpret_cast<const float4*>(p)[i4[k]];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            if (i4[k] >= n4) continue;
+            reinterpret_cast<float4*>(pk)[i4[k]] = make_float4(m * k4[k].x + om * p4[k].x, m * k4[k].y + om * p4[k].y,
+                                                               m * k4[k].z + om * p4[k].z, m * k4[k].w + om * p4[k].w);
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < FACL_ADAM_CHUNK / 256; ++k) {
+        const int i = base + k * 256 + threadIdx.x;
+        if (i < n) pk[i] = m * pk[i] + om * p[i];
+    }
+}
+
 }  // namespace
 
 extern "C" int facl_adam_prep(const float* lr, float* step, float b1, float b2, float* consts, void* stream) {
@@ -120,5 +171,25 @@ extern "C" int facl_adam_apply(int nt, float* const* p, const float* const* g, f
     tb.chunk0[nt] = chunks;
     tb.nt = nt;
     hipLaunchKernelGGL(k_adam_apply, dim3(chunks), dim3(256), 0, (hipStream_t)stream, tb, consts, b1, b2, eps);
+    return facl_launch_status();
+}
+
+// pk / p: HOST arrays of nt device pointers (the averaged copy, the trained parameter); n: HOST array of element counts
+extern "C" int facl_ema_apply(int nt, float* const* pk, const float* const* p, const int* n, float m, void* stream) {
+    if (!pk || !p || !n) return FACL_E_NULL;
+    if (nt < 1 || nt > FACL_ADAM_MAX_TENSORS) return FACL_E_SHAPE;
+    if (!(m >= 0.f && m <= 1.f)) return FACL_E_SHAPE;            // NaN included
+    FaclEmaTable tb;
+    int chunks = 0;
+    for (int i = 0; i < nt; ++i) {
+        if (!pk[i] || !p[i]) return FACL_E_NULL;
+        if (n[i] < 1) return FACL_E_SHAPE;
+        tb.pk[i] = pk[i]; tb.p[i] = p[i]; tb.n[i] = n[i];
+        tb.chunk0[i] = chunks;
+        chunks += (n[i] + FACL_ADAM_CHUNK - 1) / FACL_ADAM_CHUNK;
+    }
+    tb.chunk0[nt] = chunks;
+    tb.nt = nt;
+    hipLaunchKernelGGL(k_ema_apply, dim3(chunks), dim3(256), 0, (hipStream_t)stream, tb, m);
     return facl_launch_status();
 }

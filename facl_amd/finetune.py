@@ -127,6 +127,8 @@ def check_finetune_flags(opt, world=None):
                            "cross-entropy only")
     if opt.neg_queue:
         raise RuntimeError("--neg_queue holds negatives of the contrastive loss: fine-tuning has the cross-entropy only")
+    if opt.key_encoder:
+        raise RuntimeError("--key_encoder fills the negative queue of the contrastive loss: fine-tuning has the cross-entropy only")
     if not opt.num_class:
         opt.num_class = 60 if opt.dataset == 'ntu60' else 120
     if not 2 <= opt.num_class <= 1024 or opt.num_class % 4:

@@ -113,6 +113,12 @@ def build_parser(default_branch):
     p.add_argument('--neg_queue', type=int, default=0,
                    help='NEW (one rank): L > 0 = the global / circle losses also see the x_global rows of the last L clips as '
                         'negatives (a device-side ring buffer, facl_amd/neg_queue.py); a multiple of --batchSize; 0 = off')
+    p.add_argument('--key_encoder', type=int, default=0, choices=(0, 1),
+                   help='NEW (--neg_queue L > 0): 1 = the rows stored in the queue come from a momentum-averaged copy of the '
+                        'encoder (facl_amd/key_encoder.py), saved beside every checkpoint as <name>_key.pth; 0 = from the '
+                        'trained encoder')
+    p.add_argument('--key_momentum', type=float, default=0.999,
+                   help='NEW (--key_encoder 1): m of key <- m key + (1 - m) model after every optimizer step, 0 <= m < 1')
     return p
 
 
@@ -177,6 +183,11 @@ class ContrastiveStep:
         self.queue = None
         if self.neg_queue and fdist.is_distributed():
             raise RuntimeError("the negative queue runs on one rank only")
+        # momentum key encoder (facl_amd/key_encoder.py): created on the first step; its rows are the ones the queue stores
+        self.key_momentum = float(getattr(opt, "key_momentum", 0.999)) if int(getattr(opt, "key_encoder", 0)) else None
+        self.key_encoder = None
+        if self.key_momentum is not None and not self.neg_queue:
+            raise RuntimeError("the key encoder supplies the rows of the negative queue: it needs neg_queue > 0")
         self.rank = torch.distributed.get_rank() if fdist.is_distributed() else 0
         self.grad_sync = fdist.GradSync(list(netR.named_parameters())) if fdist.is_distributed() else None
 
@@ -211,6 +222,8 @@ class ContrastiveStep:
                                     start_idx=torch.zeros(data1.shape[0], dtype=torch.int32, device=data1.device))
         xt, yt = self.group(data1)
         out = self._encode_and_step(xt, yt, B, order)
+        if self.key_encoder is not None:
+            self.key_encoder.update()              # after Adam: the average MoCo takes at the start of the next step
         if self.queue is not None:
             self.queue.push()                      # this step's x_global rows, after the backward has read the queue
         return out
@@ -219,6 +232,14 @@ class ContrastiveStep:
         netR, G = self.netR, self.G
         # x_nor / code feed the SwAV / CLD terms only: without them F.normalize + mapping run beside the loss block
         netR.lazy_code = not (self.swa_if or self.cld_if) and not fdist.is_distributed()
+        # The key forward runs BEFORE the query forward: the passes share the stream's scratch workspace, and the query forward
+        # leaves there (and in what autograd saved) what its backward reads -- nothing may run between the two
+        key_rows = None
+        if self.key_momentum is not None:
+            if self.key_encoder is None:
+                from .key_encoder import KeyEncoder
+                self.key_encoder = KeyEncoder(netR, self.key_momentum)
+            key_rows = self.key_encoder.rows(xt, yt)
         x, code, x_nor, x_global = netR(xt, yt, 1)                                 # :234
         if fdist.is_distributed() and not is_default_loss_mode(**self.loss_mode):
             # the loss modes map the rows first: this rank's view rows are normalised / scaled locally, THEN gathered
@@ -234,7 +255,8 @@ class ContrastiveStep:
         with _precision(getattr(netR, "precision", "f32")):    # the similarity GEMMs follow the model's arithmetic
             loss_c, loss_circle, loss = contrastive_losses_stacked(G, netR._stacked, order, x_keys=None if x_keys is x else x_keys,
                                                                    clip_offset=off, with_sum=True, **self.loss_mode,
-                                                                   **({} if self.queue is None else {"queue": self.queue}))
+                                                                   **({} if self.queue is None else {"queue": self.queue}),
+                                                                   **({} if key_rows is None else {"queue_rows": key_rows}))
         # loss = loss_circle + loss_c (:329; swa, CLD terms are 0 ...): the fp32 sum comes out of the loss launch itself
         if self.swa_if:                                                            # ... unless switched on: :239-263
             from . import swav_cld
@@ -326,10 +348,12 @@ class GraphedStep:
                    "param_groups": sd["param_groups"]}
         queue = getattr(step, "queue", None)             # a step class without the attribute (dense.DenseStep) has no queue
         queue = None if queue is None else queue.snapshot()              # None: no step has run yet, the queue is empty
-        return net, opt, [(m, m.steps) for m in self._bn_modules()], queue
+        key = getattr(step, "key_encoder", None)         # likewise; None: no step has run yet, the copy would equal the model
+        key = None if key is None else key.snapshot()
+        return net, opt, [(m, m.steps) for m in self._bn_modules(False)], queue, key
 
     def _restore(self, snap):
-        net, opt, steps, queue = snap
+        net, opt, steps, queue, key = snap
         if getattr(self.step, "queue", None) is not None:                # the warm-up steps are real steps: their rows leave the queue again
             self.step.queue.restore(queue)
         with torch.no_grad():                            # in place: a captured graph holds the addresses of these tensors
@@ -340,6 +364,8 @@ class GraphedStep:
             m.steps = n
         if opt is not None:
             self.step.optimizer.load_state_dict(opt)
+        if getattr(self.step, "key_encoder", None) is not None:          # after the model: None takes the restored model's state
+            self.step.key_encoder.restore(key)
 
     def _capture(self, distributed, dev):
         step = self.step
@@ -419,8 +445,13 @@ class GraphedStep:
             raise GraphCaptureFailed("replayed graph segments do not reproduce the eager step (this rank: eager loss %r, "
                                      "replayed %r)" % (loss_e, loss_g))
 
-    def _bn_modules(self):
-        return [m for m in self.step.netR.modules() if hasattr(m, "count_batch")]
+    def _encoders(self, with_key=True):
+        key = getattr(self.step, "key_encoder", None) if with_key else None
+        return [self.step.netR] + ([] if key is None else [key.key])
+
+    def _bn_modules(self, with_key=True):
+        """The host-side BatchNorm counters a replay has to advance: the model's and, once it exists, the key encoder's."""
+        return [m for net in self._encoders(with_key) for m in net.modules() if hasattr(m, "count_batch")]
 
     def __call__(self, out_points, epoch=0, order=None):
         if order is None:
@@ -438,7 +469,8 @@ class GraphedStep:
             self.graph.replay()
         for m in self._bn_modules():                     # host-side num_batches_tracked (netR_FC.1 counts twice)
             m.count_batch()
-        self.step.netR.netR_FC[1].count_batch()
+        for net in self._encoders():
+            net.netR_FC[1].count_batch()
         return self.out
 
 
@@ -516,6 +548,27 @@ def check_queue_flags(opt, world=None):
     if world > 1:
         raise RuntimeError("--neg_queue %d runs on one rank only (got %d ranks): the gathered queue is not implemented"
                            % (opt.neg_queue, world))
+
+
+def check_key_flags(opt, world=None):
+    """--key_encoder 1 needs a queue to fill (--neg_queue L > 0), 0 <= --key_momentum < 1 and one rank (the queue's own limit).
+    Raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    if not opt.key_encoder:
+        return
+    if not opt.neg_queue:
+        raise RuntimeError("--key_encoder 1 supplies the rows of the negative queue: without --neg_queue L > 0 nothing would "
+                           "read its keys")
+    if not 0.0 <= opt.key_momentum < 1.0:                    # NaN fails both comparisons
+        raise RuntimeError("--key_momentum must be in [0, 1) (got %r): at 1 the key encoder would never move" % opt.key_momentum)
+    world = fdist.env_world_size() if world is None else world
+    if world > 1:
+        raise RuntimeError("--key_encoder 1 runs on one rank only (got %d ranks), like the queue it fills" % world)
+
+
+def key_checkpoint_name(path):
+    """<name>_key.pth beside the query checkpoint <name>.pth."""
+    stem, ext = os.path.splitext(path)
+    return stem + "_key" + ext
 
 
 def check_loss_flags(opt, world=None):
@@ -657,6 +710,8 @@ def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, aft
     run_step = step
     for epoch in range(0, opt.nepoch):
         step.netR.train()
+        if getattr(step, "key_encoder", None) is not None:
+            step.key_encoder.key.train()                 # MoCo's convention: the key copy normalises with batch statistics too
         for g in step.optimizer.param_groups:
             g["lr"] = lr_for_epoch(opt.learning_rate, epoch, lr_step)
         loss_sigma, t0 = 0.0, time.time()
@@ -685,6 +740,7 @@ def run(default_branch, ckpt_pattern, args=None):
     check_knn_flags(opt)
     check_loss_flags(opt)
     check_queue_flags(opt)
+    check_key_flags(opt)
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)
@@ -732,7 +788,10 @@ def run(default_branch, ckpt_pattern, args=None):
             logging.info('{} --epoch{} ==knn top1:{}'.format('Valid', epoch, top1))
             print('epoch:', epoch, 'knn top1:', top1)
         if rank == 0 and epoch % 5 == 0:
-            torch.save(netR.state_dict(), ckpt_pattern % (opt.save_root_dir, epoch))
+            path = ckpt_pattern % (opt.save_root_dir, epoch)
+            torch.save(netR.state_dict(), path)
+            if step.key_encoder is not None:                 # the model's format: extract_* / finetune --checkpoint load it
+                torch.save(step.key_encoder.state_dict(), key_checkpoint_name(path))
 
     train_epochs(opt, step, source, world, lr_step=4, next_batch=next_batch, after_epoch=after_epoch)
     return netR

@@ -431,7 +431,7 @@ def _check_order(order, G):
 
 
 def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offset=0, with_sum=False, normalize=False,
-                               temperature=1.0, mask='zero', queue=None):
+                               temperature=1.0, mask='zero', queue=None, queue_rows=None):
     """(loss_c, loss_circle) from the model's stacked output [x ; x_global] (facl_amd.cn3d_model_conbag: ``_stacked``);
     with_sum: also `loss_circle + loss_c` (fp32, cn3d_train_motion_GL.py:329) as a third output of the same launch.
 
@@ -442,9 +442,19 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
 
     ``queue``: a facl_amd.neg_queue.NegativeQueue whose valid rows are extra negatives of every clip (see _ContrastivePair).
     The step's own key rows for it, n[G*B:] (x_global after the row map, detached), are staged on the queue; the caller
-    pushes them (``queue.push()``) after the backward.  None: today's launches, nothing else."""
+    pushes them (``queue.push()``) after the backward.  None: today's launches, nothing else.
+
+    ``queue_rows``: raw (B, C) rows to stage instead -- the x_global rows of a key encoder (facl_amd/key_encoder.py).  They take
+    the same row map, in a launch of their own; the loss does not read them.  None: the step's own rows, as above."""
     G = num_crop
     GB = G * (stacked.shape[0] // (G + 1))
+    if queue_rows is not None:
+        if queue is None:
+            raise ValueError("queue_rows are rows for a negative queue: pass queue= as well")
+        if queue_rows.dim() != 2 or queue_rows.shape != (stacked.shape[0] - GB, stacked.shape[1]):
+            raise ValueError("queue_rows must be one raw row per clip, (%d, %d); got %s"
+                             % (stacked.shape[0] - GB, stacked.shape[1], tuple(queue_rows.shape)))
+        queue_rows = queue_rows.detach()
     if is_default_loss_mode(normalize, temperature, mask):
         mask_mode = 0
         if callable(x_keys):
@@ -454,6 +464,8 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
         s, mask_mode = check_loss_mode(temperature, mask, None if callable(x_keys) else key_rows // G)
         if normalize or s != 1.0:
             stacked = _LossRows.apply(stacked, bool(normalize), s)
+            if queue_rows is not None:
+                queue_rows = _LossRows.apply(queue_rows, bool(normalize), s)
             if x_keys is not None and not callable(x_keys):
                 x_keys = _LossRows.apply(x_keys, bool(normalize), s)
         if callable(x_keys):
@@ -465,7 +477,7 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
     if queue is None:
         out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode)
     else:
-        queue.stage(stacked.detach()[GB:])
+        queue.stage(stacked.detach()[GB:] if queue_rows is None else queue_rows)
         out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, queue)
     return out if with_sum else out[:2]
 

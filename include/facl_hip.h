@@ -511,6 +511,15 @@ int facl_mailbox_allreduce(const double* in, double* out, int n, int n_max, void
 int facl_adam_prep(const float* lr, float* step, float b1, float b2, float* consts, void* stream);
 int facl_adam_apply(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const int* n,
                     const float* consts, float b1, float b2, float eps, void* stream);
+/* Momentum average of the key encoder (facl_amd/key_encoder.py; MoCo's param_k = param_k * m + param_q * (1 - m)):
+ * pk[i][j] = m * pk[i][j] + (1 - m) * p[i][j] in fp32 (three roundings and the one of 1 - m) for ALL tensors in one launch.
+ * pk / p are HOST arrays of nt <= 64 device pointers (the averaged copy, the trained parameter), n their element counts; the
+ * pointers travel by value in the kernel arguments, as in facl_adam_apply, and a captured graph bakes them.  16 bytes per lane
+ * where n[i] % 4 == 0 and both pointers are 16-byte aligned, else a scalar walk; nothing outside [0, n[i]) is touched and p is
+ * only read.  m is a launch constant.  On finite data m == 0 copies p and m == 1 leaves pk as it is, through the formula.
+ * A NULL array or entry: FACL_E_NULL; nt outside 1..64, an n[i] < 1 or m outside [0, 1] (NaN included): FACL_E_SHAPE; every
+ * refusal comes before the launch. */
+int facl_ema_apply(int nt, float* const* pk, const float* const* p, const int* n, float m, void* stream);
 
 /* ---- optional loss terms of the training loop (switched off in the shipped loop) ----------------------
  * facl_sinkhorn: distributed_sinkhorn + shoot_infs (cn3d_model_conbag.py:391-425).  Q (R,C) = exp(scores)^T, R prototypes

@@ -119,6 +119,14 @@ def build_parser(default_branch):
                         'trained encoder')
     p.add_argument('--key_momentum', type=float, default=0.999,
                    help='NEW (--key_encoder 1): m of key <- m key + (1 - m) model after every optimizer step, 0 <= m < 1')
+    p.add_argument('--save_state_every', type=int, default=0,
+                   help='NEW (one rank): after every E-th epoch write the full training state -- model, Adam, negative queue, key '
+                        'encoder, SwAV queue, every RNG stream -- as <save_root_dir>/state_<epoch>.pth (facl_amd/train_state.py); '
+                        '0 = off')
+    p.add_argument('--keep_states', type=int, default=2, help='NEW (--save_state_every): the K newest states are kept; 0 = all')
+    p.add_argument('--resume', type=str, default='',
+                   help='NEW (one rank): a state_<epoch>.pth to continue from, bit-exactly as if the run had never stopped, or '
+                        '"auto" = the newest state under --save_root_dir (none there: the run starts from scratch)')
     return p
 
 
@@ -193,6 +201,46 @@ class ContrastiveStep:
 
     def group(self, data1):
         return group_views(data1, self.opt, self.r2)
+
+    # ---- the state the step keeps between iterations besides model and optimizer (facl_amd/train_state.py)
+    def state_dict(self):
+        """{queue: {buf, state}, key_encoder: its state_dict, swav: {queue, filled}}, each None while it does not exist.  The
+        tensors are the live ones (like FusedAdam.state_dict()'s moments): train_state.assemble copies them."""
+        queue = None if self.queue is None else {"buf": self.queue.buf, "state": self.queue.state}
+        key = None if self.key_encoder is None else self.key_encoder.state_dict()
+        sw = self.swav_state
+        swav = None if sw is None or sw.queue is None else {"queue": sw.queue, "filled": int(sw.filled)}
+        return {"queue": queue, "key_encoder": key, "swav": swav}
+
+    def load_state_dict(self, sd):
+        """Creates queue, key encoder and SwAV queue HERE, before the first batch: the step itself creates them lazily, and
+        GraphedStep(restore=True) takes a queue or key encoder that does not exist yet for "empty" / "equal to the model" and
+        restores exactly that after its warm-up steps."""
+        device = next(self.netR.parameters()).device
+        B = self.opt.batchSize
+        if sd["queue"] is not None:
+            from .neg_queue import NegativeQueue
+            buf = sd["queue"]["buf"]
+            if buf.dim() != 2 or buf.shape[0] != self.neg_queue:
+                raise RuntimeError("the saved queue holds %s rows, this step --neg_queue %d" % (tuple(buf.shape)[:1], self.neg_queue))
+            self.queue = NegativeQueue(buf.shape[0], buf.shape[1], B, device)
+            self.queue.restore((buf.to(device), sd["queue"]["state"].to(device)))
+        if sd["key_encoder"] is not None:
+            if self.key_momentum is None:
+                raise RuntimeError("the state holds a key encoder, this step runs with --key_encoder 0")
+            from .key_encoder import KeyEncoder
+            self.key_encoder = KeyEncoder(self.netR, self.key_momentum)
+            self.key_encoder.load_state_dict(sd["key_encoder"], strict=True)  # the BatchNorm `steps`: num_batches_tracked's load hook
+        if sd["swav"] is not None:
+            from . import swav_cld
+            q = sd["swav"]["queue"]
+            if self.swav_state is None:
+                self.swav_state = swav_cld.SwavState(B, self.G, q.shape[2], queue_length=q.shape[1])
+            sw = self.swav_state
+            if tuple(q.shape) != (sw.G - 1, sw.queue_length, sw.dim):
+                raise RuntimeError("the saved SwAV queue is %s, this step's %s" % (tuple(q.shape), (sw.G - 1, sw.queue_length, sw.dim)))
+            sw.queue = q.to(device).clone()
+            sw.filled = int(sd["swav"]["filled"])
 
     def __call__(self, out_points, epoch=0, order=None):
         netR, G = self.netR, self.G
@@ -565,6 +613,45 @@ def check_key_flags(opt, world=None):
         raise RuntimeError("--key_encoder 1 runs on one rank only (got %d ranks), like the queue it fills" % world)
 
 
+def check_state_flags(opt, world=None):
+    """--save_state_every E >= 0, --keep_states K >= 0; either of --save_state_every / --resume needs one rank (the per-rank
+    generators are not in a rank-0 file).  Raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    if opt.save_state_every < 0 or opt.keep_states < 0:
+        raise RuntimeError("--save_state_every and --keep_states must be >= 0 (got %d, %d)" % (opt.save_state_every, opt.keep_states))
+    world = fdist.env_world_size() if world is None else world
+    if world > 1:
+        for flag, on in (("--resume %s" % opt.resume, bool(opt.resume)),
+                         ("--save_state_every %d" % opt.save_state_every, bool(opt.save_state_every))):
+            if on:
+                raise RuntimeError("%s runs on one rank only (got %d ranks): the per-rank generators are not in a state file"
+                                   % (flag, world))
+
+
+def load_resume_state(opt):
+    """The state --resume names, on the CPU and checked against this run's options, with its path -- or (None, None) when
+    `auto` finds no state.  `auto` skips a newest state that does not load (a damaged file), with a warning, for the next older."""
+    from . import train_state
+    if not opt.resume:
+        return None, None
+    if opt.resume != "auto":
+        paths = [opt.resume]
+    else:
+        paths = [p for _, p in reversed(train_state.list_states(opt.save_root_dir))]
+        if not paths:
+            print("resume: no state under %s, starting from scratch" % opt.save_root_dir)
+            return None, None
+    for n, path in enumerate(paths):
+        try:
+            state = train_state.load_state(path)
+        except train_state.StateUnreadable as e:
+            if n + 1 == len(paths):
+                raise
+            print("warning: %s; trying %s" % (e, paths[n + 1]))
+            continue
+        train_state.check_compatible(state["flags"], opt)
+        return state, path
+
+
 def key_checkpoint_name(path):
     """<name>_key.pth beside the query checkpoint <name>.pth."""
     stem, ext = os.path.splitext(path)
@@ -702,13 +789,15 @@ def check_finite_loss(lv, epoch, i):
         raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
 
 
-def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, after_step=None):
+def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, after_step=None, start_epoch=0, end_of_epoch=None):
     """The epoch loop of the training entries under StepLR(`lr_step`, 0.7).  `source`: the TrainBatches of --synthetic 0, else
     None (--steps_per_epoch steps).  The entries differ in `next_batch(disk, epoch, i)` -> the step's input (`disk`: the epoch's
-    iterator of `source`, or None), `after_step(what the step returned)` and `after_epoch(epoch, mean_loss, clips_per_s)`."""
+    iterator of `source`, or None), `after_step(what the step returned)` and `after_epoch(epoch, mean_loss, clips_per_s)`.
+    `start_epoch`: the first epoch run (a resumed run's).  `end_of_epoch(epoch)`: called last in every epoch, when the epoch's
+    producer thread has stopped, so that the view generator's state is the one the next epoch starts from."""
     steps = opt.steps_per_epoch if source is None else source.steps
     run_step = step
-    for epoch in range(0, opt.nepoch):
+    for epoch in range(start_epoch, opt.nepoch):
         step.netR.train()
         if getattr(step, "key_encoder", None) is not None:
             step.key_encoder.key.train()                 # MoCo's convention: the key copy normalises with batch statistics too
@@ -730,6 +819,8 @@ def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, aft
         if disk is not None:
             disk.close()
         after_epoch(epoch, loss_sigma / steps, opt.batchSize * steps * world / (time.time() - t0))
+        if end_of_epoch is not None:
+            end_of_epoch(epoch)
 
 
 def run(default_branch, ckpt_pattern, args=None):
@@ -741,6 +832,10 @@ def run(default_branch, ckpt_pattern, args=None):
     check_loss_flags(opt)
     check_queue_flags(opt)
     check_key_flags(opt)
+    check_state_flags(opt)
+    from . import train_state
+    flags = train_state.flags_of(opt)                  # as given: the grouper writes the reference's literals into `opt` later
+    resumed, resumed_path = load_resume_state(opt)     # on the CPU, refused here if its options differ from this run's
     local = int(os.environ.get("LOCAL_RANK", opt.main_gpu))
     torch.cuda.set_device(local)               # before the process group: RCCL binds its communicator to the current device
     device = torch.device("cuda", local)
@@ -793,5 +888,29 @@ def run(default_branch, ckpt_pattern, args=None):
             if step.key_encoder is not None:                 # the model's format: extract_* / finetune --checkpoint load it
                 torch.save(step.key_encoder.state_dict(), key_checkpoint_name(path))
 
-    train_epochs(opt, step, source, world, lr_step=4, next_batch=next_batch, after_epoch=after_epoch)
+    steps = opt.steps_per_epoch if source is None else source.steps
+    source_rng = None if source is None else source.view_rng
+
+    def end_of_epoch(epoch):
+        if not (opt.save_state_every and rank == 0 and (epoch + 1) % opt.save_state_every == 0):
+            return
+        t_w = time.time()
+        state = train_state.assemble(epoch, (epoch + 1) * steps, flags, netR.state_dict(),
+                                     optimizer.state_dict(), step.state_dict(), train_state.capture_rng(gen, view_rng, source_rng))
+        path = train_state.state_path(opt.save_root_dir, epoch)
+        train_state.write_atomic(state, path)
+        train_state.prune(opt.save_root_dir, opt.keep_states)
+        print('state: %s, %.1f MB, %.2f s' % (path, os.path.getsize(path) / 1e6, time.time() - t_w))
+
+    start_epoch = 0
+    if resumed is not None:
+        # after setup_run has reseeded and every lazily created piece can be created eagerly (ContrastiveStep.load_state_dict)
+        netR.load_state_dict(resumed["model"], strict=True)
+        optimizer.load_state_dict(resumed["optimizer"])
+        step.load_state_dict(resumed)
+        train_state.apply_rng(resumed["rng"], gen, view_rng, source_rng)
+        start_epoch = resumed["epoch"] + 1
+        print('resumed from %s: epoch %d' % (resumed_path, start_epoch))
+    train_epochs(opt, step, source, world, lr_step=4, next_batch=next_batch, after_epoch=after_epoch,
+                 start_epoch=start_epoch, end_of_epoch=end_of_epoch)
     return netR

@@ -128,6 +128,9 @@ SIGNATURES = {
     "facl_contrast_pair_queue": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_queue_push": [c_p, c_i, c_i, c_p, c_i, c_p, c_p],
     "facl_ema_apply": [c_i, c_p, c_p, c_p, c_f, c_p],
+    "facl_grad_sqnorm": [c_i, c_p, c_p, c_p, c_p],
+    "facl_adam_prep_ex": [c_p, c_p, c_f, c_f, c_p, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_p],
+    "facl_adamw_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_p],
     "facl_mailbox_bytes": [c_i, c_i],
     "facl_mailbox_alloc": [c_l, c_p, c_p],
     "facl_mailbox_open": [c_p, c_p],

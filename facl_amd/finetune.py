@@ -17,8 +17,8 @@ from . import cn3d_model_conbag as MODELL
 from . import dist as fdist
 from .cls_head import ClipClassifier
 from .extract_common import ordered_views
-from .train_common import (ContrastiveStep, TrainBatches, build_parser, check_resident_flags, check_view_flags, eval_mode,
-                           setup_run, synthetic_batch, train_epochs)
+from .train_common import (ContrastiveStep, TrainBatches, build_parser, check_optim_flags, check_resident_flags,
+                           check_view_flags, eval_mode, optim_recipe, setup_run, synthetic_batch, train_epochs)
 
 HEAD_PREFIX = "head."
 
@@ -172,6 +172,7 @@ def main(args=None):
     check_finetune_flags(opt)
     check_resident_flags(opt)
     check_view_flags(opt)
+    check_optim_flags(opt, world=1)
     torch.cuda.set_device(opt.main_gpu)
     device = torch.device("cuda", opt.main_gpu)
     setup_run(opt)
@@ -182,11 +183,6 @@ def main(args=None):
         netR.load_encoder_state_dict(torch.load(opt.checkpoint, map_location="cpu", weights_only=True))
     netR = netR.to(device)
     netR.precision = opt.precision
-    from .optim import FusedAdam
-    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06)
-    step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder))
-    gen = torch.Generator(device=device)
-    gen.manual_seed(1000)
 
     def labelled(index, split):
         keep = split[label_subset([index.label(int(v)) for v in split], opt.label_fraction, opt.label_seed)]
@@ -196,6 +192,12 @@ def main(args=None):
     source = TrainBatches(opt, device, 0, 1, subset=labelled, too_few="the labelled subset has %(clips)d clips: fewer than "
                           "one batch of %(batch)d") if opt.synthetic == 0 else None
     steps_per_epoch = opt.steps_per_epoch if source is None else source.steps
+    from .optim import FusedAdam
+    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06,
+                          **optim_recipe(opt, steps_per_epoch))
+    step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder))
+    gen = torch.Generator(device=device)
+    gen.manual_seed(1000)
     hits, top1 = 0, None
 
     def next_batch(disk, epoch, i):
@@ -215,11 +217,11 @@ def main(args=None):
             _raise_bad_labels(bad, opt.num_class, "the train split")
         hits += h
 
-    def after_epoch(epoch, mean_loss, clips):
+    def after_epoch(epoch, mean_loss, clips, grad_norms=''):
         nonlocal hits, top1
         train_top1, hits = 100.0 * hits / (opt.batchSize * steps_per_epoch), 0
         logging.info('{} --epoch{} ==Average loss:{} train top1:{}'.format('Valid', epoch, mean_loss, train_top1))
-        print('epoch:', epoch, '--loss:', mean_loss, 'train top1:', train_top1, '| clips/s: %.1f' % clips)
+        print('epoch:', epoch, '--loss:', mean_loss, 'train top1:', train_top1, '| clips/s: %.1f%s' % (clips, grad_norms))
         if opt.synthetic == 0 and opt.eval_every and (epoch + 1) % opt.eval_every == 0:
             top1 = evaluate(netR, step, opt, device)
             logging.info('{} --epoch{} ==test top1:{}'.format('Valid', epoch, top1))

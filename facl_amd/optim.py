@@ -4,18 +4,56 @@ Same update as ``torch.optim.Adam(params, lr, betas, eps)`` with weight_decay = 
 (cn3d_train_motion_GL.py:180: lr 3e-4, betas (0.5, 0.999), eps 1e-6); the step counter and the learning rate live on
 the device, so a captured HIP graph advances its step counter by itself; learning-rate changes reach a replayed graph
 through ``sync_lr()``.  Parameters without a gradient are skipped, like torch's.  The betas reach the kernels as fp32, so
-``exp_avg_sq`` is torch's with beta2 = fp32(0.999), 1.3e-5 below torch's own; the parameter updates agree to rounding."""
+``exp_avg_sq`` is torch's with beta2 = fp32(0.999), 1.3e-5 below torch's own; the parameter updates agree to rounding.
+
+The optimizer recipe, every part off by default: ``weight_decay`` (decoupled, ``torch.optim.AdamW``'s update, on
+the tensors of ``decay_mask``), ``max_grad_norm`` (``torch.nn.utils.clip_grad_norm_`` over all gradients of the step, the stored
+gradients untouched) and a learning rate evaluated ON THE DEVICE from the step counter (``warmup_steps``, ``schedule="cosine"``
+over ``decay_steps`` down to ``lr_min``; ``lr_at_step`` is its host closed form).  With all of it off ``step()`` issues
+facl_adam_prep + facl_adam_apply as it always did; otherwise [facl_grad_sqnorm when clipping] + facl_adam_prep_ex +
+facl_adamw_apply.  The schedule is a function of the saved step counter: state_dict() needs no new entry for it."""
 import ctypes
+import math
 
 import torch
 
 from . import _lib
 
+SCHEDULES = {"step": 0, "cosine": 1}                      # include/facl_hip.h: FACL_LR_STEP, FACL_LR_COSINE
+CHUNK = 2048                                              # csrc/adam.hip: FACL_ADAM_CHUNK
+
+
+def lr_at_step(lr0, t, schedule="step", warmup_steps=0, decay_steps=0, lr_min=0.0):
+    """The learning rate facl_adam_prep_ex applies at step `t` (1-based), in the kernel's own fp64 expressions.  `lr0`: the base
+    rate -- under "step" whatever the host schedule (lr_for_epoch) supplies for that step.  The warm-up factor min(1, t / W)
+    multiplies either schedule; "cosine" runs from lr0 at t = W to lr_min at t = T and stays there.  (The device holds lr0 as
+    fp32: pass float(np.float32(lr0)) to reproduce its value to the last bit.)"""
+    if schedule not in SCHEDULES:
+        raise ValueError("schedule must be one of %s (got %r)" % (sorted(SCHEDULES), schedule))
+    t, W, T, lr0, lr_min = float(t), int(warmup_steps), int(decay_steps), float(lr0), float(lr_min)
+    warm = min(1.0, t / float(W)) if W > 0 else 1.0
+    lr = lr0
+    if schedule == "cosine":
+        if T <= W:
+            raise ValueError("cosine needs decay_steps > warmup_steps (got %d, %d)" % (T, W))
+        tp, Tp = max(t - float(W), 0.0), float(T - W)
+        lr = lr_min + (lr0 - lr_min) * 0.5 * (1.0 + math.cos(math.pi * min(tp, Tp) / Tp))
+    return warm * lr
+
 
 class FusedAdam:
     MAX_TENSORS = 64
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decay_mask=None, max_grad_norm=0.0,
+                 schedule="step", warmup_steps=0, decay_steps=0, lr_min=0.0):
+        """`decay_mask`: one bool per tensor of `params` (True: `weight_decay` applies), or None = the tensors with ndim >= 2
+        (weight matrices and convolution kernels; no bias, no BatchNorm gamma / beta).  `max_grad_norm` 0 = no clipping."""
+        params = list(params)
+        if decay_mask is None:
+            decay_mask = [p.ndim >= 2 for p in params]
+        decay_mask = [bool(d) for d in decay_mask]
+        if len(decay_mask) != len(params):
+            raise ValueError("decay_mask has %d entries for %d tensors" % (len(decay_mask), len(params)))
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -25,13 +63,35 @@ class FusedAdam:
             _lib.require_cuda(p)
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise TypeError("FusedAdam needs contiguous float32 CUDA parameters")
+        weight_decay, max_grad_norm, lr_min = float(weight_decay), float(max_grad_norm), float(lr_min)
+        warmup_steps, decay_steps = int(warmup_steps), int(decay_steps)
+        if not weight_decay >= 0.0 or math.isinf(weight_decay):                    # NaN fails the comparison
+            raise ValueError("weight_decay must be finite and >= 0 (got %r)" % weight_decay)
+        if not max_grad_norm >= 0.0:
+            raise ValueError("max_grad_norm must be >= 0, 0 = off (got %r)" % max_grad_norm)
+        if schedule not in SCHEDULES:
+            raise ValueError("schedule must be one of %s (got %r)" % (sorted(SCHEDULES), schedule))
+        if warmup_steps < 0:
+            raise ValueError("warmup_steps must be >= 0 (got %d)" % warmup_steps)
+        if not lr_min >= 0.0 or math.isinf(lr_min):
+            raise ValueError("lr_min must be finite and >= 0 (got %r)" % lr_min)
+        if schedule == "cosine" and decay_steps <= warmup_steps:
+            raise ValueError("cosine needs decay_steps > warmup_steps (got %d, %d)" % (decay_steps, warmup_steps))
         dev = self.params[0].device
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.weight_decay, self.max_grad_norm = weight_decay, max_grad_norm
+        self.schedule, self.warmup_steps, self.decay_steps, self.lr_min = schedule, warmup_steps, decay_steps, lr_min
+        self.recipe = bool(weight_decay or max_grad_norm or schedule != "step" or warmup_steps)
+        self._decay = {p: d for p, d in zip(params, decay_mask) if p.requires_grad}
         self.param_groups = [{"lr": float(lr), "betas": self.betas, "eps": self.eps, "params": self.params}]
         self._lr_host = None
         self._lr = torch.zeros(1, dtype=torch.float32, device=dev)
         self._step = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._consts = torch.zeros(2, dtype=torch.float32, device=dev)
+        # (lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t)) and, written by facl_adam_prep_ex only, (lr_t, clip coefficient, gradient norm)
+        self._consts = torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float32, device=dev)
+        self._partial = None
+        if max_grad_norm:                                     # one fp64 partial per 2048-element chunk of the parameter list
+            self._partial = torch.zeros(sum((p.numel() + CHUNK - 1) // CHUNK for p in self.params), dtype=torch.float64, device=dev)
         self.state = {p: {"exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)} for p in self.params}
 
     def zero_grad(self, set_to_none=True):
@@ -50,6 +110,19 @@ class FusedAdam:
             self._lr.fill_(lr)
             self._lr_host = lr
 
+    # ---- device scalars of the last step (0-dimensional views: no copy is made here; read them after a synchronisation)
+    def grad_norm(self):
+        """The global gradient norm before clipping (0 while max_grad_norm is off: it is not computed then)."""
+        return self._consts[4]
+
+    def clip_coef(self):
+        """min(1, max_grad_norm / (norm + 1e-6)); 1 while max_grad_norm is off."""
+        return self._consts[3]
+
+    def current_lr(self):
+        """The learning rate the last step applied: the device-side schedule's, else the host-supplied one."""
+        return self._consts[2] if self.recipe else self._lr[0]
+
     @torch.no_grad()
     def step(self):
         lib = _lib.load_library()
@@ -58,8 +131,6 @@ class FusedAdam:
         if not act:
             return
         st = _lib.stream()
-        _lib.check(lib.facl_adam_prep(_lib.ptr(self._lr), _lib.ptr(self._step), self.betas[0], self.betas[1],
-                                      _lib.ptr(self._consts), st), "facl_adam_prep")
         nt = len(act)
         arr = ctypes.c_void_p * nt
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in act]
@@ -68,16 +139,31 @@ class FusedAdam:
         M = arr(*[self.state[p]["exp_avg"].data_ptr() for p in act])
         V = arr(*[self.state[p]["exp_avg_sq"].data_ptr() for p in act])
         N = (ctypes.c_int * nt)(*[p.numel() for p in act])
-        _lib.check(lib.facl_adam_apply(nt, P, G, M, V, N, _lib.ptr(self._consts), self.betas[0], self.betas[1], self.eps, st),
-                   "facl_adam_apply")
+        if not self.recipe:
+            _lib.check(lib.facl_adam_prep(_lib.ptr(self._lr), _lib.ptr(self._step), self.betas[0], self.betas[1],
+                                          _lib.ptr(self._consts), st), "facl_adam_prep")
+            _lib.check(lib.facl_adam_apply(nt, P, G, M, V, N, _lib.ptr(self._consts), self.betas[0], self.betas[1], self.eps, st),
+                       "facl_adam_apply")
+            return
+        npartial = 0
+        if self.max_grad_norm:
+            npartial = sum((p.numel() + CHUNK - 1) // CHUNK for p in act)
+            _lib.check(lib.facl_grad_sqnorm(nt, G, N, _lib.ptr(self._partial), st), "facl_grad_sqnorm")
+        _lib.check(lib.facl_adam_prep_ex(_lib.ptr(self._lr), _lib.ptr(self._step), self.betas[0], self.betas[1],
+                                         _lib.ptr(self._partial), npartial, self.max_grad_norm, SCHEDULES[self.schedule],
+                                         self.warmup_steps, self.decay_steps, self.lr_min, _lib.ptr(self._consts), st),
+                   "facl_adam_prep_ex")
+        D = (ctypes.c_int * nt)(*[int(self._decay[p]) for p in act])
+        _lib.check(lib.facl_adamw_apply(nt, P, G, M, V, N, D, _lib.ptr(self._consts), self.betas[0], self.betas[1], self.eps,
+                                        self.weight_decay, st), "facl_adamw_apply")
 
     def state_dict(self):
         """torch.optim.Adam's layout (state by parameter index), so either optimizer can resume the other's run."""
         step = self._step.detach().clone().cpu()[0]
         return {"state": {i: {"step": step.clone(), "exp_avg": self.state[p]["exp_avg"], "exp_avg_sq": self.state[p]["exp_avg_sq"]}
                           for i, p in enumerate(self.params)},
-                "param_groups": [{"lr": self.param_groups[0]["lr"], "betas": self.betas, "eps": self.eps, "weight_decay": 0,
-                                  "amsgrad": False, "params": list(range(len(self.params)))}]}
+                "param_groups": [{"lr": self.param_groups[0]["lr"], "betas": self.betas, "eps": self.eps,
+                                  "weight_decay": self.weight_decay or 0, "amsgrad": False, "params": list(range(len(self.params)))}]}
 
     def load_state_dict(self, sd):
         for i, p in enumerate(self.params):

@@ -127,6 +127,21 @@ def build_parser(default_branch):
     p.add_argument('--resume', type=str, default='',
                    help='NEW (one rank): a state_<epoch>.pth to continue from, bit-exactly as if the run had never stopped, or '
                         '"auto" = the newest state under --save_root_dir (none there: the run starts from scratch)')
+    p.add_argument('--adamw_decay', type=float, default=0.0,
+                   help='NEW (one rank): decoupled weight decay of the optimizer (torch.optim.AdamW\'s update) on every weight '
+                        'matrix and convolution kernel; biases and BatchNorm gamma / beta are not decayed; 0 = off')
+    p.add_argument('--clip_grad_norm', type=float, default=0.0,
+                   help='NEW (one rank): the gradients of a step are scaled so that their global L2 norm is at most this value '
+                        '(torch.nn.utils.clip_grad_norm_), and the epoch line reports the norms; 0 = off')
+    p.add_argument('--lr_schedule', type=str, default='step', choices=('step', 'cosine'),
+                   help='NEW (one rank for cosine): step = StepLR per epoch (the reference); cosine = half a cosine per optimizer '
+                        'step from --learning_rate down to --lr_min over --lr_decay_epochs, evaluated on the device')
+    p.add_argument('--warmup_steps', type=int, default=0,
+                   help='NEW (one rank): the learning rate of either schedule is multiplied by min(1, t / W) at optimizer step t')
+    p.add_argument('--lr_decay_epochs', type=int, default=0,
+                   help='NEW (--lr_schedule cosine, required >= 1 there): the cosine reaches --lr_min after this many epochs '
+                        '(x the steps of an epoch, warm-up included) and stays there')
+    p.add_argument('--lr_min', type=float, default=0.0, help='NEW (--lr_schedule cosine): the rate the cosine ends at')
     return p
 
 
@@ -627,6 +642,59 @@ def check_state_flags(opt, world=None):
                                    % (flag, world))
 
 
+OPTIM_FLAGS = ("adamw_decay", "clip_grad_norm", "lr_schedule", "warmup_steps", "lr_decay_epochs", "lr_min")
+
+
+def _check_cosine_span(opt, steps):
+    T = opt.lr_decay_epochs * steps
+    if T <= opt.warmup_steps:
+        raise RuntimeError("--lr_decay_epochs %d x %d steps per epoch = %d steps must exceed --warmup_steps %d: the cosine "
+                           "starts where the warm-up ends" % (opt.lr_decay_epochs, steps, T, opt.warmup_steps))
+    return T
+
+
+def check_optim_flags(opt, world=None):
+    """The optimizer recipe (facl_amd/optim.py): --adamw_decay, --clip_grad_norm, --lr_min finite and >= 0, --warmup_steps and
+    --lr_decay_epochs >= 0; cosine needs --lr_decay_epochs >= 1 and more steps than the warm-up has (with --synthetic 0 the
+    steps of an epoch are known only once the split is read: optim_recipe checks again); --lr_decay_epochs / --lr_min belong to
+    cosine; one rank.  Raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    for name in ("adamw_decay", "clip_grad_norm", "lr_min"):
+        v = getattr(opt, name)
+        if not 0.0 <= v < float("inf"):                      # NaN fails both comparisons
+            raise RuntimeError("--%s must be finite and >= 0 (got %r)" % (name, v))
+    for name in ("warmup_steps", "lr_decay_epochs"):
+        if getattr(opt, name) < 0:
+            raise RuntimeError("--%s must be >= 0 (got %d)" % (name, getattr(opt, name)))
+    if opt.lr_schedule == "cosine":
+        if opt.lr_decay_epochs < 1:
+            raise RuntimeError("--lr_schedule cosine needs --lr_decay_epochs >= 1 (got %d): the epochs over which the rate falls "
+                               "to --lr_min" % opt.lr_decay_epochs)
+        if opt.synthetic != 0:
+            _check_cosine_span(opt, opt.steps_per_epoch)
+    else:
+        if opt.lr_decay_epochs:
+            raise RuntimeError("--lr_decay_epochs %d is the span of --lr_schedule cosine (got --lr_schedule %s)"
+                               % (opt.lr_decay_epochs, opt.lr_schedule))
+        if opt.lr_min:
+            raise RuntimeError("--lr_min %r is the end of --lr_schedule cosine (got --lr_schedule %s)" % (opt.lr_min, opt.lr_schedule))
+    world = fdist.env_world_size() if world is None else world
+    if world > 1:
+        defaults = build_parser('0').parse_args([])
+        for name in OPTIM_FLAGS:
+            if getattr(opt, name) != getattr(defaults, name):
+                raise RuntimeError("--%s %s runs on one rank only (got %d ranks): the optimizer recipe has never run "
+                                   "data-parallel" % (name, getattr(opt, name), world))
+
+
+def optim_recipe(opt, steps):
+    """FusedAdam's keyword arguments for the recipe flags; `steps`: optimizer steps per epoch (T = --lr_decay_epochs x steps)."""
+    kw = dict(weight_decay=opt.adamw_decay, max_grad_norm=opt.clip_grad_norm, schedule=opt.lr_schedule,
+              warmup_steps=opt.warmup_steps, lr_min=opt.lr_min)
+    if opt.lr_schedule == "cosine":
+        kw["decay_steps"] = _check_cosine_span(opt, steps)
+    return kw
+
+
 def load_resume_state(opt):
     """The state --resume names, on the CPU and checked against this run's options, with its path -- or (None, None) when
     `auto` finds no state.  `auto` skips a newest state that does not load (a damaged file), with a warning, for the next older."""
@@ -792,18 +860,24 @@ def check_finite_loss(lv, epoch, i):
 def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, after_step=None, start_epoch=0, end_of_epoch=None):
     """The epoch loop of the training entries under StepLR(`lr_step`, 0.7).  `source`: the TrainBatches of --synthetic 0, else
     None (--steps_per_epoch steps).  The entries differ in `next_batch(disk, epoch, i)` -> the step's input (`disk`: the epoch's
-    iterator of `source`, or None), `after_step(what the step returned)` and `after_epoch(epoch, mean_loss, clips_per_s)`.
+    iterator of `source`, or None), `after_step(what the step returned)` and `after_epoch(epoch, mean_loss, clips_per_s)` --
+    with --clip_grad_norm on it gets a fourth argument, the ' | grad norm ...' tail of the epoch line.  Under --lr_schedule cosine
+    the optimizer keeps the base rate and its device-side schedule does the rest.
     `start_epoch`: the first epoch run (a resumed run's).  `end_of_epoch(epoch)`: called last in every epoch, when the epoch's
     producer thread has stopped, so that the view generator's state is the one the next epoch starts from."""
     steps = opt.steps_per_epoch if source is None else source.steps
     run_step = step
+    cosine = getattr(opt, "lr_schedule", "step") == "cosine"     # namespaces from before the recipe flags: the reference's StepLR
+    max_norm = float(getattr(opt, "clip_grad_norm", 0.0))
     for epoch in range(start_epoch, opt.nepoch):
         step.netR.train()
         if getattr(step, "key_encoder", None) is not None:
             step.key_encoder.key.train()                 # MoCo's convention: the key copy normalises with batch statistics too
         for g in step.optimizer.param_groups:
-            g["lr"] = lr_for_epoch(opt.learning_rate, epoch, lr_step)
+            # cosine: the base rate; the device evaluates the schedule from its own step counter (facl_adam_prep_ex)
+            g["lr"] = opt.learning_rate if cosine else lr_for_epoch(opt.learning_rate, epoch, lr_step)
         loss_sigma, t0 = 0.0, time.time()
+        norms, clipped = [], 0
         disk = None if source is None else source.epoch(epoch, hold_first=run_step is step and wants_graph(opt))
         for i in range(steps):
             out_points = next_batch(disk, epoch, i)
@@ -813,12 +887,18 @@ def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, aft
             torch.cuda.synchronize()
             lv = out[0].item()
             check_finite_loss(lv, epoch, i)
+            if max_norm:                                 # the step's pre-clip norm: two device scalars, already synchronised
+                norms.append(float(step.optimizer.grad_norm()))
+                clipped += float(step.optimizer.clip_coef()) < 1.0
             if after_step is not None:
                 after_step(out)
             loss_sigma += lv
         if disk is not None:
             disk.close()
-        after_epoch(epoch, loss_sigma / steps, opt.batchSize * steps * world / (time.time() - t0))
+        extra = ()
+        if max_norm:
+            extra = (' | grad norm mean/max: %.4g/%.4g, clipped %d/%d steps' % (sum(norms) / steps, max(norms), clipped, steps),)
+        after_epoch(epoch, loss_sigma / steps, opt.batchSize * steps * world / (time.time() - t0), *extra)
         if end_of_epoch is not None:
             end_of_epoch(epoch)
 
@@ -833,6 +913,7 @@ def run(default_branch, ckpt_pattern, args=None):
     check_queue_flags(opt)
     check_key_flags(opt)
     check_state_flags(opt)
+    check_optim_flags(opt)
     from . import train_state
     flags = train_state.flags_of(opt)                  # as given: the grouper writes the reference's literals into `opt` later
     resumed, resumed_path = load_resume_state(opt)     # on the CPU, refused here if its options differ from this run's
@@ -846,15 +927,17 @@ def run(default_branch, ckpt_pattern, args=None):
     netR = MODELL.PointNet_Plus(opt, gost=num_crop).to(device)
     netR.precision = opt.precision
     netR.bn_reduce_fn = fdist.make_bn_reduce_fn()
-    # cn3d_train_motion_GL.py:180: the same update as torch.optim.Adam, all tensors in one HIP launch (facl_amd/optim.py)
+    source = TrainBatches(opt, device, rank, world, report_ingest=rank == 0, too_few="the split has %(clips)d clips: fewer "
+                          "than one batch of %(batch)d per rank x %(world)d ranks") if opt.synthetic == 0 else None
+    steps = opt.steps_per_epoch if source is None else source.steps
+    # cn3d_train_motion_GL.py:180: the same update as torch.optim.Adam, all tensors in one HIP launch (facl_amd/optim.py); the
+    # recipe flags (all off by default) add decay, clipping and the device-side schedule, which counts in steps of an epoch
     from .optim import FusedAdam
-    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06)
+    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06, **optim_recipe(opt, steps))
     step = ContrastiveStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder), opt.swa_if, opt.cld_if)
     gen = torch.Generator(device=device)
     gen.manual_seed(1000 + rank)
     view_rng = np.random.RandomState(2000 + rank)         # --synthetic 2: the generator the view construction draws from
-    source = TrainBatches(opt, device, rank, world, report_ingest=rank == 0, too_few="the split has %(clips)d clips: fewer "
-                          "than one batch of %(batch)d per rank x %(world)d ranks") if opt.synthetic == 0 else None
 
     def next_batch(disk, epoch, i):
         if opt.synthetic == 0:
@@ -874,10 +957,10 @@ def run(default_branch, ckpt_pattern, args=None):
             return synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
         raise RuntimeError("--synthetic must be 0 (the dataset on disk), 1 or 2")
 
-    def after_epoch(epoch, mean_loss, clips):
+    def after_epoch(epoch, mean_loss, clips, grad_norms=''):
         logging.info('{} --epoch{} ==Average loss:{}'.format('Valid', epoch, mean_loss))
         if rank == 0:
-            print('epoch:', epoch, 'loss mode is :', 1, '--loss:', mean_loss, '| clips/s: %.1f' % clips)
+            print('epoch:', epoch, 'loss mode is :', 1, '--loss:', mean_loss, '| clips/s: %.1f%s' % (clips, grad_norms))
         if opt.knn_every and (epoch + 1) % opt.knn_every == 0:
             top1 = knn_monitor(netR, opt, device)
             logging.info('{} --epoch{} ==knn top1:{}'.format('Valid', epoch, top1))
@@ -888,7 +971,6 @@ def run(default_branch, ckpt_pattern, args=None):
             if step.key_encoder is not None:                 # the model's format: extract_* / finetune --checkpoint load it
                 torch.save(step.key_encoder.state_dict(), key_checkpoint_name(path))
 
-    steps = opt.steps_per_epoch if source is None else source.steps
     source_rng = None if source is None else source.view_rng
 
     def end_of_epoch(epoch):

@@ -19,7 +19,12 @@ TRAJECTORY_FLAGS = ("batchSize", "num_crop", "SAMPLE_NUM", "INPUT_FEATURE_NUM", 
                     "synthetic", "view_rng", "steps_per_epoch", "max_steps_per_epoch", "learning_rate", "precision",
                     "group_radius", "fps_reorder", "knn_K", "sample_num_level1", "sample_num_level2", "ball_radius", "ball_radius2",
                     "Num_Class", "swa_if", "cld_if", "loss_normalize", "loss_temperature", "loss_mask", "neg_queue", "key_encoder",
-                    "key_momentum")
+                    "key_momentum", "adamw_decay", "clip_grad_norm", "lr_schedule", "warmup_steps", "lr_decay_epochs", "lr_min")
+
+# the optimizer-recipe flags came after the first states were written: a state without them ran with the recipe off, which is
+# what these defaults (the parser's) say.  Every other flag must be in the file.
+LATER_FLAG_DEFAULTS = {"adamw_decay": 0.0, "clip_grad_norm": 0.0, "lr_schedule": "step", "warmup_steps": 0, "lr_decay_epochs": 0,
+                       "lr_min": 0.0}
 
 _STATE_NAME = re.compile(r"^state_(\d+)\.pth$")
 
@@ -122,7 +127,8 @@ def write_atomic(state, path):
 
 
 def load_state(path):
-    """The state at `path` on the CPU; refuses a format this code does not know and a state with a missing entry."""
+    """The state at `path` on the CPU; refuses a format this code does not know and a state with a missing entry (a flag of
+    LATER_FLAG_DEFAULTS that the file lacks reads as its default)."""
     try:
         state = torch.load(path, map_location="cpu", weights_only=True)
     except Exception as e:
@@ -133,9 +139,11 @@ def load_state(path):
     if state["format"] != FORMAT:
         raise RuntimeError("%s has state format %r; this code reads format %d" % (path, state["format"], FORMAT))
     missing = [k for k in KEYS if k not in state] + ["rng." + k for k in RNG_KEYS if k not in state.get("rng", {})] \
-        + ["flags." + k for k in TRAJECTORY_FLAGS if k not in state.get("flags", {})]
+        + ["flags." + k for k in TRAJECTORY_FLAGS if k not in state.get("flags", {}) and k not in LATER_FLAG_DEFAULTS]
     if missing:
         raise RuntimeError("%s lacks %s" % (path, ", ".join(missing)))
+    for k, v in LATER_FLAG_DEFAULTS.items():
+        state["flags"].setdefault(k, v)
     return state
 
 

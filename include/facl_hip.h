@@ -521,6 +521,38 @@ int facl_adam_apply(int nt, float* const* p, const float* const* g, float* const
  * refusal comes before the launch. */
 int facl_ema_apply(int nt, float* const* pk, const float* const* p, const int* n, float m, void* stream);
 
+/* ---- optimizer recipe: global-norm clipping, decoupled weight decay, warm-up / cosine learning rate ---------
+ * Off by default: facl_adam_prep + facl_adam_apply above stay the whole step.  With any of it on the step is
+ *   [facl_grad_sqnorm, only when clipping] -> facl_adam_prep_ex -> facl_adamw_apply.
+ * facl_grad_sqnorm: the chunk table of facl_adam_apply (2048 elements per 256-thread workgroup, chunks of tensor 0 first);
+ *   partial[chunk] = sum of g^2 over the chunk.  g is a HOST array of nt <= 64 device pointers, n their element counts, partial a
+ *   DEVICE array of sum_i ceil(n[i] / 2048) doubles, every one of them written.  Each element is widened to fp64 before it is
+ *   squared (the square is exact), the additions run in one fixed order (thread, wave shuffle, LDS) and no atomic takes part:
+ *   the same bits from run to run, launched eagerly or replayed.  16 bytes per lane where n[i] % 4 == 0 and g[i] is 16-byte
+ *   aligned, else a scalar walk; g is only read.
+ * facl_adam_prep_ex: one workgroup.  step[0] += 1 (t, 1-based); norm = sqrt(partial[0] + ... + partial[npartial - 1]) in fp64,
+ *   fixed order; c = min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s coefficient (an infinite norm gives
+ *   c = 0, a NaN norm c = NaN, as there); npartial == 0: no clipping, c = 1 exactly, norm = 0, max_norm is not read.  The learning
+ *   rate of step t, in fp64: warm = min(1, t / warmup_steps) (1 when warmup_steps == 0);
+ *     FACL_LR_STEP:   lr_t = warm * lr[0]                       (the host's schedule, as facl_adam_prep reads it)
+ *     FACL_LR_COSINE: lr_t = warm * (lr_min + (lr[0] - lr_min) * 0.5 * (1 + cos(pi * min(t', T') / T'))),
+ *                     t' = max(t - warmup_steps, 0), T' = decay_steps - warmup_steps: lr_min from step decay_steps on.
+ *   consts (5 floats) = (lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t), lr_t, c, norm); the host may read the last three after a
+ *   synchronisation.
+ * facl_adamw_apply: facl_adam_apply on g' = c * g (consts[3]; the stored gradient is only read), and on the tensors whose
+ *   decay[i] (HOST array of nt ints) is non-zero p *= 1 - lr_t * wd first (consts[2]; torch.optim.AdamW's order).  With c == 1 and
+ *   wd == 0 the outputs are facl_adam_apply's bit for bit.
+ * Refusals, all before the launch: a NULL array or entry (partial only when npartial > 0): FACL_E_NULL; nt outside 1..64, an
+ * n[i] < 1, npartial < 0, max_norm not positive when npartial > 0, wd negative, warmup_steps < 0, lr_min negative (NaN included
+ * in each), a schedule other than the two, decay_steps <= warmup_steps under FACL_LR_COSINE: FACL_E_SHAPE. */
+#define FACL_LR_STEP   0
+#define FACL_LR_COSINE 1
+int facl_grad_sqnorm(int nt, const float* const* g, const int* n, double* partial, void* stream);
+int facl_adam_prep_ex(const float* lr, float* step, float b1, float b2, const double* partial, int npartial, double max_norm,
+                      int schedule, int warmup_steps, int decay_steps, double lr_min, float* consts, void* stream);
+int facl_adamw_apply(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const int* n,
+                     const int* decay, const float* consts, float b1, float b2, float eps, float wd, void* stream);
+
 /* ---- optional loss terms of the training loop (switched off in the shipped loop) ----------------------
  * facl_sinkhorn: distributed_sinkhorn + shoot_infs (cn3d_model_conbag.py:391-425).  Q (R,C) = exp(scores)^T, R prototypes
  * x C samples; `iters` row/column scalings; out (C,R).  scratch: R*C + R floats.

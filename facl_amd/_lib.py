@@ -36,6 +36,8 @@ SIGNATURES = {
     "facl_adam_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_p],
     "facl_ws_bytes": [],
     "facl_bn_finalize": [c_p, c_i, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
+    "facl_bn_finalize_after": [c_p, c_i, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
+    "facl_bn_eval_consts_after": [c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_p],
     "facl_absmax": [c_p, c_l, c_p, c_p],
     "facl_rows_act_amax": [c_p, c_l, c_i, c_p, c_p, c_p, c_p],
     "facl_bn_eval_consts": [c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p],

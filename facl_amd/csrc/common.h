@@ -214,6 +214,11 @@ typedef _Float16 f16x2h __attribute__((ext_vector_type(2)));
 // gemm_rs.hip reads); the buffer the C ABI calls `amax` is FACL_AMAX_SLOTS * FACL_AMAX_STRIDE uint32, zeroed by the caller
 #define FACL_AMAX_SLOTS 64
 #define FACL_AMAX_STRIDE 32
+// word 1 of the buffer (inside slot 0's line, read by no consumer of the scale): facl_absmax raises it to NaN bits when the tensor it
+// measured held a NaN / inf, which its maximum skips; facl_bn_eval_consts_after takes the whole buffer as its `prev`
+#define FACL_AMAX_FLAG_WORD 1
+static_assert(FACL_AMAX_FLAG_WORD % FACL_AMAX_STRIDE != 0 && FACL_AMAX_FLAG_WORD < FACL_AMAX_SLOTS * FACL_AMAX_STRIDE,
+              "the flag word must lie inside the buffer and be no slot");
 static_assert(FACL_AMAX_SLOTS * FACL_AMAX_STRIDE == FACL_AMAX_WORDS, "amax buffer layout");
 
 // two ALREADY SCALED values -> packed (h1, h2) fp16 pairs (element 0 in the low half)

@@ -70,17 +70,39 @@ __global__ __launch_bounds__(1024) void k_reduce_rows(const double* __restrict__
 // taken on: Samuelson's inequality, |y_i - mean| <= sigma sqrt(n - 1) for ANY n numbers, gives
 // |.| <= |gamma| sqrt(n - 1) sigma invstd + |beta| (sigma invstd = sqrt(var / (var + eps)) <= 1).  It is the fp16x3 scale of the
 // layer's activation (common.h) -- rigorous, no pass over the data, and within a few octaves of the true maximum.
+// `prev` (or null): `nprev` floats that the INPUT of this layer was computed with -- the (scale | shift) rows of the previous
+// layer's constants.  The heavy passes apply the previous layer's ReLU as fmaxf(v, 0), which turns a NaN activation into a clean
+// zero, so a NaN / inf there never reaches this layer's sums; the reference's nn.ReLU keeps it and the next convolution spreads it
+// over every channel.  A non-finite value in `prev` therefore makes EVERY statistic of this layer NaN (constants, running buffers),
+// as the reference's are: the flag travels bnc1 -> bnc2 -> bnc3, and facl_sa_pool (relu_nan) puts it into the features.
+// Finite `prev`: nothing changes, bit for bit.
+__device__ __forceinline__ bool block_any_nonfinite(const float* __restrict__ prev, int nprev) {
+    __shared__ float flag[16];
+    float z = 0.f;
+    for (int i = threadIdx.x; i < nprev; i += blockDim.x) z = fmaf(prev[i], 0.f, z);      // 0 * finite = +-0; 0 * inf = 0 * NaN = NaN
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+    if ((threadIdx.x & 63) == 0) flag[threadIdx.x >> 6] = z;
+    __syncthreads();
+    for (int w = 0; w < (int)((blockDim.x + 63) >> 6); ++w) z += flag[w];
+    return !(z == 0.f);
+}
+
 __global__ __launch_bounds__(1024) void k_bn_finalize(const double* __restrict__ sums, int C, double count,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                       float momentum, float* __restrict__ running_mean,
                                                       float* __restrict__ running_var, float* __restrict__ bnc,
-                                                      unsigned* __restrict__ aamax, unsigned* __restrict__ zamax) {
+                                                      unsigned* __restrict__ aamax, unsigned* __restrict__ zamax,
+                                                      const float* __restrict__ prev, int nprev) {
     __shared__ float red[16];
     float bound = 0.f;
+    const bool poisoned = prev ? block_any_nonfinite(prev, nprev) : false;                // uniform over the workgroup
     if (zamax)
         for (int i = threadIdx.x; i < FACL_AMAX_WORDS; i += blockDim.x) zamax[i] = 0u;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const double mean = sums[2 * c] / count;
+        double mean = sums[2 * c] / count;
+        if (poisoned) mean = __builtin_nan("");           // (the bound below is NaN too and fmaxf drops it: `aamax` then holds 0, a
+                                                          // meaningless scale -- harmless, every constant in bnc is NaN and decides)
         double var = sums[2 * c + 1] / count - mean * mean;
         if (var < 0) var = 0;
         const double invstd = 1.0 / sqrt(var + (double)eps);
@@ -110,17 +132,28 @@ __global__ __launch_bounds__(1024) void k_bn_finalize(const double* __restrict__
     }
 }
 
-// max|x| of a contiguous fp32 array, RAISED into the FACL_AMAX_SLOTS slots of `amax` (zeroed by the caller, or holding the
-// maximum of another tensor that shares the scale): one atomic per wave, non-negative floats order like unsigned integers
+// max|x| over the FINITE elements of a contiguous fp32 array, RAISED into the FACL_AMAX_SLOTS slots of `amax` (zeroed by the caller,
+// or holding the maximum of another tensor that shares the scale): one atomic per wave, non-negative floats order like unsigned
+// integers.  A NaN / inf element does not enter the maximum -- one inf would otherwise push the operand scale of every OTHER row
+// out of the fp16 range (measured: an inf coordinate in one group left the features of all other groups 0.37 off) -- it raises
+// the flag word FACL_AMAX_FLAG_WORD of the buffer to NaN bits instead (a word no consumer of the scale reads: they take the slots).
 __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, long long n, unsigned* __restrict__ amax) {
     float m = 0.f;
+    bool bad = false;
     const long long stride = (long long)gridDim.x * 256;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) m = fmaxf(m, fabsf(x[i]));
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float a = fabsf(x[i]);
+        const bool fin = a <= 3.4028235e38f;                      // false for inf and NaN
+        m = fmaxf(m, fin ? a : 0.f);
+        bad |= !fin;
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    const bool any_bad = __ballot(bad) != 0ull;
     if ((threadIdx.x & 63) == 0) {
         const unsigned wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
         atomicMax(amax + (wave & (FACL_AMAX_SLOTS - 1)) * FACL_AMAX_STRIDE, __float_as_uint(m));
+        if (any_bad) atomicMax(amax + FACL_AMAX_FLAG_WORD, 0x7FC00000u);
     }
 }
 
@@ -147,18 +180,21 @@ __global__ __launch_bounds__(256) void k_rows_act_amax(const float* __restrict__
     }
 }
 
+// `prev` (or null): as in k_bn_finalize -- `nprev` floats the layer's input depends on (the words of the amax buffer facl_absmax
+// measured x into: its flag word holds NaN bits when x held a NaN / inf); a non-finite one makes every constant NaN.
 __global__ void k_bn_eval_consts(int C, const float* __restrict__ gamma, const float* __restrict__ beta,
                                  const float* __restrict__ rm, const float* __restrict__ rv, float eps,
-                                 float* __restrict__ bnc) {
+                                 float* __restrict__ bnc, const float* __restrict__ prev, int nprev) {
+    const bool poisoned = prev ? block_any_nonfinite(prev, nprev) : false;               // uniform over the workgroup
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double invstd = 1.0 / sqrt((double)rv[c] + (double)eps);
-    const double g = gamma[c];
+    const double g = poisoned ? __builtin_nan("") : (double)gamma[c];
     bnc[0 * C + c] = rm[c];
     bnc[1 * C + c] = (float)invstd;
     bnc[2 * C + c] = (float)(g * invstd);
     bnc[3 * C + c] = (float)((double)beta[c] - (double)rm[c] * g * invstd);
-    bnc[4 * C + c] = g < 0 ? -1.0f : 1.0f;
+    bnc[4 * C + c] = gamma[c] < 0 ? -1.0f : 1.0f;
 }
 
 // BN1 statistics analytically from the input moments: y1 = W1 x + b1  =>
@@ -366,15 +402,22 @@ int facl_reduce_rows_f32(const float* part, int rows, int V, double* out, hipStr
 
 extern "C" int64_t facl_ws_bytes(void) { return (int64_t)FACL_WS_ROWS * 4608 * sizeof(double) + FACL_WS_TICKET_BYTES; }
 
+extern "C" int facl_bn_finalize_after(const double* sums, int C, double count, const float* gamma, const float* beta,
+                                      float eps, float momentum, float* running_mean, float* running_var, float* bnc,
+                                      uint32_t* aamax, uint32_t* zamax, const float* prev, int nprev, void* stream) {
+    if (!sums || !gamma || !beta || !bnc) return FACL_E_NULL;
+    if (C < 1 || count < 1 || (prev && nprev < 1)) return FACL_E_SHAPE;
+    const int threads = C >= 1024 ? 1024 : (C + 63) / 64 * 64;
+    hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(threads), 0, (hipStream_t)stream, sums, C, count, gamma,
+                       beta, eps, momentum, running_mean, running_var, bnc, aamax, zamax, prev, nprev);
+    return facl_launch_status();
+}
+
 extern "C" int facl_bn_finalize(const double* sums, int C, double count, const float* gamma, const float* beta,
                                 float eps, float momentum, float* running_mean, float* running_var, float* bnc,
                                 uint32_t* aamax, uint32_t* zamax, void* stream) {
-    if (!sums || !gamma || !beta || !bnc) return FACL_E_NULL;
-    if (C < 1 || count < 1) return FACL_E_SHAPE;
-    const int threads = C >= 1024 ? 1024 : (C + 63) / 64 * 64;
-    hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(threads), 0, (hipStream_t)stream, sums, C, count, gamma,
-                       beta, eps, momentum, running_mean, running_var, bnc, aamax, zamax);
-    return facl_launch_status();
+    return facl_bn_finalize_after(sums, C, count, gamma, beta, eps, momentum, running_mean, running_var, bnc, aamax, zamax,
+                                  nullptr, 0, stream);
 }
 
 extern "C" int facl_absmax(const float* x, int64_t n, uint32_t* amax, void* stream) {
@@ -396,13 +439,19 @@ extern "C" int facl_rows_act_amax(const float* y, int64_t R, int C, const float*
     return facl_launch_status();
 }
 
+extern "C" int facl_bn_eval_consts_after(int C, const float* gamma, const float* beta, const float* running_mean,
+                                         const float* running_var, float eps, float* bnc, const float* prev, int nprev,
+                                         void* stream) {
+    if (!gamma || !beta || !running_mean || !running_var || !bnc) return FACL_E_NULL;
+    if (C < 1 || (prev && nprev < 1)) return FACL_E_SHAPE;
+    hipLaunchKernelGGL(k_bn_eval_consts, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, C, gamma, beta,
+                       running_mean, running_var, eps, bnc, prev, nprev);
+    return facl_launch_status();
+}
+
 extern "C" int facl_bn_eval_consts(int C, const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, float* bnc, void* stream) {
-    if (!gamma || !beta || !running_mean || !running_var || !bnc) return FACL_E_NULL;
-    if (C < 1) return FACL_E_SHAPE;
-    hipLaunchKernelGGL(k_bn_eval_consts, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, C, gamma, beta,
-                       running_mean, running_var, eps, bnc);
-    return facl_launch_status();
+    return facl_bn_eval_consts_after(C, gamma, beta, running_mean, running_var, eps, bnc, nullptr, 0, stream);
 }
 
 extern "C" int facl_bn1_sums_from_moments(const double* mom, double count, int D, const float* W1, const float* b1,

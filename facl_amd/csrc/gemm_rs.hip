@@ -669,7 +669,7 @@ __global__ __launch_bounds__(64 * WG_WAVES) void k_wgrad_rs(WgArgs g) {
     auto store_b = [&](int s, const float (&r)[8]) {
         float v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = PRO ? fmaxf(fmaf(ps, r[e], pt), 0.f) : r[e];   // (backward = training: a NaN is loud through the layer's statistics)
+        for (int e = 0; e < 8; ++e) v[e] = PRO ? fmaxf(fmaf(ps, r[e], pt), 0.f) : r[e];   // (backward = training: the forward of the same step applied relu_nan here and its loss is already non-finite)
         unsigned hi[4], mi[4], lo[4];
         uint4* d = &bring[s & 1][((ks_b * 4 + kt_b) * NPL) * 64 + lb];
         if (H3) {

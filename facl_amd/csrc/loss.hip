@@ -687,12 +687,12 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
         const size_t p0 = ((size_t)sp.n * (G + 1) + (sp.circle ? 0 : G)) * u.nch;
         float M = -INFINITY;
         for (int p = threadIdx.x; p < np; p += QT)
-            if (ps[p0 + p] > 0) M = fmaxf(M, pm[p0 + p]);
+            if (ps[p0 + p] != 0) M = fmaxf(M, pm[p0 + p]);     // != 0, not > 0: a NaN partial (a NaN / inf similarity) is no empty chunk
         M = block_reduce_max(M, smf);
         double S = 0;
         for (int p = threadIdx.x; p < np; p += QT) {
             const double s = ps[p0 + p];
-            if (s > 0) S += s * exp((double)pm[p0 + p] - (double)M);
+            if (s != 0) S += s * exp((double)pm[p0 + p] - (double)M);
         }
         S = block_reduce_sum(S, smd);
         lse = M + (float)log(S);

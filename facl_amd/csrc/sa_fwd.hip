@@ -713,7 +713,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_sa_fwd3_sb(const float* __restri
                     const float4 y = yn[(ct * 2 + rt) * 4 + 2 * m + t];
                     const float4 sc = sc2s[8 * rt + 2 * (2 * m + t) + h], sh = sh2s[8 * rt + 2 * (2 * m + t) + h];
                     if (NP == 4) {
-                        // (fmaxf drops a NaN here; in training the layer's statistics -- sums of y2 taken by facl_sa_fwd2 -- carry it)
+                        // (fmaxf drops a NaN here, and the statistics of THIS layer's output then do not see it: the flag travels
+                        // through the constants instead -- facl_bn_finalize_after makes bnc3 NaN when bnc2 is not finite, finalize.hip)
                         split_pair_h(fmaxf(fmaf(sc.x, y.x, sh.x), 0.f), fmaxf(fmaf(sc.y, y.y, sh.y), 0.f), hi[2 * t], mi[2 * t]);
                         split_pair_h(fmaxf(fmaf(sc.z, y.z, sh.z), 0.f), fmaxf(fmaf(sc.w, y.w, sh.w), 0.f), hi[2 * t + 1], mi[2 * t + 1]);
                         lo[2 * t] = lo[2 * t + 1] = 0u;

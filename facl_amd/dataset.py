@@ -128,6 +128,7 @@ def load_clip(data_root, v_name, branch):
         if a.dtype not in (np.float32, np.float64) or a.dtype != arrs[0].dtype:
             raise ValueError("clip %s: the four clouds must share one dtype, float32 or float64" % v_name)
     V.check_temporal_rows(arrs, v_name)
+    V.check_finite_coordinates(arrs, v_name)
     return arrs
 
 

@@ -219,6 +219,7 @@ class ResidentClips:
                     raise ValueError("clip %s changed on disk between the header pass and the ingest" % name)
                 if host_check:
                     V.check_temporal_rows(arrs, name)
+                V.check_finite_coordinates(arrs, name)         # always: no device-side check stands in for it
                 for k, a in enumerate(arrs):
                     o = int(table[i, k] - r0)
                     host[o:o + a.shape[0]] = a[:, :CHANNELS]

@@ -36,14 +36,19 @@ class _Workspace:
         return cls._ws[key]
 
 
-def _bn_finalize(sums, C, count, gamma, beta, running_mean, running_var, momentum=BN_MOMENTUM, aamax=None, zamax=None):
+def _bn_finalize(sums, C, count, gamma, beta, running_mean, running_var, momentum=BN_MOMENTUM, aamax=None, zamax=None, after=None):
     """`aamax` (one row of _lib.amax_buffers): receives the bound of the layer's activation, the fp16x3 scale of the GEMM that
-    consumes it (|gamma| sqrt(count - 1) sigma invstd + |beta|: csrc/finalize.hip)."""
+    consumes it (|gamma| sqrt(count - 1) sigma invstd + |beta|: csrc/finalize.hip).
+    `after`: the (5, C') constants of the layer in front.  The heavy passes apply that layer's ReLU as max(v, 0), which drops a
+    NaN; a non-finite scale or shift there makes every statistic of this layer NaN instead (facl_bn_finalize_after), as the
+    reference's are -- the same launch, nothing changes while the constants are finite."""
     lib = _lib.load_library()
     bnc = _lib.empty((5, C), dtype=torch.float32, device=sums.device)
-    _lib.check(lib.facl_bn_finalize(_lib.ptr(sums), C, float(count), _lib.ptr(gamma), _lib.ptr(beta), BN_EPS,
-                                    momentum, _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(bnc),
-                                    _lib.ptr(aamax), _lib.ptr(zamax), _lib.stream()), "facl_bn_finalize")
+    prev, nprev = (None, 0) if after is None else (after[2], 2 * after.shape[1])       # rows 2..3: scale | shift, contiguous
+    _lib.check(lib.facl_bn_finalize_after(_lib.ptr(sums), C, float(count), _lib.ptr(gamma), _lib.ptr(beta), BN_EPS,
+                                          momentum, _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(bnc),
+                                          _lib.ptr(aamax), _lib.ptr(zamax), _lib.ptr(prev), nprev, _lib.stream()),
+               "facl_bn_finalize_after")
     return bnc
 
 
@@ -70,12 +75,15 @@ def _frag_channel_order(dev):
     return _FRAG_ORDER[key]
 
 
-def _bn_eval(C, gamma, beta, running_mean, running_var):
+def _bn_eval(C, gamma, beta, running_mean, running_var, after=None):
+    """`after`: a float32 / int32 tensor the layer's input depends on; a non-finite word in it makes every constant NaN
+    (facl_bn_eval_consts_after)."""
     lib = _lib.load_library()
     bnc = _lib.empty((5, C), dtype=torch.float32, device=gamma.device)
-    _lib.check(lib.facl_bn_eval_consts(C, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
-                                       _lib.ptr(running_var), BN_EPS, _lib.ptr(bnc), _lib.stream()),
-               "facl_bn_eval_consts")
+    _lib.check(lib.facl_bn_eval_consts_after(C, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
+                                             _lib.ptr(running_var), BN_EPS, _lib.ptr(bnc), _lib.ptr(after),
+                                             0 if after is None else after.numel(), _lib.stream()),
+               "facl_bn_eval_consts_after")
     return bnc
 
 
@@ -185,7 +193,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         if reduce_fn is not None:
             reduce_fn(sums2)
         rm, rv = (p["rm2"], p["rv2"]) if direct else (None, None)
-        bnc2 = _bn_finalize(sums2, 64, count, p["g2"], p["be2"], rm, rv, aamax=amax[2])
+        bnc2 = _bn_finalize(sums2, 64, count, p["g2"], p["be2"], rm, rv, aamax=amax[2], after=bnc1)
         if update_running and not direct:
             _running_update(bnc2, p["rm2"], p["rv2"], n_true)
     else:
@@ -215,11 +223,13 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         if reduce_fn is not None:
             reduce_fn(sums3)
         rm, rv = (p["rm3"], p["rv3"]) if direct else (None, None)
-        bnc3 = _bn_finalize(sums3, 256, count, p["g3"], p["be3"], rm, rv, zamax=amax[3])
+        bnc3 = _bn_finalize(sums3, 256, count, p["g3"], p["be3"], rm, rv, zamax=amax[3], after=bnc2)
         if update_running and not direct:
             _running_update(bnc3, p["rm3"], p["rv3"], n_true)
     else:
-        bnc3 = _bn_eval(256, p["g3"], p["be3"], p["rm3"], p["rv3"])
+        # these passes drop a NaN / inf of x in their ReLUs and eval mode has no statistics to carry it: facl_absmax flagged it in
+        # amax[0], and the last layer's constants -- so every feature -- become NaN (a superset of the groups the reference loses)
+        bnc3 = _bn_eval(256, p["g3"], p["be3"], p["rm3"], p["rv3"], after=amax[0])
     ngroups, ymax_g, rsel = nunits, ymax, None
     if R > 1:                                    # a group spans R units: merge their maxima (first unit wins ties)
         ngroups = nunits // R

@@ -16,7 +16,12 @@ def knn_radius_group(points, sample_num_level1, knn_K, ball_radius, want_idx=Fal
     The returned tensors are transposed VIEWS of contiguous (M,S,K,D) / (M,S,3) buffers, exactly
     like the reference's (utils_my.py:283-284).  ``points`` is not modified.
     A 4-D ``points`` (B,G,N,D) is the loader's clip-major batch: the outputs are those of
-    ``points.permute(1,0,2,3).reshape(G*B,N,D)`` (cn3d_train_motion_GL.py:226) without materialising that copy."""
+    ``points.permute(1,0,2,3).reshape(G*B,N,D)`` (cn3d_train_motion_GL.py:226) without materialising that copy.
+
+    The xyz of the centroids (rows 0..S-1 of every cloud) must be finite: the kernel's selection is undefined for a NaN / inf
+    centroid.  The tensor is on the device, so it is not checked here; the loaders check the clips on the host
+    (facl_amd.views.check_finite_coordinates).  A non-finite value elsewhere -- another point's xyz, any feature channel --
+    is handled like the reference does (the point sorts last; the feature is gathered)."""
     _lib.require_cuda(points)
     if points.dtype != torch.float32:
         raise TypeError("points must be float32 (the reference casts with .type(torch.FloatTensor))")

@@ -148,10 +148,28 @@ def check_temporal_rows(clip, name):
                              "drawn (cn3D_data_set.py:654-663)" % (name, t))
 
 
+_F32_MAX = float(np.finfo(np.float32).max)
+
+
+def check_finite_coordinates(clip, name):
+    """Every xyz of the four source clouds must be a finite float32: the views' first 64 rows are the grouping kernel's
+    centroids, and its radix select (csrc/group.hip) orders distance bit patterns that it takes for real numbers.  With a
+    NaN / inf centroid every key is NaN; padding indices >= N (N no multiple of 64) are then kept as neighbours and read past
+    the cloud, and with a sign-bit NaN nothing is selected at all and the emission reads indices out of unwritten LDS.  The
+    clips are host arrays here, so the check costs no device synchronisation.  Feature channels are NOT checked: a NaN there
+    travels through the step and ends in check_finite_loss's FloatingPointError."""
+    for k, a in enumerate(clip):
+        xyz = a[:, :3]
+        if not (np.abs(xyz) <= _F32_MAX).all():              # False for NaN, inf and what overflows the float32 views
+            r, c = np.argwhere(~(np.abs(xyz) <= _F32_MAX))[0]
+            raise ValueError("clip %s: non-finite coordinate %r in row %d, column %d of source cloud %d: the grouping needs "
+                             "finite xyz (fix or drop the clip)" % (name, float(xyz[r, c]), r, c, k))
+
+
 def pack_clips(clips, clip_ids, out=None):
     """The batch's source clouds packed row-wise, (rows, 8) in the clips' one dtype, and the (B, 9) int32 meta of
     csrc/views_philox.hip (row offsets and counts of the four clouds, dataset index).  Checks what the kernels assume:
-    one float dtype, 2-D (rows >= 1, >= 8 channels) clouds, non-zero temporal rows.  `out`: a (>= rows, 8) array to pack
+    one float dtype, 2-D (rows >= 1, >= 8 channels) clouds, non-zero temporal rows, finite coordinates.  `out`: a (>= rows, 8) array to pack
     into (a pinned staging buffer); returns (src, meta, dtype) with src a view of it."""
     dt = clips[0][0].dtype
     if dt not in (np.float32, np.float64):
@@ -163,6 +181,7 @@ def pack_clips(clips, clip_ids, out=None):
         if any(a.dtype != dt or a.ndim != 2 or a.shape[1] < 8 or a.shape[0] < 1 for a in clip):
             raise ValueError("every source cloud must be (rows >= 1, >= 8) of one dtype")
         check_temporal_rows(clip, clip_ids[b])
+        check_finite_coordinates(clip, clip_ids[b])
         for k, a in enumerate(clip):
             meta[b, k], meta[b, 4 + k] = off, a.shape[0]
             off += a.shape[0]

@@ -90,6 +90,18 @@ int facl_bn_finalize(const double* sums, int C, double count, const float* gamma
                      uint32_t* aamax, uint32_t* zamax, void* stream);
 int facl_bn_eval_consts(int C, const float* gamma, const float* beta, const float* running_mean,
                         const float* running_var, float eps, float* bnc, void* stream);
+/* The same two calls for a layer BEHIND another one, `prev` = `nprev` floats (or NULL: exactly the calls above) that the layer's
+ * input was computed with.  The heavy passes apply the previous layer's ReLU as max(v, 0), which turns a NaN into a clean 0, so a
+ * NaN / inf in the previous layer's constants never shows in this layer's sums, where nn.ReLU keeps it and the next convolution
+ * spreads it over every channel.  With a non-finite value anywhere in `prev`, every output of the call (bnc, the running buffers)
+ * is NaN, as the reference's statistics are; with a finite `prev` every output is bit-identical to the call without it.
+ * Training: prev = rows 2..3 (scale, shift) of the previous layer's bnc, so the flag travels bnc1 -> bnc2 -> bnc3 and facl_sa_pool
+ * puts it into the features.  Eval (no statistics): prev = the FACL_AMAX_WORDS words of the buffer facl_absmax measured x into. */
+int facl_bn_finalize_after(const double* sums, int C, double count, const float* gamma, const float* beta,
+                           float eps, float momentum, float* running_mean, float* running_var, float* bnc,
+                           uint32_t* aamax, uint32_t* zamax, const float* prev, int nprev, void* stream);
+int facl_bn_eval_consts_after(int C, const float* gamma, const float* beta, const float* running_mean,
+                              const float* running_var, float eps, float* bnc, const float* prev, int nprev, void* stream);
 
 /* ---- set-abstraction point-MLP forward (net3DV_1, cn3d_model_conbag.py:43-58 / :162-177) ----
  * x is the grouped input, (P,D) rows = the memory behind the reference's (M,D,S,K) view, P = M*S*K,
@@ -158,7 +170,8 @@ int facl_sa_eval(const float* x, int64_t nunits, int D, const float* l1tab, cons
                  const float* scale2, const float* shift2, const float* W3, const float* b3, const float* scale3,
                  const float* shift3, float* pooled, const uint32_t* a1amax, void* stream);
 /* ---- fp16x3 operand scales: measured maxima for operands no BatchNorm bounds ----
- *   facl_absmax          raises the slots of `amax` (FACL_AMAX_WORDS uint32, zeroed by the caller or pre-seeded) to max|x|
+ *   facl_absmax          raises the slots of `amax` (FACL_AMAX_WORDS uint32, zeroed by the caller or pre-seeded) to max|x| over
+ *                        the FINITE elements of x; a NaN / inf element raises word 1 of the buffer (no slot) to NaN bits instead
  *   facl_rows_act_amax   the same for max relu(scale[c] y[r][c] + shift[c]) of a (R,C) array (eval-mode layers: running
  *                        statistics say nothing about the data) */
 int facl_absmax(const float* x, int64_t n, uint32_t* amax, void* stream);

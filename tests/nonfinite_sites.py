@@ -1,0 +1,407 @@
+"""Where the non-finite-data tests put a NaN or an inf, and what the torch fp64 reference does there.
+
+One table for tests/test_nonfinite_cpu.py (which evaluates the reference for every case on the CPU and records the outcome) and
+tests/test_gpu_nonfinite.py (which holds the HIP path to exactly that outcome).  A case names a *site* -- an element of an
+input or of a parameter -- and a *value* of VALUES.  Every expectation is computed here from the plain torch reference
+(oracle/encoder.py, oracle/loss.py, oracle/grouping.py, helpers.forward64, torch.optim.Adam); none is written down and none
+comes from the code under test.  Inputs are built on the CPU from seeded generators, so both test files see the same bits."""
+import functools
+
+import numpy as np
+import torch
+
+VALUES = {"nan": float("nan"), "+inf": float("inf"), "-inf": float("-inf")}
+UNIT = 64
+
+SA_KEYS = {"W1": "net3DV_1.0.weight", "b1": "net3DV_1.0.bias", "g1": "net3DV_1.1.weight", "be1": "net3DV_1.1.bias",
+           "W2": "net3DV_1.3.weight", "b2": "net3DV_1.3.bias", "g2": "net3DV_1.4.weight", "be2": "net3DV_1.4.bias",
+           "W3": "net3DV_1.6.weight", "b3": "net3DV_1.6.bias", "g3": "net3DV_1.7.weight", "be3": "net3DV_1.7.bias"}
+SA_BUFFERS = {"rm1": "net3DV_1.1.running_mean", "rv1": "net3DV_1.1.running_var", "rm2": "net3DV_1.4.running_mean",
+              "rv2": "net3DV_1.4.running_var", "rm3": "net3DV_1.7.running_mean", "rv3": "net3DV_1.7.running_var"}
+# one element of each parameter a checkpoint could hold a NaN in (flat index into the tensor)
+SA_PARAM_ELEMENT = {"W1": 5 * 4 + 1, "b1": 7, "g2": 9, "W2": 11 * 64 + 13, "W3": 100 * 64 + 17, "b3": 200, "be3": 31}
+
+
+def _case(**kw):
+    kw["id"] = "-".join(str(kw[k]) for k in sorted(kw) if k != "id")
+    return kw
+
+
+# ---- (a) the SA block in training mode -------------------------------------------------------------------------------------------
+# groups: groups of K rows; 7 and 1026 units of 64 rows lie one below and one above a grid boundary of the SA passes
+def _sa_train_cases():
+    out = []
+    for groups in (7, 1026):
+        for value in VALUES:
+            for site, D in (("x_coord", 4), ("x_feat", 4), ("x_feat", 8), ("x_first", 4), ("x_last", 4)):
+                out.append(_case(groups=groups, K=64, D=D, site=site, value=value, precision="f32"))
+    for value in VALUES:
+        out.append(_case(groups=7, K=16, D=4, site="x_coord", value=value, precision="f32"))       # replicated x4: an original row
+        out.append(_case(groups=513, K=128, D=4, site="x_coord", value=value, precision="f32"))    # a group spans two units
+    for groups in (7, 1026):
+        for site in SA_PARAM_ELEMENT:
+            out.append(_case(groups=groups, K=64, D=4, site=site, value="nan", precision="f32"))
+    for prec, site in (("x3", "x_coord"), ("x3b", "x_feat"), ("f16", "x_last")):
+        out.append(_case(groups=7, K=64, D=4, site=site, value="nan", precision=prec))
+    return out
+
+
+SA_TRAIN_CASES = _sa_train_cases()
+
+# ---- (b) the SA block in eval mode on the paths test_sa_eval_one_kernel_vs_training_kernels_and_fp64 does not reach -------------
+# path: "fused" (the default one-kernel path), "unfused" (_EVAL_FUSED = False), or an opt-in precision (never fused)
+SA_EVAL_CASES = [_case(groups=g, K=64, D=4, site="x_coord", value=v, path=p)
+                 for p, gs in (("fused", (7, 1026)), ("unfused", (7, 1026)), ("x3", (7,)), ("f16", (7,)))
+                 for g in gs for v in ("nan", "+inf")]
+
+# ---- (c) the SA backward: finite forward, one non-finite element of dpooled ------------------------------------------------------
+SA_BWD_CASES = [_case(groups=g, K=64, D=4, value=v) for g in (7, 1026) for v in ("nan", "+inf")]
+
+
+def sa_inputs(case):
+    """(x_rows (groups*K, D) fp32 with the value at an x site, numpy state_dict with the value at a parameter site)."""
+    from oracle.weights import formula_state_dict
+    groups, K, D, site = case["groups"], case["K"], case["D"], case.get("site")
+    gen = torch.Generator().manual_seed(1000 * groups + 10 * K + D)
+    x = ((torch.rand(groups * K, D, generator=gen) - 0.5) * 0.8).contiguous()
+    sd = {k: np.array(v) for k, v in formula_state_dict(D).items()}
+    v = VALUES[case["value"]] if site is not None else None
+    P = x.shape[0]
+    if site == "x_coord":
+        x[P // 2 + 3, 1] = v
+    elif site == "x_feat":
+        x[P // 3, D - 1] = v                      # the last feature column
+    elif site == "x_first":
+        x[0, 0] = v
+    elif site == "x_last":
+        x[P - 1, 2] = v                           # the last row of the last unit
+    elif site in SA_PARAM_ELEMENT:
+        sd[SA_KEYS[site]].reshape(-1)[SA_PARAM_ELEMENT[site]] = v
+    elif site is not None:
+        raise KeyError(site)
+    return x, sd
+
+
+def _xt(x_rows, K):
+    """(P, D) grouped rows -> the (1, D, groups, K) tensor the oracle's Conv2d stack takes."""
+    P, D = x_rows.shape
+    return x_rows.view(1, P // K, K, D).permute(0, 3, 1, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _sa_forward_reference(key, training):
+    from test_gpu_sa_mlp import _oracle_pooled
+    case = dict(key)
+    x, sd = sa_inputs(case)
+    pooled, sd64 = _oracle_pooled(sd, _xt(x, case["K"]), training, torch.float64)
+    return {"pooled": pooled, "buffers": {k: sd64[v] for k, v in SA_BUFFERS.items()}}
+
+
+def sa_reference(case, training=True):
+    """{"pooled": (groups, 256) fp64, "buffers": {rm1..rv3: fp64 after the forward}} of _oracle_pooled on the case's inputs.
+    Computed once per case and shared; callers must not modify it."""
+    return _sa_forward_reference(tuple(sorted(case.items())), training)
+
+
+def sa_bwd_element(case):
+    """The element (group, channel) of dpooled that takes the value: where the reference's finite forward is largest, so that
+    the ReLU behind the max-pool is open there and the value reaches the layers below."""
+    ref = sa_reference(dict(case, site=None), True)["pooled"]
+    return divmod(int(ref.argmax()), 256)
+
+
+@functools.lru_cache(maxsize=None)
+def _sa_bwd_reference(key):
+    import torch.nn.functional as F
+    from oracle import encoder as E
+    case = dict(key)
+    x, sd = sa_inputs(dict(case, site=None))
+    sdr = {k: (torch.as_tensor(v).double() if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v).clone()) for k, v in sd.items()}
+    for k in SA_KEYS.values():
+        sdr[k].requires_grad_(True)
+    h = _xt(x, case["K"]).double()
+    for li in (0, 3, 6):
+        h = E._conv_bn_relu(sdr, "net3DV_1", li, h, True)
+    pl = F.max_pool2d(h, (1, case["K"]), stride=1).squeeze(-1).permute(0, 2, 1).reshape(-1, 256)
+    (pl * sa_bwd_upstream(case).double()).sum().backward()
+    return {k: sdr[v].grad for k, v in SA_KEYS.items()}
+
+
+def sa_bwd_upstream(case):
+    """dpooled (groups, 256) fp32: seeded noise with the case's value in one element."""
+    up = torch.randn((case["groups"], 256), generator=torch.Generator().manual_seed(case["groups"]))
+    g, c = sa_bwd_element(case)
+    up[g, c] = VALUES[case["value"]]
+    return up
+
+
+def sa_bwd_reference(case):
+    """{W1, b1, ...: fp64 autograd gradient} of the oracle's net3DV_1 for sa_bwd_upstream(case)."""
+    return _sa_bwd_reference(tuple(sorted(case.items())))
+
+
+# ---- (d) the whole model and the contrastive losses, training mode, values injected behind the grouping --------------------------
+# tail "rs": M*S = 2048 rows, the row-streamed kernels; "fb": M*S = 128 rows, the fallback (linear_bn_relu)
+MODEL_SHAPES = {"rs": dict(M=32, S=64, K=64, G=4, D=4), "fb": dict(M=8, S=16, K=64, G=4, D=4)}
+MODEL_PARAM_ELEMENT = {"net3DV_3.3.weight": 3 * 256 + 7, "netR_FC.1.weight": 11, "netR_FC.3.bias": 5}
+COSINE_MODE = dict(normalize=True, temperature=0.1)
+
+
+def _model_cases():
+    out = []
+    for tail in MODEL_SHAPES:
+        for site in ("yt_centre", "xt_feat"):
+            for value in VALUES:
+                out.append(_case(tail=tail, site=site, value=value, loss="default"))
+        for site in MODEL_PARAM_ELEMENT:
+            out.append(_case(tail=tail, site=site, value="nan", loss="default"))
+        out.append(_case(tail=tail, site="xt_feat", value="nan", loss="cosine"))
+        out.append(_case(tail=tail, site="queue_row", value="nan", loss="queue"))
+    return out
+
+
+MODEL_CASES = _model_cases()
+QUEUE_L, QUEUE_VALID = 16, 8                       # slots of the negative queue and how many of them are filled
+
+
+def model_inputs(case):
+    """(x_rows (M*S*K, D), centers (M*S, 3), numpy state_dict, order, queue rows or None), all on the CPU.  The rows stand for
+    the output of the grouping: the values go in behind it, so no grouping kernel ever sees a non-finite centroid."""
+    from oracle.weights import formula_state_dict
+    c = MODEL_SHAPES[case["tail"]]
+    M, S, K, G, D = c["M"], c["S"], c["K"], c["G"], c["D"]
+    gen = torch.Generator().manual_seed(M * S)
+    x = ((torch.rand(M * S * K, D, generator=gen) - 0.5) * 0.4).contiguous()
+    cen = ((torch.rand(M * S, 3, generator=gen) - 0.5)).contiguous()
+    sd = {k: np.array(v) for k, v in formula_state_dict(D).items()}
+    queue = None
+    site, v = case["site"], VALUES[case["value"]]
+    if case["loss"] == "queue":
+        queue = torch.randn(QUEUE_VALID, 512, generator=gen) * 0.1
+    if site == "yt_centre":
+        cen[5 * S + 3, 1] = v                      # a centre coordinate: the rank-3 epilogue of the first tail GEMM
+    elif site == "xt_feat":
+        x[(7 * S + 2) * K + 9, D - 1] = v          # a neighbour's feature channel
+    elif site == "queue_row":
+        queue[QUEUE_VALID - 2, 100] = v            # inside the queue's valid rows
+    elif site in MODEL_PARAM_ELEMENT:
+        sd[site].reshape(-1)[MODEL_PARAM_ELEMENT[site]] = v
+    else:
+        raise KeyError(site)
+    order = np.random.RandomState(3).permutation(G)
+    return x, cen, sd, order, queue
+
+
+def loss64(case, x, xg, G, B, order, queue=None):
+    """The two losses of the reference (oracle/loss.py) on embeddings of any dtype / device.  "cosine": the rows are
+    F.normalize'd and scaled by 1 / sqrt(tau) first (the similarities are then cosines over tau).  "queue": the queue's valid
+    rows are further negative columns of every anchor, as MoCo's: evaluated in closed form, log-sum-exp over [negatives | queue].
+    The queue branch is written here, not in oracle/loss.py, and is anchored only by its identity with oracle.loss on an empty
+    queue (test_nonfinite_cpu.py): enough for the FINITENESS these tests compare, not a value reference for other tests."""
+    from oracle import loss as OL
+    if case["loss"] == "cosine":
+        s = 1.0 / np.sqrt(COSINE_MODE["temperature"])
+        x, xg = torch.nn.functional.normalize(x, dim=1) * s, torch.nn.functional.normalize(xg, dim=1) * s
+    if case["loss"] != "queue":
+        return OL.global_contrast(G, xg, x, B), OL.circle_contrast(G, x, B, order)
+    q = queue.to(x.device, x.dtype)
+    mask = OL._mask(B, G, x.device).to(x.dtype)
+    neg = torch.cat(((xg @ x.t()) * mask, xg @ q.t()), dim=1)
+    pos = (xg.unsqueeze(0) * x.view(G, B, -1)).sum(-1)
+    lc = (torch.logaddexp(pos, torch.logsumexp(neg, dim=1).unsqueeze(0)) - pos).mean(dim=1).sum()
+    xv = x.view(G, B, -1)
+    o = torch.as_tensor(np.asarray(order), dtype=torch.long, device=x.device)
+    anchors = xv[o[:-1]]
+    pos = (anchors * xv[o[1:]]).sum(-1)
+    mask = OL._mask(B, G * (G - 1), x.device).to(x.dtype)
+    neg = torch.stack([a @ x.t() for a in anchors]).permute(1, 0, 2).reshape(B, -1) * mask
+    negq = torch.stack([a @ q.t() for a in anchors]).permute(1, 0, 2).reshape(B, -1)
+    lo = (torch.logaddexp(pos, torch.logsumexp(torch.cat((neg, negq), dim=1), dim=1).unsqueeze(0)) - pos).mean(dim=1).sum()
+    return lc, lo
+
+
+_MODEL_REF = {}
+
+
+def model_reference(case, device="cpu"):
+    """{"loss": float, "x": (M, 512) fp64, "xg": (B, 512) fp64} of helpers.forward64 (no routing) + loss64 for the case, evaluated
+    in fp64 on `device` (finiteness does not depend on it).  Computed once per case and shared."""
+    from helpers import forward64
+    if case["id"] not in _MODEL_REF:
+        c = MODEL_SHAPES[case["tail"]]
+        x_rows, cen, sd, order, queue = model_inputs(case)
+        with torch.no_grad():
+            x, xg, _, _, _ = forward64(x_rows.to(device), cen.to(device), sd, c["G"], c["S"], c["K"], device)
+            lc, lo = loss64(case, x, xg, c["G"], c["M"] // c["G"], order, queue)
+        _MODEL_REF[case["id"]] = {"loss": float(lc + lo), "x": x.cpu(), "xg": xg.cpu()}
+    return _MODEL_REF[case["id"]]
+
+
+# ---- (e) one training step on a clip that is finite first and holds a NaN feature value afterwards --------------------------------
+STEP_SHAPE = dict(B=2, G=4, N=512, D=4)             # SAMPLE_NUM 512: the step groups with K = 64, r^2 = 0.06
+STEP_ELEMENT = (1, 2, 3, 3)                         # (clip, view, point, channel): the feature of a centroid point (index < 64)
+
+
+def step_inputs():
+    """([first clip batch, second clip batch] (B,G,N,D) fp32, numpy state_dict, order): the second batch holds one NaN."""
+    from oracle.weights import formula_state_dict
+    c = STEP_SHAPE
+    gen = torch.Generator().manual_seed(11)
+    clips = [torch.rand(c["B"], c["G"], c["N"], c["D"], generator=gen) - 0.5 for _ in range(2)]
+    clips[1][STEP_ELEMENT] = float("nan")
+    return clips, {k: np.array(v) for k, v in formula_state_dict(c["D"]).items()}, np.random.RandomState(5).permutation(c["G"])
+
+
+@functools.lru_cache(maxsize=None)
+def step_reference(k):
+    """Loss of the reference's step on batch k (oracle grouping -> encoder in fp64, train mode -> global + circle loss), each
+    batch at the INITIAL weights: a NaN input makes every batch statistic NaN whatever the finite weights are, so the
+    finiteness of the second loss does not depend on the update in between."""
+    from oracle import encoder as E, grouping as OG, loss as OL
+    c = STEP_SHAPE
+    B, G, N, D = c["B"], c["G"], c["N"], c["D"]
+    clips, sd, order = step_inputs()
+    pts = clips[k].permute(1, 0, 2, 3).reshape(-1, N, D).numpy()
+    _, xt, yt = OG.group_points(pts, 64, 64, 0.06)
+    sd = {n: (torch.as_tensor(v).double() if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v).clone()) for n, v in sd.items()}
+    with torch.no_grad():
+        x, _, _, xg = E.encoder_forward(sd, torch.from_numpy(xt).permute(0, 3, 1, 2).double(),
+                                        torch.from_numpy(yt).view(G * B, 1, 64, 3).transpose(1, 3).double(), G, training=True)
+        return float(OL.global_contrast(G, xg, x, B) + OL.circle_contrast(G, x, B, order))
+
+
+# ---- (g) the training entry on a dataset on disk with one NaN feature value -------------------------------------------------------
+ENTRY = dict(clips=24, B=4, iteration=1, row=5)      # the NaN goes into the first clip the sampler draws in `iteration` of epoch 0
+
+
+def _entry_clip(seed, P, Kp=300, R1=400, R2=150):
+    """The four (rows, 8) float64 clouds of one video, as tests/test_gpu_dataset.py builds them."""
+    r = np.random.RandomState(seed)
+    pts = r.rand(P, 8) - 0.5
+    pts[r.rand(P) < 0.3, 4] = 0
+    pts[r.rand(P) < 0.5, 7] = 0
+    pts[0, 4] = pts[0, 7] = 0.25
+    return pts, r.rand(Kp, 8) - 0.5, r.rand(R1, 8) - 0.5, r.rand(R2, 8) - 0.5
+
+
+def entry_tree(root, column=3, value=float("nan")):
+    """Writes the appearance-branch dataset (the tree of tests/test_gpu_dataset.py: cameras 2 / 3 train, 1 test) under `root`
+    with `value` in `column` (3: the feature channel; 0..2: a coordinate, which the loaders refuse) of one row of one clip.  Returns (name of that clip, [names of batch 0, ..., batch `iteration`]):
+    the batches of epoch 0 in the order the entry's sampler draws them (facl_amd.dataset.train_batches, seed 1)."""
+    import os
+    from facl_amd import dataset as fds
+    root = str(root)
+    names = ["S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4) for i in range(ENTRY["clips"])]
+    for i, nm in enumerate(names):
+        clip = _entry_clip(200 + i, 600 + 7 * i)
+        for branch in ("0", "1"):                    # branch '0' files: the folder the appearance entry lists its clips from
+            for p, a in zip(fds.clip_paths(root, nm, branch), clip):
+                os.makedirs(os.path.dirname(p), exist_ok=True)
+                np.save(p, a)
+    index = fds.ClipIndex.from_dir(os.path.join(root, fds.TRAIN_LIST_DIR["1"]), "ntu120")
+    split = np.asarray(index.select("view", full_train=True), dtype=np.int64)
+    pos = fds.train_batches(len(split), ENTRY["B"], 1, 0, 1, 0)
+    batches = [[index.v_name(int(split[p])) for p in pos[i]] for i in range(ENTRY["iteration"] + 1)]
+    bad = batches[-1][0]
+    path = fds.clip_paths(root, bad, "1")[0]
+    pts = np.load(path)
+    pts[ENTRY["row"], column] = value
+    np.save(path, pts)
+    return bad, batches
+
+
+def entry_reference(root, batches):
+    """Loss of the reference pipeline on the last batch of `batches`: oracle.views on every clip of every batch up to it, in
+    sampler order from RandomState(2000) (the stream the entry draws its views from), then the oracle grouping, encoder
+    (fp64, train mode, formula weights: a NaN input makes every batch statistic NaN whatever the finite weights are) and losses."""
+    from facl_amd import dataset as fds
+    from oracle import encoder as E, grouping as OG, loss as OL, views as OV
+    from oracle.weights import formula_state_dict
+    rng = np.random.RandomState(2000)
+    for names in batches:
+        items = [OV.get_item(rng, *[np.load(p) for p in fds.clip_paths(str(root), nm, "1")]) for nm in names]
+    views = OV.collate_view_major(items)
+    G, B = 10, len(items)
+    with np.errstate(all="ignore"):
+        _, xt, yt = OG.group_points(views, 64, 64, 0.06)
+    sd = {n: (torch.as_tensor(v).double() if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v).clone())
+          for n, v in formula_state_dict(4).items()}
+    with torch.no_grad():
+        x, _, _, xg = E.encoder_forward(sd, torch.from_numpy(xt).permute(0, 3, 1, 2).double(),
+                                        torch.from_numpy(yt).view(G * B, 1, 64, 3).transpose(1, 3).double(), G, training=True)
+        loss = float(OL.global_contrast(G, xg, x, B) + OL.circle_contrast(G, x, B, np.arange(G)))
+    return loss, views
+
+
+# ---- (f) grouping: a non-finite value in a point that is no centroid ---------------------------------------------------------------
+# D = 4 gathers the feature from LDS, D = 8 from global memory; K <= N - 2: the bad point's key sorts behind K real ones
+def _group_cases():
+    out = []
+    for D in (4, 8):
+        for N, S, K in ((100, 16, 32), (512, 64, 64)):
+            for site in ("coord", "feat"):
+                for value in ("nan", "+inf"):
+                    out.append(_case(D=D, N=N, S=S, K=K, site=site, value=value))
+    return out
+
+
+GROUP_CASES = _group_cases()
+GROUP_M, GROUP_R2 = 4, 0.06                         # the (B, G) = (2, 2) clip-major twin holds the same 4 clouds
+
+
+def group_inputs(case):
+    """(M, N, D) fp32 clouds; cloud 1 holds the value in a point of index >= S, near centroid 0 in the finite coordinates."""
+    N, S, D = case["N"], case["S"], case["D"]
+    pts = (np.random.RandomState(N + D).rand(GROUP_M, N, D) - 0.5).astype(np.float32)
+    bad = S + 5
+    pts[1, bad, :3] = pts[1, 0, :3] + np.float32(0.01)          # a close neighbour of centroid 0: it is grouped when it is finite
+    pts[1, bad, {"coord": 2, "feat": D - 1}[case["site"]]] = VALUES[case["value"]]
+    return pts
+
+
+@functools.lru_cache(maxsize=None)
+def _group_reference(key):
+    from oracle import grouping as OG
+    case = dict(key)
+    with np.errstate(all="ignore"):
+        return OG.group_points(group_inputs(case), case["S"], case["K"], GROUP_R2)
+
+
+def group_reference(case):
+    """(idx (M,S,K) ascending, xt (M,S,K,D), yt (M,S,3)) of oracle.grouping.group_points."""
+    return _group_reference(tuple(sorted(case.items())))
+
+
+# ---- (h) Adam: a non-finite gradient element ---------------------------------------------------------------------------------------
+ADAM_SIZES = (5, 2049, 300)                         # tensors of the list; the value goes into tensor 1
+ADAM_ELEMENT = (1, 2047)                            # (tensor, element): the last element of a 2048-element chunk
+ADAM_HYPER = dict(lr=3e-4, eps=1e-6)
+ADAM_CASES = [_case(value=v, max_grad_norm=m) for v in VALUES for m in (0.0, 1.0)]
+
+
+def adam_inputs(case):
+    gen = torch.Generator().manual_seed(5)
+    ps = [torch.randn(n, generator=gen) for n in ADAM_SIZES]
+    gs = [0.05 * torch.randn(n, generator=gen) for n in ADAM_SIZES]
+    gs[ADAM_ELEMENT[0]][ADAM_ELEMENT[1]] = VALUES[case["value"]]
+    return ps, gs
+
+
+def adam_reference(case):
+    """[(param, exp_avg, exp_avg_sq)] fp64 after one step of torch.optim.Adam (after clip_grad_norm_ when the case clips), and
+    the norm clip_grad_norm_ returned (None without clipping).  betas: helpers.FUSED_ADAM_BETAS (the kernels hold them in fp32)."""
+    from helpers import FUSED_ADAM_BETAS
+    ps, gs = adam_inputs(case)
+    ps = [p.double().requires_grad_(True) for p in ps]
+    for p, g in zip(ps, gs):
+        p.grad = g.double()
+    norm = None
+    if case["max_grad_norm"]:
+        norm = float(torch.nn.utils.clip_grad_norm_(ps, case["max_grad_norm"]))
+    opt = torch.optim.Adam(ps, betas=FUSED_ADAM_BETAS, foreach=False, **ADAM_HYPER)
+    opt.step()
+    return [(p.detach(), opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"]) for p in ps], norm
+
+
+def ids(cases):
+    return [c["id"] for c in cases]

@@ -104,6 +104,11 @@ SIGNATURES = {
     "facl_build_views_resident_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
     "facl_build_views_resident_gp_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
     "facl_build_views_resident_gp_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
+    "facl_build_views_philox_recipe_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
+    "facl_build_views_philox_recipe_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
+    "facl_build_views_resident_recipe_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
+    "facl_build_views_resident_recipe_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
+    "facl_view_recipe_table": [c_p, c_i, c_p, c_p],
     "facl_sa_bwd0": [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p],
     "facl_sa_bwd1": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_sa_bwd_w3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
@@ -193,6 +198,12 @@ def check(rc, what):
 
 
 AMAX_WORDS = 2048          # include/facl_hip.h: FACL_AMAX_WORDS
+
+# include/facl_hip.h: FACL_VIEW_<NAME>, the kind codes of a view recipe in code order, and the recipe's sizes
+VIEW_KINDS = ("raw", "mirror", "key", "key_mirror", "rot", "t4", "t7", "res30", "res10", "jitter", "scale", "tilt_neg", "tilt_pos")
+VIEW_POS_MAX = 12          # FACL_VIEW_POS_MAX: positions of a round at most
+VIEW_NSTRENGTH = 6         # FACL_VIEW_NSTRENGTH: jitter_sigma, jitter_clip, rot_range, scale_lo, scale_hi, tilt_angle
+VIEW_TABLE_COLS = 8        # FACL_VIEW_TABLE_COLS: int32 words per position of facl_view_recipe_table
 
 # include/facl_hip.h: the input widths of grouping and the SA point-MLP, and the D-dependent layer-1 layouts
 SA_D_MIN, SA_D_MAX = 3, 8  # FACL_SA_D_MIN, FACL_SA_D_MAX

@@ -6,14 +6,111 @@
 // required to be equal bit for bit).  Include inside an anonymous namespace, after common.h.  The recipe is written out
 // in the header of views_philox.hip and restated in NumPy by facl_amd/philox.py.
 //
-// G views of P points per clip (both run-time arguments): view v is of KIND k = v % 10 (the reference's ten views) in
-// ROUND r = v / 10; every draw slot of round r is the kind's slot + 32 * r, the point index n runs over 0..P-1.
+// G views of P points per clip (both run-time arguments) by a RECIPE: a list of L = 1..12 kinds (the positions of a round)
+// and six strengths.  View v is of the kind at position v % L in ROUND r = v / L; every draw slot of round r is the
+// position's slot + stride * r, the point index n runs over 0..P-1.  The default recipe is the reference's ten views at the
+// reference's strengths (stride 32).  The host derives a descriptor per position (view_recipe_make) and the kernels take
+// the whole recipe BY VALUE in their arguments: no device allocation, no copy, no launch of its own.
 
-constexpr int KINDS = 10;                 // the reference's ten views = the kinds of a round
-constexpr int ROUND_SLOTS = 32;           // counter slots per round (26 in use: rows 0..2, jitter 3..23, angles 24, 25)
+constexpr int KINDS = 10;                 // the reference's ten views = the positions of a round of the default recipe
+constexpr int ROUND_SLOTS = 32;           // counter slots per round of the default recipe (a recipe's own: its stride)
 constexpr int CHUNK = 512;                // points per workgroup at most (the reference's cloud: one workgroup per view)
 constexpr int G_MAX = 64, P_MIN = 64, P_MAX = 4096;
 constexpr int TR_THREADS = 256;           // temporal-row compaction: 4 waves, 256 rows per pass
+
+// what a position does with its gathered row (after the first jitter, which every operation but OP_GATHER starts with)
+enum { OP_GATHER = 0, OP_JITTER, OP_MIRROR, OP_ROT, OP_SCALE, OP_TILT_NEG, OP_TILT_POS };
+// where its row comes from: the four source clouds, or the rows of the point cloud with a non-zero channel 4 / 7
+enum { SRC_POINTS = 0, SRC_KEY, SRC_RES1, SRC_RES2, SRC_T4, SRC_T7 };
+
+// one position of a round; slots are relative to the round's first.  jit0 / jit1: the jitter draw j (slots 3 + 3 j + d)
+struct ViewPos { uint8_t src, ch, op, row_slot, row_word, jit0, jit1, scalar; };
+
+struct ViewRecipe {
+    int n, stride;                        // positions of a round; counter slots per round
+    ViewPos pos[FACL_VIEW_POS_MAX];
+    double sigma, clip, rot_range, scale_lo, scale_hi, tilt_cos, tilt_sin;     // cos / sin of +pi * tilt_angle
+};
+
+constexpr int32_t DEFAULT_KINDS[KINDS] = {FACL_VIEW_RAW, FACL_VIEW_MIRROR, FACL_VIEW_KEY, FACL_VIEW_KEY_MIRROR, FACL_VIEW_ROT,
+                                          FACL_VIEW_ROT, FACL_VIEW_T4, FACL_VIEW_T7, FACL_VIEW_RES30, FACL_VIEW_RES10};
+constexpr double DEFAULT_STRENGTHS[FACL_VIEW_NSTRENGTH] = {0.01, 0.05, 0.8, 0.5, 1.5, 0.25};
+
+// The slot rule, host side.  table (n_kinds, FACL_VIEW_TABLE_COLS) int32 per position: source, channel, operation, row
+// slot, row word, first / second jitter draw j (-1: none), scalar slot (-1: none).  Row word of position i: word i & 3 of
+// slot i >> 2.  Jitter draws are numbered in position order (the mirrored kinds take two, key / rot / jitter / scale /
+// tilt one) and draw j uses slots 3 + 3 j + d.  Scalar draws (rot, scale) are numbered in position order from
+// 3 + 3 max(7, J), J the jitter draws of the round; the stride is that plus the scalar draws, rounded up to 32.  For the
+// default list this is the layout the kernels always had: j = 0..6 on positions 1, 1, 2, 3, 3, 4, 5, scalars 24, 25, stride 32.
+static inline int view_recipe_table(const int32_t* kinds, int n_kinds, int32_t* table, int32_t* stride) {
+    if (!kinds || !table || !stride) return FACL_E_NULL;
+    if (n_kinds < 1 || n_kinds > FACL_VIEW_POS_MAX) return FACL_E_SHAPE;
+    int J = 0, A = 0;
+    for (int i = 0; i < n_kinds; ++i) {
+        const int k = kinds[i];
+        if (k < 0 || k >= FACL_VIEW_NKINDS) return FACL_E_SHAPE;
+        J += (k == FACL_VIEW_MIRROR || k == FACL_VIEW_KEY_MIRROR) ? 2
+             : (k == FACL_VIEW_KEY || k == FACL_VIEW_ROT || k >= FACL_VIEW_JITTER) ? 1 : 0;
+    }
+    const int scalar0 = 3 + 3 * (J > 7 ? J : 7);
+    int j = 0;
+    for (int i = 0; i < n_kinds; ++i) {
+        const int k = kinds[i];
+        int32_t* t = table + i * FACL_VIEW_TABLE_COLS;
+        int src = SRC_POINTS, ch = 3, op = OP_GATHER;
+        switch (k) {
+            case FACL_VIEW_MIRROR: op = OP_MIRROR; break;
+            case FACL_VIEW_KEY: src = SRC_KEY; op = OP_JITTER; break;
+            case FACL_VIEW_KEY_MIRROR: src = SRC_KEY; op = OP_MIRROR; break;
+            case FACL_VIEW_ROT: op = OP_ROT; break;
+            case FACL_VIEW_T4: src = SRC_T4; ch = 4; break;
+            case FACL_VIEW_T7: src = SRC_T7; ch = 7; break;
+            case FACL_VIEW_RES30: src = SRC_RES1; break;
+            case FACL_VIEW_RES10: src = SRC_RES2; break;
+            case FACL_VIEW_JITTER: op = OP_JITTER; break;
+            case FACL_VIEW_SCALE: op = OP_SCALE; break;
+            case FACL_VIEW_TILT_NEG: op = OP_TILT_NEG; break;
+            case FACL_VIEW_TILT_POS: op = OP_TILT_POS; break;
+            default: break;                                       // FACL_VIEW_RAW
+        }
+        t[0] = src; t[1] = ch; t[2] = op; t[3] = i >> 2; t[4] = i & 3;
+        t[5] = op != OP_GATHER ? j++ : -1;
+        t[6] = op == OP_MIRROR ? j++ : -1;
+        t[7] = (op == OP_ROT || op == OP_SCALE) ? scalar0 + A++ : -1;
+    }
+    *stride = 32 * ((scalar0 + A + 31) / 32);
+    return 0;
+}
+
+// the recipe a kernel takes, from the caller's HOST arrays; every refusal of the C ABI's recipe entries is made here
+static inline int view_recipe_make(const int32_t* kinds, int n_kinds, const double* st, ViewRecipe* rc) {
+    if (!kinds || !st) return FACL_E_NULL;
+    int32_t table[FACL_VIEW_POS_MAX * FACL_VIEW_TABLE_COLS], stride = 0;
+    const int e = view_recipe_table(kinds, n_kinds, table, &stride);
+    if (e != 0) return e;
+    for (int i = 0; i < FACL_VIEW_NSTRENGTH; ++i)
+        if (!std::isfinite(st[i])) return FACL_E_SHAPE;
+    if (st[0] < 0.0 || st[1] <= 0.0 || st[2] < 0.0 || st[2] > 2.0 || st[3] <= 0.0 || st[3] > st[4]) return FACL_E_SHAPE;
+    *rc = ViewRecipe{};
+    rc->n = n_kinds;
+    rc->stride = stride;
+    for (int i = 0; i < n_kinds; ++i) {
+        const int32_t* t = table + i * FACL_VIEW_TABLE_COLS;
+        rc->pos[i] = {(uint8_t)t[0], (uint8_t)t[1], (uint8_t)t[2], (uint8_t)t[3], (uint8_t)t[4], (uint8_t)t[5], (uint8_t)t[6],
+                      (uint8_t)t[7]};
+    }
+    rc->sigma = st[0]; rc->clip = st[1]; rc->rot_range = st[2]; rc->scale_lo = st[3]; rc->scale_hi = st[4];
+    const double tilt = 3.141592653589793 * st[5];
+    rc->tilt_cos = std::cos(tilt);
+    rc->tilt_sin = std::sin(tilt);
+    return 0;
+}
+
+static inline ViewRecipe view_recipe_default() {
+    ViewRecipe rc;
+    view_recipe_make(DEFAULT_KINDS, KINDS, DEFAULT_STRENGTHS, &rc);
+    return rc;
+}
 
 struct u32x4 { uint32_t w[4]; };
 
@@ -34,9 +131,9 @@ __device__ __forceinline__ int draw_row(uint32_t w, int count) {
     return (int)(((unsigned long long)w * (unsigned long long)(uint32_t)count) >> 32);
 }
 
-__device__ __forceinline__ double jit(double n) {          // np.clip(0.01 * n, -0.05, 0.05)
-    const double v = 0.01 * n;
-    return v < -0.05 ? -0.05 : (v > 0.05 ? 0.05 : v);
+__device__ __forceinline__ double jit(double n, double sigma, double clip) {      // np.clip(sigma * n, -clip, clip)
+    const double v = sigma * n;
+    return v < -clip ? -clip : (v > clip ? clip : v);
 }
 
 // what a (clip, view, point) draws with: the key, the clip's dataset index and the epoch
@@ -59,47 +156,135 @@ static inline ViewGrid view_grid(int P) {
     return {threads, (P + threads - 1) / threads};
 }
 
-// where a workgroup stands: clip b of the batch, view v = kind k of round `round`, point n (n >= P: nothing to do)
+// where a workgroup stands: clip b of the batch, view v = position k of the round whose first slot is slot0, point n
+// (n >= P: nothing to do).  b, v, k and slot0 are uniform across the workgroup.
 struct ViewAt { int b, v, k, slot0, n; };
 
-__device__ __forceinline__ ViewAt view_at(int G, int chunks) {
+__device__ __forceinline__ ViewAt view_at(const ViewRecipe& rc, int G, int chunks) {
     const int c = (int)blockIdx.x % chunks, bv = (int)blockIdx.x / chunks;
-    const int v = bv % G;
-    return {bv / G, v, v % KINDS, ROUND_SLOTS * (v / KINDS), c * (int)blockDim.x + (int)threadIdx.x};
+    const int v = bv % G, round = v / rc.n;
+    return {bv / G, v, v - round * rc.n, rc.stride * round, c * (int)blockDim.x + (int)threadIdx.x};
 }
 
-// source cloud of each kind: points 0,0 | key 1,1 | points 0,0 | temporal lists (of cloud 0) | res1 2 | res2 3
-__device__ __forceinline__ int view_source(int k) { return k < 2 ? 0 : (k < 4 ? 1 : (k < 8 ? 0 : k - 6)); }
-
-// the 32-bit word that picks the source row of point n of a view of kind k: draw_row(word, count) in [0, count)
-__device__ __forceinline__ uint32_t view_row_word(const ViewDraw& q, int k, int slot0, int n) {
-    const u32x4 rw = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + (k >> 2)), q.cid, q.epoch, q.k0, q.k1);
-    return rw.w[k & 3];
+// the 32-bit word that picks the source row of point n of a view at position d: draw_row(word, count) in [0, count)
+__device__ __forceinline__ uint32_t view_row_word(const ViewDraw& q, const ViewPos& d, int slot0, int n) {
+    const u32x4 rw = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + d.row_slot), q.cid, q.epoch, q.k0, q.k1);
+    return rw.w[d.row_word];
 }
 
 __device__ __forceinline__ void view_void(float* dst) {    // a view that cannot be drawn: zeros
     *reinterpret_cast<float4*>(dst) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// point n of a view of kind v (slots from slot0 = 32 * round) from its source row r (>= 8 channels): jitter in fp64
-// written back in the source dtype, mirror / rotation on float32, channel select; one float4 store to dst
+// point n of a view at position d (slots from slot0 = stride * round) from its source row r (>= 8 channels): jitter in
+// fp64 written back in the source dtype, mirror / rotation on float32, scale in the source dtype, channel select; one
+// float4 store to dst
 template <typename S>
-__device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDraw& q, int v, int slot0, int n,
-                                           float* __restrict__ dst) {
+__device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDraw& q, const ViewRecipe& rc, const ViewPos& d,
+                                           int slot0, int n, float* __restrict__ dst) {
+    const uint32_t cid = q.cid, epoch = q.epoch, k0 = q.k0, k1 = q.k1;
+    const double sigma = rc.sigma, clip = rc.clip;
+    const int op = d.op;
+    S x[3] = {r[0], r[1], r[2]};
+    const S w = r[d.ch];
+    float o[4];
+    o[3] = (float)w;
+    auto z = [&](int j, int dd) -> double {                    // standard normal of jitter draw j, coordinate dd
+        const u32x4 p = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + 3 + 3 * j + dd), cid, epoch, k0, k1);
+        const double u1 = ((double)p.w[0] + 1.0) * 0x1p-32, u2 = (double)p.w[1] * 0x1p-32;
+        return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    };
+    auto uniform53 = [&]() -> double {                         // the position's scalar draw: one per (clip, view)
+        const u32x4 p = philox4x32_10(0u, (uint32_t)(slot0 + d.scalar), cid, epoch, k0, k1);
+        return ((double)(p.w[0] >> 5) * 67108864.0 + (double)(p.w[1] >> 6)) * 0x1p-53;
+    };
+    auto rotate = [&](double c, double s) {                    // about y, on float32 coordinates (:716-732, :734-749)
+        const double fx = (double)(float)x[0], fy = (double)(float)x[1], fz = (double)(float)x[2];
+        o[0] = (float)(fx * c + fz * (-s));
+        o[1] = (float)fy;
+        o[2] = (float)(fx * s + fz * c);
+    };
+    if (op != OP_GATHER) {                                     // every other operation starts with the jitter (:767-778)
+#pragma unroll
+        for (int dd = 0; dd < 3; ++dd) x[dd] = (S)((double)x[dd] + jit(z(d.jit0, dd), sigma, clip));
+    }
+    if (op == OP_MIRROR) {                                     // reverse_transform (:708-713)
+        float f[3] = {(float)x[0], (float)x[1], (float)x[2]};
+        f[0] = -f[0];
+#pragma unroll
+        for (int dd = 0; dd < 3; ++dd) o[dd] = (float)((double)f[dd] + jit(z(d.jit1, dd), sigma, clip));
+    } else if (op == OP_ROT) {                                 // rotate_trans (:734-749)
+        const double angle = (uniform53() - 0.5) * 3.141592653589793 * rc.rot_range;
+        rotate(cos(angle), sin(angle));
+    } else if (op == OP_TILT_NEG || op == OP_TILT_POS) {       // depth_transform (:716-732): the angle is the host's
+        rotate(rc.tilt_cos, op == OP_TILT_NEG ? -rc.tilt_sin : rc.tilt_sin);
+    } else if (op == OP_SCALE) {                               // scale_trans (:757-763): a Python float times an S array
+        double sc;
+        {
+#pragma clang fp contract(off)
+            sc = rc.scale_lo + (rc.scale_hi - rc.scale_lo) * uniform53();
+        }
+        const S ss = (S)sc;
+#pragma unroll
+        for (int dd = 0; dd < 3; ++dd) o[dd] = (float)(ss * x[dd]);
+    } else {                                                   // gather / jitter alone
+        o[0] = (float)x[0]; o[1] = (float)x[1]; o[2] = (float)x[2];
+    }
+    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// ---- the default recipe as a compile-time specialisation (the kernels' REF = true) ------------------------------------------
+// The reference's ten kinds at the reference's strengths, with the list, the slots and the literals folded into the code: the
+// chain the kernels had before a recipe could be chosen.  It computes exactly what the table-driven code computes at the
+// default recipe (tests/test_gpu_view_recipe.py holds the two to each other bit for bit); it exists because the table-driven
+// form measured slower than it at 24 x 2048 out of the resident pool (DESIGN 3.10.1).  The launchers select it when the
+// recipe IS the default, strengths included.
+static inline bool view_recipe_is_default(const ViewRecipe& rc) {
+    const ViewRecipe d = view_recipe_default();
+    for (int i = 0; i < d.n; ++i) {
+        const ViewPos &a = rc.pos[i], &b = d.pos[i];
+        if (a.src != b.src || a.ch != b.ch || a.op != b.op || a.row_slot != b.row_slot || a.row_word != b.row_word ||
+            a.jit0 != b.jit0 || a.jit1 != b.jit1 || a.scalar != b.scalar)
+            return false;
+    }
+    return rc.n == d.n && rc.stride == d.stride && rc.sigma == d.sigma &&
+           rc.clip == d.clip && rc.rot_range == d.rot_range && rc.scale_lo == d.scale_lo && rc.scale_hi == d.scale_hi &&
+           rc.tilt_cos == d.tilt_cos && rc.tilt_sin == d.tilt_sin;
+}
+
+__device__ __forceinline__ ViewAt view_at_reference(int G, int chunks) {
+    const int c = (int)blockIdx.x % chunks, bv = (int)blockIdx.x / chunks;
+    const int v = bv % G;
+    return {bv / G, v, v % KINDS, ROUND_SLOTS * (v / KINDS), c * (int)blockDim.x + (int)threadIdx.x};
+}
+
+// source of each kind: points 0,0 | key 1,1 | points 0,0 | temporal rows of channel 4, 7 | res1 2 | res2 3
+__device__ __forceinline__ int view_source_reference(int k) {
+    return k < 2 ? SRC_POINTS : (k < 4 ? SRC_KEY : (k < 6 ? SRC_POINTS : (k < 8 ? SRC_T4 + (k - 6) : k - 6)));
+}
+
+__device__ __forceinline__ uint32_t view_row_word_reference(const ViewDraw& q, int k, int slot0, int n) {
+    const u32x4 rw = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + (k >> 2)), q.cid, q.epoch, q.k0, q.k1);
+    return rw.w[k & 3];
+}
+
+template <typename S>
+__device__ __forceinline__ void view_point_reference(const S* __restrict__ r, const ViewDraw& q, int v, int slot0, int n,
+                                                     float* __restrict__ dst) {
     const uint32_t cid = q.cid, epoch = q.epoch, k0 = q.k0, k1 = q.k1;
     const int c3 = v == 6 ? 4 : (v == 7 ? 7 : 3);
     S x[3] = {r[0], r[1], r[2]};
     const S w = r[c3];
     float o[4];
     o[3] = (float)w;
-    auto z = [&](int slot, int d) -> double {                  // standard normal of jitter slot `slot`, coordinate d
+    auto z = [&](int slot, int d) -> double {                  // standard normal of jitter draw `slot`, coordinate d
         const u32x4 p = philox4x32_10((uint32_t)n, (uint32_t)(slot0 + 3 + 3 * slot + d), cid, epoch, k0, k1);
         const double u1 = ((double)p.w[0] + 1.0) * 0x1p-32, u2 = (double)p.w[1] * 0x1p-32;
         return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
     };
     auto jitter_into_src = [&](int slot) {
 #pragma unroll
-        for (int d = 0; d < 3; ++d) x[d] = (S)((double)x[d] + jit(z(slot, d)));
+        for (int d = 0; d < 3; ++d) x[d] = (S)((double)x[d] + jit(z(slot, d), 0.01, 0.05));
     };
     if (v == 1 || v == 3) {                                  // jitter, then reverse_transform (:708-713)
         const int s0 = v == 1 ? 0 : 3;
@@ -107,7 +292,7 @@ __device__ __forceinline__ void view_point(const S* __restrict__ r, const ViewDr
         float f[3] = {(float)x[0], (float)x[1], (float)x[2]};
         f[0] = -f[0];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) o[d] = (float)((double)f[d] + jit(z(s0 + 1, d)));
+        for (int d = 0; d < 3; ++d) o[d] = (float)((double)f[d] + jit(z(s0 + 1, d), 0.01, 0.05));
     } else if (v == 2) {
         jitter_into_src(2);
         o[0] = (float)x[0]; o[1] = (float)x[1]; o[2] = (float)x[2];

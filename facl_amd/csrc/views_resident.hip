@@ -2,7 +2,8 @@
 // into a pool, and a batch is B table positions.  No file is read, nothing is packed and no clip data crosses to the
 // device per step.  The views equal csrc/views_philox.hip's bit for bit: the draw recipe and the per-point arithmetic are
 // the same code (views_philox_point.inc); only the way a drawn position becomes a source row differs.  G views of P
-// points per clip, by the recipe in the header of views_philox.hip (kind v % 10, round v / 10, slots + 32 * round).
+// points per clip, by the recipe in the header of views_philox.hip (default: kind v % 10, round v / 10, slots + 32 * round;
+// any other list of kinds and strengths through the same ViewRecipe, passed by value).
 //
 // Pool (device memory owned by facl_amd/resident.py):
 //   src    (rows_total, 8) in the dataset's one dtype: the clips back to back, each as its four clouds in pack_clips' order
@@ -51,15 +52,16 @@ __global__ __launch_bounds__(TR_THREADS) void k_resident_temporal_rows(const S* 
 }
 
 // workgroup = one (clip of the batch, view, chunk of up to 512 points); thread = one point.  idx_out (B, G, P) int64,
-// optional: the pool row of every point.
-template <typename S>
+// optional: the pool row of every point.  REF: the default recipe folded into the code (views_philox_point.inc).
+template <typename S, bool REF>
 __global__ __launch_bounds__(CHUNK) void k_build_views_resident(const S* __restrict__ src, const int64_t* __restrict__ table,
                                                                 const int32_t* __restrict__ lists, int n_clips,
                                                                 const int32_t* __restrict__ sel, int B, int G, int P,
                                                                 int chunks, int64_t seed, int epoch, float* __restrict__ out,
-                                                                int64_t* __restrict__ idx_out, int32_t* __restrict__ err) {
-    const ViewAt at = view_at(G, chunks);
-    const int b = at.b, k = at.k, n = at.n;
+                                                                int64_t* __restrict__ idx_out, int32_t* __restrict__ err,
+                                                                const ViewRecipe rc) {
+    const ViewAt at = REF ? view_at_reference(G, chunks) : view_at(rc, G, chunks);
+    const int b = at.b, n = at.n;
     if (n >= P) return;                                            // the ragged last chunk of a view
     float* dst = out + (((size_t)at.v * B + b) * P + n) * 4;
     int64_t* io = idx_out ? idx_out + ((size_t)b * G + at.v) * P + n : nullptr;
@@ -70,24 +72,27 @@ __global__ __launch_bounds__(CHUNK) void k_build_views_resident(const S* __restr
         if (io) *io = -1;
         return;
     }
+    const ViewPos d = REF ? ViewPos{} : rc.pos[at.k];
     const int64_t* m = table + (int64_t)pos * REC;
     const ViewDraw q = view_draw(seed, (uint32_t)m[8], epoch);
-    const int src_of = view_source(k);
-    const uint32_t word = view_row_word(q, k, at.slot0, n);
+    const int src_of = REF ? view_source_reference(at.k) : (int)d.src;
+    const uint32_t word = REF ? view_row_word_reference(q, at.k, at.slot0, n) : view_row_word(q, d, at.slot0, n);
     int64_t row;
-    if (k == 6 || k == 7) {
-        const int cnt = (int)m[10 + (k - 6)];
+    if (src_of >= SRC_T4) {
+        const int t = src_of - SRC_T4;
+        const int cnt = (int)m[10 + t];
         if (cnt == 0) {                                            // the ingest raised err for this clip: void views
             view_void(dst);
             if (io) *io = -1;
             return;
         }
-        row = m[0] + lists[2 * m[9] + (k - 6) * m[4] + draw_row(word, cnt)];
+        row = m[0] + lists[2 * m[9] + t * m[4] + draw_row(word, cnt)];
     } else {
         row = m[src_of] + draw_row(word, (int)m[4 + src_of]);
     }
     if (io) *io = row;
-    view_point<S>(src + row * RC, q, k, at.slot0, n, dst);
+    if (REF) view_point_reference<S>(src + row * RC, q, at.k, at.slot0, n, dst);
+    else view_point<S>(src + row * RC, q, rc, d, at.slot0, n, dst);
 }
 
 }  // namespace
@@ -105,14 +110,27 @@ static int launch_resident_rows(const S* src, int64_t* table, int32_t* lists, in
 template <typename S>
 static int launch_views_resident(const S* src, const int64_t* table, const int32_t* lists, int n_clips, const int32_t* sel,
                                  int B, int G, int P, int64_t seed, int epoch, float* out, int64_t* idx_out, int32_t* err,
-                                 void* stream) {
+                                 const ViewRecipe& rc, void* stream) {
     if (!src || !table || !lists || !sel || !out || !err) return FACL_E_NULL;
     if (n_clips < 1 || B < 1 || B > (1 << 20) || !views_gp_ok(G, P)) return FACL_E_SHAPE;
     if (reinterpret_cast<uintptr_t>(out) % 16) return FACL_E_ALIGN;
     const ViewGrid g = view_grid(P);
-    hipLaunchKernelGGL((k_build_views_resident<S>), dim3((unsigned)B * G * g.chunks), dim3(g.threads), 0, (hipStream_t)stream,
-                       src, table, lists, n_clips, sel, B, G, P, g.chunks, seed, epoch, out, idx_out, err);
+    const auto kernel = view_recipe_is_default(rc) ? k_build_views_resident<S, true> : k_build_views_resident<S, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B * G * g.chunks), dim3(g.threads), 0, (hipStream_t)stream, src, table, lists,
+                       n_clips, sel, B, G, P, g.chunks, seed, epoch, out, idx_out, err, rc);
     return facl_launch_status();
+}
+
+// the recipe entries: the caller's HOST arrays are checked and turned into the recipe first (no launch on a refusal)
+template <typename S>
+static int launch_views_resident_recipe(const S* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                        const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                        int64_t* idx_out, int32_t* err, const int32_t* kinds, int n_kinds,
+                                        const double* strengths, void* stream) {
+    ViewRecipe rc;
+    const int e = view_recipe_make(kinds, n_kinds, strengths, &rc);
+    if (e != 0) return e;
+    return launch_views_resident<S>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, rc, stream);
 }
 
 extern "C" int facl_resident_temporal_rows_f32(const float* src, int64_t* table, int32_t* lists, int first, int count,
@@ -128,23 +146,43 @@ extern "C" int facl_resident_temporal_rows_f64(const double* src, int64_t* table
 extern "C" int facl_build_views_resident_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
                                              const int32_t* sel, int B, int64_t seed, int epoch, float* out,
                                              int64_t* idx_out, int32_t* err, void* stream) {
-    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, KINDS, CHUNK, seed, epoch, out, idx_out, err, stream);
+    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, KINDS, CHUNK, seed, epoch, out, idx_out, err,
+                                        view_recipe_default(), stream);
 }
 
 extern "C" int facl_build_views_resident_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
                                              const int32_t* sel, int B, int64_t seed, int epoch, float* out,
                                              int64_t* idx_out, int32_t* err, void* stream) {
-    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, KINDS, CHUNK, seed, epoch, out, idx_out, err, stream);
+    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, KINDS, CHUNK, seed, epoch, out, idx_out, err,
+                                        view_recipe_default(), stream);
 }
 
 extern "C" int facl_build_views_resident_gp_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
                                                 const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
                                                 int64_t* idx_out, int32_t* err, void* stream) {
-    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, stream);
+    return launch_views_resident<float>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err,
+                                        view_recipe_default(), stream);
 }
 
 extern "C" int facl_build_views_resident_gp_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
                                                 const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
                                                 int64_t* idx_out, int32_t* err, void* stream) {
-    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, stream);
+    return launch_views_resident<double>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err,
+                                        view_recipe_default(), stream);
+}
+
+extern "C" int facl_build_views_resident_recipe_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                                    const int32_t* sel, int B, int G, int P, int64_t seed, int epoch,
+                                                    float* out, int64_t* idx_out, int32_t* err, const int32_t* kinds,
+                                                    int n_kinds, const double* strengths, void* stream) {
+    return launch_views_resident_recipe<float>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, kinds,
+                                               n_kinds, strengths, stream);
+}
+
+extern "C" int facl_build_views_resident_recipe_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                                    const int32_t* sel, int B, int G, int P, int64_t seed, int epoch,
+                                                    float* out, int64_t* idx_out, int32_t* err, const int32_t* kinds,
+                                                    int n_kinds, const double* strengths, void* stream) {
+    return launch_views_resident_recipe<double>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err,
+                                                kinds, n_kinds, strengths, stream);
 }

@@ -175,12 +175,17 @@ class DiskBatches:
     producer thread loads and draws batch i+1 (np.load, host draws, packing into pinned staging, H2D on a side stream)
     while batch i is consumed; an event orders the copy before the views launch on the compute stream.  Iterating yields
     ((G*B, P, 4) float32 views, v_names, labels); G = `num_crop` views of P = `num_point` points: 10 x 512, the
-    reference's loader, or with 'philox' any size of the kernels' domain (facl_amd/philox.py)."""
+    reference's loader, or with 'philox' any size of the kernels' domain (facl_amd/philox.py) and any view `recipe`
+    (facl_amd.philox.Recipe; None = the reference's ten kinds at its strengths)."""
 
     def __init__(self, index, data_root, branch, vids, mode, device, rng=None, seed=0, epoch=0, prefetch=True,
-                 num_crop=V.NUM_CROP, num_point=V.NUM_POINT):
+                 num_crop=V.NUM_CROP, num_point=V.NUM_POINT, recipe=None):
         if mode not in ('numpy', 'philox'):
             raise ValueError("disk batches draw with --view_rng numpy or philox")
+        if mode != 'philox' and recipe is not None and not recipe.is_default():
+            raise ValueError("the reference's NumPy stream defines its ten views only; another view recipe needs "
+                             "--view_rng philox")
+        self.recipe = recipe
         if mode == 'philox':
             V.check_view_size(num_crop, num_point)
         elif (num_crop, num_point) != (V.NUM_CROP, V.NUM_POINT):
@@ -236,7 +241,7 @@ class DiskBatches:
         B = len(s.names)
         if self.mode == 'philox':
             return V.build_views_philox(d['src'], d['meta'], s.dt, self.seed, self.epoch, num_crop=self.num_crop,
-                                        num_point=self.num_point)
+                                        num_point=self.num_point, recipe=self.recipe)
         from . import _lib
         lib = _lib.load_library()
         out = _lib.empty((V.NUM_CROP * B, V.NUM_POINT, 4), dtype=torch.float32, device=self.dev)

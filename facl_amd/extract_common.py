@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import cn3d_model_conbag as MM
-from .train_common import build_parser, check_view_flags, group_views, synthetic_batch
+from .train_common import build_parser, check_view_flags, group_views, synthetic_batch, view_recipe
 
 
 def save_single_feature(feature, save_path, name, num_crop=11):
@@ -35,6 +35,7 @@ def run(default_branch, default_ckpt, args=None):
     p.add_argument('--save_path', type=str, default='', help='NEW: output folder for <clip>.npy (reference: literal path)')
     p.add_argument('--num_batches', type=int, default=2, help='NEW: synthetic batches to extract')
     opt = p.parse_args(args)
+    view_recipe(opt)                              # refuses a bad recipe before the device is touched
     device = torch.device("cuda", opt.main_gpu)
     torch.cuda.set_device(device)
     netR = MM.PointNet_Plus(opt, gost=opt.num_crop)
@@ -65,7 +66,8 @@ def ordered_views(opt, device, index, split, rng, epoch=0):
     from . import dataset as fds
     vids = [np.asarray(split, dtype=np.int64)[p] for p in fds.ordered_batches(len(split), opt.batchSize)]
     return iter(fds.DiskBatches(index, opt.data_root, opt.branch_choose, vids, opt.view_rng, device, rng=rng, seed=2000,
-                                epoch=epoch, prefetch=bool(opt.prefetch), num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM))
+                                epoch=epoch, prefetch=bool(opt.prefetch), num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM,
+                                recipe=view_recipe(opt)))
 
 
 def extract_split(netR, opt, device, index, split, rng, save_path=''):
@@ -94,6 +96,7 @@ def run_disk(netR, opt, device):
     the view kernels' domain (a vector is (num_crop+1)*512 long whatever SAMPLE_NUM is)."""
     from . import dataset as fds
     check_view_flags(opt)
+    print(view_recipe(opt).describe())
     index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
     rng = np.random.RandomState(2000)
     feats = []

@@ -18,7 +18,8 @@ from . import dist as fdist
 from .cls_head import ClipClassifier
 from .extract_common import ordered_views
 from .train_common import (ContrastiveStep, TrainBatches, build_parser, check_optim_flags, check_resident_flags,
-                           check_view_flags, eval_mode, optim_recipe, setup_run, synthetic_batch, train_epochs)
+                           check_view_flags, eval_mode, optim_recipe, setup_run, synthetic_batch, train_epochs,
+                           view_recipe)
 
 HEAD_PREFIX = "head."
 
@@ -172,6 +173,8 @@ def main(args=None):
     check_finetune_flags(opt)
     check_resident_flags(opt)
     check_view_flags(opt)
+    if opt.synthetic != 1:
+        print(view_recipe(opt).describe())
     check_optim_flags(opt, world=1)
     torch.cuda.set_device(opt.main_gpu)
     device = torch.device("cuda", opt.main_gpu)

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from . import cls_head
 from . import dist as fdist
-from .train_common import build_parser, check_view_flags, group_views
+from .train_common import build_parser, check_view_flags, group_views, view_recipe
 
 MAX_TOPK = 64              # facl_cls_topk: one list entry per lane
 
@@ -230,6 +230,7 @@ def check_predict_flags(opt, world=None):
     if opt.encoder:
         opt.synthetic = 0
         check_view_flags(opt)
+        print(view_recipe(opt).describe())
 
 
 def _subset(index, opt):

@@ -259,10 +259,11 @@ class ResidentClips:
         return int(self.err[0].item())
 
 
-def build_views_resident(res, sel, seed, epoch, return_idx=False, num_crop=V.NUM_CROP, num_point=V.NUM_POINT):
+def build_views_resident(res, sel, seed, epoch, return_idx=False, num_crop=V.NUM_CROP, num_point=V.NUM_POINT, recipe=None):
     """The (G*B, P, 4) float32 views (G = num_crop views of P = num_point points, facl_amd/philox.py's recipe) of the clips
     at table positions `sel` (device (B,) int32), one launch on the current stream.  With return_idx also the (B, G, P) int64
-    pool rows.  A position outside the table raises the pool's error word and yields zeros for that clip."""
+    pool rows.  A position outside the table raises the pool's error word and yields zeros for that clip.  `recipe`: a
+    facl_amd.philox.Recipe, None = the default (the _gp entry)."""
     import torch
     from . import _lib
     V.check_view_size(num_crop, num_point)
@@ -274,24 +275,26 @@ def build_views_resident(res, sel, seed, epoch, return_idx=False, num_crop=V.NUM
     _lib.require_cuda(sel, res.src)
     out = _lib.empty((G * B, P, 4), dtype=torch.float32, device=res.dev)
     idx = _lib.empty((B, G, P), dtype=torch.int64, device=res.dev) if return_idx else None
-    fn = lib.facl_build_views_resident_gp_f64 if res.dtype == np.float64 else lib.facl_build_views_resident_gp_f32
+    name = "facl_build_views_resident_%s_%s" % ("gp" if recipe is None else "recipe", "f64" if res.dtype == np.float64 else "f32")
+    keep, extra = ((), ()) if recipe is None else V.recipe_args(recipe)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.check(fn(_lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B, G, P,
-                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), _lib.ptr(out), _lib.ptr(idx),
-                  _lib.ptr(res.err), _lib.stream()), "facl_build_views_resident_gp")
+    _lib.check(getattr(lib, name)(_lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B, G, P,
+                                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), _lib.ptr(out), _lib.ptr(idx),
+                                  _lib.ptr(res.err), *extra, _lib.stream()), name)
+    del keep
     return (out, idx) if return_idx else out
 
 
 class ResidentBatches:
     """What `DiskBatches(index, ..., vids, 'philox', device, seed=seed, epoch=epoch)` yields, from the resident pool:
     ((G*B, P, 4) float32 views, v_names, labels) per entry of `vids` (a list of (B_i,) arrays of dataset indices); G =
-    `num_crop`, P = `num_point`, any size of the kernels' domain.  Per batch: one (B,) int32 copy out of a reused pinned
+    `num_crop`, P = `num_point`, any size of the kernels' domain; `recipe`: the view recipe (None = the default).  Per batch: one (B,) int32 copy out of a reused pinned
     buffer and one launch, both on the current stream; no thread."""
 
-    def __init__(self, resident, vids, seed=0, epoch=0, num_crop=V.NUM_CROP, num_point=V.NUM_POINT):
+    def __init__(self, resident, vids, seed=0, epoch=0, num_crop=V.NUM_CROP, num_point=V.NUM_POINT, recipe=None):
         import torch
         V.check_view_size(num_crop, num_point)
-        self.num_crop, self.num_point = int(num_crop), int(num_point)
+        self.num_crop, self.num_point, self.recipe = int(num_crop), int(num_point), recipe
         self.res, self.seed, self.epoch = resident, seed, epoch
         self.vids = [np.asarray(v).reshape(-1) for v in vids]
         bmax = max([len(v) for v in self.vids] + [1])
@@ -319,7 +322,8 @@ class ResidentBatches:
             sel.copy_(self._pin[:B], non_blocking=True)
             self._copied = torch.cuda.Event()
             self._copied.record()
-            views = build_views_resident(res, sel, self.seed, self.epoch, num_crop=self.num_crop, num_point=self.num_point)
+            views = build_views_resident(res, sel, self.seed, self.epoch, num_crop=self.num_crop, num_point=self.num_point,
+                                         recipe=self.recipe)
         names = [res.index.v_name(int(v)) for v in vids]
         labels = [res.index.label(int(v)) for v in vids]
         return views, names, labels

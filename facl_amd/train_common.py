@@ -142,7 +142,51 @@ def build_parser(default_branch):
                    help='NEW (--lr_schedule cosine, required >= 1 there): the cosine reaches --lr_min after this many epochs '
                         '(x the steps of an epoch, warm-up included) and stays there')
     p.add_argument('--lr_min', type=float, default=0.0, help='NEW (--lr_schedule cosine): the rate the cosine ends at')
+    add_view_recipe_flags(p)
     return p
+
+
+VIEW_RECIPE_FLAGS = ("view_kinds", "jitter_sigma", "jitter_clip", "rot_range", "scale_lo", "scale_hi", "tilt_angle")
+VIEW_RECIPE_DEFAULTS = ("reference", 0.01, 0.05, 0.8, 0.5, 1.5, 0.25)       # = facl_amd.philox.DEFAULT_STRENGTHS
+
+
+def add_view_recipe_flags(p):
+    """The view recipe of --view_rng philox (facl_amd.philox.Recipe): the kinds of a round and six strengths."""
+    p.add_argument('--view_kinds', type=str, default='reference',
+                   help='NEW (--view_rng philox): the kinds of a round, 1..12 comma-separated names; view v is of the kind at '
+                        'position v %% L in round v // L.  raw, mirror, key, key_mirror, rot, t4, t7, res30, res10: the '
+                        'reference\'s views; jitter, scale, tilt_neg, tilt_pos: transforms it defines and never wires in.  '
+                        'reference = raw,mirror,key,key_mirror,rot,rot,t4,t7,res30,res10.  A view\'s draws depend on the kinds '
+                        'before it in the list')
+    p.add_argument('--jitter_sigma', type=float, default=0.01, help='NEW (--view_rng philox): sigma of the jitter, >= 0 (literal 0.01 at :765)')
+    p.add_argument('--jitter_clip', type=float, default=0.05, help='NEW (--view_rng philox): the jitter is clipped to +- this, > 0 (literal 0.05 at :765)')
+    p.add_argument('--rot_range', type=float, default=0.8,
+                   help='NEW (--view_rng philox): a rot view turns about y by (u - 0.5) * pi * this, in [0, 2] (literal 0.8 at :739)')
+    p.add_argument('--scale_lo', type=float, default=0.5, help='NEW (--view_rng philox): a scale view multiplies xyz by s in [scale_lo, scale_hi) (literal 0.5 at :759)')
+    p.add_argument('--scale_hi', type=float, default=1.5, help='NEW (--view_rng philox): see --scale_lo (literal 1.5 at :759)')
+    p.add_argument('--tilt_angle', type=float, default=0.25,
+                   help='NEW (--view_rng philox): tilt_neg / tilt_pos turn about y by -/+ pi * this (literal 0.25 at :723)')
+
+
+def view_recipe(opt):
+    """The facl_amd.philox.Recipe of the seven flags (a namespace without them: the default), checked.  Any non-default value
+    needs the counter-based draws on clips: refused with --view_rng numpy / device and with --synthetic 1.  Touches no device."""
+    from .philox import Recipe
+    given = [getattr(opt, k, d) for k, d in zip(VIEW_RECIPE_FLAGS, VIEW_RECIPE_DEFAULTS)]
+    try:
+        recipe = Recipe.parse(given[0], **dict(zip(VIEW_RECIPE_FLAGS[1:], given[1:])))
+    except ValueError as e:
+        raise RuntimeError(str(e)) from None
+    if not recipe.is_default():
+        changed = ", ".join("--%s %s" % (k, v) for k, v, d in zip(VIEW_RECIPE_FLAGS, given, VIEW_RECIPE_DEFAULTS) if v != d)
+        if getattr(opt, "synthetic", 0) == 1:
+            raise RuntimeError("%s with --synthetic 1: iid clouds are no views of a clip, and the reference's stream defines its "
+                               "ten views only; a view recipe needs --synthetic 0 or 2 with --view_rng philox" % changed)
+        if opt.view_rng != 'philox':
+            raise RuntimeError("%s with --view_rng %s: the reference's stream defines its ten views only (the kinds and "
+                               "strengths of cn3D_data_set.py:285-350); another recipe needs --view_rng philox, whose "
+                               "counter-based draws cover it" % (changed, opt.view_rng))
+    return recipe
 
 
 def synthetic_batch(B, G, N, D, device, generator=None):
@@ -544,7 +588,9 @@ def lr_for_epoch(base_lr, epoch, step_size=4, gamma=0.7):
 
 def check_view_flags(opt):
     """--synthetic 0 / 2 build views from clips: 4 channels; 10 views of 512 points on the reference's streams, any size of
-    the kernels' domain on the counter-based one.  Raises before the device is touched."""
+    the kernels' domain on the counter-based one; the view recipe (`view_recipe`) on the counter-based one only.  Raises
+    before the device is touched."""
+    view_recipe(opt)
     if opt.synthetic not in (0, 2):
         return
     what = "--synthetic %d" % opt.synthetic
@@ -803,6 +849,7 @@ class TrainBatches:
         if self.steps < 1:
             raise RuntimeError(too_few % dict(clips=len(self.split), batch=opt.batchSize, world=world))
         self.view_rng = np.random.RandomState(2000 + rank)    # --view_rng numpy: the generator the views draw from
+        self.recipe = view_recipe(opt)
         self.resident = None
         if opt.resident:
             # every rank holds the whole split: the permutation is over the whole split, a rank's shard changes every epoch
@@ -824,10 +871,10 @@ class TrainBatches:
         vids = [self.split[p] for p in pos]
         if self.resident is not None:
             return fres.ResidentBatches(self.resident, vids, seed=2000, epoch=epoch,
-                                        num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM)
+                                        num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM, recipe=self.recipe)
         disk = fds.DiskBatches(self.index, opt.data_root, opt.branch_choose, vids, opt.view_rng, self.device,
                                rng=self.view_rng, seed=2000, epoch=epoch, prefetch=bool(opt.prefetch),
-                               num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM)
+                               num_crop=opt.num_crop, num_point=opt.SAMPLE_NUM, recipe=self.recipe)
         disk.hold_first = hold_first
         return iter(disk)
 
@@ -914,6 +961,9 @@ def run(default_branch, ckpt_pattern, args=None):
     check_key_flags(opt)
     check_state_flags(opt)
     check_optim_flags(opt)
+    recipe = view_recipe(opt)
+    if opt.synthetic != 1:
+        print(recipe.describe())
     from . import train_state
     flags = train_state.flags_of(opt)                  # as given: the grouper writes the reference's literals into `opt` later
     resumed, resumed_path = load_resume_state(opt)     # on the CPU, refused here if its options differ from this run's
@@ -952,7 +1002,8 @@ def run(default_branch, ckpt_pattern, args=None):
             # device: the same distributions drawn by a torch generator on the GPU (no per-clip host work)
             return build_views(clips, view_rng, device, device_rng=gen if opt.view_rng == "device" else None,
                                philox=(2000, epoch, [base + b for b in range(opt.batchSize)])
-                               if opt.view_rng == "philox" else None, num_crop=num_crop, num_point=opt.SAMPLE_NUM)
+                               if opt.view_rng == "philox" else None, num_crop=num_crop, num_point=opt.SAMPLE_NUM,
+                               recipe=recipe)
         if opt.synthetic == 1:
             return synthetic_batch(opt.batchSize, num_crop, opt.SAMPLE_NUM, opt.INPUT_FEATURE_NUM, device, gen)
         raise RuntimeError("--synthetic must be 0 (the dataset on disk), 1 or 2")

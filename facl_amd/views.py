@@ -84,7 +84,8 @@ def check_view_size(num_crop, num_point):
                          % (num_crop, num_point))
 
 
-def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None, num_crop=NUM_CROP, num_point=NUM_POINT):
+def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None, num_crop=NUM_CROP, num_point=NUM_POINT,
+                recipe=None):
     """clips: list of (points (P,>=8), key_points, res_points_1, res_points_2) NumPy arrays of one dtype (float32 or
     float64), the arrays `__getitem__` loads for a video.  Returns the (10*B, 512, 4) float32 CUDA tensor = the
     reference's `data1` (view-major rows g*B+b).  `rng`: np.random.RandomState (default: NumPy's global generator,
@@ -93,13 +94,17 @@ def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None, nu
     no per-clip host work.  `philox` = (seed, epoch, clip_ids): counter-based draws on the device (csrc/views_philox.hip):
     a clip's views depend on (seed, epoch, its dataset index clip_ids[b]) only.  `num_crop`, `num_point`: with `philox`
     any (G, P) of the kernels' domain -> (G*B, P, 4) (the recipe is in facl_amd/philox.py); the other two streams are the
-    reference's and know 10 x 512 only."""
+    reference's and know 10 x 512 only.  `recipe` (facl_amd.philox.Recipe; None = the reference's ten kinds at its strengths):
+    the kinds of a round and the strengths, with `philox` only."""
+    if philox is None and recipe is not None and not recipe.is_default():
+        raise ValueError("the reference's stream defines its ten views only; another view recipe needs the counter-based "
+                         "draws (philox)")
     if philox is not None:
         check_view_size(num_crop, num_point)
         src, meta, dt = pack_clips(clips, philox[2])
         dev = torch.device(device)
         return build_views_philox(torch.from_numpy(src).to(dev), torch.from_numpy(meta).to(dev), dt, philox[0], philox[1],
-                                  num_crop=num_crop, num_point=num_point)
+                                  num_crop=num_crop, num_point=num_point, recipe=recipe)
     if (num_crop, num_point) != (NUM_CROP, NUM_POINT):
         raise ValueError("the reference's stream defines %d views of %d points only; other sizes need the counter-based "
                          "draws (philox)" % (NUM_CROP, NUM_POINT))
@@ -195,11 +200,18 @@ def pack_clips(clips, clip_ids, out=None):
     return src, meta, dt
 
 
-def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NUM_CROP, num_point=NUM_POINT):
+def recipe_args(recipe):
+    """The three trailing arguments of the C ABI's recipe entries: HOST arrays, read before the launch.  Returns (the two
+    arrays -- keep them alive over the call --, (kinds, n_kinds, strengths))."""
+    kinds, strengths = np.ascontiguousarray(recipe.codes(), dtype=np.int32), np.ascontiguousarray(recipe.strengths(), dtype=np.float64)
+    return (kinds, strengths), (kinds.ctypes.data, int(kinds.shape[0]), strengths.ctypes.data)
+
+
+def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NUM_CROP, num_point=NUM_POINT, recipe=None):
     """Device half of the philox mode: src (rows, 8) and meta (B, 9) int32 on the device (pack_clips' layout, temporal
     rows already checked).  Two launches on the current stream: the temporal-row compaction, then the views.
     Returns the (G*B, P, 4) float32 views of G = num_crop views of P = num_point points (and, with return_idx, the
-    (B, G, P) source rows and the error word)."""
+    (B, G, P) source rows and the error word).  `recipe`: a facl_amd.philox.Recipe, None = the default (the _gp entry)."""
     check_view_size(num_crop, num_point)
     G, P = int(num_crop), int(num_point)
     lib = _lib.load_library()
@@ -215,11 +227,13 @@ def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NU
     rt = lib.facl_views_temporal_rows_f64 if f64 else lib.facl_views_temporal_rows_f32
     _lib.check(rt(_lib.ptr(src), rows, 8, _lib.ptr(meta), B, _lib.ptr(lists), _lib.ptr(counts), _lib.ptr(err),
                   _lib.stream()), "facl_views_temporal_rows")
-    fn = lib.facl_build_views_philox_gp_f64 if f64 else lib.facl_build_views_philox_gp_f32
+    name = "facl_build_views_philox_%s_%s" % ("gp" if recipe is None else "recipe", "f64" if f64 else "f32")
+    keep, extra = ((), ()) if recipe is None else recipe_args(recipe)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.check(fn(_lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts),
-                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), B, G, P, _lib.ptr(out), _lib.ptr(idx),
-                  _lib.stream()), "facl_build_views_philox_gp")
+    _lib.check(getattr(lib, name)(_lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts),
+                                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), B, G, P, _lib.ptr(out),
+                                  _lib.ptr(idx), *extra, _lib.stream()), name)
+    del keep
     return (out, idx, err) if return_idx else out
 
 

@@ -662,6 +662,66 @@ int facl_build_views_resident_gp_f64(const double* src, const int64_t* table, co
                                      const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
                                      int64_t* idx_out, int32_t* err, void* stream);
 
+/* ---- the philox views by a RECIPE: which kinds a round holds and how strongly they are augmented (csrc/views_philox_point.inc;
+ * restated by facl_amd/philox.py's Recipe).  A recipe is a list of 1..FACL_VIEW_POS_MAX kind codes, the positions of a round,
+ * and FACL_VIEW_NSTRENGTH strengths.  View v is of the kind at position v % n_kinds in round v / n_kinds.
+ *   kinds      RAW, MIRROR, KEY, KEY_MIRROR, ROT, T4, T7, RES30, RES10: the reference's views (the default list is RAW, MIRROR,
+ *              KEY, KEY_MIRROR, ROT, ROT, T4, T7, RES30, RES10).  JITTER: the jittered point cloud.  SCALE: jitter, then xyz * s,
+ *              s = scale_lo + (scale_hi - scale_lo) * u.  TILT_NEG / TILT_POS: jitter, then a rotation about y by -/+ pi *
+ *              tilt_angle
+ *   strengths  [0] jitter_sigma 0.01, [1] jitter_clip 0.05, [2] rot_range 0.8 (the angle of ROT is (u - 0.5) * pi * rot_range),
+ *              [3] scale_lo 0.5, [4] scale_hi 1.5, [5] tilt_angle 0.25; each applies to every position of the recipe
+ *   slots      row word of position i: word i & 3 of slot i >> 2.  Jitter draws are numbered j = 0, 1, ... in position order
+ *              (MIRROR and KEY_MIRROR take two; KEY, ROT, JITTER, SCALE, TILT_* one) and draw j uses slots 3 + 3 j + d.  The
+ *              scalar draws of ROT and SCALE are numbered in position order from 3 + 3 max(7, J), J = jitter draws of the round.
+ *              A round takes `stride` = 32 ceil((3 + 3 max(7, J) + A) / 32) slots, A = its scalar draws.  So a view's draws
+ *              depend on the kinds BEFORE it in the list; the default list gives the layout of the _gp entries above.
+ * facl_build_views_philox_recipe_* / facl_build_views_resident_recipe_*: the _gp entries with a recipe; every entry above IS
+ * this one at the default recipe (one kernel), bit for bit.  The recipe travels in the kernel's arguments.  Same domain of
+ * (G, P): 1 <= G <= 64; 64 <= P <= 4096 with P % 64 == 0; otherwise FACL_E_SHAPE and no launch.
+ * `kinds` AND `strengths` ARE HOST POINTERS, READ BEFORE THE LAUNCH; EVERY OTHER POINTER OF THIS ABI IS A DEVICE POINTER.
+ * Refused without a launch: NULL kinds / strengths: FACL_E_NULL; n_kinds outside 1..12, an unknown kind code, a strength
+ * that is not finite, jitter_sigma < 0, jitter_clip <= 0, rot_range outside [0, 2], scale_lo <= 0 or scale_lo > scale_hi:
+ * FACL_E_SHAPE.  A temporal kind at any position keeps the void-view behaviour (zeros, idx_out -1, err raised).
+ * facl_view_recipe_table: HOST ONLY, no HIP call.  table (n_kinds, FACL_VIEW_TABLE_COLS) int32 per position: source (0..3 the
+ * four clouds, 4 / 5 the rows with a non-zero channel 4 / 7), channel copied to output channel 3, operation (0 gather, 1 jitter,
+ * 2 mirror, 3 rot, 4 scale, 5 tilt_neg, 6 tilt_pos), row slot, row word, first and second jitter draw j (-1: none), scalar
+ * slot (-1: none); *stride = the slots of a round.  All three pointers are host pointers. */
+#define FACL_VIEW_RAW        0
+#define FACL_VIEW_MIRROR     1
+#define FACL_VIEW_KEY        2
+#define FACL_VIEW_KEY_MIRROR 3
+#define FACL_VIEW_ROT        4
+#define FACL_VIEW_T4         5
+#define FACL_VIEW_T7         6
+#define FACL_VIEW_RES30      7
+#define FACL_VIEW_RES10      8
+#define FACL_VIEW_JITTER     9
+#define FACL_VIEW_SCALE      10
+#define FACL_VIEW_TILT_NEG   11
+#define FACL_VIEW_TILT_POS   12
+#define FACL_VIEW_NKINDS     13
+#define FACL_VIEW_POS_MAX    12
+#define FACL_VIEW_NSTRENGTH  6
+#define FACL_VIEW_TABLE_COLS 8
+int facl_build_views_philox_recipe_f32(const float* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
+                                       const int32_t* counts, int64_t seed, int epoch, int B, int G, int P, float* out,
+                                       int32_t* idx_out, const int32_t* kinds, int n_kinds, const double* strengths,
+                                       void* stream);
+int facl_build_views_philox_recipe_f64(const double* src, int64_t rows, int C, const int32_t* meta, const int32_t* list,
+                                       const int32_t* counts, int64_t seed, int epoch, int B, int G, int P, float* out,
+                                       int32_t* idx_out, const int32_t* kinds, int n_kinds, const double* strengths,
+                                       void* stream);
+int facl_build_views_resident_recipe_f32(const float* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                         const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                         int64_t* idx_out, int32_t* err, const int32_t* kinds, int n_kinds,
+                                         const double* strengths, void* stream);
+int facl_build_views_resident_recipe_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
+                                         const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
+                                         int64_t* idx_out, int32_t* err, const int32_t* kinds, int n_kinds,
+                                         const double* strengths, void* stream);
+int facl_view_recipe_table(const int32_t* kinds, int n_kinds, int32_t* table, int32_t* stride);
+
 /* ---- 3DV generation: depth frames -> motion, key and appearance clouds (generate_data/generate_NTU.py; csrc/gen3dv.hip,
  * whose header describes the stages and the layouts) for a batch of B clips.  int32 unless said otherwise:
  *   frames uint16 (NF,H,W): per clip the first file of its folder, then its chosen frames (at most FACL_GEN3DV_MAX_FRAMES)

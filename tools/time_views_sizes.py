@@ -10,6 +10,8 @@
    and the kernel's share of the step of the training entry at that size (--synthetic 1 --graph 1: B / clips per second).
 3. End to end: clips/s of the training entry at --num_crop 24 --SAMPLE_NUM 2048 --resident 1 --graph 1 on a synthetic tree
    (tools/time_disk_entry.make_dataset), from disk (--resident 0), and on the synthetic iid input of the same size.
+With --sizes_every_round 1 the _gp sizes are timed in EVERY round and library (medians and spread per library), and, where
+   the library has the recipe entries, a non-default view recipe (scale,tilt_neg,tilt_pos,jitter,rot,mirror,t7) next to them.
 A child that fails ends the measurement at once.  Prints one JSON line (and writes it to --out).
 
     python tools/time_views_sizes.py [--baseline_lib PATH] [--out profiles/views_sizes.json]
@@ -49,6 +51,10 @@ def kernel_worker(a):
            "facl_build_views_philox_gp_f64": [P_, L_, I_, P_, P_, P_, L_, I_, I_, I_, I_, P_, P_, P_],
            "facl_build_views_resident_gp_f64": [P_, P_, P_, I_, P_, I_, I_, I_, L_, I_, P_, P_, P_, P_]}
     has_gp = hasattr(lib, "facl_build_views_philox_gp_f64")
+    has_recipe = hasattr(lib, "facl_build_views_philox_recipe_f64")       # a baseline library lacks the recipe entries
+    if has_recipe:
+        sig["facl_build_views_philox_recipe_f64"] = sig["facl_build_views_philox_gp_f64"][:-1] + [P_, I_, P_, P_]
+        sig["facl_build_views_resident_recipe_f64"] = sig["facl_build_views_resident_gp_f64"][:-1] + [P_, I_, P_, P_]
     for name, args in sig.items():
         if has_gp or "_gp_" not in name:
             getattr(lib, name).argtypes = args
@@ -93,6 +99,20 @@ def kernel_worker(a):
             return lambda: lib.facl_build_views_resident_f64(*head, 2000, 1, out.data_ptr(), None, err2.data_ptr(), s)
         return lambda: lib.facl_build_views_resident_gp_f64(*head, G, P, 2000, 1, out.data_ptr(), None, err2.data_ptr(), s)
 
+    # a non-default recipe: every new kind, a mirrored one and a temporal one (seven jitter draws, as the default list has)
+    kinds = np.array([10, 11, 12, 9, 4, 1, 6], dtype=np.int32)             # scale,tilt_neg,tilt_pos,jitter,rot,mirror,t7
+    strengths = np.array([0.01, 0.05, 0.8, 0.5, 1.5, 0.25])
+    tail = (kinds.ctypes.data, len(kinds), strengths.ctypes.data)
+
+    def disk_recipe(G, P):
+        head = (src.data_ptr(), total, 8, meta.data_ptr(), list_d.data_ptr(), counts.data_ptr(), 2000, 1, B)
+        return lambda: lib.facl_build_views_philox_recipe_f64(*head, G, P, out.data_ptr(), None, *tail, s)
+
+    def resident_recipe(G, P):
+        head = (src.data_ptr(), tab.data_ptr(), list_r.data_ptr(), B, sel.data_ptr(), B)
+        return lambda: lib.facl_build_views_resident_recipe_f64(*head, G, P, 2000, 1, out.data_ptr(), None, err2.data_ptr(),
+                                                                *tail, s)
+
     def time_us(fn):
         for _ in range(a.launches):
             ok(fn())
@@ -111,6 +131,9 @@ def kernel_worker(a):
     res = {"old_entries_us": {"disk": time_us(disk()), "resident": time_us(resident())}}
     if has_gp and a.sizes:
         res["sizes_us"] = {"%dx%d" % gp: {"disk": time_us(disk(*gp)), "resident": time_us(resident(*gp))} for gp in SIZES}
+    if has_recipe and a.sizes:
+        res["recipe_us"] = {"%dx%d" % gp: {"disk": time_us(disk_recipe(*gp)), "resident": time_us(resident_recipe(*gp))}
+                            for gp in ((10, 512), (24, 2048))}
     assert int(err1.item()) == 0 and err2.cpu().tolist()[0] == 0
     print("RESULT " + json.dumps(res))
 
@@ -155,6 +178,8 @@ def main():
     ap.add_argument("--worker", type=str, default="", choices=["", "kernel"] + list(ENTRY))
     ap.add_argument("--lib", type=str, default="")
     ap.add_argument("--sizes", type=int, default=0)
+    ap.add_argument("--sizes_every_round", type=int, default=0,
+                    help="1 = time the _gp sizes (and, where the library has them, the recipe entries) in every round and library")
     ap.add_argument("--data", type=str, default="")
     ap.add_argument("--G", type=int, default=24)
     ap.add_argument("--P", type=int, default=2048)
@@ -169,14 +194,22 @@ def main():
         libs["baseline"] = os.path.abspath(a.baseline_lib)
     common = ["--B", str(a.B), "--reps", str(a.reps), "--launches", str(a.launches)]
     runs = {k: [] for k in libs}
+    size_runs, recipe_runs = {k: [] for k in libs}, []
     sizes = None
     for i in range(a.rounds):
         for k in sorted(libs):                                      # baseline, this, baseline, this, ...
+            every = bool(a.sizes_every_round)
             last = k == "this" and i == a.rounds - 1
-            res = child(["--worker", "kernel", "--lib", libs[k], "--sizes", str(int(last))] + common, a.child_timeout)
+            res = child(["--worker", "kernel", "--lib", libs[k], "--sizes", str(int(last or every))] + common, a.child_timeout)
             runs[k].append(res["old_entries_us"])
-            sizes = res.get("sizes_us", sizes)
-            print("%s round %d: %s" % (k, i, res["old_entries_us"]), file=sys.stderr, flush=True)
+            if k == "this":
+                sizes = res.get("sizes_us", sizes)
+            if "sizes_us" in res:
+                size_runs[k].append(res["sizes_us"])
+            if "recipe_us" in res:
+                recipe_runs.append(res["recipe_us"])
+            print("%s round %d: %s %s" % (k, i, res["old_entries_us"], res.get("sizes_us", {}).get("24x2048", "")),
+                  file=sys.stderr, flush=True)
     out = {"B": a.B, "launches_per_window": a.launches, "windows_per_run": a.reps, "rounds": a.rounds, "process_per_run": True,
            "source": "four (2048, 8) float64 clouds per clip", "old_entries_us": {}}
     for k, v in runs.items():
@@ -189,6 +222,15 @@ def main():
                                     "baseline_spread_us": o["baseline"][p]["spread"],
                                     "holds": o["this"][p]["median"] - o["baseline"][p]["median"] <= o["baseline"][p]["spread"]}
                                 for p in ("disk", "resident")}
+    def spread(vals):
+        return {"medians": vals, "median": float(np.median(vals)), "spread": float(max(vals) - min(vals))}
+    if a.sizes_every_round:                                          # the _gp entries per library and round, and a recipe's time
+        out["sizes_us_by_library"] = {k: {gp: {p: spread([r[gp][p] for r in v]) for p in ("disk", "resident")} for gp in v[0]}
+                                      for k, v in size_runs.items() if v}
+        if recipe_runs:
+            out["recipe_us"] = {"kinds": "scale,tilt_neg,tilt_pos,jitter,rot,mirror,t7",
+                                **{gp: {p: spread([r[gp][p] for r in recipe_runs]) for p in ("disk", "resident")}
+                                   for gp in recipe_runs[0]}}
     out["sizes"] = {k: {p: {"us_per_launch": us, "points_per_s": a.B * int(k.split("x")[0]) * int(k.split("x")[1]) / (us * 1e-6)}
                         for p, us in v.items()} for k, v in (sizes or {}).items()}
     if a.entries:

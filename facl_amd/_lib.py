@@ -121,6 +121,10 @@ SIGNATURES = {
     "facl_viewmax_bwd": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
     "facl_viewmax_bwd_add": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
     "facl_sa_bwd_final": [c_p] * 13 + [c_i, c_d] + [c_p] * 9 + [c_p],
+    "facl_bn_bwd_consts_frozen": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    "facl_sa_bwd_consts3_frozen": [c_p, c_p, c_p],
+    "facl_sa_bwd_consts2_frozen": [c_p, c_p, c_p],
+    "facl_sa_bwd_final_frozen": [c_p] * 9 + [c_i] + [c_p] * 12 + [c_p],
     "facl_viewmax_stack": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     "facl_fc_bn_stats": [c_p, c_l, c_l, c_i, c_p, c_p, c_p],
     "facl_fc_bn_apply": [c_p, c_l, c_l, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p],

@@ -642,3 +642,120 @@ extern "C" int facl_sa_bwd_final(const double* out3, const double* sums0_g, cons
                        dbe2, dW1, dg1, dbe1);
     return facl_launch_status();
 }
+
+// ================================================================================================
+// Frozen (eval-mode) BatchNorm: z = s y + t with s = gamma / sqrt(running_var + eps), t = beta - running_mean s, both constants.
+// With dz the gradient behind the ReLU (or the max-pool routing), the same (C,2) sums the train-mode passes form -- sum dz and
+// sum dz (y - mean) invstd, taken with the RUNNING mean / invstd of the (5,C) constants -- ARE dbeta and dgamma, dy = s dz has no
+// batch-statistic term (kk = 0), and the bias of the conv / Linear in front gets a real gradient sum dy = s dbeta.  Nothing is
+// global any more: no sum here is all-reduced.  Same style as the train-mode forms above: fp64, one thread per output, fixed order.
+namespace {
+
+__global__ void k_bn_bwd_consts_frozen(const double* __restrict__ sums, const float* __restrict__ bnc, int C,
+                                       float* __restrict__ dbeta, float* __restrict__ dgamma, float* __restrict__ dbias,
+                                       float* __restrict__ kk) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    dbeta[c] = (float)sums[2 * c];
+    dgamma[c] = (float)sums[2 * c + 1];
+    dbias[c] = (float)((double)bnc[2 * C + c] * sums[2 * c]);
+    kk[c] = 0.f;
+    kk[C + c] = 0.f;
+}
+
+// G3 = 0, h3 = 0: the dense part of da2 (the batch-statistic terms of BN3's backward) is gone, the sparse rows remain
+__global__ void k_sa_bwd_consts3_frozen(float* __restrict__ G3, float* __restrict__ h3) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o < 4096) G3[o] = 0.f;
+    else if (o < 4096 + 64) h3[o - 4096] = 0.f;
+}
+
+// bw2 (4,64): dy2 = scale2*dz2 + A + B*(y2 - mean2) with A = B = 0
+__global__ void k_sa_bwd_consts2_frozen(const float* __restrict__ bnc2, float* __restrict__ bw2) {
+    const int c = threadIdx.x;
+    if (c >= 64) return;
+    bw2[c] = bnc2[128 + c];
+    bw2[64 + c] = 0.f;
+    bw2[128 + c] = 0.f;
+    bw2[192 + c] = bnc2[c];
+}
+
+// the twelve gradients of net3DV_1 (b1, b2, b3 among them) from the partial sums of the heavy passes: no Gram / sum a2 /
+// x-moment term is left (out3: only its sparse part is read)
+__global__ __launch_bounds__(256) void k_sa_bwd_final_frozen(
+    const double* __restrict__ out3, const double* __restrict__ sums0, const float* __restrict__ bnc3,
+    const double* __restrict__ out2, const double* __restrict__ sums1, const float* __restrict__ bnc2,
+    const float* __restrict__ bnc1, const float* __restrict__ W1, const float* __restrict__ b1, int D,
+    float* __restrict__ dW3, float* __restrict__ dg3, float* __restrict__ dbe3, float* __restrict__ db3,
+    float* __restrict__ dW2, float* __restrict__ dg2, float* __restrict__ dbe2, float* __restrict__ db2,
+    float* __restrict__ dW1, float* __restrict__ dg1, float* __restrict__ dbe1, float* __restrict__ db1) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o < 16384) { dW3[o] = (float)out3[o]; return; }         // sum_g coef a2[arg]: coef = scale3 dz3 is dy3 at its one position
+    int r = o - 16384;
+    if (r < 256) {
+        dbe3[r] = (float)sums0[2 * r];
+        dg3[r] = (float)sums0[2 * r + 1];
+        db3[r] = (float)((double)bnc3[512 + r] * sums0[2 * r]);
+        return;
+    }
+    r -= 256;
+    if (r < 4096) { dW2[r] = (float)out2[r]; return; }
+    r -= 4096;
+    if (r < 64) {
+        dbe2[r] = (float)sums1[2 * r];
+        dg2[r] = (float)sums1[2 * r + 1];
+        db2[r] = (float)((double)bnc2[128 + r] * sums1[2 * r]);
+        return;
+    }
+    r -= 64;
+    if (r < 64) {                                               // layer 1, channel c = r
+        const int c = r;
+        const double* R1 = out2 + 4096;                         // (FACL_SA_L1_COLS(D),64): rows x_d (d<D), then sum dz1
+        const double mean = bnc1[c], inv = bnc1[64 + c], sc = bnc1[128 + c];
+        double wr = 0;
+        for (int d = 0; d < D; ++d) wr += (double)W1[c * D + d] * R1[d * 64 + c];
+        const double dbe = R1[D * 64 + c];
+        dbe1[c] = (float)dbe;
+        dg1[c] = (float)(inv * (wr + ((double)b1[c] - mean) * dbe));      // sum_p dz1 (y1 - mean) invstd, y1 = W1 x + b1
+        db1[c] = (float)(sc * dbe);
+        for (int d = 0; d < D; ++d) dW1[c * D + d] = (float)(sc * R1[d * 64 + c]);
+    }
+}
+
+}  // namespace
+
+extern "C" int facl_bn_bwd_consts_frozen(const double* sums, const float* bnc, int C, float* dbeta, float* dgamma,
+                                         float* dbias, float* kk, void* stream) {
+    if (!sums || !bnc || !dbeta || !dgamma || !dbias || !kk) return FACL_E_NULL;
+    if (C < 1) return FACL_E_SHAPE;
+    hipLaunchKernelGGL(k_bn_bwd_consts_frozen, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, bnc, C,
+                       dbeta, dgamma, dbias, kk);
+    return facl_launch_status();
+}
+
+extern "C" int facl_sa_bwd_consts3_frozen(float* G3, float* h3, void* stream) {
+    if (!G3 || !h3) return FACL_E_NULL;
+    hipLaunchKernelGGL(k_sa_bwd_consts3_frozen, dim3((4096 + 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, G3, h3);
+    return facl_launch_status();
+}
+
+extern "C" int facl_sa_bwd_consts2_frozen(const float* bnc2, float* bw2, void* stream) {
+    if (!bnc2 || !bw2) return FACL_E_NULL;
+    hipLaunchKernelGGL(k_sa_bwd_consts2_frozen, dim3(1), dim3(64), 0, (hipStream_t)stream, bnc2, bw2);
+    return facl_launch_status();
+}
+
+extern "C" int facl_sa_bwd_final_frozen(const double* out3, const double* sums0, const float* bnc3, const double* out2,
+                                        const double* sums1, const float* bnc2, const float* bnc1, const float* W1,
+                                        const float* b1, int D, float* dW3, float* dg3, float* dbe3, float* db3, float* dW2,
+                                        float* dg2, float* dbe2, float* db2, float* dW1, float* dg1, float* dbe1, float* db1,
+                                        void* stream) {
+    if (!out3 || !sums0 || !bnc3 || !out2 || !sums1 || !bnc2 || !bnc1 || !W1 || !b1 || !dW3 || !dg3 || !dbe3 || !db3 ||
+        !dW2 || !dg2 || !dbe2 || !db2 || !dW1 || !dg1 || !dbe1 || !db1)
+        return FACL_E_NULL;
+    if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX) return FACL_E_SHAPE;
+    const int total = 16384 + 256 + 4096 + 64 + 64;
+    hipLaunchKernelGGL(k_sa_bwd_final_frozen, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out3, sums0, bnc3,
+                       out2, sums1, bnc2, bnc1, W1, b1, D, dW3, dg3, dbe3, db3, dW2, dg2, dbe2, db2, dW1, dg1, dbe1, db1);
+    return facl_launch_status();
+}

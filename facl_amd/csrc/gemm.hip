@@ -165,7 +165,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[T
             const float ob = __shfl_xor(best, 32, 64);
             const int op = __shfl_xor(bp, 32, 64);
             if ((ob > best || (ob == best && op < bp) || ob != ob) && best == best) { best = ob; bp = op; }   // first max wins; NaN stays (MaxPool2d)
-            if (h == 0 && jin) {
+            if (h == 0 && jin && i0 + WR * wr < g.MI) {                    // (MI % 128 == 64: the last block's second wave row holds no cloud)
                 const size_t o = (size_t)((i0 + WR * wr) >> 6) * g.NJ + j;
                 g.smax[o] = best;
                 g.sarg[o] = bp;
@@ -275,7 +275,7 @@ __device__ __forceinline__ void gemm_epilogue_h(const GemmArgs& g, f32x16 (&acc)
             const float ob = __shfl_xor(bv, 32, 64);
             const int op = __shfl_xor(p, 32, 64);
             if ((ob > bv || (ob == bv && op < p) || ob != ob) && bv == bv) { bv = ob; p = op; }      // first max wins; NaN stays (MaxPool2d)
-            if (h == 0 && jin[b]) {
+            if (h == 0 && jin[b] && i0 + WR * wr < g.MI) {                 // (MI % 128 == 64: the last block's second wave row holds no cloud)
                 const size_t o = (size_t)((i0 + WR * wr) >> 6) * g.NJ + j;
                 g.smax[o] = bv;
                 g.sarg[o] = p;

@@ -54,12 +54,24 @@ class FineTuneNet(MODELL.PointNet_Plus):
 class FineTuneStep(ContrastiveStep):
     """One supervised iteration: grouping (ContrastiveStep.group) -> encoder forward -> head -> cross-entropy -> backward
     -> FusedAdam, with no host round trip (`run` is what GraphedStep captures).  The labels come from the static int32
-    device tensor ``self.labels`` (batch,), which the caller fills in place before each call; `order` is ignored."""
+    device tensor ``self.labels`` (batch,), which the caller fills in place before each call; `order` is ignored.
 
-    def __init__(self, netR, optimizer, opt, num_crop, group_radius=None, fps_reorder=False):
+    ``freeze_bn``: the model is put in eval() for the step, so every BatchNorm is the constant affine of its running statistics
+    (which the step leaves untouched) and the backward runs the frozen closed forms.  Such a step runs on eager
+    launches only: capturing a step whose model is in eval() is refused here."""
+
+    def __init__(self, netR, optimizer, opt, num_crop, group_radius=None, fps_reorder=False, freeze_bn=False):
         super().__init__(netR, optimizer, opt, num_crop, group_radius, fps_reorder)
         dev = next(netR.parameters()).device
         self.labels = torch.zeros(opt.batchSize, dtype=torch.int32, device=dev)
+        self.freeze_bn = bool(freeze_bn)
+
+    def run(self, out_points, order):
+        if self.freeze_bn:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("a step with frozen BatchNorm (model in eval()) runs eager: it is not captured into a graph")
+            self.netR.eval()                                # the epoch loop switches to train() at the start of every epoch
+        return super().run(out_points, order)
 
     def _encode_and_step(self, xt, yt, B, order):
         netR, G = self.netR, self.G
@@ -104,6 +116,9 @@ def finetune_parser():
                    help='NEW: 0 < f <= 1, the stratified fraction of the train split whose labels are used (label_subset)')
     p.add_argument('--label_seed', type=int, default=0, help='NEW: seed of the per-class permutations of --label_fraction')
     p.add_argument('--eval_every', type=int, default=1, help='NEW (--synthetic 0): test top-1 after every E-th epoch; 0 = off')
+    p.add_argument('--freeze_bn', type=int, default=0, choices=(0, 1),
+                   help='NEW: 1 = fine-tune with frozen BatchNorm: the model stays in eval() for the training step, the running '
+                        'statistics of --checkpoint (required) are kept, all weights train; the step runs eager')
     return p
 
 
@@ -136,6 +151,9 @@ def check_finetune_flags(opt, world=None):
         raise RuntimeError("--num_class must be a multiple of 4 in 2..1024 (got %d)" % opt.num_class)
     if not 1 <= opt.num_crop <= 64:
         raise RuntimeError("--num_crop must be in 1..64 (got %d)" % opt.num_crop)
+    if getattr(opt, "freeze_bn", 0) and not opt.checkpoint:
+        raise RuntimeError("--freeze_bn 1 keeps the running statistics of a pre-trained encoder: it needs --checkpoint (the "
+                           "initial statistics, mean 0 and variance 1, describe no data)")
 
 
 def _raise_bad_labels(bad, num_class, where):
@@ -198,7 +216,12 @@ def main(args=None):
     from .optim import FusedAdam
     optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06,
                           **optim_recipe(opt, steps_per_epoch))
-    step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder))
+    step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder), freeze_bn=bool(opt.freeze_bn))
+    if opt.freeze_bn:
+        opt.graph = 0                                    # no capture of a step whose model is in eval()
+        msg = 'BatchNorm frozen: running statistics of %s kept; step runs eager' % opt.checkpoint
+        logging.info(msg)
+        print(msg)
     gen = torch.Generator(device=device)
     gen.manual_seed(1000)
     hits, top1 = 0, None

@@ -97,10 +97,12 @@ def _running_update(bnc, rm, rv, n_true):
     rv.mul_(1 - BN_MOMENTUM).add_(unb, alpha=BN_MOMENTUM)
 
 
-def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=64, precision="f32"):
+def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=64, precision="f32", eval_backward=False):
     """x_rows (P,D) contiguous fp32, P = groups*K rows.  ``p``: dict with W1,b1,g1,be1,rm1,rv1, ...3.
     Returns (pooled (groups,256), ctx) where ctx carries what the backward needs.
     ``reduce_fn(t)`` (optional) all-reduces an fp64 tensor in place (SyncBN).
+    ``eval_backward`` (eval mode only): a backward may follow (frozen BatchNorm), so the forward takes the storing passes, which
+    keep y2 / ymax / arg, instead of the one-kernel eval path, which keeps nothing.
 
     The kernels work on units of 64 positions.  K = 64 (the reference's live value, utils_my.py:260) maps one
     group to one unit.  Other K are served around the same kernels (cold path, tensor glue):
@@ -171,7 +173,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         l1tab = _lib.empty((64, L1C), dtype=torch.float32, device=dev)
         _lib.check(lib.facl_sa_l1tab(_lib.ptr(W1), _lib.ptr(p["b1"]), D, _lib.ptr(bnc1[2]), _lib.ptr(bnc1[3]),
                                      _lib.ptr(l1tab), _lib.ptr(xa), _lib.ptr(amax[1]), st), "facl_sa_l1tab")
-    if not training and _EVAL_FUSED and precision in ("f32", "x3b") and _FWD_H3:
+    if not training and not eval_backward and _EVAL_FUSED and precision in ("f32", "x3b") and _FWD_H3:
         # eval mode = the extraction path (extract_motion_feature.py:143-221): every BatchNorm is a constant affine, so the whole
         # block is ONE kernel per unit, x -> pooled, with nothing stored in between (csrc/sa_eval.hip)
         bnc2 = _bn_eval(64, p["g2"], p["be2"], p["rm2"], p["rv2"])
@@ -249,7 +251,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         _lib.tap_relu("relu_sa3", a=pooled)
     ctx["amax"] = amax                               # [1], [2]: the backward's operand scales; [3]: max(pooled) for the next GEMM
     ctx.update(y2f=y2f, ymax=ymax_g, arg=arg, bnc1=bnc1, bnc2=bnc2, bnc3=bnc3, sgn3=sgn3, l1tab=l1tab, count=count,
-               nunits=nunits, D=D, R=R, rsel=rsel, ngroups=ngroups, x_rows=x_rows)
+               nunits=nunits, D=D, R=R, rsel=rsel, ngroups=ngroups, x_rows=x_rows, training=training)
     return pooled, ctx
 
 
@@ -263,7 +265,11 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
 
     Four heavy passes (csrc/sa_bwd.hip) with three fp64 closed-form assembly kernels between them
     (csrc/finalize.hip).  ``reduce_fn`` all-reduces the BN-backward sums (SyncBN); parameter gradients stay
-    LOCAL sums (the data-parallel wrapper averages them)."""
+    LOCAL sums (the data-parallel wrapper averages them).
+
+    A forward in eval mode (``ctx["training"]`` False: BatchNorm frozen at its running statistics) runs the SAME heavy passes:
+    every batch-statistic term reaches them through the tables G3 / h3 / bw2 only, which the frozen closed forms hand over
+    without those terms; nothing is all-reduced, and b1, b2, b3 get real gradients."""
     lib = _lib.load_library()
     dev = x_rows.device
     st = _lib.stream()
@@ -288,12 +294,18 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
         cu = torch.zeros((ngroups, R, 256), **f32)
         cu.scatter_(1, ctx["rsel"].unsqueeze(1), coef.unsqueeze(1))
         coef = cu.view(nunits, 256)
+    frozen = not ctx.get("training", True)
+    if frozen:
+        reduce_fn = None                         # a constant affine: no sum of this backward is global
     sums0_l = sums0
     if reduce_fn is not None:
         sums0 = reduce_fn(sums0.clone())
     G3, h3 = _lib.empty((64, 64), **f32), _lib.empty(64, **f32)
-    _lib.check(lib.facl_sa_bwd_consts3(ptr(sums0), ptr(bnc3), ptr(W3), ptr(p["b3"]), P, ptr(G3), ptr(h3), st),
-               "facl_sa_bwd_consts3")
+    if frozen:
+        _lib.check(lib.facl_sa_bwd_consts3_frozen(ptr(G3), ptr(h3), st), "facl_sa_bwd_consts3_frozen")
+    else:
+        _lib.check(lib.facl_sa_bwd_consts3(ptr(sums0), ptr(bnc3), ptr(W3), ptr(p["b3"]), P, ptr(G3), ptr(h3), st),
+                   "facl_sa_bwd_consts3")
 
     # ---- pass 1: dz2 + (dbeta2, dgamma2)
     dz2f = _lib.empty_like(ctx["y2f"])
@@ -308,7 +320,10 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
     # ---- pass 2: dy2, da1, dz1, dW2, R1 -- launched right behind pass 1 and walking the units backwards: the ends of dz2 / y2
     # that pass 1 touched last are still in the memory-side cache (FACL_BWD2_REV=0: front to back)
     bw2 = _lib.empty((4, 64), **f32)
-    _lib.check(lib.facl_sa_bwd_consts2(ptr(sums1), ptr(bnc2), P, ptr(bw2), st), "facl_sa_bwd_consts2")
+    if frozen:
+        _lib.check(lib.facl_sa_bwd_consts2_frozen(ptr(bnc2), ptr(bw2), st), "facl_sa_bwd_consts2_frozen")
+    else:
+        _lib.check(lib.facl_sa_bwd_consts2(ptr(sums1), ptr(bnc2), P, ptr(bw2), st), "facl_sa_bwd_consts2")
     out2 = _lib.empty(_lib.sa_bwd2_out(D), **f64)
     with _lib.timed("facl_sa_bwd2"):
         _lib.check(lib.facl_sa_bwd2(ptr(dz2f), ptr(ctx["y2f"]), ptr(x_rows), nunits, D, ptr(bw2), ptr(W2), ptr(ctx["l1tab"]),
@@ -319,15 +334,21 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
         _lib.check(lib.facl_sa_bwd_w3(ptr(ctx["y2f"]), nunits, ptr(bnc2), ptr(coef), ptr(ctx["arg"]), ptr(out3), ptr(ws),
                                       ptr(ctx["amax"][2]), st), "facl_sa_bwd_w3")
 
-    R1_g = out2[4096:]                           # (sa_l1_cols(D), 64): rows x_0..x_{D-1}, sum dz1, zeros
-    if reduce_fn is not None:
-        R1_g = reduce_fn(R1_g.clone())
-
     g = {"W3": _lib.empty_like(p["W3"]), "g3": _lib.empty(256, **f32), "be3": _lib.empty(256, **f32),
          "W2": _lib.empty_like(p["W2"]), "g2": _lib.empty(64, **f32), "be2": _lib.empty(64, **f32),
          "W1": _lib.empty_like(p["W1"]), "g1": _lib.empty(64, **f32), "be1": _lib.empty(64, **f32),
          # d(bias) of a conv that feeds a train-mode BN is identically zero: None (the parameter is left untouched)
          "b1": None, "b2": None, "b3": None}
+    if frozen:                                   # ... and a real gradient behind a frozen one: sum dy = scale * dbeta
+        g.update(b1=_lib.empty(64, **f32), b2=_lib.empty(64, **f32), b3=_lib.empty(256, **f32))
+        _lib.check(lib.facl_sa_bwd_final_frozen(ptr(out3), ptr(sums0), ptr(bnc3), ptr(out2), ptr(sums1), ptr(bnc2), ptr(bnc1),
+                                                ptr(W1), ptr(p["b1"]), D, ptr(g["W3"]), ptr(g["g3"]), ptr(g["be3"]), ptr(g["b3"]),
+                                                ptr(g["W2"]), ptr(g["g2"]), ptr(g["be2"]), ptr(g["b2"]), ptr(g["W1"]),
+                                                ptr(g["g1"]), ptr(g["be1"]), ptr(g["b1"]), st), "facl_sa_bwd_final_frozen")
+        return g
+    R1_g = out2[4096:]                           # (sa_l1_cols(D), 64): rows x_0..x_{D-1}, sum dz1, zeros
+    if reduce_fn is not None:
+        R1_g = reduce_fn(R1_g.clone())
     _lib.check(lib.facl_sa_bwd_final(ptr(out3), ptr(sums0), ptr(sums0_l), ptr(bnc3), ptr(W3), ptr(p["b3"]), ptr(out2),
                                      ptr(sums1_l), ptr(R1_g), ptr(ctx["mom_local"]), ptr(bnc1), ptr(W1), ptr(p["b1"]),
                                      D, P, ptr(g["W3"]), ptr(g["g3"]), ptr(g["be3"]), ptr(g["W2"]), ptr(g["g2"]),
@@ -346,8 +367,10 @@ class SAMLPFunction(torch.autograd.Function):
     def forward(ctx, x_rows, state, *params):
         p = dict(zip(_PARAM_ORDER, [t.detach().contiguous() for t in params]))
         p.update(state["buffers"])
+        # eval mode: the one-kernel path keeps nothing for a backward; the storing passes run only when one can follow
         pooled, c = sa_mlp_forward(x_rows, p, state["training"], state.get("reduce_fn"), K=state.get("K", UNIT),
-                                   precision=state.get("precision", "f32"))
+                                   precision=state.get("precision", "f32"),
+                                   eval_backward=not state["training"] and any(ctx.needs_input_grad))
         # max(pooled): the fp16x3 scale of the GEMM that consumes the features (the fused eval kernel keeps none: measured there)
         state["pooled_amax"] = None if c.get("amax") is None else c["amax"][3]
         ctx.c, ctx.p, ctx.x_rows, ctx.reduce_fn = c, p, x_rows, state.get("reduce_fn")
@@ -356,7 +379,5 @@ class SAMLPFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpooled):
-        if not ctx.training:
-            raise RuntimeError("backward through the eval-mode (folded BN) encoder is not supported")
-        g = sa_mlp_backward(ctx.c, dpooled, ctx.x_rows, ctx.p, ctx.reduce_fn)
+        g = sa_mlp_backward(ctx.c, dpooled, ctx.x_rows, ctx.p, ctx.reduce_fn)    # ctx.c["training"] selects the frozen closed forms
         return (None, None) + tuple(g[k] for k in _PARAM_ORDER)

@@ -157,20 +157,37 @@ def _bn_bwd_consts(sums, C, count, reduce_fn):
     return dbeta, dgamma, kk
 
 
-def _bn_relu_backward(da, y, bnc, count, reduce_fn, ws, sums=None, amax=None):
+def _bn_bwd_consts_mode(sums, bnc, C, count, reduce_fn, training):
+    """The constants step of every BatchNorm backward of the tail, by the mode its forward ran in -> (dbeta, dgamma, kk, dbias).
+    Training: `_bn_bwd_consts`; dbias, the gradient of the bias in front of the BatchNorm, is identically zero there: None.
+    Eval (BatchNorm frozen at its running statistics, a constant affine): the sums taken with the running mean / invstd of
+    `bnc` ARE (dbeta, dgamma), kk = 0 makes the apply kernels give dy = scale dz, dbias = scale dbeta is a real gradient, and
+    nothing is all-reduced (facl_bn_bwd_consts_frozen)."""
+    if training:
+        return _bn_bwd_consts(sums, C, count, reduce_fn) + (None,)
+    lib = _lib.load_library()
+    f32 = dict(dtype=torch.float32, device=sums.device)
+    dbeta, dgamma, dbias, kk = _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty((2, C), **f32)
+    _lib.check(lib.facl_bn_bwd_consts_frozen(_lib.ptr(sums), _lib.ptr(bnc), C, _lib.ptr(dbeta), _lib.ptr(dgamma), _lib.ptr(dbias),
+                                             _lib.ptr(kk), _lib.stream()), "facl_bn_bwd_consts_frozen")
+    return dbeta, dgamma, kk, dbias
+
+
+def _bn_relu_backward(da, y, bnc, count, reduce_fn, ws, sums=None, amax=None, training=True):
     """Backward of relu(bn(y)) over rows: column sums (unless the producer of `da` left them in `sums`) -> constants -> dense
-    dy, which also raises `amax` (or None) to max|dy|.  Returns (dy, dgamma, dbeta); the parameter gradients stay local sums."""
+    dy, which also raises `amax` (or None) to max|dy|.  Returns (dy, dgamma, dbeta, dbias); the parameter gradients stay local
+    sums; dbias is None behind a train-mode BatchNorm (`_bn_bwd_consts_mode`)."""
     lib = _lib.load_library()
     R, C = y.shape
     if sums is None:
         sums = _lib.empty((C, 2), dtype=torch.float64, device=y.device)
         _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws),
                                            _lib.stream()), "facl_rows_bwd_stats")
-    dbeta, dgamma, kk = _bn_bwd_consts(sums, C, count, reduce_fn)
+    dbeta, dgamma, kk, dbias = _bn_bwd_consts_mode(sums, bnc, C, count, reduce_fn, training)
     dy = _lib.empty_like(y)
     _lib.check(lib.facl_rows_bwd_apply_amax(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy),
                                             _lib.ptr(amax), _lib.stream()), "facl_rows_bwd_apply_amax")
-    return dy, dgamma, dbeta
+    return dy, dgamma, dbeta, dbias
 
 
 def _first_layer_wgrad(dy, h, centers, ws, prec, amax=None, amax_b=None):
@@ -237,15 +254,13 @@ class _LinearBNReLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, da):
         bp = backward_precision(ctx.prec)   # the backward GEMMs run in the arithmetic the forward recorded
-        if not ctx.training:
-            raise RuntimeError("backward through the eval-mode (folded BN) encoder is not supported")
         h, W, y, bnc = ctx.saved_tensors
         ws = _Workspace.get(y.device)
-        dy, dgamma, dbeta = _bn_relu_backward(da.contiguous(), y, bnc, ctx.count, ctx.reduce_fn, ws)
+        dy, dgamma, dbeta, db = _bn_relu_backward(da.contiguous(), y, bnc, ctx.count, ctx.reduce_fn, ws, training=ctx.training)
         dW = gemm_wgrad(dy, h, prec=bp) if ctx.centers is None else _first_layer_wgrad(dy, h, ctx.centers, ws, bp)
         dh = gemm_dgrad(dy, ctx.Wh, prec=bp) if ctx.needs_input_grad[0] else None
-        # d(bias) is identically zero in front of a train-mode BN: None leaves the parameter untouched
-        return dh, dW, None, dgamma, dbeta, None, None, None, None
+        # d(bias) is identically zero in front of a train-mode BN: None leaves the parameter untouched (eval mode: scale * dbeta)
+        return dh, dW, db, dgamma, dbeta, None, None, None, None
 
 
 class _LinearBNSegmax(torch.autograd.Function):
@@ -297,8 +312,6 @@ class _LinearBNSegmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dxpre, _darg):
         bp = backward_precision(ctx.prec)   # the backward GEMMs run in the arithmetic the forward recorded
-        if not ctx.training:
-            raise RuntimeError("backward through the eval-mode (folded BN) encoder is not supported")
         lib = _lib.load_library()
         h, W, y, bnc, xpre, arg = ctx.saved_tensors
         ws = _Workspace.get(y.device)
@@ -310,14 +323,14 @@ class _LinearBNSegmax(torch.autograd.Function):
         _lib.check(lib.facl_segmax_bwd_stats(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(y), _lib.ptr(arg), M, S, C,
                                              _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws), _lib.stream()),
                    "facl_segmax_bwd_stats")
-        dbeta, dgamma, kk = _bn_bwd_consts(sums, C, ctx.count, ctx.reduce_fn)   # parameter gradients stay local sums
+        dbeta, dgamma, kk, db = _bn_bwd_consts_mode(sums, bnc, C, ctx.count, ctx.reduce_fn, ctx.training)   # parameter gradients stay local sums
         dy = _lib.empty_like(y)
         _lib.check(lib.facl_segmax_bwd_apply(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(y), _lib.ptr(arg), M, S, C,
                                              _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy), _lib.stream()),
                    "facl_segmax_bwd_apply")
         dW = gemm_wgrad(dy, h, prec=bp)
         dh = gemm_dgrad(dy, W, prec=bp)
-        return dh, dW, None, dgamma, dbeta, None, None, None, None
+        return dh, dW, db, dgamma, dbeta, None, None, None, None
 
 
 def linear_bn_relu(h, affine, bn, training, reduce_fn=None, centers=None):
@@ -445,8 +458,6 @@ class _FCHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         bp = backward_precision(ctx.prec)   # the backward GEMMs run in the arithmetic the forward recorded
-        if not ctx.training:
-            raise RuntimeError("backward through the eval-mode (folded BN) encoder is not supported")
         lib = _lib.load_library()
         h, W1, y, a, W2, arg, *bncs = ctx.saved_tensors
         bnc2 = bncs[0] if ctx.fused else None
@@ -469,6 +480,7 @@ class _FCHead(torch.autograd.Function):
                 db2 = dout.sum(0)
         dact = gemm_dgrad(dout, W2, prec=bp)
         dy = _lib.empty_like(y)
+        db1 = None                                               # zero in front of a train-mode BN
         if ctx.fused:
             sums2 = sums2_g = None
             if ctx.reduce_fn is not None:
@@ -486,14 +498,23 @@ class _FCHead(torch.autograd.Function):
             for i, ((r0, r1), bnc) in enumerate(zip(ctx.segs, (bnc_a, bnc_b))):
                 _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(dact[r0:r1]), _lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(bnc),
                                                    _lib.ptr(sums2[i]), _lib.ptr(ws), _lib.stream()), "facl_rows_bwd_stats")
-            sums2_g = ctx.reduce_fn(sums2.clone()) if ctx.reduce_fn is not None else sums2       # one all-reduce for the pair
+            frozen = not ctx.training                            # eval mode: both segments share the running statistics
+            sums2_g = ctx.reduce_fn(sums2.clone()) if ctx.reduce_fn is not None and not frozen else sums2   # one all-reduce for the pair
             dbe, dga, kk = _lib.empty((2, C), **f32), _lib.empty((2, C), **f32), _lib.empty((2, 2, C), **f32)
+            parts = []
             for i, ((r0, r1), bnc, count) in enumerate(zip(ctx.segs, (bnc_a, bnc_b), ctx.counts)):
-                _lib.check(lib.facl_bn_bwd_consts(_lib.ptr(sums2[i]), _lib.ptr(sums2_g[i]), C, float(count), _lib.ptr(dbe[i]),
-                                                  _lib.ptr(dga[i]), _lib.ptr(kk[i]), _lib.stream()), "facl_bn_bwd_consts")
+                if frozen:
+                    part = _bn_bwd_consts_mode(sums2[i], bnc, C, count, None, False)
+                else:
+                    _lib.check(lib.facl_bn_bwd_consts(_lib.ptr(sums2[i]), _lib.ptr(sums2_g[i]), C, float(count), _lib.ptr(dbe[i]),
+                                                      _lib.ptr(dga[i]), _lib.ptr(kk[i]), _lib.stream()), "facl_bn_bwd_consts")
+                    part = (dbe[i], dga[i], kk[i], None)
                 _lib.check(lib.facl_rows_bwd_apply(_lib.ptr(dact[r0:r1]), _lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(bnc),
-                                                   _lib.ptr(kk[i]), _lib.ptr(dy[r0:r1]), _lib.stream()), "facl_rows_bwd_apply")
-            dgamma, dbeta = dga[0] + dga[1], dbe[0] + dbe[1]
+                                                   _lib.ptr(part[2]), _lib.ptr(dy[r0:r1]), _lib.stream()), "facl_rows_bwd_apply")
+                parts.append(part)
+            dgamma, dbeta = parts[0][1] + parts[1][1], parts[0][0] + parts[1][0]
+            if frozen:
+                db1 = parts[0][3] + parts[1][3]
         with _lib.fork(enabled=side) as f1:
             dW1 = gemm_wgrad(dy, h, prec=bp)
         dh = gemm_dgrad(dy, W1, prec=bp)
@@ -503,7 +524,7 @@ class _FCHead(torch.autograd.Function):
         f2.join(dW2, db2)
         f1.join(dW1)
         # d(bias of the first Linear) is identically zero in front of a train-mode BN: None leaves it untouched
-        return dh[:M], None, dW1, None, dgamma, dbeta, None, dW2, db2, None, None
+        return dh[:M], None, dW1, db1, dgamma, dbeta, None, dW2, db2, None, None
 
 
 def fc_head(x_pre, G, affine1, bn, affine2, training, reduce_fn=None):
@@ -757,7 +778,8 @@ class _Net3DV3(torch.autograd.Function):
         # do not change between the two)
         h3 = FWD_H3
         jobs = [(W1[:, 3:], False, W1[:, :3], h3), (W2, False, None, h3), (W3, False, None, h3)]
-        want_bwd = training and backward_precision(ctx.prec) == "f32"
+        # (eval mode: only when a backward can follow -- BatchNorm frozen; under no_grad nothing is prepared, as before)
+        want_bwd = (training or any(ctx.needs_input_grad)) and backward_precision(ctx.prec) == "f32"
         if want_bwd:
             jobs += [(W3, True, None, BWD_H3), (W2, True, None, BWD_H3), (W1[:, 3:], True, None, BWD_H3)]
         # fp16x3 operand maxima of the three row operands (csrc/common.h): [0] max(pooled, |centres|) -- the pooled features
@@ -793,8 +815,6 @@ class _Net3DV3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dxpre):
-        if not ctx.training:
-            raise RuntimeError("backward through the eval-mode (folded BN) encoder is not supported")
         bp = backward_precision(ctx.prec)
         lib = _lib.load_library()
         pooled, centers, W1, W2, W3, y1, y2, y3, bnc1, bnc2, bnc3, xpre, arg, ymax = ctx.saved_tensors
@@ -815,7 +835,7 @@ class _Net3DV3(torch.autograd.Function):
         _lib.check(lib.facl_segmax_bwd_stats_ymax(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(ymax), M, C3, _lib.ptr(bnc3),
                                                   _lib.ptr(sums), _lib.ptr(ws), _lib.ptr(amax), 3 * _lib.AMAX_WORDS if h3 else 0, st),
                    "facl_segmax_bwd_stats")
-        dbe3, dga3, kk = _bn_bwd_consts(sums, C3, ctx.count, ctx.reduce_fn)
+        dbe3, dga3, kk, db3 = _bn_bwd_consts_mode(sums, bnc3, C3, ctx.count, ctx.reduce_fn, ctx.training)
         dy = _lib.empty_like(y3)
         am = (lambda i: amax[i]) if h3 else (lambda i: None)
         _lib.check(lib.facl_segmax_bwd_apply_amax(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(y3), _lib.ptr(arg), M, S, C3,
@@ -829,17 +849,18 @@ class _Net3DV3(torch.autograd.Function):
         # ---- layers 2 and 1: BN backward rows passes, weight gradient with the recomputed activation, dgrad
         grads = []
         for li, (y, bnc, yin, bnc_in, W) in enumerate(((y2, bnc2, y1, bnc1, W2), (y1, bnc1, None, None, W1)), 1):
-            dy, dga, dbe = _bn_relu_backward(da, y, bnc, ctx.count, ctx.reduce_fn, ws, sums, am(li))
+            dy, dga, dbe, db = _bn_relu_backward(da, y, bnc, ctx.count, ctx.reduce_fn, ws, sums, am(li), training=ctx.training)
             if yin is not None:
                 dW = _wgrad_pro(dy, yin, bnc_in, bp, am(li), a1b)
                 da, sums = _rs_dgrad(dy, W, bp, bpl[1], yin, bnc_in, ws, am(li))
             else:                                                       # first layer: input = pooled | centres
                 dW = _first_layer_wgrad(dy, pooled, centers, ws, bp, am(li), a0b)
                 da = _rs_dgrad(dy, W[:, 3:], bp, bpl[2], amax=am(li))[0] if ctx.needs_input_grad[0] else None
-            grads.append((dW, dga, dbe))
-        (dW2, dga2, dbe2), (dW1, dga1, dbe1) = grads
-        # d(bias) of a conv in front of a train-mode BN is identically zero: None leaves the parameter untouched
-        return (da, None, None, None, None, None, None, dW1, None, dga1, dbe1, dW2, None, dga2, dbe2, dW3, None, dga3, dbe3)
+            grads.append((dW, db, dga, dbe))
+        (dW2, db2, dga2, dbe2), (dW1, db1, dga1, dbe1) = grads
+        # d(bias) of a conv in front of a train-mode BN is identically zero: None leaves the parameter untouched (eval mode:
+        # BatchNorm frozen, scale * dbeta)
+        return (da, None, None, None, None, None, None, dW1, db1, dga1, dbe1, dW2, db2, dga2, dbe2, dW3, db3, dga3, dbe3)
 
 
 def net3dv3(pooled, centers, net, training, S, reduce_fn=None, pooled_amax=None):

@@ -220,6 +220,27 @@ int facl_sa_bwd_final(const double* out3, const double* sums0_g, const double* s
                       const double* R1_g, const double* mom_l, const float* bnc1, const float* W1,
                       const float* b1, int D, double P, float* dW3, float* dg3, float* dbe3, float* dW2,
                       float* dg2, float* dbe2, float* dW1, float* dg1, float* dbe1, void* stream);
+/* Frozen (eval-mode) BatchNorm backward: bnc = the (5,C) constants of facl_bn_eval_consts (running statistics), so
+ * z = scale*y + shift is a constant affine and dy = scale*dz.  The (C,2) sums of the SAME statistics passes
+ * (facl_rows_bwd_stats, facl_segmax_bwd_stats[_ymax], facl_gemm_rs_dgrad_bnstats; facl_sa_bwd0 / facl_sa_bwd1) are then
+ * (dbeta, dgamma) themselves; nothing is all-reduced.
+ *   facl_bn_bwd_consts_frozen   sums (C,2), bnc -> dbeta (C), dgamma (C), dbias (C) = scale*dbeta (the gradient of the bias
+ *                               of the conv / Linear in front, identically zero in train mode) and kk (2,C) = 0, with which
+ *                               facl_rows_bwd_apply[_amax] / facl_segmax_bwd_apply[_amax] give dy = scale*dz
+ *   facl_sa_bwd_consts3_frozen  G3 (64,64) = 0, h3 (64) = 0 for facl_sa_bwd1: da2 keeps its sparse rows only
+ *   facl_sa_bwd_consts2_frozen  bnc2 -> bw2 (4,64) = [scale2 | 0 | 0 | mean2] for facl_sa_bwd2: dy2 = scale2*dz2
+ *   facl_sa_bwd_final_frozen    out3 (facl_sa_bwd_w3; its sparse part), sums0 (facl_sa_bwd0), out2 (facl_sa_bwd2), sums1
+ *                               (facl_sa_bwd1), bnc3 / bnc2 / bnc1 -> the twelve gradients of net3DV_1:
+ *                               dW3 = sparse part, dW2 = out2's, dW1 = scale1*R1[x rows]; (dbeta, dgamma) = the sums
+ *                               (layer 1: from R1 in closed form); db = scale*dbeta.  No x moments (an eval forward has none). */
+int facl_bn_bwd_consts_frozen(const double* sums, const float* bnc, int C, float* dbeta, float* dgamma, float* dbias,
+                              float* kk, void* stream);
+int facl_sa_bwd_consts3_frozen(float* G3, float* h3, void* stream);
+int facl_sa_bwd_consts2_frozen(const float* bnc2, float* bw2, void* stream);
+int facl_sa_bwd_final_frozen(const double* out3, const double* sums0, const float* bnc3, const double* out2,
+                             const double* sums1, const float* bnc2, const float* bnc1, const float* W1, const float* b1,
+                             int D, float* dW3, float* dg3, float* dbe3, float* db3, float* dW2, float* dg2, float* dbe2,
+                             float* db2, float* dW1, float* dg1, float* dbe1, float* db1, void* stream);
 
 /* ---- encoder tail: row-major (R,C) BatchNorm / ReLU / max-over-S kernels ----------------------
  * net3DV_3 + my_max_pool + netR_FC (cn3d_model_conbag.py:61-88, :199-207).  The dense contractions

@@ -138,6 +138,9 @@ SIGNATURES = {
     "facl_loss_rows_bwd": [c_p, c_p, c_p, c_l, c_i, c_i, c_f, c_p, c_p],
     "facl_contrast_pair_queue": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_queue_push": [c_p, c_i, c_i, c_p, c_i, c_p, c_p],
+    "facl_contrast_pair_sum_cls": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "facl_contrast_pair_queue_cls": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "facl_queue_push_ids": [c_p, c_i, c_p, c_i, c_p, c_p],
     "facl_ema_apply": [c_i, c_p, c_p, c_p, c_f, c_p],
     "facl_grad_sqnorm": [c_i, c_p, c_p, c_p, c_p],
     "facl_adam_prep_ex": [c_p, c_p, c_f, c_f, c_p, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_p],

@@ -181,7 +181,20 @@ __global__ __launch_bounds__(1024) void k_contrast_reg(const float* __restrict__
 // sum at all (negatives only), so none of the three holds: the maximum starts at -inf and masked / past-the-end elements are
 // skipped by the maximum and by the sum (Bk >= 2: at least one negative exists).  In both modes the masked columns' dsim is 0
 // and the positives are read before masking.
-constexpr int MASK_ZERO = 0, MASK_EXCLUDE = 1;
+// MASK_CLASS: `exclude`, and beside the clip's own columns every column of a clip KNOWN to share the anchor's class leaves the
+// sum (false-negative removal with labels): cls (Bk int32) holds one class id per key clip, >= 0 a class, < 0 unknown; column j
+// is masked iff j % Bk == myclip || (cls[myclip] >= 0 && cls[j % Bk] == cls[myclip]).  The ids are only compared, never used
+// as an index.  Here a clip may have NO negative (a batch of one class): mx = -inf and se = 0 give lse = -inf + log(0) = -inf,
+// every slot's t = pos + log1p(exp(-inf)) = pos, so loss, dpos and dlse are exactly 0 and no exp(x - lse) is evaluated (every
+// column is masked) -- the arithmetic below needs no special case.
+constexpr int MASK_ZERO = 0, MASK_EXCLUDE = 1, MASK_CLASS = 2;
+
+// jm = j % Bk, mycls = cls[myclip] (MASK_CLASS only)
+template <int MASK>
+__device__ __forceinline__ bool col_masked(int jm, int myclip, int mycls, const int* __restrict__ cls) {
+    if constexpr (MASK == MASK_CLASS) return jm == myclip || (mycls >= 0 && cls[jm] == mycls);
+    else return jm == myclip;
+}
 
 struct PairSpec {
     int nA, nS, slot_rows, circle, G, B, Bk, J, myclip, n;
@@ -201,7 +214,8 @@ struct PairSpec {
 template <int MASK>
 __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restrict__ sim, int G, int B, int Bk, int J,
                                                            const long long* __restrict__ order, int clip_offset,
-                                                           float* __restrict__ dsim, double* __restrict__ part) {
+                                                           float* __restrict__ dsim, double* __restrict__ part,
+                                                           const int* __restrict__ cls) {
     __shared__ float smf[16];
     __shared__ double smd[16];
     __shared__ int rb_s[1024];
@@ -211,6 +225,8 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
     sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
+    int mycls = -1;
+    if constexpr (MASK == MASK_CLASS) mycls = cls[myclip];
     if ((int)threadIdx.x < nA) rb_s[threadIdx.x] = sp.row_block(threadIdx.x);
     __syncthreads();
     const int total = nA * J;
@@ -222,6 +238,24 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     int wi = (int)threadIdx.x / J, wj = (int)threadIdx.x - wi * J, wjm = wj % Bk;
     float v[CK];
     unsigned off[CK];
+    // MASK_CLASS: bit k = element k lies in a column of the anchor's known class.  The CK lookups run FIRST, in a pass of their
+    // own over the same column index and without a condition (the index stays inside [0, Bk) past the end of the block too), so
+    // that they are CK requests in flight at once: with the lookup inside the loop below every similarity load waited for its id,
+    // CK round trips instead of one, +28 us per step at the headline size.
+    unsigned same_cls = 0u;
+    if constexpr (MASK == MASK_CLASS) {
+        if (mycls >= 0) {                                  // workgroup-uniform
+            int pj = wj, pjm = wjm;
+#pragma unroll
+            for (int k = 0; k < CK; ++k) {
+                same_cls |= (unsigned)(cls[pjm] == mycls) << k;
+                pj += dj; pjm += djm;
+                if (pj >= J) { pj -= J; pjm += Bk - Jm; }
+                if (pjm >= Bk) pjm -= Bk;
+                if (pjm >= Bk) pjm -= Bk;
+            }
+        }
+    }
     float mx = MASK == MASK_ZERO ? 0.f : -INFINITY;        // zero: masked entries are 0, there is at least one
 #pragma unroll
     for (int k = 0; k < CK; ++k) {
@@ -230,7 +264,8 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
         off[k] = 0x80000000u;
         if (e < total) {
             const unsigned o = (unsigned)((rb_s[wi] * B + n) * J + wj);
-            const bool masked = wjm == myclip;
+            bool masked = wjm == myclip;
+            if constexpr (MASK == MASK_CLASS) masked = masked || ((same_cls >> k) & 1u);
             off[k] = masked ? (o | 0x80000000u) : o;
             if (!masked) x = sim[o];
         }
@@ -283,7 +318,8 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
 template <int MASK>
 __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__ sim, int G, int B, int Bk, int J,
                                                        const long long* __restrict__ order, int clip_offset,
-                                                       float* __restrict__ dsim, double* __restrict__ part) {
+                                                       float* __restrict__ dsim, double* __restrict__ part,
+                                                       const int* __restrict__ cls) {
     __shared__ float smf[4];
     __shared__ double smd[4];
     PairSpec sp;
@@ -292,12 +328,14 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
     sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
     sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
+    int mycls = -1;
+    if constexpr (MASK == MASK_CLASS) mycls = cls[myclip];
     float mx = MASK == MASK_ZERO ? 0.f : -INFINITY;
     for (int i = 0; i < nA; ++i) {
         const float* row = sim + (size_t)(sp.row_block(i) * B + n) * J;
         for (int j = threadIdx.x; j < J; j += 256) {
             if constexpr (MASK == MASK_ZERO) mx = fmaxf(mx, (j % Bk == myclip) ? 0.f : row[j]);
-            else if (j % Bk != myclip) mx = fmaxf(mx, row[j]);
+            else if (!col_masked<MASK>(j % Bk, myclip, mycls, cls)) mx = fmaxf(mx, row[j]);
         }
     }
     mx = block_reduce_max(mx, smf);
@@ -306,7 +344,7 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
         const float* row = sim + (size_t)(sp.row_block(i) * B + n) * J;
         for (int j = threadIdx.x; j < J; j += 256) {
             if constexpr (MASK == MASK_ZERO) se += (double)__expf(((j % Bk == myclip) ? 0.f : row[j]) - mx);
-            else if (j % Bk != myclip) se += (double)__expf(row[j] - mx);
+            else if (!col_masked<MASK>(j % Bk, myclip, mycls, cls)) se += (double)__expf(row[j] - mx);
         }
     }
     se = block_reduce_sum(se, smd);
@@ -323,7 +361,8 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
     dlse *= invB;
     for (int i = 0; i < nA; ++i) {
         const size_t ro = (size_t)(sp.row_block(i) * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256) dsim[ro + j] = (j % Bk == myclip) ? 0.f : dlse * __expf(sim[ro + j] - lse);
+        for (int j = threadIdx.x; j < J; j += 256)
+            dsim[ro + j] = col_masked<MASK>(j % Bk, myclip, mycls, cls) ? 0.f : dlse * __expf(sim[ro + j] - lse);
     }
     if (sp.circle) {
         float* z = dsim + (size_t)(sp.ord(G - 1) * B + n) * J;
@@ -432,23 +471,25 @@ namespace {
 // shape checks and launch of the pair kernels: per-clip partial losses [loss_c, loss_circle] into ws, d/dsim into dsim
 template <int MASK>
 void launch_pair_kernel(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, float* dsim,
-                        void* ws, hipStream_t st) {
+                        void* ws, hipStream_t st, const int32_t* cls = nullptr) {
     if ((long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL)
         hipLaunchKernelGGL(k_contrast_pair_reg<MASK>, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws);
+                           clip_offset, dsim, (double*)ws, (const int*)cls);
     else
         hipLaunchKernelGGL(k_contrast_pair<MASK>, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws);
+                           clip_offset, dsim, (double*)ws, (const int*)cls);
 }
 
+// cls: the class ids of MASK_CLASS; the entries with a mask_mode argument pass none, and mode 2 is no mode of theirs
 int launch_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, float* dsim,
-                void* ws, hipStream_t st) {
+                void* ws, hipStream_t st, const int32_t* cls = nullptr) {
     if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return FACL_E_SHAPE;
     if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
-    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE) return FACL_E_SHAPE;
-    if (mask_mode == MASK_EXCLUDE && Bk < 2) return FACL_E_SHAPE;            // one key clip: no negative exists
+    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !(mask_mode == MASK_CLASS && cls)) return FACL_E_SHAPE;
+    if (mask_mode != MASK_ZERO && Bk < 2) return FACL_E_SHAPE;               // one key clip: no negative exists
     if (mask_mode == MASK_ZERO) launch_pair_kernel<MASK_ZERO>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
-    else launch_pair_kernel<MASK_EXCLUDE>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
+    else if (mask_mode == MASK_EXCLUDE) launch_pair_kernel<MASK_EXCLUDE>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
+    else launch_pair_kernel<MASK_CLASS>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st, cls);
     return facl_launch_status();
 }
 }  // namespace
@@ -544,7 +585,10 @@ extern "C" int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_
 // ---------------------------------------------------------------------------------------------------------------------
 // The pair loss with a queue of negative keys from earlier steps.  sim_q ((G+1)*B, L) = [x ; x_global] @ queue^T holds, in its
 // first `valid` columns (qstate = {head, valid}, read on the device: a captured step replays while the queue fills), extra
-// negatives of every clip in both losses; they carry no clip identity, so no mask mode touches them.  Columns >= valid are
+// negatives of every clip in both losses; they carry no clip identity, so MASK_ZERO and MASK_EXCLUDE do not touch them; under
+// MASK_CLASS column k carries qcls[k], the class id of the clip that pushed it, and is masked iff the anchor's class is known
+// and equal to it (q_load; a clip whose every column is masked has the partials (-inf, 0) everywhere, so M = -inf, S = 0 and
+// lse = -inf: exactly 0 everywhere, as in the pair kernels).  Columns >= valid are
 // never used (V = 4 loads the vector that straddles `valid` whole, inside the row, and q_load drops its dead lanes, NaN
 // included) and their dsim_q is written as exactly 0.  A clip's block is now nA x (J + valid) values: too large for the
 // register form, and 2B workgroups reading it three times would leave most CUs idle.  The block is therefore spread over
@@ -603,8 +647,12 @@ __device__ __forceinline__ QUnit q_unit(int G, int B, int Bk, int J, int L, cons
 
 // The chunk's values into registers.  Bit i of `grad`: value i is a live column that is not a same-clip one (it receives a
 // gradient); bit i of `mem`: it is a member of the log-sum-exp (MASK_ZERO: the same-clip columns too, as the value 0).
+// MASK_CLASS: ids = cls (Bk) for a chunk of sim, looked up through the same-clip column index, or qcls (L) for a chunk of sim_q,
+// read beside the values (V = 4: one 16-byte load, the launcher checks qcls's alignment); a queue column is masked iff the
+// anchor's class is known and equals the column's.  Ids of dead lanes (columns >= valid) are never looked at.
 template <int MASK, int V>
-__device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__ m, float (&x)[QN], unsigned& mem, unsigned& grad) {
+__device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__ m, float (&x)[QN], unsigned& mem, unsigned& grad,
+                                       const int* __restrict__ ids = nullptr, int mycls = -1) {
     const float* src = m + u.base;
     const int Bk = u.sp.Bk;
     int jm = 0, step = 0;
@@ -614,8 +662,9 @@ __device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__
     for (int k = 0; k < QN / V; ++k) {
         const int e = (k * QT + (int)threadIdx.x) * V;
         float v[V];
+        int id[V];
 #pragma unroll
-        for (int c = 0; c < V; ++c) v[c] = 0.f;
+        for (int c = 0; c < V; ++c) { v[c] = 0.f; id[c] = -1; }
         if (e < u.len) {                                   // V = 4: wlen % 4 == 0, the whole vector lies inside the row
             if constexpr (V == 4) {
                 const float4 q = *reinterpret_cast<const float4*>(src + e);
@@ -623,11 +672,25 @@ __device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__
             } else {
                 v[0] = src[e];
             }
+            if constexpr (MASK == MASK_CLASS) {
+                if (!u.in_sim && mycls >= 0) {             // workgroup-uniform
+                    if constexpr (V == 4) {
+                        const int4 q = *reinterpret_cast<const int4*>(ids + u.c0 + e);
+                        id[0] = q.x; id[1] = q.y; id[2] = q.z; id[3] = q.w;
+                    } else {
+                        id[0] = ids[u.c0 + e];
+                    }
+                }
+            }
         }
 #pragma unroll
         for (int c = 0; c < V; ++c) {
             const bool live = e + c < u.len;
-            const bool masked = u.in_sim && jm == u.sp.myclip;
+            bool masked = u.in_sim && jm == u.sp.myclip;
+            if constexpr (MASK == MASK_CLASS) {
+                if (u.in_sim) masked = live && col_masked<MASK>(jm, u.sp.myclip, mycls, ids);
+                else masked = mycls >= 0 && id[c] == mycls;
+            }
             const bool g = live && !masked;
             x[k * V + c] = g ? v[c] : 0.f;
             grad |= (unsigned)g << (k * V + c);
@@ -642,14 +705,16 @@ template <int MASK, int V>
 __global__ __launch_bounds__(QT) void k_contrast_queue_part(const float* __restrict__ sim, const float* __restrict__ sim_q, int G,
                                                             int B, int Bk, int J, int L, const long long* __restrict__ order,
                                                             int clip_offset, const int* __restrict__ qstate,
-                                                            float* __restrict__ pm, double* __restrict__ ps) {
+                                                            float* __restrict__ pm, double* __restrict__ ps,
+                                                            const int* __restrict__ cls, const int* __restrict__ qcls) {
     __shared__ float smf[QT / 64];
     __shared__ double smd[QT / 64];
     const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
     if (u.slot == G - 1) return;                           // no anchor: no member of any log-sum-exp
     float x[QN];
     unsigned mem, grad;
-    q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);
+    if constexpr (MASK == MASK_CLASS) q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[u.sp.myclip]);
+    else q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);
     float mx = -INFINITY;                                  // a chunk without a member: (-inf, 0), skipped by the combination
 #pragma unroll
     for (int i = 0; i < QN; ++i)
@@ -669,7 +734,8 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
                                                              int clip_offset, const int* __restrict__ qstate,
                                                              const float* __restrict__ pm, const double* __restrict__ ps,
                                                              float* __restrict__ dsim, float* __restrict__ dsim_q,
-                                                             double* __restrict__ part) {
+                                                             double* __restrict__ part, const int* __restrict__ cls,
+                                                             const int* __restrict__ qcls) {
     __shared__ float smf[QT / 64];
     __shared__ double smd[QT / 64];
     const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
@@ -681,7 +747,9 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
     double loss = 0;
     const float invB = 1.f / (float)B;
     if (u.slot != G - 1) {                                 // workgroup-uniform
-        q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);      // requested ahead of the reductions below
+        // requested ahead of the reductions below
+        if constexpr (MASK == MASK_CLASS) q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[sp.myclip]);
+        else q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);
         // the log-sum-exp of the clip's block from its nA * nch chunk partials (circle: slots 0..G-2 are adjacent units)
         const int np = sp.nA * u.nch;
         const size_t p0 = ((size_t)sp.n * (G + 1) + (sp.circle ? 0 : G)) * u.nch;
@@ -735,12 +803,12 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
 template <int MASK, int V>
 void launch_queue_kernels(unsigned units, const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
                           const int64_t* order, int clip_offset, const int32_t* qstate, float* dsim, float* dsim_q, double* part,
-                          double* ps, float* pm, hipStream_t st) {
+                          double* ps, float* pm, hipStream_t st, const int32_t* cls, const int32_t* qcls) {
     hipLaunchKernelGGL((k_contrast_queue_part<MASK, V>), dim3(units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
-                       (const long long*)order, clip_offset, (const int*)qstate, pm, ps);
+                       (const long long*)order, clip_offset, (const int*)qstate, pm, ps, (const int*)cls, (const int*)qcls);
     hipLaunchKernelGGL((k_contrast_queue_write<MASK, V>), dim3(units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
                        (const long long*)order, clip_offset, (const int*)qstate, (const float*)pm, (const double*)ps, dsim, dsim_q,
-                       part);
+                       part, (const int*)cls, (const int*)qcls);
 }
 
 // head clamped to a multiple of P below L: a corrupt state cannot address outside the queue
@@ -769,14 +837,16 @@ __global__ __launch_bounds__(64) void k_queue_advance(int* __restrict__ qstate, 
 }
 }  // namespace
 
-extern "C" int facl_contrast_pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
-                                        const int64_t* order, int clip_offset, int mask_mode, const int32_t* qstate, float* dsim,
-                                        float* dsim_q, double* losses, float* losses32, void* ws, void* stream) {
+namespace {
+// cls / qcls: the class ids of MASK_CLASS; the entry with a mask_mode argument passes none, and mode 2 is no mode of its
+int pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order, int clip_offset,
+               int mask_mode, const int32_t* cls, const int32_t* qcls, const int32_t* qstate, float* dsim, float* dsim_q,
+               double* losses, float* losses32, void* ws, void* stream) {
     if (!sim || !sim_q || !order || !qstate || !dsim || !dsim_q || !losses || !losses32 || !ws) return FACL_E_NULL;
     if (G < 2 || B < 1 || Bk < 1 || J != G * Bk || L < 1) return FACL_E_SHAPE;
     if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
-    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE) return FACL_E_SHAPE;
-    if (mask_mode == MASK_EXCLUDE && Bk < 2) return FACL_E_SHAPE;            // one key clip: no negative exists in an empty queue
+    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !(mask_mode == MASK_CLASS && cls && qcls)) return FACL_E_SHAPE;
+    if (mask_mode != MASK_ZERO && Bk < 2) return FACL_E_SHAPE;               // one key clip: no negative exists in an empty queue
     if (J > 0x7fffffff - QC || L > 0x7fffffff - QC) return FACL_E_SHAPE;      // the kernels round both up to chunks in int
     const long long nch = (J + QC - 1) / QC + (L + QC - 1) / QC, units = (long long)(G + 1) * B * nch;
     if (units > 0x7fffffffLL) return FACL_E_SHAPE;
@@ -789,13 +859,60 @@ extern "C" int facl_contrast_pair_queue(const float* sim, const float* sim_q, in
     hipStream_t st = (hipStream_t)stream;
     const bool vec = J % 4 == 0 && L % 4 == 0 && !(((uintptr_t)sim | (uintptr_t)sim_q | (uintptr_t)dsim | (uintptr_t)dsim_q) & 15);
 #define FACL_QUEUE_LAUNCH(MASK, V) \
-    launch_queue_kernels<MASK, V>((unsigned)units, sim, sim_q, G, B, Bk, J, L, order, clip_offset, qstate, dsim, dsim_q, part, ps, pm, st)
+    launch_queue_kernels<MASK, V>((unsigned)units, sim, sim_q, G, B, Bk, J, L, order, clip_offset, qstate, dsim, dsim_q, part, ps, pm, st, \
+                                  cls, qcls)
     if (mask_mode == MASK_ZERO) { if (vec) FACL_QUEUE_LAUNCH(MASK_ZERO, 4); else FACL_QUEUE_LAUNCH(MASK_ZERO, 1); }
-    else { if (vec) FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 4); else FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 1); }
+    else if (mask_mode == MASK_EXCLUDE) { if (vec) FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 4); else FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 1); }
+    else { if (vec && !((uintptr_t)qcls & 15)) FACL_QUEUE_LAUNCH(MASK_CLASS, 4); else FACL_QUEUE_LAUNCH(MASK_CLASS, 1); }
 #undef FACL_QUEUE_LAUNCH
     int rc = facl_launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)part, B, losses, losses32);
+    return facl_launch_status();
+}
+
+// slots [head, head + P) of the ids beside the queue's rows; `head` as k_queue_push reads it (this launch runs BEFORE
+// facl_queue_push's advance in stream order) and the state is left as it is
+__global__ __launch_bounds__(256) void k_queue_push_ids(const int* __restrict__ ids, int P, int* __restrict__ qcls, int L,
+                                                        const int* __restrict__ qstate) {
+    int* dst = qcls + q_head(qstate, P, L);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256) dst[i] = ids[i];
+}
+}  // namespace
+
+extern "C" int facl_contrast_pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
+                                        const int64_t* order, int clip_offset, int mask_mode, const int32_t* qstate, float* dsim,
+                                        float* dsim_q, double* losses, float* losses32, void* ws, void* stream) {
+    return pair_queue(sim, sim_q, G, B, Bk, J, L, order, clip_offset, mask_mode, nullptr, nullptr, qstate, dsim, dsim_q, losses,
+                      losses32, ws, stream);
+}
+
+// the pair loss and its queue form under the class-aware mask (MASK_CLASS above)
+extern "C" int facl_contrast_pair_sum_cls(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                          const int32_t* cls, float* dsim, double* losses, float* losses32, void* ws, void* stream) {
+    if (!sim || !order || !cls || !dsim || !losses || !losses32 || !ws) return FACL_E_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, MASK_CLASS, dsim, ws, st, cls);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)ws, B, losses, losses32);
+    return facl_launch_status();
+}
+
+extern "C" int facl_contrast_pair_queue_cls(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
+                                            const int64_t* order, int clip_offset, const int32_t* cls, const int32_t* qcls,
+                                            const int32_t* qstate, float* dsim, float* dsim_q, double* losses, float* losses32,
+                                            void* ws, void* stream) {
+    if (!cls || !qcls) return FACL_E_NULL;
+    return pair_queue(sim, sim_q, G, B, Bk, J, L, order, clip_offset, MASK_CLASS, cls, qcls, qstate, dsim, dsim_q, losses, losses32,
+                      ws, stream);
+}
+
+extern "C" int facl_queue_push_ids(const int32_t* ids, int P, int32_t* qcls, int L, const int32_t* qstate, void* stream) {
+    if (P < 1 || L < 1 || L % P) return FACL_E_SHAPE;
+    if (!ids || !qcls || !qstate) return FACL_E_NULL;
+    const int grid = (P + 255) / 256 < 1024 ? (P + 255) / 256 : 1024;
+    hipLaunchKernelGGL(k_queue_push_ids, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const int*)ids, P, (int*)qcls, L,
+                       (const int*)qstate);
     return facl_launch_status();
 }
 

@@ -112,9 +112,8 @@ def finetune_parser():
     p.description = "Supervised fine-tuning"
     p.add_argument('--checkpoint', type=str, default='', help='NEW: encoder state_dict to start from; empty = from scratch')
     p.add_argument('--num_class', type=int, default=0, help='NEW: classes of the head (0 = 60 for ntu60, 120 for ntu120)')
-    p.add_argument('--label_fraction', type=float, default=1.0,
-                   help='NEW: 0 < f <= 1, the stratified fraction of the train split whose labels are used (label_subset)')
-    p.add_argument('--label_seed', type=int, default=0, help='NEW: seed of the per-class permutations of --label_fraction')
+    # --label_fraction / --label_seed: build_parser's (the pre-training entries read them for --loss_mask class); here they
+    # narrow the train split to the labelled subset
     p.add_argument('--eval_every', type=int, default=1, help='NEW (--synthetic 0): test top-1 after every E-th epoch; 0 = off')
     p.add_argument('--freeze_bn', type=int, default=0, choices=(0, 1),
                    help='NEW: 1 = fine-tune with frozen BatchNorm: the model stays in eval() for the training step, the running '

@@ -107,9 +107,14 @@ def build_parser(default_branch):
                         '0 = raw dot products (the reference)')
     p.add_argument('--loss_temperature', type=float, default=1.0,
                    help='NEW: the similarities of the global / circle losses are divided by this temperature (reference: 1)')
-    p.add_argument('--loss_mask', type=str, default='zero', choices=('zero', 'exclude'),
+    p.add_argument('--loss_mask', type=str, default='zero', choices=('zero', 'exclude', 'class'),
                    help='NEW: same-clip key columns of the global / circle losses: zero = multiplied by 0, they stay in the '
-                        'softmax as exp(0) (the reference); exclude = taken out of the log-sum-exp (negatives only)')
+                        'softmax as exp(0) (the reference); exclude = taken out of the log-sum-exp (negatives only); class '
+                        '(--synthetic 0, one rank) = exclude, and the keys and queue rows of clips known to share the '
+                        'anchor\'s action leave it too; --label_fraction of the train clips are "known"')
+    p.add_argument('--label_fraction', type=float, default=1.0,
+                   help='NEW: 0 < f <= 1, the stratified fraction of the train split whose labels are used (label_subset)')
+    p.add_argument('--label_seed', type=int, default=0, help='NEW: seed of the per-class permutations of --label_fraction')
     p.add_argument('--neg_queue', type=int, default=0,
                    help='NEW (one rank): L > 0 = the global / circle losses also see the x_global rows of the last L clips as '
                         'negatives (a device-side ring buffer, facl_amd/neg_queue.py); a multiple of --batchSize; 0 = off')
@@ -250,6 +255,13 @@ class ContrastiveStep:
         self.queue = None
         if self.neg_queue and fdist.is_distributed():
             raise RuntimeError("the negative queue runs on one rank only")
+        # class-aware mask: the class ids of the batch's clips (< 0: unknown), a static tensor that the caller fills in place
+        # before each call (like FineTuneStep.labels), so that a replayed graph reads the current batch's
+        self.clip_classes = None
+        if self.loss_mode["mask"] == "class":
+            if fdist.is_distributed():
+                raise RuntimeError("the class-aware loss mask runs on one rank only")
+            self.clip_classes = torch.full((int(opt.batchSize),), -1, dtype=torch.int32, device=next(netR.parameters()).device)
         # momentum key encoder (facl_amd/key_encoder.py): created on the first step; its rows are the ones the queue stores
         self.key_momentum = float(getattr(opt, "key_momentum", 0.999)) if int(getattr(opt, "key_encoder", 0)) else None
         self.key_encoder = None
@@ -266,6 +278,8 @@ class ContrastiveStep:
         """{queue: {buf, state}, key_encoder: its state_dict, swav: {queue, filled}}, each None while it does not exist.  The
         tensors are the live ones (like FusedAdam.state_dict()'s moments): train_state.assemble copies them."""
         queue = None if self.queue is None else {"buf": self.queue.buf, "state": self.queue.state}
+        if queue is not None and self.queue.ids is not None:
+            queue["ids"] = self.queue.ids
         key = None if self.key_encoder is None else self.key_encoder.state_dict()
         sw = self.swav_state
         swav = None if sw is None or sw.queue is None else {"queue": sw.queue, "filled": int(sw.filled)}
@@ -282,8 +296,12 @@ class ContrastiveStep:
             buf = sd["queue"]["buf"]
             if buf.dim() != 2 or buf.shape[0] != self.neg_queue:
                 raise RuntimeError("the saved queue holds %s rows, this step --neg_queue %d" % (tuple(buf.shape)[:1], self.neg_queue))
-            self.queue = NegativeQueue(buf.shape[0], buf.shape[1], B, device)
-            self.queue.restore((buf.to(device), sd["queue"]["state"].to(device)))
+            with_ids = self.loss_mode["mask"] == "class"
+            if with_ids and sd["queue"].get("ids") is None:
+                raise RuntimeError("the saved queue holds no class ids of its rows (ids): a run with --loss_mask class needs them")
+            self.queue = NegativeQueue(buf.shape[0], buf.shape[1], B, device, with_ids=with_ids)
+            self.queue.restore((buf.to(device), sd["queue"]["state"].to(device))
+                               + ((sd["queue"]["ids"].to(device),) if with_ids else ()))
         if sd["key_encoder"] is not None:
             if self.key_momentum is None:
                 raise RuntimeError("the state holds a key encoder, this step runs with --key_encoder 0")
@@ -356,13 +374,17 @@ class ContrastiveStep:
         off = self.rank * B
         if self.neg_queue and self.queue is None:
             from .neg_queue import NegativeQueue
-            self.queue = NegativeQueue(self.neg_queue, netR._stacked.shape[1], B, netR._stacked.device)
+            self.queue = NegativeQueue(self.neg_queue, netR._stacked.shape[1], B, netR._stacked.device,
+                                       with_ids=self.clip_classes is not None)
+        if self.clip_classes is not None and B != self.clip_classes.shape[0]:
+            raise RuntimeError("a batch of %d clips, the step holds %d class ids" % (B, self.clip_classes.shape[0]))
         # global (:265-287) + circle (:290-316) losses: similarity GEMMs + one HIP kernel each (csrc/loss.hip)
         from .tail import precision as _precision
         with _precision(getattr(netR, "precision", "f32")):    # the similarity GEMMs follow the model's arithmetic
             loss_c, loss_circle, loss = contrastive_losses_stacked(G, netR._stacked, order, x_keys=None if x_keys is x else x_keys,
                                                                    clip_offset=off, with_sum=True, **self.loss_mode,
                                                                    **({} if self.queue is None else {"queue": self.queue}),
+                                                                   **({} if self.clip_classes is None else {"classes": self.clip_classes}),
                                                                    **({} if key_rows is None else {"queue_rows": key_rows}))
         # loss = loss_circle + loss_c (:329; swa, CLD terms are 0 ...): the fp32 sum comes out of the loss launch itself
         if self.swa_if:                                                            # ... unless switched on: :239-263
@@ -782,6 +804,32 @@ def check_loss_flags(opt, world=None):
         raise RuntimeError("--loss_temperature / --loss_mask: %s" % e) from None
 
 
+def check_class_mask_flags(opt, world=None):
+    """--loss_mask class: one rank, labelled clips (--synthetic 0) and 0 < --label_fraction <= 1.  Raises before the device is
+    touched (`world` None: the launcher's WORLD_SIZE)."""
+    if opt.loss_mask != 'class':
+        return
+    world = fdist.env_world_size() if world is None else world
+    if world > 1:
+        raise RuntimeError("--loss_mask class runs on one rank only (got %d ranks): gathered class ids are not implemented" % world)
+    if opt.synthetic != 0:
+        raise RuntimeError("--loss_mask class masks the keys of clips with the anchor's action label: it needs --synthetic 0 "
+                           "(got --synthetic %d, which has no labelled clips)" % opt.synthetic)
+    if not 0.0 < opt.label_fraction <= 1.0:                  # NaN fails both comparisons
+        raise RuntimeError("--label_fraction must be in (0, 1] (got %r)" % opt.label_fraction)
+
+
+def split_class_ids(labels, fraction, seed):
+    """The class id of every clip of a labelled split as the class-aware mask sees it: the clip's label inside the stratified
+    `label_subset` (facl_amd/finetune.py: nested in `fraction` for one seed), -1 outside.  (N,) int32; pure host code."""
+    from .finetune import label_subset
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    ids = np.full(labels.shape, -1, dtype=np.int32)
+    keep = label_subset(labels, fraction, seed)
+    ids[keep] = labels[keep]
+    return ids
+
+
 @contextlib.contextmanager
 def eval_mode(netR):
     """eval() and no_grad() for the block; the model returns to the mode it was in, also when the block raises."""
@@ -957,6 +1005,7 @@ def run(default_branch, ckpt_pattern, args=None):
     check_view_flags(opt)
     check_knn_flags(opt)
     check_loss_flags(opt)
+    check_class_mask_flags(opt)
     check_queue_flags(opt)
     check_key_flags(opt)
     check_state_flags(opt)
@@ -988,10 +1037,19 @@ def run(default_branch, ckpt_pattern, args=None):
     gen = torch.Generator(device=device)
     gen.manual_seed(1000 + rank)
     view_rng = np.random.RandomState(2000 + rank)         # --synthetic 2: the generator the view construction draws from
+    class_of = None
+    if opt.loss_mask == 'class':
+        # every clip trains; the stratified subset keeps its label as class id, every other clip is unknown (-1)
+        ids = split_class_ids([source.index.label(int(v)) for v in source.split], opt.label_fraction, opt.label_seed)
+        class_of = {source.index.v_name(int(v)): int(c) for v, c in zip(source.split, ids)}
+        print('class mask: %d of %d train clips labelled, %d classes' % (int((ids >= 0).sum()), len(ids), len(np.unique(ids[ids >= 0]))))
 
     def next_batch(disk, epoch, i):
         if opt.synthetic == 0:
-            return next(disk)[0]                      # (G*B, N, 4) view-major views of the next batch
+            views, names, _ = next(disk)              # (G*B, N, 4) view-major views of the next batch
+            if class_of is not None:                  # in place: a replayed graph reads this tensor
+                step.clip_classes.copy_(torch.as_tensor([class_of[n] for n in names], dtype=torch.int32))
+            return views
         if opt.synthetic == 2:
             # the loop body from the loader's output on (:224-228): raw clips -> the augmented views of every clip,
             # built on the GPU in one launch, view-major float32 (facl_amd/views.py; draws in the reference's NumPy order)

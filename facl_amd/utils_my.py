@@ -103,7 +103,12 @@ def group_points(points, opt):
 #   temperature  similarities are divided by tau; folded into the rows as the factor s = fp32(1 / sqrt(tau))
 #   mask         'zero': same-clip key columns are multiplied by 0 and stay in the softmax as exp(0) (the reference);
 #                'exclude': they are no members of the log-sum-exp at all (negatives only)
-MASK_MODES = {"zero": 0, "exclude": 1}
+#                'class': 'exclude', and the keys of clips KNOWN to share the anchor's class leave the log-sum-exp too (false-
+#                negative removal with labels).  Every key clip carries an int32 class id, >= 0 a class, < 0 unknown; key column
+#                j of anchor clip c is masked iff clip(j) == c or (id[c] >= 0 and id[clip(j)] == id[c]); a queue row with the id
+#                q of the clip that pushed it iff id[c] >= 0 and q == id[c].  Positives stay the clip's own views.  A clip may
+#                be left without a negative: its log-sum-exp is -inf, its terms and gradients are exactly 0
+MASK_MODES = {"zero": 0, "exclude": 1, "class": 2}
 
 
 def loss_scale(temperature):
@@ -122,8 +127,8 @@ def check_loss_mode(temperature, mask, key_clips=None):
     s = loss_scale(temperature)
     if mask not in MASK_MODES:
         raise ValueError("unknown loss mask %r (one of %s)" % (mask, ", ".join(sorted(MASK_MODES))))
-    if mask == "exclude" and key_clips is not None and key_clips < 2:
-        raise ValueError("mask 'exclude' with one key clip leaves no negative: it needs batch x world >= 2")
+    if mask in ("exclude", "class") and key_clips is not None and key_clips < 2:
+        raise ValueError("mask %r with one key clip leaves no negative: it needs batch x world >= 2" % mask)
     return s, MASK_MODES[mask]
 
 
@@ -140,22 +145,70 @@ def _loss_rows_torch(x, normalize, temperature):
     return (torch.nn.functional.normalize(x, p=2, dim=1, eps=1e-12) if normalize else x) * s
 
 
-def _masked_sim(anchors, keys, anchor_clip, key_clip, mask="zero"):
+def _check_classes(mask, key_classes, Bk, queue=None, queue_classes=None):
+    """mask 'class' needs one id per key clip (and per queue row); any other mask takes none.  The ids as int64 on their device."""
+    if mask != "class":
+        if key_classes is not None or queue_classes is not None:
+            raise ValueError("class ids belong to mask 'class' (got mask %r)" % (mask,))
+        return None, None
+    if key_classes is None:
+        raise ValueError("mask 'class' needs the class ids of the key clips")
+    if key_classes.dim() != 1 or key_classes.shape[0] != Bk:
+        raise ValueError("mask 'class' takes one class id per key clip, (%d,); got %s" % (Bk, tuple(key_classes.shape)))
+    Q = 0 if queue is None else queue.shape[0]
+    if Q and (queue_classes is None or queue_classes.dim() != 1 or queue_classes.shape[0] != Q):
+        raise ValueError("mask 'class' with a queue takes one class id per queue row, (%d,)" % Q)
+    return key_classes.long(), (queue_classes.long() if Q else None)
+
+
+def _masked_sim(anchors, keys, anchor_clip, key_clip, mask="zero", key_classes=None):
     """l_neg = (anchors @ keys^T) * mask, mask = 0 where the key belongs to the anchor's own clip
     (utils_my.py:55-56,71-72).  Same-clip columns are multiplied by 0 -- NOT removed -- so each of them
     still contributes exp(0) = 1 to the softmax denominator, exactly like the reference.  mask 'exclude': they become
-    -inf, i.e. they leave the log-sum-exp."""
+    -inf, i.e. they leave the log-sum-exp.  mask 'class': so do the columns of clips known to share the anchor's class
+    (``key_classes`` (Bk,): the class id of every key clip, < 0 = unknown, which matches nothing)."""
     sim = anchors @ keys.t()
     same = anchor_clip[:, None] == key_clip[None, :]
+    if mask == "class":
+        kc = key_classes.to(sim.device)
+        a_cls, k_cls = kc[anchor_clip], kc[key_clip]
+        same = same | ((a_cls[:, None] >= 0) & (a_cls[:, None] == k_cls[None, :]))
     fill = 0.0 if mask == "zero" else float("-inf")
     return torch.where(same, torch.full((), fill, dtype=sim.dtype, device=sim.device), sim)
 
 
-def _queue_sim(anchors, queue):
-    """anchors @ queue^T for the valid rows of a negative queue (stored as they are: never mapped again); None without rows."""
+def _queue_sim(anchors, queue, anchor_classes=None, queue_classes=None):
+    """anchors @ queue^T for the valid rows of a negative queue (stored as they are: never mapped again); None without rows.
+    mask 'class' (``anchor_classes`` given): -inf where the anchor's class is known and is the queue row's."""
     if queue is None or queue.shape[0] == 0:
         return None
-    return anchors @ queue.to(device=anchors.device, dtype=anchors.dtype).t()
+    sim = anchors @ queue.to(device=anchors.device, dtype=anchors.dtype).t()
+    if anchor_classes is None:
+        return sim
+    a_cls, q_cls = anchor_classes.to(sim.device), queue_classes.to(sim.device)
+    same = (a_cls[:, None] >= 0) & (a_cls[:, None] == q_cls[None, :])
+    return torch.where(same, torch.full((), float("-inf"), dtype=sim.dtype, device=sim.device), sim)
+
+
+def _lse_rows(neg, mask):
+    """logsumexp over dim 1.  mask 'class' may leave a row without a member (all -inf): its value is -inf, and -- treated
+    explicitly, autograd of logsumexp over an all -inf row yields NaN -- it sends no gradient anywhere."""
+    if mask != "class":
+        return torch.logsumexp(neg, dim=1)
+    empty = (neg == float("-inf")).all(dim=1)
+    lse = torch.logsumexp(torch.where(empty[:, None], torch.zeros((), dtype=neg.dtype, device=neg.device), neg), dim=1)
+    return torch.where(empty, torch.full((), float("-inf"), dtype=neg.dtype, device=neg.device), lse)
+
+
+def _pair_terms(pos, lse):
+    """sum over slots of mean over clips of logaddexp(pos, lse) - pos; a clip with lse = -inf (no negative) contributes exactly
+    0 and no gradient (logaddexp(pos, -inf) - pos is 0 with derivative 0, which autograd would form as 1 - 1)."""
+    empty = (lse == float("-inf")).unsqueeze(0)
+    if not bool(empty.any()):
+        return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
+    zero = torch.zeros((), dtype=pos.dtype, device=pos.device)
+    t = torch.logaddexp(torch.where(empty, zero, pos), torch.where(empty, zero, lse.unsqueeze(0))) - torch.where(empty, zero, pos)
+    return torch.where(empty, zero, t).mean(dim=1).sum()
 
 
 def _clip_ids(G, B, device, offset=0):
@@ -163,7 +216,7 @@ def _clip_ids(G, B, device, offset=0):
 
 
 def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, clip_offset=0, normalize=False, temperature=1.0,
-                    mask='zero', queue=None):
+                    mask='zero', queue=None, key_classes=None, queue_classes=None):
     """utils_my.py:53-83.  loss_c = sum_g CE([<xg_n, x_{gB+n}> | (xg @ x^T)*mask], 0), CE = mean over B.
     The (G,B,1+GB) logits tensor and its ``repeat`` are never built: every g shares the negatives, so
     CE_g[n] = logaddexp(pos[g,n], LSE_n) - pos[g,n].
@@ -175,27 +228,33 @@ def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, cli
     embeddings: normalising a row commutes with gathering it) are mapped first; the rest is unchanged.
 
     ``queue``: the valid rows (Q, C) of a negative queue (facl_amd/neg_queue.py), extra negative columns <xg_n, q_k> of every
-    clip.  They carry no clip identity (no mask touches them) and are used as stored."""
+    clip.  They carry no clip identity (masks 'zero' and 'exclude' do not touch them) and are used as stored.
+
+    ``key_classes`` (Bk,) / ``queue_classes`` (Q,): the class ids of mask 'class' (see the loss modes above), integer tensors;
+    required with that mask (the queue's whenever the queue has rows), refused with any other."""
     B, G = x_global.shape[0], num_crop
     check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     x_global, x = _loss_rows_torch(x_global, normalize, temperature), _loss_rows_torch(x, normalize, temperature)
     keys = x if x_keys is None else _loss_rows_torch(x_keys, normalize, temperature)
     Bk = keys.shape[0] // G
+    kc, qc = _check_classes(mask, key_classes, Bk, queue, queue_classes)
     a_clip = torch.arange(B, device=x.device) + clip_offset
-    neg = _masked_sim(x_global, keys, a_clip, _clip_ids(G, Bk, x.device), mask)      # (B, G*Bk)
-    neg_q = _queue_sim(x_global, queue)
+    neg = _masked_sim(x_global, keys, a_clip, _clip_ids(G, Bk, x.device), mask, kc)  # (B, G*Bk)
+    neg_q = _queue_sim(x_global, queue, *(() if qc is None else (kc.to(x.device)[a_clip], qc)))
     if neg_q is not None:
         neg = torch.cat((neg, neg_q), dim=1)
-    lse = torch.logsumexp(neg, dim=1)
+    lse = _lse_rows(neg, mask)
     pos = (x_global.unsqueeze(0) * x.view(G, B, -1)).sum(-1)                   # (G,B)
+    if mask == "class":
+        return _pair_terms(pos, lse)
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
 
 def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=None, clip_offset=0, normalize=False,
-                    temperature=1.0, mask='zero', queue=None):
+                    temperature=1.0, mask='zero', queue=None, key_classes=None, queue_classes=None):
     """utils_my.py:85-116.  ``order`` replaces the reference's np.random.shuffle(arange(num_crop)) (:96-97);
-    when omitted it is drawn from NumPy's global RNG like the reference.  Loss modes and ``queue``: as in global_contrast
-    (the shared negative set of a clip becomes the (G-1) x (J + Q) block)."""
+    when omitted it is drawn from NumPy's global RNG like the reference.  Loss modes, ``queue`` and the class ids: as in
+    global_contrast (the shared negative set of a clip becomes the (G-1) x (J + Q) block)."""
     G, B = num_crop, batchSize
     check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     if order is None:
@@ -208,13 +267,16 @@ def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=N
     xv = x.view(G, B, -1)
     anchors = xv[order[:-1]]                                                   # (G-1,B,C)
     pos = (anchors * xv[order[1:]]).sum(-1)                                    # (G-1,B)   :100
+    kc, qc = _check_classes(mask, key_classes, Bk, queue, queue_classes)
     a_clip = (torch.arange(B, device=x.device) + clip_offset).repeat(G - 1)
-    neg = _masked_sim(anchors.reshape((G - 1) * B, -1), keys, a_clip, _clip_ids(G, Bk, x.device), mask)
+    neg = _masked_sim(anchors.reshape((G - 1) * B, -1), keys, a_clip, _clip_ids(G, Bk, x.device), mask, kc)
     neg = neg.view(G - 1, B, G * Bk).permute(1, 0, 2).reshape(B, -1)           # all anchors' negatives, shared (:105-109)
-    neg_q = _queue_sim(anchors.reshape((G - 1) * B, -1), queue)
+    neg_q = _queue_sim(anchors.reshape((G - 1) * B, -1), queue, *(() if qc is None else (kc.to(x.device)[a_clip], qc)))
     if neg_q is not None:
         neg = torch.cat((neg, neg_q.view(G - 1, B, -1).permute(1, 0, 2).reshape(B, -1)), dim=1)
-    lse = torch.logsumexp(neg, dim=1)
+    lse = _lse_rows(neg, mask)
+    if mask == "class":
+        return _pair_terms(pos, lse)
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
 
@@ -290,10 +352,13 @@ class _ContrastivePair(torch.autograd.Function):
 
     ``queue`` (a facl_amd.neg_queue.NegativeQueue): a second similarity GEMM sim_q = stacked @ queue^T, the loss launch is
     facl_contrast_pair_queue (the valid queue rows are extra negatives, read on the device), and the backward adds
-    dsim_q @ queue to d stacked.  The queue itself gets no gradient and is not written here."""
+    dsim_q @ queue to d stacked.  The queue itself gets no gradient and is not written here.
+
+    ``classes`` (mask mode 2, `class`): the int32 class ids of the Bk key clips on the device; the launches are
+    facl_contrast_pair_sum_cls resp. facl_contrast_pair_queue_cls with the queue's own ``ids``."""
 
     @staticmethod
-    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0, queue=None):
+    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0, queue=None, classes=None):
         from . import tail as _tail
         from .sa_mlp import _Workspace
         lib = _lib.load_library()
@@ -315,7 +380,21 @@ class _ContrastivePair(torch.autograd.Function):
         # [loss_c, loss_circle, loss_circle + loss_c] in fp32 from the loss launch's own finishing kernel (no cast / add launches)
         out32 = _lib.empty(3, dtype=torch.float32, device=dev)
         ctx.queue = queue is not None
-        if queue is None:
+        if (mask_mode == MASK_MODES["class"]) != (classes is not None):
+            raise ValueError("mask 'class' and the class ids of the key clips come together")
+        if classes is not None:
+            _lib.require_cuda(classes)
+            if classes.dtype != torch.int32 or tuple(classes.shape) != (Bk,) or classes.device != dev or not classes.is_contiguous():
+                raise ValueError("classes must be a contiguous int32 (%d,) tensor on %s: one id per key clip; got %s %s on %s"
+                                 % (Bk, dev, classes.dtype, tuple(classes.shape), classes.device))
+            if queue is not None and getattr(queue, "ids", None) is None:
+                raise ValueError("mask 'class' needs a queue that keeps the class ids of its rows: NegativeQueue(..., with_ids=True)")
+        if queue is None and classes is not None:
+            _lib.check(lib.facl_contrast_pair_sum_cls(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, _lib.ptr(classes),
+                                                      _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
+                       "facl_contrast_pair_sum_cls")
+            ctx.save_for_backward(stacked, keys, dsim)
+        elif queue is None:
             _lib.check(lib.facl_contrast_pair_sum_mask(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, mask_mode,
                                                        _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
                        "facl_contrast_pair_sum_mask")
@@ -328,10 +407,16 @@ class _ContrastivePair(torch.autograd.Function):
             ctx.mfma_q = (L % 4 == 0 and C % 4 == 0)
             sim_q = _tail.gemm_fwd(stacked, queue.buf, None, prec=ctx.prec)[0] if ctx.mfma_q else stacked @ queue.buf.t()
             dsim_q = _lib.empty_like(sim_q)
-            _lib.check(lib.facl_contrast_pair_queue(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order), clip_offset,
-                                                    mask_mode, _lib.ptr(queue.state), _lib.ptr(dsim), _lib.ptr(dsim_q),
-                                                    _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
-                       "facl_contrast_pair_queue")
+            if classes is not None:
+                _lib.check(lib.facl_contrast_pair_queue_cls(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order),
+                                                            clip_offset, _lib.ptr(classes), _lib.ptr(queue.ids), _lib.ptr(queue.state),
+                                                            _lib.ptr(dsim), _lib.ptr(dsim_q), _lib.ptr(out), _lib.ptr(out32),
+                                                            _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_queue_cls")
+            else:
+                _lib.check(lib.facl_contrast_pair_queue(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order), clip_offset,
+                                                        mask_mode, _lib.ptr(queue.state), _lib.ptr(dsim), _lib.ptr(dsim_q),
+                                                        _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
+                           "facl_contrast_pair_queue")
             ctx.save_for_backward(stacked, keys, dsim, dsim_q, queue.buf)
         ctx.GB = G * B
         ctx.set_materialize_grads(False)           # an unused loss output arrives as None, not as a freshly filled zero tensor
@@ -351,7 +436,7 @@ class _ContrastivePair(torch.autograd.Function):
             return g if g_s is None else g + g_s.float()
         g_c, g_o = tot(g_c), tot(g_o)
         if g_c is None and g_o is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         zero = None
         if g_c is None or g_o is None:
             zero = torch.zeros((), dtype=torch.float32, device=dsim.device)
@@ -378,14 +463,14 @@ class _ContrastivePair(torch.autograd.Function):
                 rc = lib.facl_gemm_wgrad_acc(_lib.ptr(ds), _lib.ptr(stacked), M_, N_, K_, stacked.stride(0), _lib.ptr(d_stacked), pc,
                                              _lib.stream())
             if rc == 0:
-                return d_stacked, None, None, None, None, None, None
+                return d_stacked, None, None, None, None, None, None, None
             if rc != -4:
                 _lib.check(rc, "facl_gemm_wgrad_acc")
         d_keys = _tail.gemm_wgrad(ds, stacked, prec=bp) if ctx.mfma else ds.t() @ stacked
         if ctx.own_keys:
             d_stacked[:ctx.GB] += d_keys
             d_keys = None
-        return d_stacked, d_keys, None, None, None, None, None
+        return d_stacked, d_keys, None, None, None, None, None, None
 
 
 class _LossRows(torch.autograd.Function):
@@ -436,7 +521,7 @@ def _check_order(order, G):
 
 
 def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offset=0, with_sum=False, normalize=False,
-                               temperature=1.0, mask='zero', queue=None, queue_rows=None):
+                               temperature=1.0, mask='zero', queue=None, queue_rows=None, classes=None):
     """(loss_c, loss_circle) from the model's stacked output [x ; x_global] (facl_amd.cn3d_model_conbag: ``_stacked``);
     with_sum: also `loss_circle + loss_c` (fp32, cn3d_train_motion_GL.py:329) as a third output of the same launch.
 
@@ -450,7 +535,14 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
     pushes them (``queue.push()``) after the backward.  None: today's launches, nothing else.
 
     ``queue_rows``: raw (B, C) rows to stage instead -- the x_global rows of a key encoder (facl_amd/key_encoder.py).  They take
-    the same row map, in a launch of their own; the loss does not read them.  None: the step's own rows, as above."""
+    the same row map, in a launch of their own; the loss does not read them.  None: the step's own rows, as above.
+
+    ``classes``: mask 'class' only, and required there -- the int32 device tensor of the Bk key clips' class ids (< 0: unknown).
+    With a queue (created ``with_ids``) the ids of this rank's clips, classes[clip_offset : clip_offset + B], are staged beside
+    the rows.  The tensor is read by the launches, not copied: a captured step sees what it holds at replay."""
+    if (mask == "class") != (classes is not None):
+        raise ValueError("mask 'class' needs classes=, the class ids of the key clips, and no other mask takes them "
+                         "(got mask %r %s classes)" % (mask, "without" if classes is None else "with"))
     G = num_crop
     GB = G * (stacked.shape[0] // (G + 1))
     if queue_rows is not None:
@@ -480,10 +572,14 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
         _check_order(order, G)
         order = torch.as_tensor(order, device=stacked.device, dtype=torch.long)
     if queue is None:
-        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode)
+        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, None, classes)
     else:
-        queue.stage(stacked.detach()[GB:] if queue_rows is None else queue_rows)
-        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, queue)
+        rows = stacked.detach()[GB:] if queue_rows is None else queue_rows
+        if classes is None:
+            queue.stage(rows)
+        else:
+            queue.stage(rows, ids=classes[clip_offset:clip_offset + rows.shape[0]])
+        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, queue, classes)
     return out if with_sum else out[:2]
 
 

@@ -508,6 +508,29 @@ int facl_contrast_pair_queue(const float* sim, const float* sim_q, int G, int B,
  * never wraps inside itself; head is clamped to a multiple of P below L and valid to [0, L] before use.  C % 4 == 0, L % P == 0,
  * else FACL_E_SHAPE (checked first); a NULL pointer: FACL_E_NULL; rows / queue 16-byte aligned, else FACL_E_ALIGN. */
 int facl_queue_push(const float* rows, int P, int C, float* queue, int L, int32_t* qstate, void* stream);
+/* The class-aware negative mask (mask mode `class`): facl_contrast_pair_sum_mask's mode 1 (exclude) that also takes the keys of
+ * clips KNOWN to share the anchor's class out of the log-sum-exp.  cls (Bk int32): one class id per key clip, >= 0 a class, < 0
+ * unknown (the ids are compared, never used as an index).  For anchor clip n, myclip = n + clip_offset, column j of sim is masked
+ * iff j % Bk == myclip || (cls[myclip] >= 0 && cls[j % Bk] == cls[myclip]): no member of the log-sum-exp, dsim exactly 0.  The
+ * positives (same-clip columns) are read before masking and keep their gradient.  A clip may be left without any negative (a
+ * batch of one class): then lse = -inf, every term of the clip and its rows of dsim, positives included, are exactly 0, nothing
+ * is NaN.  With every id < 0, or all ids distinct, the outputs equal mode 1's bit for bit.  A NULL cls: FACL_E_NULL; shapes as
+ * mode 1 (Bk >= 2), else FACL_E_SHAPE. */
+int facl_contrast_pair_sum_cls(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                               const int32_t* cls, float* dsim, double* losses, float* losses32, void* ws, void* stream);
+/* facl_contrast_pair_queue under the class-aware mask.  qcls (L int32): the class id of the clip that pushed queue row k
+ * (facl_queue_push_ids); column k < valid of sim_q is masked iff cls[myclip] >= 0 && qcls[k] == cls[myclip] (dsim_q exactly 0).
+ * Columns >= valid are ignored as in facl_contrast_pair_queue, whatever qcls holds there.  With an empty queue the outputs equal
+ * facl_contrast_pair_sum_cls's bit for bit; with every id of cls < 0 they equal facl_contrast_pair_queue(mode 1)'s.  A NULL cls
+ * or qcls: FACL_E_NULL; otherwise the domain of facl_contrast_pair_queue with mode 1.  The 16-byte kernels also need qcls
+ * 16-byte aligned (else the scalar ones run). */
+int facl_contrast_pair_queue_cls(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order,
+                                 int clip_offset, const int32_t* cls, const int32_t* qcls, const int32_t* qstate, float* dsim,
+                                 float* dsim_q, double* losses, float* losses32, void* ws, void* stream);
+/* Writes ids (P int32) into the slots [head, head + P) of qcls (L int32), head clamped as in facl_queue_push.  The state is
+ * only read: the caller launches this BEFORE facl_queue_push in stream order, so that both see the same head.  L % P == 0, else
+ * FACL_E_SHAPE (checked first); a NULL pointer: FACL_E_NULL. */
+int facl_queue_push_ids(const int32_t* ids, int P, int32_t* qcls, int L, const int32_t* qstate, void* stream);
 /* dst (R,J) = src scaled by *g1 in rows [0,R1) and by *g2 in rows [R1,R): the two upstream gradients (device scalars)
  * of loss_circle / loss_c applied to the shared d/dsim matrix. */
 int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_t R, int J, const float* g1, const float* g2,

@@ -12,6 +12,9 @@ static inline int facl_launch_status() {
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// workgroups of 256 threads for a grid-stride kernel over n elements: one per 256 elements, 1024 at the most
+static inline int grid_1d(long long n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
+
 // integer A/B knob from the environment; call sites keep the value in a `static const int` (read once per process)
 static inline int facl_env_int(const char* name, int dflt) {
     const char* v = getenv(name);

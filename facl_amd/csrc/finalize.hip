@@ -423,8 +423,7 @@ extern "C" int facl_bn_finalize(const double* sums, int C, double count, const f
 extern "C" int facl_absmax(const float* x, int64_t n, uint32_t* amax, void* stream) {
     if (!x || !amax) return FACL_E_NULL;
     if (n < 1) return FACL_E_SHAPE;
-    const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_absmax, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (long long)n, amax);
+    hipLaunchKernelGGL(k_absmax, dim3(grid_1d(n)), dim3(256), 0, (hipStream_t)stream, x, (long long)n, amax);
     return facl_launch_status();
 }
 

@@ -1,16 +1,15 @@
 // Global / circle InfoNCE-style losses on a similarity matrix (utils_my.py:53-116 =
 // cn3d_train_motion_GL.py:265-316), forward value and d(loss)/d(sim) in one kernel.
 //
-// sim is (R, J) = anchors @ keys^T with R = nA*B anchor rows (row r = i*B + n: anchor slot i of clip n;
-// nA = 1 for the global loss, G-1 for the circle loss) and J = G*Bk key columns (column j belongs to
-// clip j % Bk).  Reference semantics:
+// sim = anchors @ keys^T has J = G*Bk key columns (column j belongs to clip j % Bk); a clip n has nA anchor rows (1 for the
+// global loss, G-1 for the circle loss) and nS positive slots (G resp. G-1).  Reference semantics:
 //   * same-clip columns are MULTIPLIED BY 0 (utils_my.py:72,106), i.e. they stay in the softmax as exp(0);
-//   * all nA anchor slots of a clip share ONE negative set (the `repeat` at :74 / :108), so
-//     lse[n] = log sum_{i,j} exp(sim'[i*B+n, j]);
-//   * logits[i] = [pos[i,n] | negatives], label 0, CE = mean over the B clips, summed over i.
-// pos[i,n] = sim[i*B+n, poscol[i*B+n]] (read BEFORE masking: the positive key is a same-clip column).
-// Per clip: loss_n = sum_i (logaddexp(pos, lse) - pos) / B;   dsim follows by the chain rule.
-// HBM-bound (2 reads + 1 write of R*J floats); one workgroup per clip.
+//   * all nA anchor rows of a clip share ONE negative set (the `repeat` at :74 / :108), so
+//     lse[n] = log sum_{i,j} exp(sim'[row(i, n), j]);
+//   * logits[s] = [pos[s,n] | negatives], label 0, CE = mean over the B clips, summed over the slots s.
+// pos[s,n] is read BEFORE masking: the positive key is a same-clip column.
+// Per clip: loss_n = sum_s (logaddexp(pos, lse) - pos) / B;   dsim follows by the chain rule.
+#include <type_traits>
 #include "common.h"
 #include "norm_rows.h"
 
@@ -40,132 +39,13 @@ __device__ __forceinline__ double block_reduce_sum(double v, double* sm) {
     return r;
 }
 
-// nA = similarity rows per clip that feed the shared negative set (row i*B+n); nS = positive slots per clip;
-// slot s reads its positive from row (slot_rows ? s : 0)*B+n, column poscol[s*B+n].
-//   circle: nA = nS = G-1, slot_rows = 1.      global: nA = 1, nS = G, slot_rows = 0.
-__global__ __launch_bounds__(256) void k_contrast(const float* __restrict__ sim, int J, int B, int Bk, int nA, int nS,
-                                                  int slot_rows, const int* __restrict__ poscol, int clip_offset,
-                                                  float* __restrict__ dsim, double* __restrict__ part) {
-    __shared__ float smf[4];
-    __shared__ double smd[4];
-    const int n = blockIdx.x;
-    const int myclip = n + clip_offset;
-    // pass 1: lse over all anchor slots of this clip (masked columns count as exp(0))
-    float mx = 0.f;                                        // masked entries are 0, there is at least one
-    for (int i = 0; i < nA; ++i) {
-        const float* row = sim + (size_t)(i * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256) {
-            const float v = (j % Bk == myclip) ? 0.f : row[j];
-            mx = fmaxf(mx, v);
-        }
-    }
-    mx = block_reduce_max(mx, smf);
-    double se = 0;
-    for (int i = 0; i < nA; ++i) {
-        const float* row = sim + (size_t)(i * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256) {
-            const float v = (j % Bk == myclip) ? 0.f : row[j];
-            se += (double)__expf(v - mx);
-        }
-    }
-    se = block_reduce_sum(se, smd);
-    const float lse = mx + (float)log(se);
-    // per-slot terms: t = logaddexp(pos, lse); loss += t - pos; dpos = (sigma - 1)/B; dlse += (1 - sigma)/B
-    float dlse = 0.f;
-    double loss = 0;
-    for (int s = 0; s < nS; ++s) {
-        const int r = (slot_rows ? s : 0) * B + n;
-        const float pos = sim[(size_t)r * J + poscol[s * B + n]];
-        const float m2 = fmaxf(pos, lse);
-        const float t = m2 + log1pf(__expf(-fabsf(pos - lse)));
-        loss += (double)(t - pos);
-        dlse += (1.f - __expf(pos - t));
-    }
-    const float invB = 1.f / (float)B;
-    dlse *= invB;
-    // pass 2: negatives' gradient (same-clip columns are constants: 0)
-    for (int i = 0; i < nA; ++i) {
-        const float* row = sim + (size_t)(i * B + n) * J;
-        float* drow = dsim + (size_t)(i * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256)
-            drow[j] = (j % Bk == myclip) ? 0.f : dlse * __expf(row[j] - lse);
-    }
-    __syncthreads();
-    // positives: distinct (row, column) per slot, all inside this clip's masked columns
-    for (int s = threadIdx.x; s < nS; s += 256) {
-        const int r = (slot_rows ? s : 0) * B + n;
-        const int pc = poscol[s * B + n];
-        const float pos = sim[(size_t)r * J + pc];
-        const float m2 = fmaxf(pos, lse);
-        const float t = m2 + log1pf(__expf(-fabsf(pos - lse)));
-        dsim[(size_t)r * J + pc] = (__expf(pos - t) - 1.f) * invB;
-    }
-    if (threadIdx.x == 0) part[n] = loss * (double)invB;
+// One positive slot against the clip's log-sum-exp: t = logaddexp(pos, lse), sigma = exp(pos - t).  loss = t - pos is the slot's
+// loss term, dlse = 1 - sigma its share of d/dlse, dpos = sigma - 1 its d/dpos; the caller accumulates and applies the 1/B.
+struct SlotTerm { float loss, dlse, dpos; };
+__device__ __forceinline__ SlotTerm slot_term(float pos, float lse) {
+    const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
+    return {t - pos, 1.f - __expf(pos - t), __expf(pos - t) - 1.f};
 }
-
-// The same computation with 1024 threads per clip and the clip's nA x J similarities held in registers between the
-// passes (one read of sim, no per-element integer modulo in the inner passes): the grid is only B workgroups, so the
-// kernel is latency-bound and three streaming passes with 256 threads took 65 us for the circle loss at H.
-constexpr int CK = 24;                      // cached values per thread: nA*J <= 24*1024
-
-__global__ __launch_bounds__(1024) void k_contrast_reg(const float* __restrict__ sim, int J, int B, int Bk, int nA, int nS,
-                                                      int slot_rows, const int* __restrict__ poscol, int clip_offset,
-                                                      float* __restrict__ dsim, double* __restrict__ part) {
-    __shared__ float smf[16];
-    __shared__ double smd[16];
-    const int n = blockIdx.x;
-    const int myclip = n + clip_offset;
-    const int total = nA * J;
-    float v[CK];
-    float mx = 0.f;                                        // masked entries are 0, there is at least one
-#pragma unroll
-    for (int k = 0; k < CK; ++k) {
-        const int e = threadIdx.x + k * 1024;
-        float x = 0.f;                                     // beyond the end: behaves like a masked column
-        if (e < total) {
-            const int i = e / J, j = e - i * J;
-            x = (j % Bk == myclip) ? 0.f : sim[(size_t)(i * B + n) * J + j];
-        }
-        v[k] = x;
-        mx = fmaxf(mx, x);
-    }
-    mx = block_reduce_max(mx, smf);
-    double se = 0;
-#pragma unroll
-    for (int k = 0; k < CK; ++k)
-        if (threadIdx.x + k * 1024 < total) se += (double)__expf(v[k] - mx);
-    se = block_reduce_sum(se, smd);
-    const float lse = mx + (float)log(se);
-    // per-slot terms, one slot per thread (the serial loop of k_contrast is nS dependent load pairs per thread)
-    double loss_t = 0, dlse_t = 0;
-    float dpos = 0.f;
-    size_t ppos = 0;
-    const float invB = 1.f / (float)B;
-    for (int s = threadIdx.x; s < nS; s += 1024) {       // nS <= 1024 in every use: at most one trip per thread
-        const int r = (slot_rows ? s : 0) * B + n;
-        ppos = (size_t)r * J + poscol[s * B + n];
-        const float pos = sim[ppos];
-        const float m2 = fmaxf(pos, lse);
-        const float t = m2 + log1pf(__expf(-fabsf(pos - lse)));
-        loss_t += (double)(t - pos);
-        dlse_t += (double)(1.f - __expf(pos - t));
-        dpos = (__expf(pos - t) - 1.f) * invB;
-    }
-    const double loss = block_reduce_sum(loss_t, smd);
-    const float dlse = (float)block_reduce_sum(dlse_t, smd) * invB;
-#pragma unroll
-    for (int k = 0; k < CK; ++k) {
-        const int e = threadIdx.x + k * 1024;
-        if (e < total) {
-            const int i = e / J, j = e - i * J;
-            dsim[(size_t)(i * B + n) * J + j] = (j % Bk == myclip) ? 0.f : dlse * __expf(v[k] - lse);
-        }
-    }
-    __syncthreads();                                       // the positives overwrite zeros written just above
-    if (threadIdx.x < nS) dsim[ppos] = dpos;
-    if (threadIdx.x == 0) part[n] = loss * (double)invB;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Both losses of a step in ONE launch on ONE similarity matrix.  sim is ((G+1)*B, J) = [x ; x_global] @ keys^T: row
@@ -173,7 +53,7 @@ __global__ __launch_bounds__(1024) void k_contrast_reg(const float* __restrict__
 // 0..B-1 evaluate the global loss of clip n (anchor block G, one positive per view g in column g*Bk + clip), workgroups
 // B..2B-1 the circle loss (anchor blocks order[0..G-2], positive of slot i in block order[i], column order[i+1]*Bk + clip;
 // block order[G-1] is no anchor: its dsim row is zeroed here so that every row of dsim is written exactly once).
-// The anchors gather, the positive-column index tensors and the second similarity GEMM of the two-call form disappear.
+// No anchors gather, no positive-column index tensors and one similarity GEMM for both losses.
 //
 // MASK selects what a same-clip column is inside the log-sum-exp.  MASK_ZERO: the reference's rule above, the column is the
 // value 0 and counts exp(0); since every clip has such a column, the running maximum may start at 0, an element past the end of
@@ -196,20 +76,32 @@ __device__ __forceinline__ bool col_masked(int jm, int myclip, int mycls, const 
     else return jm == myclip;
 }
 
+// One loss of one clip: the circle loss (circle = 1) or the global loss of local clip n, key clip myclip = n + clip_offset.
+// nA = anchor rows of the clip that feed its shared negative set, nS = its positive slots (kept as fields: as functions of
+// (circle, G) at each use they changed the generated code of the pair and queue kernels).
 struct PairSpec {
-    int nA, nS, slot_rows, circle, G, B, Bk, J, myclip, n;
+    int nA, nS, circle, G, B, Bk, J, myclip, n;
     const long long* order;
+    __device__ __forceinline__ PairSpec(int circle, int n, int G, int B, int Bk, int J, int clip_offset, const long long* order)
+        : nA(circle ? G - 1 : 1), nS(circle ? G - 1 : G), circle(circle), G(G), B(B), Bk(Bk), J(J), myclip(n + clip_offset), n(n),
+          order(order) {}
     __device__ __forceinline__ int ord(int i) const {            // clamped: a corrupt entry cannot address outside sim / dsim
         const long long o = order[i];
         return o < 0 ? 0 : (o >= G ? G - 1 : (int)o);
     }
     __device__ __forceinline__ int row_block(int i) const { return circle ? ord(i) : G; }
+    // slot s reads its positive from its own anchor row (circle) or from the one global row
     __device__ __forceinline__ size_t pos_index(int s) const {
-        const int rb = row_block(slot_rows ? s : 0);
+        const int rb = row_block(circle ? s : 0);
         const int col = (circle ? ord(s + 1) : s) * Bk + myclip;
         return (size_t)(rb * B + n) * J + col;
     }
 };
+
+// 1024 threads per clip and the clip's nA x J similarities held in registers between the passes (one read of sim, no
+// per-element integer modulo in the inner passes): the grid is only 2B workgroups, so the kernel is latency-bound and three
+// streaming passes with 256 threads took 65 us for the circle loss at H.
+constexpr int CK = 24;                      // cached values per thread: nA*J <= 24*1024
 
 template <int MASK>
 __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restrict__ sim, int G, int B, int Bk, int J,
@@ -219,11 +111,8 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     __shared__ float smf[16];
     __shared__ double smd[16];
     __shared__ int rb_s[1024];
-    PairSpec sp;
-    sp.circle = blockIdx.x >= (unsigned)B;
-    sp.n = sp.circle ? blockIdx.x - B : blockIdx.x;
-    sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
-    sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
+    const int circle = blockIdx.x >= (unsigned)B;
+    const PairSpec sp(circle, circle ? blockIdx.x - B : blockIdx.x, G, B, Bk, J, clip_offset, order);
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
     int mycls = -1;
     if constexpr (MASK == MASK_CLASS) mycls = cls[myclip];
@@ -236,6 +125,12 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     // arithmetic (23.5 us on 64 workgroups); the offsets are kept for the write pass (bit 31 = masked column).
     const int di = 1024 / J, dj = 1024 - di * J, djm = dj % Bk, Jm = J % Bk;
     int wi = (int)threadIdx.x / J, wj = (int)threadIdx.x - wi * J, wjm = wj % Bk;
+    const auto advance = [&](int& i, int& j, int& jm) {    // (row, column, column % Bk) of the element 1024 further on
+        i += di; j += dj; jm += djm;
+        if (j >= J) { j -= J; ++i; jm += Bk - Jm; }
+        if (jm >= Bk) jm -= Bk;
+        if (jm >= Bk) jm -= Bk;
+    };
     float v[CK];
     unsigned off[CK];
     // MASK_CLASS: bit k = element k lies in a column of the anchor's known class.  The CK lookups run FIRST, in a pass of their
@@ -245,20 +140,14 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     unsigned same_cls = 0u;
     if constexpr (MASK == MASK_CLASS) {
         if (mycls >= 0) {                                  // workgroup-uniform
-            int pj = wj, pjm = wjm;
+            int pi = wi, pj = wj, pjm = wjm;
 #pragma unroll
-            for (int k = 0; k < CK; ++k) {
-                same_cls |= (unsigned)(cls[pjm] == mycls) << k;
-                pj += dj; pjm += djm;
-                if (pj >= J) { pj -= J; pjm += Bk - Jm; }
-                if (pjm >= Bk) pjm -= Bk;
-                if (pjm >= Bk) pjm -= Bk;
-            }
+            for (int k = 0; k < CK; ++k, advance(pi, pj, pjm)) same_cls |= (unsigned)(cls[pjm] == mycls) << k;
         }
     }
     float mx = MASK == MASK_ZERO ? 0.f : -INFINITY;        // zero: masked entries are 0, there is at least one
 #pragma unroll
-    for (int k = 0; k < CK; ++k) {
+    for (int k = 0; k < CK; ++k, advance(wi, wj, wjm)) {
         const int e = threadIdx.x + k * 1024;
         float x = 0.f;                                     // beyond the end: behaves like a masked column
         off[k] = 0x80000000u;
@@ -271,10 +160,6 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
         }
         v[k] = x;
         if (MASK == MASK_ZERO || !(off[k] >> 31)) mx = fmaxf(mx, x);
-        wi += di; wj += dj; wjm += djm;
-        if (wj >= J) { wj -= J; ++wi; wjm += Bk - Jm; }
-        if (wjm >= Bk) wjm -= Bk;
-        if (wjm >= Bk) wjm -= Bk;
     }
     // the positives' similarities do not depend on the log-sum-exp: requested with the block, not behind two reductions
     float pos = 0.f;
@@ -292,11 +177,10 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     float dpos = 0.f;
     const float invB = 1.f / (float)B;
     if (has_pos) {
-        const float m2 = fmaxf(pos, lse);
-        const float t = m2 + log1pf(__expf(-fabsf(pos - lse)));
-        loss_t += (double)(t - pos);
-        dlse_t += (double)(1.f - __expf(pos - t));
-        dpos = (__expf(pos - t) - 1.f) * invB;
+        const SlotTerm st = slot_term(pos, lse);
+        loss_t += (double)st.loss;
+        dlse_t += (double)st.dlse;
+        dpos = st.dpos * invB;
     }
     const double loss = block_reduce_sum(loss_t, smd);
     const float dlse = (float)block_reduce_sum(dlse_t, smd) * invB;
@@ -322,11 +206,8 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
                                                        const int* __restrict__ cls) {
     __shared__ float smf[4];
     __shared__ double smd[4];
-    PairSpec sp;
-    sp.circle = blockIdx.x >= (unsigned)B;
-    sp.n = sp.circle ? blockIdx.x - B : blockIdx.x;
-    sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
-    sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
+    const int circle = blockIdx.x >= (unsigned)B;
+    const PairSpec sp(circle, circle ? blockIdx.x - B : blockIdx.x, G, B, Bk, J, clip_offset, order);
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
     int mycls = -1;
     if constexpr (MASK == MASK_CLASS) mycls = cls[myclip];
@@ -352,10 +233,9 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
     float dlse = 0.f;
     double loss = 0;
     for (int s = 0; s < nS; ++s) {
-        const float pos = sim[sp.pos_index(s)];
-        const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
-        loss += (double)(t - pos);
-        dlse += (1.f - __expf(pos - t));
+        const SlotTerm st = slot_term(sim[sp.pos_index(s)], lse);
+        loss += (double)st.loss;
+        dlse += st.dlse;
     }
     const float invB = 1.f / (float)B;
     dlse *= invB;
@@ -371,9 +251,7 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
     __syncthreads();
     for (int s = threadIdx.x; s < nS; s += 256) {
         const size_t pp = sp.pos_index(s);
-        const float pos = sim[pp];
-        const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
-        dsim[pp] = (__expf(pos - t) - 1.f) * invB;
+        dsim[pp] = slot_term(sim[pp], lse).dpos * invB;
     }
     if (threadIdx.x == 0) part[2 * n + sp.circle] = loss * (double)invB;
 }
@@ -446,67 +324,9 @@ __global__ __launch_bounds__(256) void k_scale_rows2(const V* __restrict__ src, 
     }
 }
 
-}  // namespace
-
-extern "C" int facl_contrast(const float* sim, int R, int J, int B, int Bk, int nA, int nS, int slot_rows,
-                             const int32_t* poscol, int clip_offset, float* dsim, double* loss, void* ws,
-                             void* stream) {
-    if (!sim || !poscol || !dsim || !loss || !ws) return FACL_E_NULL;
-    if (B < 1 || nA < 1 || nS < 1 || R != nA * B || J < 1 || Bk < 1 || J % Bk) return FACL_E_SHAPE;
-    if (slot_rows && nS != nA) return FACL_E_SHAPE;
-    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
-    hipStream_t st = (hipStream_t)stream;
-    if ((long long)nA * J <= (long long)CK * 1024 && nS <= 1024)
-        hipLaunchKernelGGL(k_contrast_reg, dim3(B), dim3(1024), 0, st, sim, J, B, Bk, nA, nS, slot_rows, poscol, clip_offset,
-                           dsim, (double*)ws);
-    else
-        hipLaunchKernelGGL(k_contrast, dim3(B), dim3(256), 0, st, sim, J, B, Bk, nA, nS, slot_rows, poscol, clip_offset,
-                           dsim, (double*)ws);
-    int rc = facl_launch_status();
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, B, 1, loss, st);
-}
-
-namespace {
-// shape checks and launch of the pair kernels: per-clip partial losses [loss_c, loss_circle] into ws, d/dsim into dsim
-template <int MASK>
-void launch_pair_kernel(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, float* dsim,
-                        void* ws, hipStream_t st, const int32_t* cls = nullptr) {
-    if ((long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL)
-        hipLaunchKernelGGL(k_contrast_pair_reg<MASK>, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws, (const int*)cls);
-    else
-        hipLaunchKernelGGL(k_contrast_pair<MASK>, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                           clip_offset, dsim, (double*)ws, (const int*)cls);
-}
-
-// cls: the class ids of MASK_CLASS; the entries with a mask_mode argument pass none, and mode 2 is no mode of theirs
-int launch_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, float* dsim,
-                void* ws, hipStream_t st, const int32_t* cls = nullptr) {
-    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return FACL_E_SHAPE;
-    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
-    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !(mask_mode == MASK_CLASS && cls)) return FACL_E_SHAPE;
-    if (mask_mode != MASK_ZERO && Bk < 2) return FACL_E_SHAPE;               // one key clip: no negative exists
-    if (mask_mode == MASK_ZERO) launch_pair_kernel<MASK_ZERO>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
-    else if (mask_mode == MASK_EXCLUDE) launch_pair_kernel<MASK_EXCLUDE>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st);
-    else launch_pair_kernel<MASK_CLASS>(sim, G, B, Bk, J, order, clip_offset, dsim, ws, st, cls);
-    return facl_launch_status();
-}
-}  // namespace
-
-extern "C" int facl_contrast_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
-                                  float* dsim, double* losses /* [loss_c, loss_circle] */, void* ws, void* stream) {
-    if (!sim || !order || !dsim || !losses || !ws) return FACL_E_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, MASK_ZERO, dsim, ws, st);
-    if (rc) return rc;
-    return facl_reduce_rows((const double*)ws, B, 2, losses, st);
-}
-
-// facl_contrast_pair whose final reduction also writes the fp32 values the training loop works with: losses32 =
-// [loss_c, loss_circle, loss_circle + loss_c] (the sum in fp32, exactly the reference's `loss = loss_circle + loss_c` on the two
-// fp32 losses, cn3d_train_motion_GL.py:329) -- one single-workgroup launch instead of a reduction, a dtype cast and an add.
-namespace {
+// The fp32 values the training loop works with, from the per-clip partials: losses32 = [loss_c, loss_circle, loss_circle + loss_c]
+// (the sum in fp32, exactly the reference's `loss = loss_circle + loss_c` on the two fp32 losses, cn3d_train_motion_GL.py:329)
+// -- one single-workgroup launch instead of a reduction, a dtype cast and an add.
 __global__ __launch_bounds__(64) void k_loss_finish(const double* __restrict__ part, int B, double* __restrict__ losses,
                                                     float* __restrict__ losses32) {
     double c = 0, o = 0;
@@ -519,30 +339,80 @@ __global__ __launch_bounds__(64) void k_loss_finish(const double* __restrict__ p
         losses32[0] = fc; losses32[1] = fo; losses32[2] = fo + fc;
     }
 }
-}  // namespace
 
-// facl_contrast_pair_sum with the mask mode of the same-clip columns as an argument (0 = zero, 1 = exclude)
-extern "C" int facl_contrast_pair_sum_mask(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
-                                           int mask_mode, float* dsim, double* losses, float* losses32, void* ws, void* stream) {
+int finish_losses(const void* part, int B, double* losses, float* losses32, hipStream_t st) {
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)part, B, losses, losses32);
+    return facl_launch_status();
+}
+
+// The shapes every pair entry takes.  have_ids: the class ids MASK_CLASS reads were passed; the entries with a mask_mode argument
+// pass none, so mode 2 is no mode of theirs.
+bool pair_shape_ok(int G, int B, int Bk, int J, int clip_offset, int mask_mode, bool have_ids) {
+    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return false;
+    if (clip_offset < 0 || clip_offset + B > Bk) return false;               // the local clips must be columns of the keys
+    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !(mask_mode == MASK_CLASS && have_ids)) return false;
+    return mask_mode == MASK_ZERO || Bk >= 2;                                // one key clip: no negative exists
+}
+
+// f(integral_constant<int, MASK>) for a mask mode that pair_shape_ok has admitted
+template <class F>
+void with_mask(int mask_mode, F&& f) {
+    if (mask_mode == MASK_ZERO) f(std::integral_constant<int, MASK_ZERO>{});
+    else if (mask_mode == MASK_EXCLUDE) f(std::integral_constant<int, MASK_EXCLUDE>{});
+    else f(std::integral_constant<int, MASK_CLASS>{});
+}
+
+// shape checks and launch of the pair kernels: per-clip partial losses [loss_c, loss_circle] into ws, d/dsim into dsim
+int launch_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, float* dsim,
+                void* ws, hipStream_t st, const int32_t* cls = nullptr) {
+    if (!pair_shape_ok(G, B, Bk, J, clip_offset, mask_mode, cls != nullptr)) return FACL_E_SHAPE;
+    const bool reg = (long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL;
+    with_mask(mask_mode, [&](auto m) {
+        constexpr int MASK = decltype(m)::value;
+        if (reg)
+            hipLaunchKernelGGL(k_contrast_pair_reg<MASK>, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
+                               clip_offset, dsim, (double*)ws, (const int*)cls);
+        else
+            hipLaunchKernelGGL(k_contrast_pair<MASK>, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
+                               clip_offset, dsim, (double*)ws, (const int*)cls);
+    });
+    return facl_launch_status();
+}
+
+// facl_contrast_pair_sum_mask / _cls behind their NULL checks
+int pair_sum(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, const int32_t* cls,
+             float* dsim, double* losses, float* losses32, void* ws, void* stream) {
     if (!sim || !order || !dsim || !losses || !losses32 || !ws) return FACL_E_NULL;
     hipStream_t st = (hipStream_t)stream;
-    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, mask_mode, dsim, ws, st);
+    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, mask_mode, dsim, ws, st, cls);
+    return rc ? rc : finish_losses(ws, B, losses, losses32, st);
+}
+
+inline bool loss_rows_ok(int64_t R, int C, int normalize, float s) {
+    return R >= 1 && (R + LR_WAVES - 1) / LR_WAVES <= 0x7fffffffLL && C >= 4 && C % 4 == 0 && (normalize == 0 || normalize == 1) &&
+           s > 0.f && s <= 3.402823466e38f;
+}
+}  // namespace
+
+extern "C" int facl_contrast_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                  float* dsim, double* losses /* [loss_c, loss_circle] */, void* ws, void* stream) {
+    if (!sim || !order || !dsim || !losses || !ws) return FACL_E_NULL;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, MASK_ZERO, dsim, ws, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)ws, B, losses, losses32);
-    return facl_launch_status();
+    return facl_reduce_rows((const double*)ws, B, 2, losses, st);
+}
+
+// facl_contrast_pair finished by k_loss_finish, with the mask mode of the same-clip columns as an argument (0 = zero, 1 = exclude)
+extern "C" int facl_contrast_pair_sum_mask(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                           int mask_mode, float* dsim, double* losses, float* losses32, void* ws, void* stream) {
+    return pair_sum(sim, G, B, Bk, J, order, clip_offset, mask_mode, nullptr, dsim, losses, losses32, ws, stream);
 }
 
 extern "C" int facl_contrast_pair_sum(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
                                       float* dsim, double* losses, float* losses32, void* ws, void* stream) {
     return facl_contrast_pair_sum_mask(sim, G, B, Bk, J, order, clip_offset, MASK_ZERO, dsim, losses, losses32, ws, stream);
 }
-
-namespace {
-inline bool loss_rows_ok(int64_t R, int C, int normalize, float s) {
-    return R >= 1 && (R + LR_WAVES - 1) / LR_WAVES <= 0x7fffffffLL && C >= 4 && C % 4 == 0 && (normalize == 0 || normalize == 1) &&
-           s > 0.f && s <= 3.402823466e38f;
-}
-}  // namespace
 
 extern "C" int facl_loss_rows_fwd(const float* x, int64_t R, int C, int normalize, float s, float* n, float* inv_norm, void* stream) {
     if (!loss_rows_ok(R, C, normalize, s)) return FACL_E_SHAPE;
@@ -573,11 +443,9 @@ extern "C" int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_
     hipStream_t st = (hipStream_t)stream;
     if (!(n & 3) && !(split & 3) && !((((uintptr_t)src) | ((uintptr_t)dst)) & 15)) {
         const long long n4 = n / 4;
-        const int grid = (int)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
-        hipLaunchKernelGGL((k_scale_rows2<float4>), dim3(grid), dim3(256), 0, st, (const float4*)src, (float4*)dst, n4, split / 4, g1, g2);
+        hipLaunchKernelGGL((k_scale_rows2<float4>), dim3(grid_1d(n4)), dim3(256), 0, st, (const float4*)src, (float4*)dst, n4, split / 4, g1, g2);
     } else {
-        const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-        hipLaunchKernelGGL((k_scale_rows2<float>), dim3(grid), dim3(256), 0, st, src, dst, n, split, g1, g2);
+        hipLaunchKernelGGL((k_scale_rows2<float>), dim3(grid_1d(n)), dim3(256), 0, st, src, dst, n, split, g1, g2);
     }
     return facl_launch_status();
 }
@@ -615,17 +483,13 @@ struct QUnit {
 
 __device__ __forceinline__ QUnit q_unit(int G, int B, int Bk, int J, int L, const long long* order, int clip_offset,
                                         const int* __restrict__ qstate) {
-    QUnit u;
-    const int cJ = (J + QC - 1) / QC;
-    u.nch = cJ + (L + QC - 1) / QC;
-    u.ch = (int)(blockIdx.x % (unsigned)u.nch);
-    const int t = (int)(blockIdx.x / (unsigned)u.nch);
-    u.slot = t % (G + 1);
-    PairSpec& sp = u.sp;
-    sp.n = t / (G + 1);
-    sp.circle = u.slot < G;
-    sp.nA = sp.circle ? G - 1 : 1; sp.nS = sp.circle ? G - 1 : G; sp.slot_rows = sp.circle;
-    sp.G = G; sp.B = B; sp.Bk = Bk; sp.J = J; sp.myclip = sp.n + clip_offset; sp.order = order;
+    const int cJ = (J + QC - 1) / QC, nch = cJ + (L + QC - 1) / QC;
+    const int t = (int)(blockIdx.x / (unsigned)nch), slot = t % (G + 1);
+    QUnit u{PairSpec(slot < G, t / (G + 1), G, B, Bk, J, clip_offset, order)};
+    const PairSpec& sp = u.sp;
+    u.slot = slot;
+    u.nch = nch;
+    u.ch = (int)(blockIdx.x % (unsigned)nch);
     const int v = qstate[1];
     const int valid = v < 0 ? 0 : (v > L ? L : v);         // clamped: a corrupt state cannot address outside sim_q / dsim_q
     const size_t r = (size_t)(u.slot == G ? G : sp.ord(u.slot)) * B + sp.n;
@@ -766,10 +630,9 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
         lse = M + (float)log(S);
         double loss_t = 0, dlse_t = 0;
         for (int s = threadIdx.x; s < sp.nS; s += QT) {
-            const float pos = sim[sp.pos_index(s)];
-            const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
-            loss_t += (double)(t - pos);
-            dlse_t += (double)(1.f - __expf(pos - t));
+            const SlotTerm st = slot_term(sim[sp.pos_index(s)], lse);
+            loss_t += (double)st.loss;
+            dlse_t += (double)st.dlse;
         }
         loss = block_reduce_sum(loss_t, smd);
         dlse = (float)block_reduce_sum(dlse_t, smd) * invB;
@@ -793,22 +656,9 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
         const int col = (sp.circle ? sp.ord(s + 1) : s) * Bk + sp.myclip;
         if (col < u.c0 || col >= u.c0 + u.wlen) continue;
         const size_t pp = sp.pos_index(s);
-        const float pos = sim[pp];
-        const float t = fmaxf(pos, lse) + log1pf(__expf(-fabsf(pos - lse)));
-        dsim[pp] = (__expf(pos - t) - 1.f) * invB;
+        dsim[pp] = slot_term(sim[pp], lse).dpos * invB;
     }
     if (u.ch == 0 && (u.slot == 0 || u.slot == G) && threadIdx.x == 0) part[2 * sp.n + sp.circle] = loss * (double)invB;
-}
-
-template <int MASK, int V>
-void launch_queue_kernels(unsigned units, const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
-                          const int64_t* order, int clip_offset, const int32_t* qstate, float* dsim, float* dsim_q, double* part,
-                          double* ps, float* pm, hipStream_t st, const int32_t* cls, const int32_t* qcls) {
-    hipLaunchKernelGGL((k_contrast_queue_part<MASK, V>), dim3(units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
-                       (const long long*)order, clip_offset, (const int*)qstate, pm, ps, (const int*)cls, (const int*)qcls);
-    hipLaunchKernelGGL((k_contrast_queue_write<MASK, V>), dim3(units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
-                       (const long long*)order, clip_offset, (const int*)qstate, (const float*)pm, (const double*)ps, dsim, dsim_q,
-                       part, (const int*)cls, (const int*)qcls);
 }
 
 // head clamped to a multiple of P below L: a corrupt state cannot address outside the queue
@@ -835,18 +685,14 @@ __global__ __launch_bounds__(64) void k_queue_advance(int* __restrict__ qstate, 
         qstate[1] = valid + P > L ? L : valid + P;
     }
 }
-}  // namespace
 
-namespace {
 // cls / qcls: the class ids of MASK_CLASS; the entry with a mask_mode argument passes none, and mode 2 is no mode of its
 int pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order, int clip_offset,
                int mask_mode, const int32_t* cls, const int32_t* qcls, const int32_t* qstate, float* dsim, float* dsim_q,
                double* losses, float* losses32, void* ws, void* stream) {
     if (!sim || !sim_q || !order || !qstate || !dsim || !dsim_q || !losses || !losses32 || !ws) return FACL_E_NULL;
-    if (G < 2 || B < 1 || Bk < 1 || J != G * Bk || L < 1) return FACL_E_SHAPE;
-    if (clip_offset < 0 || clip_offset + B > Bk) return FACL_E_SHAPE;        // the local clips must be columns of the keys
-    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !(mask_mode == MASK_CLASS && cls && qcls)) return FACL_E_SHAPE;
-    if (mask_mode != MASK_ZERO && Bk < 2) return FACL_E_SHAPE;               // one key clip: no negative exists in an empty queue
+    // Bk >= 2 outside `zero` here too: the queue may be empty
+    if (!pair_shape_ok(G, B, Bk, J, clip_offset, mask_mode, cls && qcls) || L < 1) return FACL_E_SHAPE;
     if (J > 0x7fffffff - QC || L > 0x7fffffff - QC) return FACL_E_SHAPE;      // the kernels round both up to chunks in int
     const long long nch = (J + QC - 1) / QC + (L + QC - 1) / QC, units = (long long)(G + 1) * B * nch;
     if (units > 0x7fffffffLL) return FACL_E_SHAPE;
@@ -858,17 +704,22 @@ int pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J
     float* pm = (float*)(ps + units);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = J % 4 == 0 && L % 4 == 0 && !(((uintptr_t)sim | (uintptr_t)sim_q | (uintptr_t)dsim | (uintptr_t)dsim_q) & 15);
-#define FACL_QUEUE_LAUNCH(MASK, V) \
-    launch_queue_kernels<MASK, V>((unsigned)units, sim, sim_q, G, B, Bk, J, L, order, clip_offset, qstate, dsim, dsim_q, part, ps, pm, st, \
-                                  cls, qcls)
-    if (mask_mode == MASK_ZERO) { if (vec) FACL_QUEUE_LAUNCH(MASK_ZERO, 4); else FACL_QUEUE_LAUNCH(MASK_ZERO, 1); }
-    else if (mask_mode == MASK_EXCLUDE) { if (vec) FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 4); else FACL_QUEUE_LAUNCH(MASK_EXCLUDE, 1); }
-    else { if (vec && !((uintptr_t)qcls & 15)) FACL_QUEUE_LAUNCH(MASK_CLASS, 4); else FACL_QUEUE_LAUNCH(MASK_CLASS, 1); }
-#undef FACL_QUEUE_LAUNCH
+    with_mask(mask_mode, [&](auto m) {
+        constexpr int MASK = decltype(m)::value;
+        auto launch = [&](auto v) {
+            constexpr int V = decltype(v)::value;
+            hipLaunchKernelGGL((k_contrast_queue_part<MASK, V>), dim3((unsigned)units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
+                               (const long long*)order, clip_offset, (const int*)qstate, pm, ps, (const int*)cls, (const int*)qcls);
+            hipLaunchKernelGGL((k_contrast_queue_write<MASK, V>), dim3((unsigned)units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
+                               (const long long*)order, clip_offset, (const int*)qstate, (const float*)pm, (const double*)ps, dsim,
+                               dsim_q, part, (const int*)cls, (const int*)qcls);
+        };
+        // MASK_CLASS reads qcls beside the values: 16-byte loads need it aligned too
+        if (vec && (MASK != MASK_CLASS || !((uintptr_t)qcls & 15))) launch(std::integral_constant<int, 4>{});
+        else launch(std::integral_constant<int, 1>{});
+    });
     int rc = facl_launch_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)part, B, losses, losses32);
-    return facl_launch_status();
+    return rc ? rc : finish_losses(part, B, losses, losses32, st);
 }
 
 // slots [head, head + P) of the ids beside the queue's rows; `head` as k_queue_push reads it (this launch runs BEFORE
@@ -890,12 +741,8 @@ extern "C" int facl_contrast_pair_queue(const float* sim, const float* sim_q, in
 // the pair loss and its queue form under the class-aware mask (MASK_CLASS above)
 extern "C" int facl_contrast_pair_sum_cls(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
                                           const int32_t* cls, float* dsim, double* losses, float* losses32, void* ws, void* stream) {
-    if (!sim || !order || !cls || !dsim || !losses || !losses32 || !ws) return FACL_E_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, MASK_CLASS, dsim, ws, st, cls);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, st, (const double*)ws, B, losses, losses32);
-    return facl_launch_status();
+    if (!cls) return FACL_E_NULL;
+    return pair_sum(sim, G, B, Bk, J, order, clip_offset, MASK_CLASS, cls, dsim, losses, losses32, ws, stream);
 }
 
 extern "C" int facl_contrast_pair_queue_cls(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
@@ -910,8 +757,7 @@ extern "C" int facl_contrast_pair_queue_cls(const float* sim, const float* sim_q
 extern "C" int facl_queue_push_ids(const int32_t* ids, int P, int32_t* qcls, int L, const int32_t* qstate, void* stream) {
     if (P < 1 || L < 1 || L % P) return FACL_E_SHAPE;
     if (!ids || !qcls || !qstate) return FACL_E_NULL;
-    const int grid = (P + 255) / 256 < 1024 ? (P + 255) / 256 : 1024;
-    hipLaunchKernelGGL(k_queue_push_ids, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const int*)ids, P, (int*)qcls, L,
+    hipLaunchKernelGGL(k_queue_push_ids, dim3(grid_1d(P)), dim3(256), 0, (hipStream_t)stream, (const int*)ids, P, (int*)qcls, L,
                        (const int*)qstate);
     return facl_launch_status();
 }
@@ -922,8 +768,7 @@ extern "C" int facl_queue_push(const float* rows, int P, int C, float* queue, in
     if (((uintptr_t)rows | (uintptr_t)queue) & 15) return FACL_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const long long n4 = (long long)P * (C / 4);
-    const int grid = (int)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024);
-    hipLaunchKernelGGL(k_queue_push, dim3(grid), dim3(256), 0, st, (const float4*)rows, n4, P, C / 4, (float4*)queue, L,
+    hipLaunchKernelGGL(k_queue_push, dim3(grid_1d(n4)), dim3(256), 0, st, (const float4*)rows, n4, P, C / 4, (float4*)queue, L,
                        (const int*)qstate);
     hipLaunchKernelGGL(k_queue_advance, dim3(1), dim3(64), 0, st, (int*)qstate, P, L);
     return facl_launch_status();

@@ -456,15 +456,12 @@ int facl_scatter_rows(const float* drows, int ldd, int col_off, int M, int S1, i
                       int rows_per_cloud, float* dfeat, void* stream);
 
 /* ---- contrastive losses on a similarity matrix (utils_my.py:53-116) ----------------------------
- * sim (R,J) = anchors @ keys^T, R = nA*B rows (row i*B+n: clip n), J = G*Bk columns (column j belongs to
- * clip j % Bk).  Same-clip columns count as exp(0) (the reference multiplies them by 0); the nA rows of a
- * clip form ONE shared negative set; nS positive slots per clip, slot s reads its positive from row
- * (slot_rows ? s : 0)*B+n, column poscol[s*B+n]; CE = mean over B, summed over the slots.
- *   circle loss: nA = nS = G-1, slot_rows = 1;   global loss: nA = 1, nS = G, slot_rows = 0.
- * clip_offset = rank*B under data parallelism.  Outputs: loss (1 double), dsim (R,J) = d loss / d sim. */
-int facl_contrast(const float* sim, int R, int J, int B, int Bk, int nA, int nS, int slot_rows,
-                  const int32_t* poscol, int clip_offset, float* dsim, double* loss, void* ws, void* stream);
-/* Both losses of a training step (cn3d_train_motion_GL.py:265-316) in one launch on ONE similarity matrix
+ * sim = anchors @ keys^T with J = G*Bk columns (column j belongs to clip j % Bk).  Same-clip columns count as exp(0) (the
+ * reference multiplies them by 0); the anchor rows of a clip (one for the global loss, G-1 for the circle loss) form ONE
+ * shared negative set; the clip's positive slots (G resp. G-1) are same-clip columns read before masking; CE = mean over B,
+ * summed over the slots.  clip_offset = rank*B under data parallelism.
+ *
+ * Both losses of a training step (cn3d_train_motion_GL.py:265-316) in one launch on ONE similarity matrix
  * sim ((G+1)*B, J) = [x ; x_global] @ keys^T (row block g < G: view g of the local clips, block G: x_global; J = G*Bk).
  * order (G) int64 = the circle loss's view permutation (utils_my.py:96-97).  losses = [loss_c, loss_circle];
  * dsim ((G+1)*B, J) = d(loss_c + loss_circle)/d sim, every row written (the block of view order[G-1], which is no

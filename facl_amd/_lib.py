@@ -211,6 +211,10 @@ VIEW_POS_MAX = 12          # FACL_VIEW_POS_MAX: positions of a round at most
 VIEW_NSTRENGTH = 6         # FACL_VIEW_NSTRENGTH: jitter_sigma, jitter_clip, rot_range, scale_lo, scale_hi, tilt_angle
 VIEW_TABLE_COLS = 8        # FACL_VIEW_TABLE_COLS: int32 words per position of facl_view_recipe_table
 
+# include/facl_hip.h: the chunk table of the optimizer entries (facl_adam_apply, facl_ema_apply, facl_grad_sqnorm, facl_adamw_apply)
+ADAM_MAX_TENSORS = 64      # FACL_ADAM_MAX_TENSORS: tensors per launch at most
+ADAM_CHUNK = 2048          # FACL_ADAM_CHUNK: elements per workgroup; facl_grad_sqnorm writes one partial per chunk
+
 # include/facl_hip.h: the input widths of grouping and the SA point-MLP, and the D-dependent layer-1 layouts
 SA_D_MIN, SA_D_MAX = 3, 8  # FACL_SA_D_MIN, FACL_SA_D_MAX
 
@@ -239,6 +243,16 @@ def amax_buffers(n, device, zero=True):
 def ptr(t):
     """device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()
+
+
+def ptr_array(tensors):
+    """HOST array of the tensors' device pointers (a column of the optimizer entries' chunk table)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def int_array(values):
+    """HOST array of C ints (the table's element counts and flags)."""
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
 
 
 def stream():

@@ -7,7 +7,6 @@ weights that moved slowly instead of from the encoder as it was on the step that
 Its BatchNorm follows MoCo's convention: train() whenever the trained model is, batch statistics, its own running buffers and
 ``steps`` counters, updated by its own forwards."""
 import copy
-import ctypes
 
 import torch
 
@@ -15,7 +14,7 @@ from . import _lib
 
 
 class KeyEncoder:
-    MAX_TENSORS = 64           # csrc/adam.hip: FACL_ADAM_MAX_TENSORS
+    MAX_TENSORS = _lib.ADAM_MAX_TENSORS
 
     def __init__(self, netR, momentum):
         momentum = float(momentum)
@@ -44,11 +43,9 @@ class KeyEncoder:
             _lib.require_cuda(k, q)
             if k.dtype != torch.float32 or q.dtype != torch.float32 or not k.is_contiguous() or not q.is_contiguous():
                 raise TypeError("the key encoder needs contiguous float32 parameters")
-        nt = self.nt = len(pairs)
-        arr = ctypes.c_void_p * nt
-        self._pk = arr(*[k.data_ptr() for k, _ in pairs])
-        self._p = arr(*[q.data_ptr() for _, q in pairs])
-        self._n = (ctypes.c_int * nt)(*[k.numel() for k, _ in pairs])
+        self.nt = len(pairs)
+        self._pk, self._p = _lib.ptr_array([k for k, _ in pairs]), _lib.ptr_array([q for _, q in pairs])
+        self._n = _lib.int_array([k.numel() for k, _ in pairs])
 
     def rows(self, xt, yt):
         """The copy's x_global rows (B, C) on the step's grouped input, before the row map of the loss modes; no graph."""

@@ -12,7 +12,6 @@ gradients untouched) and a learning rate evaluated ON THE DEVICE from the step c
 over ``decay_steps`` down to ``lr_min``; ``lr_at_step`` is its host closed form).  With all of it off ``step()`` issues
 facl_adam_prep + facl_adam_apply as it always did; otherwise [facl_grad_sqnorm when clipping] + facl_adam_prep_ex +
 facl_adamw_apply.  The schedule is a function of the saved step counter: state_dict() needs no new entry for it."""
-import ctypes
 import math
 
 import torch
@@ -20,7 +19,7 @@ import torch
 from . import _lib
 
 SCHEDULES = {"step": 0, "cosine": 1}                      # include/facl_hip.h: FACL_LR_STEP, FACL_LR_COSINE
-CHUNK = 2048                                              # csrc/adam.hip: FACL_ADAM_CHUNK
+CHUNK = _lib.ADAM_CHUNK                                   # elements per fp64 partial of facl_grad_sqnorm
 
 
 def lr_at_step(lr0, t, schedule="step", warmup_steps=0, decay_steps=0, lr_min=0.0):
@@ -42,7 +41,7 @@ def lr_at_step(lr0, t, schedule="step", warmup_steps=0, decay_steps=0, lr_min=0.
 
 
 class FusedAdam:
-    MAX_TENSORS = 64
+    MAX_TENSORS = _lib.ADAM_MAX_TENSORS
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decay_mask=None, max_grad_norm=0.0,
                  schedule="step", warmup_steps=0, decay_steps=0, lr_min=0.0):
@@ -132,13 +131,11 @@ class FusedAdam:
             return
         st = _lib.stream()
         nt = len(act)
-        arr = ctypes.c_void_p * nt
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in act]
-        P = arr(*[p.data_ptr() for p in act])
-        G = arr(*[g.data_ptr() for g in grads])
-        M = arr(*[self.state[p]["exp_avg"].data_ptr() for p in act])
-        V = arr(*[self.state[p]["exp_avg_sq"].data_ptr() for p in act])
-        N = (ctypes.c_int * nt)(*[p.numel() for p in act])
+        P, G = _lib.ptr_array(act), _lib.ptr_array(grads)
+        M = _lib.ptr_array([self.state[p]["exp_avg"] for p in act])
+        V = _lib.ptr_array([self.state[p]["exp_avg_sq"] for p in act])
+        N = _lib.int_array([p.numel() for p in act])
         if not self.recipe:
             _lib.check(lib.facl_adam_prep(_lib.ptr(self._lr), _lib.ptr(self._step), self.betas[0], self.betas[1],
                                           _lib.ptr(self._consts), st), "facl_adam_prep")
@@ -153,7 +150,7 @@ class FusedAdam:
                                          _lib.ptr(self._partial), npartial, self.max_grad_norm, SCHEDULES[self.schedule],
                                          self.warmup_steps, self.decay_steps, self.lr_min, _lib.ptr(self._consts), st),
                    "facl_adam_prep_ex")
-        D = (ctypes.c_int * nt)(*[int(self._decay[p]) for p in act])
+        D = _lib.int_array([self._decay[p] for p in act])
         _lib.check(lib.facl_adamw_apply(nt, P, G, M, V, N, D, _lib.ptr(self._consts), self.betas[0], self.betas[1], self.eps,
                                         self.weight_decay, st), "facl_adamw_apply")
 

@@ -560,30 +560,33 @@ int facl_mailbox_allreduce(const double* in, double* out, int n, int n_max, void
  * facl_adam_prep: step[0] += 1 (device float), consts = (lr[0] / (1 - b1^t), 1 / sqrt(1 - b2^t)) -- lr and the step
  * counter live on the device so that a captured HIP graph advances them by itself.
  * facl_adam_apply: ALL parameter tensors in one launch.  p / g / m / v are HOST arrays of nt <= 64 device pointers
- * (parameter, gradient, exp_avg, exp_avg_sq), n their element counts; the pointers travel by value in the kernel
- * arguments. */
+ * (parameter, gradient, exp_avg, exp_avg_sq), n their element counts.
+ * The chunk table, shared by facl_adam_apply, facl_ema_apply, facl_grad_sqnorm and facl_adamw_apply: the entry copies its nt <=
+ * FACL_ADAM_MAX_TENSORS pointers and counts into the kernel arguments, where they travel by value (a captured graph bakes
+ * them), and cuts every tensor into chunks of FACL_ADAM_CHUNK elements, one 256-thread workgroup each, the chunks of tensor 0
+ * first: sum_i ceil(n[i] / FACL_ADAM_CHUNK) workgroups.  A chunk is walked 16 bytes per lane where n[i] % 4 == 0 and every
+ * pointer of tensor i is 16-byte aligned, else element by element; nothing outside [0, n[i]) is touched.  A NULL array or
+ * entry: FACL_E_NULL; nt outside 1..FACL_ADAM_MAX_TENSORS or an n[i] < 1: FACL_E_SHAPE; every refusal comes before the launch. */
+#define FACL_ADAM_MAX_TENSORS 64
+#define FACL_ADAM_CHUNK 2048
 int facl_adam_prep(const float* lr, float* step, float b1, float b2, float* consts, void* stream);
 int facl_adam_apply(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const int* n,
                     const float* consts, float b1, float b2, float eps, void* stream);
 /* Momentum average of the key encoder (facl_amd/key_encoder.py; MoCo's param_k = param_k * m + param_q * (1 - m)):
  * pk[i][j] = m * pk[i][j] + (1 - m) * p[i][j] in fp32 (three roundings and the one of 1 - m) for ALL tensors in one launch.
- * pk / p are HOST arrays of nt <= 64 device pointers (the averaged copy, the trained parameter), n their element counts; the
- * pointers travel by value in the kernel arguments, as in facl_adam_apply, and a captured graph bakes them.  16 bytes per lane
- * where n[i] % 4 == 0 and both pointers are 16-byte aligned, else a scalar walk; nothing outside [0, n[i]) is touched and p is
- * only read.  m is a launch constant.  On finite data m == 0 copies p and m == 1 leaves pk as it is, through the formula.
- * A NULL array or entry: FACL_E_NULL; nt outside 1..64, an n[i] < 1 or m outside [0, 1] (NaN included): FACL_E_SHAPE; every
- * refusal comes before the launch. */
+ * pk / p are HOST arrays of nt <= 64 device pointers (the averaged copy, the trained parameter), n their element counts: the
+ * chunk table above, with its walk and its refusals; p is only read.  m is a launch constant.  On finite data m == 0 copies p
+ * and m == 1 leaves pk as it is, through the formula.  m outside [0, 1] (NaN included): FACL_E_SHAPE, before the launch. */
 int facl_ema_apply(int nt, float* const* pk, const float* const* p, const int* n, float m, void* stream);
 
 /* ---- optimizer recipe: global-norm clipping, decoupled weight decay, warm-up / cosine learning rate ---------
  * Off by default: facl_adam_prep + facl_adam_apply above stay the whole step.  With any of it on the step is
  *   [facl_grad_sqnorm, only when clipping] -> facl_adam_prep_ex -> facl_adamw_apply.
- * facl_grad_sqnorm: the chunk table of facl_adam_apply (2048 elements per 256-thread workgroup, chunks of tensor 0 first);
- *   partial[chunk] = sum of g^2 over the chunk.  g is a HOST array of nt <= 64 device pointers, n their element counts, partial a
- *   DEVICE array of sum_i ceil(n[i] / 2048) doubles, every one of them written.  Each element is widened to fp64 before it is
- *   squared (the square is exact), the additions run in one fixed order (thread, wave shuffle, LDS) and no atomic takes part:
- *   the same bits from run to run, launched eagerly or replayed.  16 bytes per lane where n[i] % 4 == 0 and g[i] is 16-byte
- *   aligned, else a scalar walk; g is only read.
+ * facl_grad_sqnorm: partial[chunk] = sum of g^2 over the chunk, in the chunk table's order (see facl_adam_apply).  g is a HOST
+ *   array of nt <= 64 device pointers, n their element counts, partial a DEVICE array of sum_i ceil(n[i] / FACL_ADAM_CHUNK)
+ *   doubles, every one of them written.  Each element is widened to fp64 before it is squared (the square is exact), the
+ *   additions run in one fixed order (thread, wave shuffle, LDS) and no atomic takes part: the same bits from run to run,
+ *   launched eagerly or replayed.  g is only read.
  * facl_adam_prep_ex: one workgroup.  step[0] += 1 (t, 1-based); norm = sqrt(partial[0] + ... + partial[npartial - 1]) in fp64,
  *   fixed order; c = min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s coefficient (an infinite norm gives
  *   c = 0, a NaN norm c = NaN, as there); npartial == 0: no clipping, c = 1 exactly, norm = 0, max_norm is not read.  The learning

@@ -38,6 +38,12 @@ def test_header_constants_match_the_python_binding():
     slots = int(re.search(r"#define\s+FACL_AMAX_SLOTS\s+(\d+)", common).group(1))
     stride = int(re.search(r"#define\s+FACL_AMAX_STRIDE\s+(\d+)", common).group(1))
     assert slots * stride == _lib.AMAX_WORDS and stride * 4 == 128           # one 128-byte line per slot
+    # the chunk table of the optimizer entries: the caller sizes facl_grad_sqnorm's partials by the chunk
+    from facl_amd import key_encoder, optim
+    for name, mirror in (("FACL_ADAM_MAX_TENSORS", _lib.ADAM_MAX_TENSORS), ("FACL_ADAM_CHUNK", _lib.ADAM_CHUNK)):
+        defs = re.findall(r"#define\s+%s\s+(\d+)" % name, txt + common + open(os.path.join(ROOT, "facl_amd", "csrc", "adam.hip")).read())
+        assert defs == [str(mirror)], (name, defs)                           # defined once, in the header
+    assert optim.CHUNK == _lib.ADAM_CHUNK and optim.FusedAdam.MAX_TENSORS == key_encoder.KeyEncoder.MAX_TENSORS == _lib.ADAM_MAX_TENSORS
 
 
 def test_no_cpu_fallback():

@@ -1,7 +1,6 @@
 """GPU tests of the momentum key encoder (--key_encoder): the averaging kernel facl_ema_apply against fp64 with guard bands,
 the training step with a key encoder (eager and graph-replayed) and the training entry.  The step tests run at the `ragged`
 size of test_gpu_neg_queue.py with its mode and its bound TOL.  The whole module runs on NaN-poisoned scratch."""
-import ctypes
 import os
 import re
 from types import SimpleNamespace
@@ -10,10 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+from chunk_cases import DEV, _banded, _bands_intact, _case, _ints, _ptrs
 from helpers import snapshot
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TOL = 1e-4                           # test_gpu_neg_queue.py / test_gpu_trajectory.py: losses of one step
 U = 2.0 ** -24                       # unit roundoff of fp32
 
@@ -26,30 +25,6 @@ def _poisoned_scratch():
 
 
 # ---- 1: the kernel ------------------------------------------------------------------------------------------------------------------
-SIZES = (1, 3, 4, 2047, 2048, 2049, 4100)                  # both sides of a 2048-element chunk and of a float4
-SENTINEL = 12345.0
-GUARD = 8                                                  # floats; 32 bytes keep the data 16-byte aligned behind it
-
-
-def _banded(n, shift, gen):
-    """[GUARD + shift sentinels | n values | GUARD sentinels] in one allocation; shift = 1 puts the data 4 bytes off a
-    16-byte boundary.  Returns (buffer, data view)."""
-    buf = torch.full((GUARD + shift + n + GUARD,), SENTINEL, device=DEV)
-    data = buf[GUARD + shift:GUARD + shift + n]
-    data.copy_(torch.randn(n, device=DEV, generator=gen))
-    assert buf.data_ptr() % 16 == 0 and data.data_ptr() % 16 == 4 * shift
-    return buf, data
-
-
-def _ema_case(nt):
-    """nt = 14: every size of SIZES aligned, then every size with both tensors one float off (the scalar walk).
-    nt = 64: small tensors of 1..9 and 2044..2052 elements, alternating alignment."""
-    if nt == 14:
-        return [(n, s) for s in (0, 1) for n in SIZES]
-    small = [1, 2, 3, 4, 5, 7, 8, 9, 12, 16, 2044, 2047, 2048, 2049, 2050, 2052]
-    return [(small[i % 16], (i // 16) % 2) for i in range(64)]
-
-
 @pytest.mark.parametrize("m", [0.0, 0.5, 0.999, 1.0])
 @pytest.mark.parametrize("nt", [14, 64])
 def test_ema_apply_vs_fp64_with_guard_bands(nt, m):
@@ -61,23 +36,20 @@ def test_ema_apply_vs_fp64_with_guard_bands(nt, m):
     lib = _lib.load_library()
     gen = torch.Generator(device=DEV)
     gen.manual_seed(nt)
-    case = _ema_case(nt)
+    case = _case(nt)
     assert len(case) == nt
-    ks = [_banded(n, s, gen) for n, s in case]
-    ps = [_banded(n, s, gen) for n, s in case]
+    ks = [_banded(torch.randn(n, device=DEV, generator=gen), s) for n, s in case]
+    ps = [_banded(torch.randn(n, device=DEV, generator=gen), s) for n, s in case]
     k_old = [d.clone() for _, d in ks]
     p_buf_old = [b.clone() for b, _ in ps]
-    arr = ctypes.c_void_p * nt
-    PK, P = arr(*[d.data_ptr() for _, d in ks]), arr(*[d.data_ptr() for _, d in ps])
-    N = (ctypes.c_int * nt)(*[n for n, _ in case])
+    PK, P, N = _ptrs([d for _, d in ks]), _ptrs([d for _, d in ps]), _ints([n for n, _ in case])
     _lib.check(lib.facl_ema_apply(nt, PK, P, N, m, _lib.stream()), "facl_ema_apply")
     torch.cuda.synchronize()
     m32 = float(np.float32(m))                              # the launch constant the kernel got
     worst = 0.0
     for i, (n, s) in enumerate(case):
         buf, got = ks[i]
-        lo, hi = GUARD + s, GUARD + s + n
-        assert bool((buf[:lo] == SENTINEL).all()) and bool((buf[hi:] == SENTINEL).all()), (i, n, s)
+        assert _bands_intact(buf, s, n), (i, n, s)
         assert torch.equal(ps[i][0], p_buf_old[i]), (i, n, s)                      # p and its bands: not written
         p = ps[i][1]
         assert torch.isfinite(got).all()

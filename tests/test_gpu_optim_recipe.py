@@ -1,10 +1,9 @@
 """GPU tests of the optimizer recipe (FusedAdam's weight_decay / max_grad_norm / schedule): the kernels
 facl_grad_sqnorm, facl_adam_prep_ex and facl_adamw_apply on guard-banded tensors against fp64, the ABI refusals beside a device,
 the training step (eager and graph-replayed), the default path against the direct facl_adam_prep / facl_adam_apply sequence, and
-the entries.  The kernel cases are those of test_gpu_key_encoder.py, the step runs at its `ragged` size and mode.  The whole
+the entries.  The kernel cases are those of chunk_cases.py, the step runs at test_gpu_key_encoder.py's `ragged` size and mode.  The whole
 module runs on NaN-poisoned scratch."""
 import contextlib
-import ctypes
 import io
 import os
 import re
@@ -14,10 +13,10 @@ import numpy as np
 import pytest
 import torch
 
+from chunk_cases import CHUNK, DEV, _banded, _bands_intact, _case, _chunks, _ints, _ptrs
 from helpers import FUSED_ADAM_BETAS, snapshot
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ADAM_TOL = 2e-6                      # test_gpu_trajectory.py / test_gpu_tail.py: Adam on given gradients, of max |.| per tensor
 NORM_TOL = 2.0 ** -22                # the gradient norm: see test_grad_sqnorm_and_prep_ex
 B1, B2 = 0.5, 0.999
@@ -32,52 +31,8 @@ def _poisoned_scratch():
         yield
 
 
-# ---- the kernel cases (test_gpu_key_encoder.py) ------------------------------------------------------------------------------
-SIZES = (1, 3, 4, 2047, 2048, 2049, 4100)                  # both sides of a 2048-element chunk and of a float4
-SENTINEL = 12345.0
-GUARD = 8                                                  # floats; 32 bytes keep the data 16-byte aligned behind it
-CHUNK = 2048
-
-
-def _case(nt):
-    """nt = 14: every size of SIZES aligned, then every size one float off a 16-byte boundary (the scalar walk).
-    nt = 64: small tensors of 1..16 and 2044..2052 elements, alternating alignment."""
-    if nt == 14:
-        return [(n, s) for s in (0, 1) for n in SIZES]
-    small = [1, 2, 3, 4, 5, 7, 8, 9, 12, 16, 2044, 2047, 2048, 2049, 2050, 2052]
-    return [(small[i % 16], (i // 16) % 2) for i in range(64)]
-
-
-def _banded(values, shift, dtype=torch.float32):
-    """[GUARD + shift sentinels | values | GUARD sentinels] in one allocation; shift = 1 puts the data one element off a
-    16-byte boundary (fp32).  Returns (buffer, data view)."""
-    n = values.numel()
-    buf = torch.full((GUARD + shift + n + GUARD,), SENTINEL, device=DEV, dtype=dtype)
-    data = buf[GUARD + shift:GUARD + shift + n]
-    data.copy_(values)
-    assert buf.data_ptr() % 16 == 0
-    return buf, data
-
-
-def _bands_intact(buf, shift, n):
-    lo, hi = GUARD + shift, GUARD + shift + n
-    return bool((buf[:lo] == SENTINEL).all()) and bool((buf[hi:] == SENTINEL).all())
-
-
-def _chunks(case):
-    return sum((n + CHUNK - 1) // CHUNK for n, _ in case)
-
-
 def _norm64(gs):
     return float(torch.sqrt(sum((g.double() ** 2).sum() for g in gs)))
-
-
-def _ptrs(views):
-    return (ctypes.c_void_p * len(views))(*[v.data_ptr() for v in views])
-
-
-def _ints(vals):
-    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
 
 
 def _inputs(nt, steps=3):

@@ -158,7 +158,7 @@ extern "C" int facl_cls_gather_norm_bwd(const float* dout, const float* out, con
 extern "C" int facl_softmax_ce(const float* logits, int ld, const int* labels, int R, int ncls, float* loss, float* dlogits,
                                int* stats, void* ws, void* stream) {
     if (ncls < 2 || ncls > 1024 || R < 1 || ld < ncls) return FACL_E_SHAPE;
-    if ((size_t)R * (sizeof(double) + sizeof(int)) > (size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES) return FACL_E_SHAPE;
+    if ((size_t)R * (sizeof(double) + sizeof(int)) > (size_t)facl_ws_bytes()) return FACL_E_SHAPE;
     if (!logits || !labels || !loss || !stats || !ws) return FACL_E_NULL;
     if ((uintptr_t)ws & 7) return FACL_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/facl_hip.h"
 
 #define FACL_WAVE 64
@@ -21,30 +22,42 @@ static inline int facl_env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: `done` = one flag per device ordinal (a
-// process may drive several devices through this C ABI; a forward on the main thread can race a backward on the autograd
-// thread, in which case the attribute is merely set twice).  Returns a HIP error code or 0.
-static inline int facl_set_dynamic_lds(bool (&done)[64], const void* const* fns, int nfns, int bytes) {
+// Launch KERN with `lds` bytes of dynamic LDS.  hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel
+// and is set on first use: one flag per device ordinal and per instantiation of this template, i.e. per kernel (a process may
+// drive several devices through this C ABI; a forward on the main thread can race a backward on the autograd thread, in which
+// case the attribute is merely set twice).  A kernel must always be launched with the same `lds`, or name the largest value it is
+// launched with as ATTR_LDS.  Returns a HIP error code or 0.
+template <auto KERN, int ATTR_LDS = 0, class... ARGS>
+static inline int facl_launch_dynamic_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const ARGS&... args) {
+    static bool attr_done[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (done[dev]) return 0;
-    for (int i = 0; i < nfns; ++i) {
-        hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (!attr_done[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, ATTR_LDS ? ATTR_LDS : lds);
         if (e != hipSuccess) return (int)e;
+        attr_done[dev] = true;
     }
-    done[dev] = true;
-    return 0;
+    hipLaunchKernelGGL(KERN, grid, block, lds, st, args...);
+    return facl_launch_status();
 }
 
-// Launch KERN with `lds` bytes of dynamic LDS; its per-device attribute is set on first use (the flags are per instantiation of
-// this template, i.e. per kernel; a kernel must always be launched with the same `lds`)
-template <auto KERN, class ARGS>
-static inline int facl_launch_dynamic_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const ARGS& args) {
-    static bool attr_done[64] = {};
-    const void* fns[1] = {(const void*)KERN};
-    if (int rc = facl_set_dynamic_lds(attr_done, fns, 1, lds)) return rc;
-    hipLaunchKernelGGL(KERN, grid, block, lds, st, args);
-    return facl_launch_status();
+// The run-time input width of grouping and the SA point-MLP as a compile-time constant: f(facl_int<D>{}) for
+// D in FACL_SA_D_MIN..FACL_SA_D_MAX, FACL_E_SHAPE outside.  `f` is a generic lambda that returns the launch status; a kernel
+// that exists only for D <= 4 starts it with `if constexpr (decltype(d)::value > 4) return FACL_E_CONFIG;`.
+template <int V>
+using facl_int = std::integral_constant<int, V>;
+template <class F>
+static inline int facl_dispatch_d(int D, F&& f) {
+    static_assert(FACL_SA_D_MIN == 3 && FACL_SA_D_MAX == 8, "one case per supported width");
+    switch (D) {
+        case 3: return f(facl_int<3>{});
+        case 4: return f(facl_int<4>{});
+        case 5: return f(facl_int<5>{});
+        case 6: return f(facl_int<6>{});
+        case 7: return f(facl_int<7>{});
+        case 8: return f(facl_int<8>{});
+        default: return FACL_E_SHAPE;
+    }
 }
 
 // XCD-aware tile order: workgroup b of a linearised grid of `total` is dispatched to XCD b % 8 (8 XCDs, one L2 each).  Returns
@@ -137,8 +150,6 @@ __device__ __forceinline__ float l1_chain(const float4* row, const float (&xv)[8
 
 // partial-sum workspace: every wave (or block) of a reducing kernel writes one row of doubles
 #define FACL_WS_ROWS 4096
-// the last bytes of the workspace: ticket counters of the single-launch partial-row reduction (finalize.hip), zero between launches
-#define FACL_WS_TICKET_BYTES 4096
 
 // ---- split-bf16 ("bf16x6") helpers ---------------------------------------------------------------------------
 // gfx950 runs the fp32-input MFMA at 1/16 of the bf16 rate.  An fp32 value is split EXACTLY into three bf16 pieces

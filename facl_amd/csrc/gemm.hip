@@ -1058,7 +1058,7 @@ static int split_k(GemmArgs g, int nz, float* dW, hipStream_t st, LAUNCH launch_
 // the statistics partials (one row per rows_per_part output rows, rounded to the workgroup's two wave rows) must fit the workspace
 static bool stats_rows_fit(int64_t M, int N, int rows_per_part, int* prow) {
     *prow = (int)((M + 2 * rows_per_part - 1) / (2 * rows_per_part)) * 2;
-    return (size_t)*prow * N * 2 * sizeof(double) <= (size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES;
+    return (size_t)*prow * N * 2 * sizeof(double) <= (size_t)facl_ws_bytes();
 }
 
 // y (M,N) = opA(a) W^T + bias (+ centres term), optional BN+ReLU prologue on a, optional column statistics

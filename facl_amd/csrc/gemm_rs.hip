@@ -32,6 +32,8 @@ namespace {
 
 constexpr int RS_CT = 8;                          // 32-column tiles per workgroup (256 output columns)
 constexpr int RS_WAVES = 4;                       // one 32-row tile per wave (128 rows per workgroup), two workgroups per CU
+constexpr int RS_ROWS = 32 * RS_WAVES;            // rows per workgroup = rows per partial-sum row
+constexpr int RS_PHASE_TICKS = 30;                // phase offset of a CU's second workgroup: timer ticks per k-step (rs_launch)
 constexpr int RS_WPP = RS_CT * 3 / RS_WAVES;      // 1-KiB weight pieces a wave issues per k-step
 constexpr int RS_WSLOT = RS_CT * 3 * 1024;        // bytes of one k-step (16 k) of planes for 256 columns: 24 KiB
 constexpr int RS_ASLOT = 32 * 128;                // bytes of one stage (32 k) of a wave's 32 rows, fp32: 4 KiB
@@ -65,7 +67,7 @@ struct RsArgs {
     const unsigned* amax = nullptr;               // h3 only: bits of (a bound of) max|A| in FACL_AMAX_SLOTS slots -> the
                                                   // power-of-two scale of A (activations: their bound, gradients: max|dy|)
     const int* wse = nullptr;                     // h3 only: biased exponent of the weight scale per 32-column tile (k_rs_planes)
-    int phase_ticks = 0;                          // experiment (FACL_RS_PHASE): first-round workgroups in the CU's second slot start this many 100-MHz ticks late
+    int phase_ticks = 0;                          // first-round workgroups in the CU's second slot start this many 100-MHz ticks late
     int first_round = 0;                          // number of workgroups resident at launch (2 per CU)
 };
 
@@ -211,12 +213,10 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
 
-// WV = waves per workgroup: 4 (128 rows, two workgroups per CU: the default) or 8 (256 rows, one workgroup per CU: every k-step
-// of weight planes serves twice the rows; opt-in experiment, measured equal: rs_waves below)
-template <bool PRO, bool SEG, bool BST, bool H3 = false, int WV = RS_WAVES>
-__global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void k_gemm_rs(RsArgs g) {
+template <bool PRO, bool SEG, bool BST, bool H3>
+__global__ __launch_bounds__(64 * RS_WAVES, 2) void k_gemm_rs(RsArgs g) {
     constexpr int NPL = H3 ? 2 : 3;                                     // planes per fragment (fp16x3 / bf16x6, common.h)
-    constexpr int WPP = RS_CT * NPL / WV;                         // 1-KiB weight pieces a wave issues per k-step
+    constexpr int WPP = RS_CT * NPL / RS_WAVES;                         // 1-KiB weight pieces a wave issues per k-step
     extern __shared__ __attribute__((aligned(16))) char lds[];
     // The two workgroups of a CU start together and take the same time, so they stay in phase for the whole launch -- both in
     // the main loop (MFMA pipe shared) or both draining their output (pipe idle).  On multi-round launches the first-round
@@ -228,12 +228,12 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void k_gemm_rs(RsArgs g) 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     char* const wring = lds;
     char* const abuf = lds + RS_LDS_W + wave * RS_ASLOT;
-    float* const tab = reinterpret_cast<float*>(lds + RS_LDS_W + WV * RS_ASLOT);
+    float* const tab = reinterpret_cast<float*>(lds + RS_LDS_W + RS_WAVES * RS_ASLOT);
     const unsigned wring_a = __builtin_amdgcn_readfirstlane(lds_addr(wring));
     const unsigned abuf_a = __builtin_amdgcn_readfirstlane(lds_addr(abuf));
     const RsTile tile = rs_tile();
     const int cb = tile.x;
-    const int row0 = (tile.y * WV + wave) * 32;
+    const int row0 = (tile.y * RS_WAVES + wave) * 32;
     const int nks = g.K >> 4, nst = g.K >> 5;
     const int nks_all = nks + (g.centers ? 1 : 0);
     int seA = 127;                                                      // fp16x3: biased exponent of the A operand's scale
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void k_gemm_rs(RsArgs g) 
     // proves that all waves have left k-step j-1, whose slot the next issue overwrites.
     issueA(0); issueW(0);
     if (PRO) {
-        for (int i = tid; i < g.K; i += 64 * WV) { tab[i] = g.pscale[i]; tab[RS_KPRO + i] = g.pshift[i]; }
+        for (int i = tid; i < g.K; i += 64 * RS_WAVES) { tab[i] = g.pscale[i]; tab[RS_KPRO + i] = g.pshift[i]; }
     }
     unsigned P0[12], P1[12];
     float4 raw[4];
@@ -462,8 +462,7 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void k_gemm_rs(RsArgs g) 
     // its y tile in the same way, reversed (4 wide loads -> image -> 16 ds_read_b32).
     // Statistics / max-pool hand-off areas live in the weight-ring slot that the final k-step does NOT read.
     float* const stg = reinterpret_cast<float*>(abuf);
-    // (8-wave workgroups: 8 x 6 KiB do not fit a ring slot; they have an area of their own behind the prologue tables)
-    char* const freeslot = WV == 8 ? lds + RS_LDS_W + WV * RS_ASLOT + 2 * RS_KPRO * 4 : wring + (((nks_all - 1) & 1) ^ 1) * RS_WSLOT;
+    char* const freeslot = wring + (((nks_all - 1) & 1) ^ 1) * RS_WSLOT;
     float* const wstat = reinterpret_cast<float*>(freeslot + wave * 6144);       // (sum, sumsq) per column: 2 KiB
     float* const wbest = wstat + 512;                                            // SEG, odd waves: (max, arg): 2 KiB
     float* const ystg = wstat + 512;                                             // BST: y tile image, 4 KiB
@@ -587,7 +586,7 @@ __global__ __launch_bounds__(64 * WV, WV == 8 ? 1 : 2) void k_gemm_rs(RsArgs g) 
     if (g.part && tid < 256) {                                         // the waves in wave order, fp64: one partial row per workgroup
         double s = 0.0, sq = 0.0;
 #pragma unroll
-        for (int w = 0; w < WV; ++w) {
+        for (int w = 0; w < RS_WAVES; ++w) {
             const float* ps = reinterpret_cast<const float*>(freeslot + w * 6144);
             s += (double)ps[2 * tid]; sq += (double)ps[2 * tid + 1];
         }
@@ -848,44 +847,33 @@ int wg_launch_k(const WgArgs& g, dim3 grid, hipStream_t st) {
     return facl_launch_dynamic_lds<k_wgrad_rs<PRO, H3, WIDE>>(grid, dim3(64 * WG_WAVES), lds, st, g);
 }
 
-constexpr int RS_LDS8 = RS_LDS_W + 8 * RS_ASLOT + 2 * RS_KPRO * 4 + 8 * 6144;     // 132 KiB: one 8-wave workgroup per CU
-
-// waves per workgroup of the fp16x3 kernels.  FACL_RS_W8=1: 8-wave workgroups (256 rows per k-step of weight planes: half the
-// plane re-reads).  Measured equal or slower (round 4, same box, bit-identical results: forward 49152x512x1024 0.182 vs
-// 0.184 ms, dgrad 1024->512 0.187 vs 0.176, step 3.023 vs 3.006 ms; gpurun_out/r5g_ab.log) -- the weight-plane traffic is
-// not what bounds these kernels.  Default: 4 waves, two workgroups per CU.
-int rs_waves(int h3) {
-    static const int w8 = facl_env_int("FACL_RS_W8", 0);
-    return (h3 && w8) ? 8 : RS_WAVES;
-}
-
-template <bool PRO, bool SEG, bool BST, bool H3, int WV>
+// 4-wave workgroups, two per CU.  8-wave workgroups (256 rows per k-step of weight planes: half the plane re-reads) were measured
+// equal or slower (round 4, same box, bit-identical results: forward 49152x512x1024 0.182 vs 0.184 ms, dgrad 1024->512 0.187 vs
+// 0.176, step 3.023 vs 3.006 ms) -- the weight-plane traffic is not what bounds these kernels -- and are no longer built.
+template <bool PRO, bool SEG, bool BST, bool H3>
 int rs_launch_k(const RsArgs& g, hipStream_t st) {
-    const dim3 grid(g.N / 256, (g.M + 32 * WV - 1) / (32 * WV));
-    return facl_launch_dynamic_lds<k_gemm_rs<PRO, SEG, BST, H3, WV>>(grid, dim3(64 * WV), WV == 8 ? RS_LDS8 : RS_LDS, st, g);
+    const dim3 grid(g.N / 256, (g.M + RS_ROWS - 1) / RS_ROWS);
+    return facl_launch_dynamic_lds<k_gemm_rs<PRO, SEG, BST, H3>>(grid, dim3(64 * RS_WAVES), RS_LDS, st, g);
 }
 // the BatchNorm-backward statistics (g.by) exclude prologue and segment maximum (dgrad only)
-template <bool H3, int WV>
+template <bool H3>
 int rs_launch_form(const RsArgs& g, hipStream_t st) {
-    if (g.by) return rs_launch_k<false, false, true, H3, WV>(g, st);
-    if (g.pscale && g.smax) return rs_launch_k<true, true, false, H3, WV>(g, st);
-    if (g.pscale) return rs_launch_k<true, false, false, H3, WV>(g, st);
-    if (g.smax) return rs_launch_k<false, true, false, H3, WV>(g, st);
-    return rs_launch_k<false, false, false, H3, WV>(g, st);
+    if (g.by) return rs_launch_k<false, false, true, H3>(g, st);
+    if (g.pscale && g.smax) return rs_launch_k<true, true, false, H3>(g, st);
+    if (g.pscale) return rs_launch_k<true, false, false, H3>(g, st);
+    if (g.smax) return rs_launch_k<false, true, false, H3>(g, st);
+    return rs_launch_k<false, false, false, H3>(g, st);
 }
 
 int rs_launch(const RsArgs& g0, hipStream_t st) {
     RsArgs g = g0;
-    {   // Phase offset of the CU's second workgroup slot (see the kernel): ticks x k-steps + 500 of the 100-MHz counter, i.e. about
-        // half a workgroup's life; only where the launch runs MORE than one round of workgroups (else the wait is pure loss:
-        // measured +5..9 % on the 384-workgroup launches).  FACL_RS_PHASE=<ticks per k-step> overrides, 0 = off.
-        static const int per_ks = facl_env_int("FACL_RS_PHASE", 30);
-        const long long wgs = (long long)(g.N / 256) * ((g.M + 32 * rs_waves(g.h3) - 1) / (32 * rs_waves(g.h3)));
-        g.first_round = 512;
-        g.phase_ticks = (per_ks > 0 && wgs > g.first_round && rs_waves(g.h3) == RS_WAVES) ? per_ks * (g.K >> 4) + 500 : 0;
-    }
-    if (rs_waves(g.h3) == 8) return rs_launch_form<true, 8>(g, st);
-    return g.h3 ? rs_launch_form<true, RS_WAVES>(g, st) : rs_launch_form<false, RS_WAVES>(g, st);
+    // Phase offset of the CU's second workgroup slot (see the kernel): RS_PHASE_TICKS x k-steps + 500 of the 100-MHz counter, i.e.
+    // about half a workgroup's life; only where the launch runs MORE than one round of workgroups (else the wait is pure loss:
+    // measured +5..9 % on the 384-workgroup launches)
+    const long long wgs = (long long)(g.N / 256) * ((g.M + RS_ROWS - 1) / RS_ROWS);
+    g.first_round = 512;
+    g.phase_ticks = wgs > g.first_round ? RS_PHASE_TICKS * (g.K >> 4) + 500 : 0;
+    return g.h3 ? rs_launch_form<true>(g, st) : rs_launch_form<false>(g, st);
 }
 
 }  // namespace
@@ -969,9 +957,8 @@ extern "C" int facl_gemm_rs_fwd(const float* a, int64_t M, int K, const void* pl
     if ((sgn == nullptr) != (ymax == nullptr) || (sgn == nullptr) != (arg == nullptr)) return FACL_E_NULL;
     if (sgn && (M & 63)) return FACL_E_SHAPE;
     if (((uintptr_t)a | (uintptr_t)planes) & 15) return FACL_E_ALIGN;
-    const int rpw = 32 * rs_waves(half ? 1 : 0);
-    const int prow = (int)((M + rpw - 1) / rpw);
-    if (sums && (size_t)prow * N * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
+    const int prow = (int)((M + RS_ROWS - 1) / RS_ROWS);
+    if (sums && (size_t)prow * N * 2 * sizeof(double) > (size_t)facl_ws_bytes()) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int* wse = (const int*)((const char*)planes + rs_planes_only_bytes(N, K, centers ? 1 : 0));
     RsArgs g{a, K, (int)M, K, (const uint4*)planes, N / 32, N};
@@ -1010,9 +997,8 @@ extern "C" int facl_gemm_rs_dgrad_bnstats(const float* dy, int64_t M, int N, con
     if (!dy || !planes || !da || !y || !bnc || !sums || !ws || (half && !amax)) return FACL_E_NULL;
     if (!facl_gemm_rs_supported(M, N, K)) return FACL_E_SHAPE;
     if (((uintptr_t)dy | (uintptr_t)planes) & 15) return FACL_E_ALIGN;
-    const int rpw = 32 * rs_waves(half ? 1 : 0);
-    const int prow = (int)((M + rpw - 1) / rpw);
-    if ((size_t)prow * K * 2 * sizeof(double) > ((size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES)) return FACL_E_SHAPE;
+    const int prow = (int)((M + RS_ROWS - 1) / RS_ROWS);
+    if ((size_t)prow * K * 2 * sizeof(double) > (size_t)facl_ws_bytes()) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int* wse = (const int*)((const char*)planes + rs_planes_only_bytes(K, N, 0));
     RsArgs g{dy, N, (int)M, N, (const uint4*)planes, K / 32, K};
@@ -1057,8 +1043,7 @@ extern "C" int facl_gemm_rs_wgrad(const float* dy, const float* y, int64_t M, in
     hipStream_t st = (hipStream_t)stream;
     WgArgs g{dy, y, (int)M, N, K, pscale, pshift, slices, rps, amax, amax_b};
     const dim3 grid(K / 128, N / 512, nz);
-    static const int wide_env = facl_env_int("FACL_WGRAD_WIDE", 1);                                // 0: dword fragment loads (A/B)
-    const int wide = wide_env && !(((uintptr_t)dy) & 15);                                          // the 16-byte row loads need an aligned dy
+    const int wide = !(((uintptr_t)dy) & 15);                      // the 16-byte row loads need an aligned dy; else dword fragment loads
     int rc;
     if (pscale && amax && wide) rc = wg_launch_k<true, true, true>(g, grid, st);
     else if (amax && wide) rc = wg_launch_k<false, true, true>(g, grid, st);

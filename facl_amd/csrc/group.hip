@@ -14,7 +14,7 @@
 namespace {
 
 constexpr int GROUP_THREADS = 256;           // 4 waves
-constexpr int CENTROIDS_PER_WG = 16;         // 4 per wave (the default; the kernel takes the count as a template argument)
+constexpr int CENTROIDS_PER_WG = 16;         // 4 per wave: four workgroups stage each cloud, the measured optimum
 constexpr int CKEYS = 4;                     // keys per lane once the candidate set fits (radix select, second phase)
 constexpr int CKE = 7;                       // K <= 256: entries per lane of the compacted list (keys under the candidate range's top)
 constexpr int CAP = 64 * CKE;                // capacity of that list (per wave: CAP (key, index) pairs of 8 bytes in LDS)
@@ -32,7 +32,7 @@ __device__ __forceinline__ int rank_below(unsigned long long m, int base) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)base));
 }
 
-template <int D, int NPL, int CPW = CENTROIDS_PER_WG, bool FULL = false>
+template <int D, int NPL, bool FULL>
 __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict__ points, int N, int S,
                                                          int K, float r2, int32_t* __restrict__ idx_out,
                                                          float* __restrict__ xt_out, float* __restrict__ yt_out,
@@ -66,8 +66,8 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group(const float* __restrict
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the per-wave LDS slot's address stays scalar
 
     uint32_t eguess = 122;                    // wave-persistent exponent guess of the K-th distance^2 (2^-5 .. 2^-4 to start with)
-    for (int ci = wave; ci < CPW; ci += GROUP_THREADS / 64) {
-        const int c = blockIdx.x * CPW + ci;                     // wave-uniform
+    for (int ci = wave; ci < CENTROIDS_PER_WG; ci += GROUP_THREADS / 64) {
+        const int c = blockIdx.x * CENTROIDS_PER_WG + ci;                     // wave-uniform
         if (c >= S) break;
         const float cx = xs[c], cy = ys[c], cz = zs[c];
 
@@ -351,36 +351,12 @@ int launch_group(const float* points, int M, int N, int S, int K, float r2, int3
                  int clipB, hipStream_t st) {
     constexpr int DS = D <= 4 ? D : 3;                                   // D > 4: only xyz is staged
     const size_t lds = (size_t)N * DS * sizeof(float) + 4 * SLOT_BYTES;  // cloud (SoA, DS arrays) + one compacted-list / emission slot per wave
-    // centroids per workgroup (A/B knob FACL_GROUP_CPW: 16 = four workgroups stage each cloud, 32 = two, 64 = one)
-    static const int cpw = facl_env_int("FACL_GROUP_CPW", CENTROIDS_PER_WG);
-    if constexpr (D > 4) {                  // the A/B knob is not instantiated for the wide inputs: default geometry only
-        if (N == 64 * NPL)
-            hipLaunchKernelGGL((k_group<D, NPL, CENTROIDS_PER_WG, true>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-        else
-            hipLaunchKernelGGL((k_group<D, NPL>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    } else if (cpw == 32) {
-        hipLaunchKernelGGL((k_group<D, NPL, 32>), dim3((S + 31) / 32, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    } else if (cpw == 8) {
-        hipLaunchKernelGGL((k_group<D, NPL, 8>), dim3((S + 7) / 8, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    } else if (cpw == 4) {
-        hipLaunchKernelGGL((k_group<D, NPL, 4>), dim3((S + 3) / 4, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    } else if (cpw == 64) {
-        hipLaunchKernelGGL((k_group<D, NPL, 64>), dim3((S + 63) / 64, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    } else if (N == 64 * NPL) {
-        hipLaunchKernelGGL((k_group<D, NPL, CENTROIDS_PER_WG, true>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    } else {
-        hipLaunchKernelGGL((k_group<D, NPL>), dim3((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M), dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
-    }
+    const dim3 grid((S + CENTROIDS_PER_WG - 1) / CENTROIDS_PER_WG, M);
+    if (N == 64 * NPL)
+        hipLaunchKernelGGL((k_group<D, NPL, true>), grid, dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
+    else
+        hipLaunchKernelGGL((k_group<D, NPL, false>), grid, dim3(GROUP_THREADS), lds, st, points, N, S, K, r2, idx, xt, yt, clipB);
     return facl_launch_status();
-}
-
-template <int D>
-int dispatch_group(const float* points, int M, int N, int S, int K, float r2, int32_t* idx, float* xt, float* yt,
-                   int clipB, hipStream_t st) {
-    if (N <= 512) return launch_group<D, 8>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    if (N <= 1024) return launch_group<D, 16>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    if (N <= 2048) return launch_group<D, 32>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    return launch_group<D, 64>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
 }
 
 }  // namespace
@@ -393,14 +369,13 @@ static int group_entry(const float* points, int M, int N, int D, int S, int K, f
     if (D == 4 && ((((uintptr_t)points) & 15) || (xt && (((uintptr_t)xt) & 15)))) return FACL_E_ALIGN;
     if (M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-    case 4: return dispatch_group<4>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    case 3: return dispatch_group<3>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    case 5: return dispatch_group<5>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    case 6: return dispatch_group<6>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    case 7: return dispatch_group<7>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    default: return dispatch_group<8>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
-    }
+    return facl_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if (N <= 512) return launch_group<DD, 8>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+        if (N <= 1024) return launch_group<DD, 16>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+        if (N <= 2048) return launch_group<DD, 32>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+        return launch_group<DD, 64>(points, M, N, S, K, r2, idx, xt, yt, clipB, st);
+    });
 }
 
 extern "C" int facl_group(const float* points, int M, int N, int D, int S, int K, float r2, int32_t* idx,

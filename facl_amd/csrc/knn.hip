@@ -356,12 +356,11 @@ extern "C" int facl_knn_topk(const float* q, int nq, int ldq, const float* x, in
         g.pi = reinterpret_cast<int*>(g.pv + (size_t)nq * g.splits * k);
     }
     const int lds = KOPER_BYTES + KINFO_BYTES + KBM * k * 8;
-    static bool done[64];
-    const void* fns[1] = {(const void*)k_knn_topk};
-    if (int e = facl_set_dynamic_lds(done, fns, 1, KOPER_BYTES + KINFO_BYTES + KBM * KMAX * 8)) return e;
     k_knn_rowinfo<<<(nq + 3) / 4, 256, 0, st>>>(q, nq, C, ldq, scq, postq);
     k_knn_rowinfo<<<(nb + 3) / 4, 256, 0, st>>>(x, nb, C, ldx, scb, postb);
-    k_knn_topk<<<dim3((nq + KBM - 1) / KBM, g.splits), 256, lds, st>>>(g);
+    // the candidate lists grow with k: the attribute covers k = KMAX
+    if (int e = facl_launch_dynamic_lds<k_knn_topk, KOPER_BYTES + KINFO_BYTES + KBM * KMAX * 8>(dim3((nq + KBM - 1) / KBM, g.splits), dim3(256),
+                                                                                                lds, st, g)) return e;
     if (!g.final) k_knn_merge<<<(nq + 3) / 4, 256, 0, st>>>(g.pv, g.pi, nq, k, g.splits, top_val, top_idx);
     return facl_launch_status();
 }

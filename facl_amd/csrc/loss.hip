@@ -698,7 +698,7 @@ int pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J
     if (units > 0x7fffffffLL) return FACL_E_SHAPE;
     // workspace: [per-clip losses (2B doubles) | chunk sums (units doubles) | chunk maxima (units floats)]
     if ((size_t)(2 * (long long)B + units) * sizeof(double) + (size_t)units * sizeof(float) >
-        (size_t)facl_ws_bytes() - FACL_WS_TICKET_BYTES) return FACL_E_SHAPE;
+        (size_t)facl_ws_bytes()) return FACL_E_SHAPE;
     double* part = (double*)ws;
     double* ps = part + 2 * (size_t)B;
     float* pm = (float*)(ps + units);

@@ -852,12 +852,8 @@ extern "C" int facl_sa_bwd1(const float* y2f, int64_t nunits, const float* bnc2,
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)(nunits < SA_GRID * 4 ? (nunits + 3) / 4 : SA_GRID);
     const size_t lds = (1024 + 4096 + 80) * sizeof(float4) + 4 * 64 * TP * sizeof(float);
-    static bool attr_done[64] = {};
-    const void* fns[1] = {(const void*)k_sa_bwd1};
-    if (int rc = facl_set_dynamic_lds(attr_done, fns, 1, (int)lds)) return rc;
-    hipLaunchKernelGGL(k_sa_bwd1, dim3(grid), dim3(512), lds, st, y2f, (int)nunits, bnc2, G3, h3, W3, coef, arg, dz2f,
-                       (double*)ws, a2amax);
-    int rc = facl_launch_status();
+    const int rc = facl_launch_dynamic_lds<k_sa_bwd1>(dim3(grid), dim3(512), (int)lds, st, y2f, (int)nunits, bnc2, G3, h3, W3, coef, arg,
+                                                      dz2f, (double*)ws, a2amax);
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, grid * 4, 128, sums, st);
 }
@@ -873,21 +869,14 @@ extern "C" int facl_sa_bwd_w3(const float* y2f, int64_t nunits, const float* bnc
     if (pairk) {
         const size_t tiles = (size_t)8 * 64 * TP, combs = (size_t)256 * 65 + 64 * 64 + 64;
         const size_t lds = 32 * sizeof(float4) + (tiles > combs ? tiles : combs) * sizeof(float);
-        static bool attr_done[64] = {};
-        const void* fns[1] = {(const void*)k_sa_bwd_w3p};
-        if (int rc = facl_set_dynamic_lds(attr_done, fns, 1, (int)lds)) return rc;
-        hipLaunchKernelGGL(k_sa_bwd_w3p, dim3(grid), dim3(512), lds, st, y2f, (int)nunits, bnc2, coef, arg, (double*)ws, a2amax);
-        int rc = facl_launch_status();
+        const int rc = facl_launch_dynamic_lds<k_sa_bwd_w3p>(dim3(grid), dim3(512), (int)lds, st, y2f, (int)nunits, bnc2, coef, arg,
+                                                             (double*)ws, a2amax);
         if (rc) return rc;
         return facl_reduce_rows_f32((const float*)ws, grid, W3_V, out, st);
-    } else {
-        const size_t lds = 32 * sizeof(float4) + (256 * 65 + 64 * 64 + 64 + 4 * 64 * TP) * sizeof(float);
-        static bool attr_done[64] = {};
-        const void* fns[1] = {(const void*)k_sa_bwd_w3};
-        if (int rc = facl_set_dynamic_lds(attr_done, fns, 1, (int)lds)) return rc;
-        hipLaunchKernelGGL(k_sa_bwd_w3, dim3(grid), dim3(256), lds, st, y2f, (int)nunits, bnc2, coef, arg, (double*)ws, a2amax);
     }
-    int rc = facl_launch_status();
+    const size_t lds = 32 * sizeof(float4) + (256 * 65 + 64 * 64 + 64 + 4 * 64 * TP) * sizeof(float);
+    const int rc = facl_launch_dynamic_lds<k_sa_bwd_w3>(dim3(grid), dim3(256), (int)lds, st, y2f, (int)nunits, bnc2, coef, arg, (double*)ws,
+                                                        a2amax);
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, grid, W3_V, out, st);
 }
@@ -910,15 +899,13 @@ extern "C" int facl_sa_bwd2(const float* dz2f, const float* y2f, const float* x,
         if (rc) return rc;
         return facl_reduce_rows((const double*)ws, grid, FACL_SA_BWD2_OUT(D), out, st);   // one row per workgroup (combined in LDS)
     }
-    if (D > 4) return FACL_E_CONFIG;          // the fp32 kernel does not fit a CU's LDS at D > 4 (above): the split-bf16 one serves
     const int grid = (int)(nunits < SA_GRID * 4 ? (nunits + 3) / 4 : SA_GRID);
     const size_t lds = (1024 + 128 + 64) * sizeof(float4) + 4 * (2 * 64 * TQ + 64 * 8) * sizeof(float);
-    static bool attr_done[64] = {};
-    const void* fns[2] = {(const void*)k_sa_bwd2<4>, (const void*)k_sa_bwd2<3>};
-    if (int rc = facl_set_dynamic_lds(attr_done, fns, 2, (int)lds)) return rc;
-    if (D == 4) hipLaunchKernelGGL((k_sa_bwd2<4>), dim3(grid), dim3(256), lds, st, dz2f, y2f, x, (int)nunits, bw2, W2, l1tab, (double*)ws);
-    else hipLaunchKernelGGL((k_sa_bwd2<3>), dim3(grid), dim3(256), lds, st, dz2f, y2f, x, (int)nunits, bw2, W2, l1tab, (double*)ws);
-    int rc = facl_launch_status();
+    const int rc = facl_dispatch_d(D, [&](auto d) {
+        if constexpr (decltype(d)::value > 4) return FACL_E_CONFIG;   // the fp32 kernel does not fit a CU's LDS at D > 4 (above): the split-bf16 one serves
+        else return facl_launch_dynamic_lds<k_sa_bwd2<decltype(d)::value>>(dim3(grid), dim3(256), (int)lds, st, dz2f, y2f, x, (int)nunits, bw2, W2,
+                                                                           l1tab, (double*)ws);
+    });
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, grid * 4, B2_V, out, st);
 }

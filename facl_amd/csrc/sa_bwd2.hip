@@ -65,9 +65,7 @@ __device__ __forceinline__ bf16x8 tr_read_pair(const char* p_lo, const char* p_h
 // two that puts the maximum of the wave's half unit in [2^13, 2^14) (one DPP reduction per half unit, no LDS, no host).  The
 // da1 tiles are scaled back when they are consumed; dW2's contribution of a half unit is accumulated in a temporary tile
 // and added to the running sums with the inverse scale, so half units of different magnitude mix exactly.
-// PREF (round 4 experiment, FACL_BWD2_PREF=1): the NEXT half unit's 16 loads are issued as soon as this half unit's dz2 / y2
-// registers are consumed (step 1), so they fly under the MFMA / layer-1 / dW2 work instead of being waited for at the top.
-template <int D, bool H3, bool PREF = false>
+template <int D, bool H3>
 __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
     const float* __restrict__ dz2f, const float* __restrict__ y2f, const float* __restrict__ x, int nunits,
     const float* __restrict__ bw2 /* (4,64): scale2, A, B, mean2 */, const float* __restrict__ W2,
@@ -159,7 +157,6 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
             yv[i] = *reinterpret_cast<const float4*>(yt + (i * 64 + lane) * 4);
         }
     };
-    if (PREF && wave_g < nunits) load_half(rev ? nunits - 1 - wave_g : wave_g, 0);
     for (int uu = wave_g; uu < nunits; uu += nwaves) {
         const int u = rev ? nunits - 1 - uu : uu;
         if constexpr (D <= 4) {   // x of the unit -> LDS (one float4 per position)
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
         }
 #pragma unroll 1
         for (int ct = 0; ct < 2; ++ct) {
-            if (!PREF) load_half(u, ct);                    // all 16 loads in flight before the first use
+            load_half(u, ct);                               // all 16 loads in flight before the first use
             if constexpr (D > 4) {  // x of the HALF unit -> LDS: lane (q, h) writes channels 4h..4h+3 of position 32 ct + q
                 const float* xp = x + ((size_t)u * 64 + 32 * ct + q) * D + 4 * h;
                 float4 xv;
@@ -252,10 +249,6 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
                 ap[kk][1] = as_bf16x8(mi[0], mi[1], mi[2], mi[3]);
                 ap[kk][2] = as_bf16x8(lo[0], lo[1], lo[2], lo[3]);
             }
-            }
-            if (PREF) {                                     // zv / yv are consumed: the next half unit's loads take their place
-                const int un = uu + nwaves < nunits ? (rev ? nunits - 1 - (uu + nwaves) : uu + nwaves) : u;   // last round: re-reads its own (L2 hit)
-                if (ct == 0) load_half(u, 1); else load_half(un, 0);
             }
             // ---- 2. da1[p][c1] = sum_c2 dy2[p][c2] W2[c2][c1]   (tiles: rows = positions, lane = c1)
             f32x16 da1[2];                                  // [c1 tile]
@@ -432,43 +425,14 @@ __global__ __launch_bounds__(64 * B2S_WAVES, 2) void k_sa_bwd2_sb(
 // launcher for facl_sa_bwd2 (sa_bwd.hip): `grid` workgroups of B2S_WAVES waves, one partial row per WORKGROUP in `ws`
 int facl_sa_bwd2_sb_launch(const float* dz2f, const float* y2f, const float* x, int nunits, int D, const float* bw2,
                            const float* W2, const float* l1tab, double* ws, int grid, const uint32_t* a1amax, hipStream_t st) {
-    const size_t lds = b2s_lds_bytes();
     static const int rev = facl_env_int("FACL_BWD2_REV", 1);
     static const int h3 = facl_env_int("FACL_BWD_H3", 1);     // 0: bf16x6 (A/B)
     const dim3 g(grid), b(64 * B2S_WAVES);
-    static const int pref = facl_env_int("FACL_BWD2_PREF", 0);
-    if (D > 4) {
-        // the wide inputs (5..8 channels): default geometry; the FACL_BWD2_PREF experiment is not instantiated for them
-        static bool attr_wide[64] = {};
-        const void* wf[8] = {(const void*)k_sa_bwd2_sb<5, true>, (const void*)k_sa_bwd2_sb<6, true>, (const void*)k_sa_bwd2_sb<7, true>,
-                             (const void*)k_sa_bwd2_sb<8, true>, (const void*)k_sa_bwd2_sb<5, false>, (const void*)k_sa_bwd2_sb<6, false>,
-                             (const void*)k_sa_bwd2_sb<7, false>, (const void*)k_sa_bwd2_sb<8, false>};
-        if (int rc = facl_set_dynamic_lds(attr_wide, wf, 8, (int)lds)) return rc;
-#define FACL_BWD2_WIDE(DD)                                                                                                          \
-        if (h3) hipLaunchKernelGGL((k_sa_bwd2_sb<DD, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);  \
-        else hipLaunchKernelGGL((k_sa_bwd2_sb<DD, false>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-        if (D == 5) { FACL_BWD2_WIDE(5) }
-        else if (D == 6) { FACL_BWD2_WIDE(6) }
-        else if (D == 7) { FACL_BWD2_WIDE(7) }
-        else { FACL_BWD2_WIDE(8) }
-#undef FACL_BWD2_WIDE
-        return facl_launch_status();
-    }
-    static bool attr_done[64] = {};
-    const void* fns[6] = {(const void*)k_sa_bwd2_sb<4, true>, (const void*)k_sa_bwd2_sb<3, true>, (const void*)k_sa_bwd2_sb<4, false>,
-                          (const void*)k_sa_bwd2_sb<3, false>, (const void*)k_sa_bwd2_sb<4, true, true>, (const void*)k_sa_bwd2_sb<3, true, true>};
-    if (int rc = facl_set_dynamic_lds(attr_done, fns, 6, (int)lds)) return rc;
-    if (h3 && pref) {
-        if (D == 4) hipLaunchKernelGGL((k_sa_bwd2_sb<4, true, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-        else hipLaunchKernelGGL((k_sa_bwd2_sb<3, true, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-    } else if (h3) {
-        if (D == 4) hipLaunchKernelGGL((k_sa_bwd2_sb<4, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-        else hipLaunchKernelGGL((k_sa_bwd2_sb<3, true>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-    } else {
-        if (D == 4) hipLaunchKernelGGL((k_sa_bwd2_sb<4, false>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-        else hipLaunchKernelGGL((k_sa_bwd2_sb<3, false>), g, b, lds, st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
-    }
-    return facl_launch_status();
+    return facl_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if (h3) return facl_launch_dynamic_lds<k_sa_bwd2_sb<DD, true>>(g, b, (int)b2s_lds_bytes(), st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
+        return facl_launch_dynamic_lds<k_sa_bwd2_sb<DD, false>>(g, b, (int)b2s_lds_bytes(), st, dz2f, y2f, x, nunits, bw2, W2, l1tab, ws, rev, a1amax);
+    });
 }
 
 int facl_sa_bwd2_sb_waves() { return B2S_WAVES; }

@@ -33,6 +33,7 @@ __device__ __forceinline__ float wave_max_nonneg_e(float v) {
 
 constexpr int EV_LDS_BYTES = (4096 + 1024) * 16 + (128 + 16 + 16 + 16) * 16 + 3 * 256 * 4 + 64;
 // D > 4: the layer-1 table rows are three float4s instead of two (include/facl_hip.h, FACL_SA_L1_COLS)
+constexpr int EV_WAVES = 12;                             // waves per workgroup (facl_sa_eval)
 constexpr int ev_lds_bytes(int D) { return EV_LDS_BYTES + (FACL_SA_L1_COLS(D) / 4 - 2) * 64 * 16; }
 
 template <int D, int WAVES>
@@ -312,41 +313,12 @@ extern "C" int facl_sa_eval(const float* x, int64_t nunits, int D, const float* 
     if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     // 12 waves per workgroup = three per SIMD (the kernel needs 145 registers; one workgroup per CU: 86 KiB of LDS):
-    // 0.304 ms vs 0.3135 ms with 8 waves at the headline shape, same box, alternating runs (FACL_EVAL_WAVES=8 for the A/B)
-    static const int waves = facl_env_int("FACL_EVAL_WAVES", 12);
-    const int W = waves == 8 ? 8 : 12;
+    // 0.304 ms vs 0.3135 ms with 8 waves at the headline shape, same box, alternating runs
+    constexpr int W = EV_WAVES;
     const int grid = (int)(nunits < 256 * W ? (nunits + W - 1) / W : 256);
-    static bool attr_done_dev[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done_dev[dev]) {
-        const void* fns[4] = {(const void*)k_sa_eval<3, 8>, (const void*)k_sa_eval<4, 8>, (const void*)k_sa_eval<3, 12>, (const void*)k_sa_eval<4, 12>};
-        for (int i = 0; i < 4; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, EV_LDS_BYTES);
-            if (e != hipSuccess) return (int)e;
-        }
-        const void* wide[8] = {(const void*)k_sa_eval<5, 8>, (const void*)k_sa_eval<6, 8>, (const void*)k_sa_eval<7, 8>, (const void*)k_sa_eval<8, 8>,
-                               (const void*)k_sa_eval<5, 12>, (const void*)k_sa_eval<6, 12>, (const void*)k_sa_eval<7, 12>, (const void*)k_sa_eval<8, 12>};
-        for (int i = 0; i < 8; ++i) {
-            hipError_t e = hipFuncSetAttribute(wide[i], hipFuncAttributeMaxDynamicSharedMemorySize, ev_lds_bytes(8));
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_done_dev[dev] = true;
-    }
-#define FACL_EVAL_LAUNCH(DD, WW) hipLaunchKernelGGL((k_sa_eval<DD, WW>), dim3(grid), dim3(64 * WW), ev_lds_bytes(DD), st, x, (int)nunits, l1tab, W2, \
-                                                    b2, scale2, shift2, W3, b3, scale3, shift3, pooled, a1amax)
-    if (D == 4 && W == 12) FACL_EVAL_LAUNCH(4, 12);
-    else if (D == 4) FACL_EVAL_LAUNCH(4, 8);
-    else if (D == 3 && W == 12) FACL_EVAL_LAUNCH(3, 12);
-    else if (D == 3) FACL_EVAL_LAUNCH(3, 8);
-    else if (D == 5 && W == 12) FACL_EVAL_LAUNCH(5, 12);
-    else if (D == 5) FACL_EVAL_LAUNCH(5, 8);
-    else if (D == 6 && W == 12) FACL_EVAL_LAUNCH(6, 12);
-    else if (D == 6) FACL_EVAL_LAUNCH(6, 8);
-    else if (D == 7 && W == 12) FACL_EVAL_LAUNCH(7, 12);
-    else if (D == 7) FACL_EVAL_LAUNCH(7, 8);
-    else if (W == 12) FACL_EVAL_LAUNCH(8, 12);
-    else FACL_EVAL_LAUNCH(8, 8);
-#undef FACL_EVAL_LAUNCH
-    return facl_launch_status();
+    return facl_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        return facl_launch_dynamic_lds<k_sa_eval<DD, W>>(dim3(grid), dim3(64 * W), ev_lds_bytes(DD), st, x, (int)nunits, l1tab, W2, b2,
+                                                         scale2, shift2, W3, b3, scale3, shift3, pooled, a1amax);
+    });
 }

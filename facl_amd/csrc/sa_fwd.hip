@@ -592,6 +592,7 @@ __device__ __forceinline__ unsigned pk_f16q(float x0, float x1) {
 }
 // WAVES / PREF: 8 waves per workgroup (two per SIMD) with the next unit's y2 tile prefetched into a second register set (206
 // registers), or -- the fp16x3 default since round 4 -- 12 waves (three per SIMD) without the prefetch (160 registers).
+constexpr int FWD3_H3_WAVES = 12;              // waves per workgroup of the fp16x3 form (sa_fwd3_p)
 template <int NP, int WAVES = 8, bool PREF = true>
 __global__ __launch_bounds__(64 * WAVES) void k_sa_fwd3_sb(const float* __restrict__ y2f, int nunits,
                                                     const float* __restrict__ sc2, const float* __restrict__ sh2,
@@ -892,13 +893,10 @@ extern "C" int facl_sa_x_moments(const float* x, int64_t P, int D, double* mom, 
     if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || P < 1) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int grid = 512, V = D + D * D;       // 512 blocks x 4 waves = 2048 partial rows
-    if (D == 4) hipLaunchKernelGGL((k_x_moments<4>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    else if (D == 3) hipLaunchKernelGGL((k_x_moments<3>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    else if (D == 5) hipLaunchKernelGGL((k_x_moments<5>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    else if (D == 6) hipLaunchKernelGGL((k_x_moments<6>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    else if (D == 7) hipLaunchKernelGGL((k_x_moments<7>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    else hipLaunchKernelGGL((k_x_moments<8>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
-    int rc = facl_launch_status();
+    const int rc = facl_dispatch_d(D, [&](auto d) {
+        hipLaunchKernelGGL((k_x_moments<decltype(d)::value>), dim3(grid), dim3(256), 0, st, x, (long long)P, (double*)ws);
+        return facl_launch_status();
+    });
     if (rc) return rc;
     return facl_reduce_rows((const double*)ws, grid * 4, V, mom, st);
 }
@@ -912,34 +910,16 @@ extern "C" int facl_sa_fwd2(const float* x, int64_t nunits, int D, const float* 
     const int grid = (int)(nunits < 2 * SA_GRID * 4 ? (nunits + 3) / 4 : 2 * SA_GRID);   // 2 workgroups per CU
     double* part = sums2 ? (double*)ws : nullptr;
     static const int use_f32 = facl_env_int("FACL_SA_F32", 0);     // exact-fp32 MFMA kernel instead
-    if (D > 4) {
-        // the wide inputs (5..8 channels): same kernels, layer-1 table rows of FACL_SA_L1_COLS(D) floats
-#define FACL_FWD2_WIDE(DD)                                                                                                         \
-        if (use_f32) hipLaunchKernelGGL((k_sa_fwd2<DD>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);   \
-        else if (h3w) hipLaunchKernelGGL((k_sa_fwd2_sb<DD, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, \
-                                         part, a1amax);                                                                            \
+    // fp16x3 (two fp16 planes, three products: csrc/common.h) unless FACL_FWD_H3=0 selects bf16x6 (A/B)
+    static const int h3 = facl_env_int("FACL_FWD_H3", 1);
+    // every width runs the same kernels; D > 4: layer-1 table rows of FACL_SA_L1_COLS(D) floats
+    const int rc = facl_dispatch_d(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        if (use_f32) hipLaunchKernelGGL((k_sa_fwd2<DD>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);
+        else if (h3) hipLaunchKernelGGL((k_sa_fwd2_sb<DD, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
         else hipLaunchKernelGGL((k_sa_fwd2_sb<DD, false>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
-        static const int h3w = facl_env_int("FACL_FWD_H3", 1);
-        if (D == 5) { FACL_FWD2_WIDE(5) }
-        else if (D == 6) { FACL_FWD2_WIDE(6) }
-        else if (D == 7) { FACL_FWD2_WIDE(7) }
-        else { FACL_FWD2_WIDE(8) }
-#undef FACL_FWD2_WIDE
-    } else if (use_f32) {
-        if (D == 4) hipLaunchKernelGGL((k_sa_fwd2<4>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);
-        else hipLaunchKernelGGL((k_sa_fwd2<3>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part);
-    } else {
-        // fp16x3 (two fp16 planes, three products: csrc/common.h) unless FACL_FWD_H3=0 selects bf16x6 (A/B)
-        static const int h3 = facl_env_int("FACL_FWD_H3", 1);
-        if (h3) {
-            if (D == 4) hipLaunchKernelGGL((k_sa_fwd2_sb<4, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
-            else hipLaunchKernelGGL((k_sa_fwd2_sb<3, true>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
-        } else {
-            if (D == 4) hipLaunchKernelGGL((k_sa_fwd2_sb<4, false>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
-            else hipLaunchKernelGGL((k_sa_fwd2_sb<3, false>), dim3(grid), dim3(256), 0, st, x, (int)nunits, l1tab, W2, b2, y2f, part, a1amax);
-        }
-    }
-    int rc = facl_launch_status();
+        return facl_launch_status();
+    });
     if (rc || !sums2) return rc;
     // waves beyond nunits never enter the loop and still write their (zero) rows
     return facl_reduce_rows(part, grid * 4, 128, sums2, st);
@@ -951,49 +931,28 @@ static int sa_fwd3_p(const float* y2f, int64_t nunits, const float* scale2, cons
     if (!y2f || !scale2 || !shift2 || !W3 || !b3 || !sgn3 || !ymax || !arg || (sums3 && !ws) || (prec == 3 && !a2amax)) return FACL_E_NULL;
     if (nunits < 1 || nunits > 0x7fffffff) return FACL_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    // 12 waves per workgroup (three per SIMD, 160 registers, no register prefetch of the next y2 tile) since round 4: 0.350 vs
-    // 0.359 ms at the headline shape, three alternating same-box runs (gpurun_out: FACL_FWD3_W12=0 restores 8 waves + prefetch)
-    static const int w12 = facl_env_int("FACL_FWD3_W12", 1);
-    const int WV = (w12 && prec == 3) ? 12 : 8;
+    if (prec < 0 || prec > 3) return FACL_E_CONFIG;
+    // fp16x3: 12 waves per workgroup (three per SIMD, 160 registers, no register prefetch of the next y2 tile) since round 4: 0.350 vs
+    // 0.359 ms at the headline shape with 8 waves + prefetch, three alternating same-box runs; the other precisions keep that form
+    const int WV = prec == 3 ? FWD3_H3_WAVES : 8;
     const int grid = (int)(nunits < SA_GRID * WV ? (nunits + WV - 1) / WV : SA_GRID);
     // FACL_SA_F32=1 selects the exact-fp32 MFMA kernel (v_mfma_f32_32x32x2_f32) instead of the split-bf16 one
     static const int env_f32 = facl_env_int("FACL_SA_F32", 0);
     const int use_f32 = env_f32 && prec == 0;
     const size_t lds = use_f32 ? (4096 + 32) * sizeof(float4) + 256 * sizeof(float) + 8 * 512 * sizeof(double2)
                                : (6144 + 32) * sizeof(float4) + 256 * sizeof(float) + WV * 256 * sizeof(double2);
-    const void* fn = use_f32 ? (const void*)k_sa_fwd3 : prec == 1 ? (const void*)k_sa_fwd3_sb<1>
-                   : prec == 2 ? (const void*)k_sa_fwd3_sb<2> : prec == 3 ? (const void*)k_sa_fwd3_sb<4> : (const void*)k_sa_fwd3_sb<3>;
-    if (prec < 0 || prec > 3) return FACL_E_CONFIG;
-    static bool attr_done[64][5] = {};                 // per device ordinal (the attribute is per device) and kernel variant
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    const int slot = WV == 12 ? 4 : prec;
-    if (!attr_done[dev][slot]) {
-        hipError_t e = hipFuncSetAttribute(WV == 12 ? (const void*)k_sa_fwd3_sb<4, 12, false> : fn,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done[dev][slot] = true;
-    }
     double* part = sums3 ? (double*)ws : nullptr;
-    if (use_f32)
-        hipLaunchKernelGGL(k_sa_fwd3, dim3(grid), dim3(512), lds, st, y2f, (int)nunits, scale2, shift2, W3, b3, sgn3, ymax,
-                           arg, part);
-    else if (prec == 1)
-        hipLaunchKernelGGL((k_sa_fwd3_sb<1>), dim3(grid), dim3(512), lds, st, y2f, (int)nunits, scale2, shift2, W3, b3, sgn3,
-                           ymax, arg, part, a2amax);
-    else if (prec == 2)
-        hipLaunchKernelGGL((k_sa_fwd3_sb<2>), dim3(grid), dim3(512), lds, st, y2f, (int)nunits, scale2, shift2, W3, b3, sgn3,
-                           ymax, arg, part, a2amax);
-    else if (prec == 3 && WV == 12)
-        hipLaunchKernelGGL((k_sa_fwd3_sb<4, 12, false>), dim3(grid), dim3(768), lds, st, y2f, (int)nunits, scale2, shift2, W3, b3, sgn3,
-                           ymax, arg, part, a2amax);
-    else if (prec == 3)
-        hipLaunchKernelGGL((k_sa_fwd3_sb<4>), dim3(grid), dim3(512), lds, st, y2f, (int)nunits, scale2, shift2, W3, b3, sgn3,
-                           ymax, arg, part, a2amax);
-    else
-        hipLaunchKernelGGL((k_sa_fwd3_sb<3>), dim3(grid), dim3(512), lds, st, y2f, (int)nunits, scale2, shift2, W3, b3, sgn3,
-                           ymax, arg, part, a2amax);
-    int rc = facl_launch_status();
+    auto sb = [&](auto np, auto wv) {
+        constexpr int NP = decltype(np)::value, W = decltype(wv)::value;
+        return facl_launch_dynamic_lds<k_sa_fwd3_sb<NP, W, W == 8>>(dim3(grid), dim3(64 * W), (int)lds, st, y2f, (int)nunits, scale2, shift2,
+                                                                    W3, b3, sgn3, ymax, arg, part, a2amax);
+    };
+    const int rc = use_f32 ? facl_launch_dynamic_lds<k_sa_fwd3>(dim3(grid), dim3(512), (int)lds, st, y2f, (int)nunits, scale2, shift2, W3, b3,
+                                                                sgn3, ymax, arg, part)
+                 : prec == 1 ? sb(facl_int<1>{}, facl_int<8>{})
+                 : prec == 2 ? sb(facl_int<2>{}, facl_int<8>{})
+                 : prec == 3 ? sb(facl_int<4>{}, facl_int<FWD3_H3_WAVES>{})
+                             : sb(facl_int<3>{}, facl_int<8>{});
     if (rc || !sums3) return rc;
     return facl_reduce_rows(part, grid * WV, 512, sums3, st);
 }

@@ -77,7 +77,6 @@ class FineTuneStep(ContrastiveStep):
         netR, G = self.netR, self.G
         if B > self.labels.shape[0]:
             raise RuntimeError("a batch of %d clips, the step holds %d labels" % (B, self.labels.shape[0]))
-        netR.lazy_code = False
         netR(xt, yt, 1)
         logits = netR.head(netR._stacked, G, B)
         loss, stats = netR.head.loss(logits, self.labels[:B])
@@ -172,7 +171,6 @@ def evaluate(netR, step, opt, device):
     with eval_mode(netR):
         for views, names, labels in ordered_views(opt, device, index, split, np.random.RandomState(2000)):
             xt, yt = step.group(views if views.dtype == torch.float32 else views.float())
-            netR.lazy_code = False
             netR(xt, yt, 1)
             logits = netR.head(netR._stacked, opt.num_crop, len(names))
             y = torch.as_tensor(labels, dtype=torch.int32).to(device)

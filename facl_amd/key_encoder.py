@@ -29,7 +29,6 @@ class KeyEncoder:
             if stacked is not None:
                 netR._stacked = stacked
         self.key.bn_reduce_fn = None
-        self.key.lazy_code = False
         for p in self.key.parameters():
             p.requires_grad_(False)
             p.grad = None

@@ -155,7 +155,6 @@ class Classifier:
             raise RuntimeError("this classifier has no encoder: it reads extracted features (logits_of_features)")
         with torch.no_grad():
             xt, yt = group_views(views if views.dtype == torch.float32 else views.float(), self.opt, self.opt.group_radius)
-            self.encoder.lazy_code = False
             self.encoder(xt, yt, 1)
             return self.head(self.encoder._stacked, self.views, B)
 

@@ -12,7 +12,6 @@ from . import _lib
 _FWD_H3 = __import__("os").environ.get("FACL_FWD_H3", "1") != "0"
 # eval mode through the ONE-kernel path (csrc/sa_eval.hip); FACL_EVAL_FUSED=0: the training passes with folded constants (A/B)
 _EVAL_FUSED = __import__("os").environ.get("FACL_EVAL_FUSED", "1") != "0"
-_EXTRA_LAUNCHES = int(__import__("os").environ.get("FACL_EXTRA_LAUNCHES", "0"))
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 UNIT = 64
@@ -30,9 +29,8 @@ class _Workspace:
         if key not in cls._ws:
             n = _lib.load_library().facl_ws_bytes()
             cls._ws[key] = torch.empty(n, dtype=torch.uint8, device=device)
-            cls._ws[key][-4096:].zero_()                 # ticket counters of the single-launch reduction (include/facl_hip.h)
         if _lib.POISON:
-            cls._ws[key][:-4096].fill_(0xFF)             # NaN bytes: every partial row a reduction reads must be rewritten
+            cls._ws[key].fill_(0xFF)                     # NaN bytes: every partial row a reduction reads must be rewritten
         return cls._ws[key]
 
 
@@ -113,8 +111,6 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         only the unbiased running-variance factor needs the true count."""
     lib = _lib.load_library()
     _lib.require_cuda(x_rows)
-    for _ in range(_EXTRA_LAUNCHES):                 # experiment knob: what does one more tiny dependent kernel cost inside the step?
-        _bn_eval(64, p["g1"], p["be1"], p["rm1"], p["rv1"])
     rep, R = 1, 1
     if K != UNIT:
         if K > UNIT and K % UNIT == 0:

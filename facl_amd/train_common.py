@@ -355,8 +355,6 @@ class ContrastiveStep:
 
     def _encode_and_step(self, xt, yt, B, order):
         netR, G = self.netR, self.G
-        # x_nor / code feed the SwAV / CLD terms only: without them F.normalize + mapping run beside the loss block
-        netR.lazy_code = not (self.swa_if or self.cld_if) and not fdist.is_distributed()
         # The key forward runs BEFORE the query forward: the passes share the stream's scratch workspace, and the query forward
         # leaves there (and in what autograd saved) what its backward reads -- nothing may run between the two
         key_rows = None
@@ -402,8 +400,6 @@ class ContrastiveStep:
         loss.backward(self._one)
         if self.grad_sync is not None:
             self.grad_sync.finish()                                                # tail bucket overlapped with the SA backward
-        from . import _lib as _flib
-        _flib.join_pending()                                                       # the side-stream branch of x_nor / code
         self.optimizer.step()
         return loss, loss_c, loss_circle
 
@@ -860,8 +856,6 @@ def knn_monitor(netR, opt, device):
             f = extract_split(netR, opt, device, index, split, rng)
             y = torch.as_tensor([index.label(v) for v in split], dtype=torch.int64, device=device)
             data.append((f, y))
-        from . import _lib
-        _lib.join_pending()
         (ftr, ytr), (fte, yte) = data
         return knn_top1(fte, yte, ftr, ytr, k=opt.knn_k, T=opt.knn_T)
 

@@ -78,8 +78,8 @@ int facl_group_clips(const float* clips, int B, int G, int N, int D, int S, int 
  * `bnc` is (5,C) float: mean, invstd, scale = gamma*invstd, shift = beta - mean*scale, sign(gamma).
  * running_mean / running_var (may both be NULL) are updated in place with `momentum` and the
  * unbiased variance, like F.batch_norm(training=True). */
-/* size of the scratch buffer `ws` the reducing calls need.  Its LAST 4096 bytes are ticket counters of the single-launch
- * partial-row reduction: the caller zeroes them once after allocating the buffer; every call leaves them zero again. */
+/* size of the scratch buffer `ws` the reducing calls need.  Nothing in it has to survive between calls and nothing has to be
+ * initialised: every partial row a call reads, the same call has written. */
 int64_t facl_ws_bytes(void);
 /* aamax (or NULL): FACL_AMAX_WORDS uint32 that receive (in every slot) the bits of a rigorous BOUND of the layer's activation
  * max|gamma (y - mean) invstd + beta| over the batch: |gamma| sqrt(count - 1) sigma invstd + |beta| (Samuelson's inequality).

@@ -202,7 +202,7 @@ def test_sa_ragged_unit_counts_wide(D, nunits, poisoned):
         assert err <= 2e-3 * max(float(g64.norm()), 1e-2 * gmax), (k, err, float(g64.norm()), flips)
 
 
-@pytest.mark.parametrize("D,K", [(8, 64), (5, 64), (8, 128)])
+@pytest.mark.parametrize("D,K", [(8, 64), (5, 64), (6, 64), (7, 64), (8, 128)])
 def test_sa_eval_one_kernel_wide(D, K, poisoned):
     TSA.test_sa_eval_one_kernel_vs_training_kernels_and_fp64(D, False, K)
 

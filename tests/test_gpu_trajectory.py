@@ -1,7 +1,7 @@
 """Consecutive training steps, eager and graph-replayed, against a plain torch-fp64 evaluation of the reference's step from
 the state the kernels actually left behind.  The one-step parity tests (test_gpu_headline.py, test_gpu_encoder.py) start
-from fresh memory; what carries over between steps does not: the fp16x3 operand-scale words raised with atomics, the
-ticket counters of the single-launch reduction, Adam's device-resident step and lr, the BatchNorm running buffers and the
+from fresh memory; what carries over between steps does not: the fp16x3 operand-scale words raised with atomics,
+Adam's device-resident step and lr, the BatchNorm running buffers and the
 host-side num_batches_tracked, and whatever a graph replay reuses.  The four steps of SCHEDULE are chosen so that state
 left over from the previous step is wrong for the next one: the input scale drops 4x, then rises 16x, the learning rate
 changes twice and the circle-loss order changes.  The whole module runs on NaN-poisoned scratch."""
@@ -289,7 +289,7 @@ def _graph_vs_eager_twin(c, tag, check=None):
 def test_graph_replay_steps_equal_eager_steps_bitwise(cfg):
     """Every replay of the captured step == one eager step from the same state, bit for bit: losses, every p.grad,
     parameters, running buffers, num_batches_tracked, Adam moments and step.  Both run the same kernels in the same order
-    and the step has no float atomics (the only atomicAdd in csrc/ draws a ticket; reductions sum in a fixed slice order),
+    and the step has no float atomics (csrc/ has no atomicAdd at all; reductions sum in a fixed slice order),
     so nothing may differ.  Every replay is also held to fp64 like test A (_step_vs_fp64): a defect shared by the graph and
     the eager path does not pass."""
     c = CONFIGS[cfg]

@@ -140,6 +140,8 @@ SIGNATURES = {
     "facl_contrast_pair_sum_cls": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_contrast_pair_queue_cls": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_queue_push_ids": [c_p, c_i, c_p, c_i, c_p, c_p],
+    "facl_contrast_pair_sum_sup": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p],
+    "facl_contrast_pair_queue_sup": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
     "facl_ema_apply": [c_i, c_p, c_p, c_p, c_f, c_p],
     "facl_grad_sqnorm": [c_i, c_p, c_p, c_p, c_p],
     "facl_adam_prep_ex": [c_p, c_p, c_f, c_f, c_p, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_p],

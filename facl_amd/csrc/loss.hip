@@ -39,6 +39,18 @@ __device__ __forceinline__ double block_reduce_sum(double v, double* sm) {
     return r;
 }
 
+// counts: exact, in the same fixed order as the sums above (sm: 16 words, e.g. block_reduce_max's floats)
+__device__ __forceinline__ int block_reduce_count(int v, int* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane_id() == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int r = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sm[w];
+    __syncthreads();
+    return r;
+}
+
 // One positive slot against the clip's log-sum-exp: t = logaddexp(pos, lse), sigma = exp(pos - t).  loss = t - pos is the slot's
 // loss term, dlse = 1 - sigma its share of d/dlse, dpos = sigma - 1 its d/dpos; the caller accumulates and applies the 1/B.
 struct SlotTerm { float loss, dlse, dpos; };
@@ -67,14 +79,25 @@ __device__ __forceinline__ SlotTerm slot_term(float pos, float lse) {
 // as an index.  Here a clip may have NO negative (a batch of one class): mx = -inf and se = 0 give lse = -inf + log(0) = -inf,
 // every slot's t = pos + log1p(exp(-inf)) = pos, so loss, dpos and dlse are exactly 0 and no exp(x - lse) is evaluated (every
 // column is masked) -- the arithmetic below needs no special case.
-constexpr int MASK_ZERO = 0, MASK_EXCLUDE = 1, MASK_CLASS = 2;
+// MASK_SUP: MASK_CLASS, and the cells it masks for a reason other than "own clip" -- the clip's CLASS CELLS C -- are positive
+// slots as well, against the same lse: loss_n = sum_s term(pos_s) + w sum_{c in C} term(v_c) with w = pw * nS / |C| (nothing is
+// added when |C| = 0), so the class cells enter through their mean term and weigh, at pw = 1, as much as the nS own slots.  A
+// class cell's gradient is w dpos / B, its dlse share times w joins the own slots' in the coefficient of the negatives; |C| is
+// a count and is not differentiated.  The class cells stay out of the maximum and the exp-sum; the own slots are reduced
+// exactly as in the other modes, so with |C| = 0 everywhere every output has MASK_EXCLUDE's bits.  lse = -inf: slot_term gives
+// exact zeros for the class cells too.  Internal to this file (facl_contrast_pair_sum_sup / _queue_sup); no mask_mode argument
+// of the ABI takes it.
+constexpr int MASK_ZERO = 0, MASK_EXCLUDE = 1, MASK_CLASS = 2, MASK_SUP = 3;
 
-// jm = j % Bk, mycls = cls[myclip] (MASK_CLASS only)
+// jm = j % Bk, mycls = cls[myclip] (MASK_CLASS and MASK_SUP only)
 template <int MASK>
 __device__ __forceinline__ bool col_masked(int jm, int myclip, int mycls, const int* __restrict__ cls) {
-    if constexpr (MASK == MASK_CLASS) return jm == myclip || (mycls >= 0 && cls[jm] == mycls);
+    if constexpr (MASK >= MASK_CLASS) return jm == myclip || (mycls >= 0 && cls[jm] == mycls);
     else return jm == myclip;
 }
+
+// w = pw * nS / |C| of MASK_SUP, in fp64 from the fp32 weight and the two counts
+__device__ __forceinline__ double sup_weight(float pw, int nS, int cells) { return (double)pw * (double)nS / (double)cells; }
 
 // One loss of one clip: the circle loss (circle = 1) or the global loss of local clip n, key clip myclip = n + clip_offset.
 // nA = anchor rows of the clip that feed its shared negative set, nS = its positive slots (kept as fields: as functions of
@@ -107,7 +130,7 @@ template <int MASK>
 __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restrict__ sim, int G, int B, int Bk, int J,
                                                            const long long* __restrict__ order, int clip_offset,
                                                            float* __restrict__ dsim, double* __restrict__ part,
-                                                           const int* __restrict__ cls) {
+                                                           const int* __restrict__ cls, float pw) {
     __shared__ float smf[16];
     __shared__ double smd[16];
     __shared__ int rb_s[1024];
@@ -115,7 +138,7 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     const PairSpec sp(circle, circle ? blockIdx.x - B : blockIdx.x, G, B, Bk, J, clip_offset, order);
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
     int mycls = -1;
-    if constexpr (MASK == MASK_CLASS) mycls = cls[myclip];
+    if constexpr (MASK >= MASK_CLASS) mycls = cls[myclip];
     if ((int)threadIdx.x < nA) rb_s[threadIdx.x] = sp.row_block(threadIdx.x);
     __syncthreads();
     const int total = nA * J;
@@ -137,8 +160,10 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
     // own over the same column index and without a condition (the index stays inside [0, Bk) past the end of the block too), so
     // that they are CK requests in flight at once: with the lookup inside the loop below every similarity load waited for its id,
     // CK round trips instead of one, +28 us per step at the headline size.
-    unsigned same_cls = 0u;
-    if constexpr (MASK == MASK_CLASS) {
+    // MASK_SUP: the same word; bit k of `cell` = element k is a class cell (same class, not the own clip): it is loaded, stays
+    // out of the maximum and the sum (bit 31 of off) and becomes a positive slot once lse is known.
+    unsigned same_cls = 0u, cell = 0u;
+    if constexpr (MASK >= MASK_CLASS) {
         if (mycls >= 0) {                                  // workgroup-uniform
             int pi = wi, pj = wj, pjm = wjm;
 #pragma unroll
@@ -154,9 +179,15 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
         if (e < total) {
             const unsigned o = (unsigned)((rb_s[wi] * B + n) * J + wj);
             bool masked = wjm == myclip;
-            if constexpr (MASK == MASK_CLASS) masked = masked || ((same_cls >> k) & 1u);
+            if constexpr (MASK >= MASK_CLASS) masked = masked || ((same_cls >> k) & 1u);
             off[k] = masked ? (o | 0x80000000u) : o;
-            if (!masked) x = sim[o];
+            if constexpr (MASK == MASK_SUP) {
+                const bool c = wjm != myclip && ((same_cls >> k) & 1u);
+                cell |= (unsigned)c << k;
+                if (!masked || c) x = sim[o];
+            } else {
+                if (!masked) x = sim[o];
+            }
         }
         v[k] = x;
         if (MASK == MASK_ZERO || !(off[k] >> 31)) mx = fmaxf(mx, x);
@@ -182,12 +213,39 @@ __global__ __launch_bounds__(1024) void k_contrast_pair_reg(const float* __restr
         dlse_t += (double)st.dlse;
         dpos = st.dpos * invB;
     }
-    const double loss = block_reduce_sum(loss_t, smd);
-    const float dlse = (float)block_reduce_sum(dlse_t, smd) * invB;
+    double loss = block_reduce_sum(loss_t, smd);
+    const double dlse_s = block_reduce_sum(dlse_t, smd);
+    float dlse = (float)dlse_s * invB;
+    float wB = 0.f;                                        // MASK_SUP: w / B, the factor on a class cell's dpos
+    if constexpr (MASK == MASK_SUP) {
+        int cn = 0;
+        double ct = 0, cd = 0;
+#pragma unroll
+        for (int k = 0; k < CK; ++k)
+            if ((cell >> k) & 1u) {
+                const SlotTerm st = slot_term(v[k], lse);
+                ++cn;
+                ct += (double)st.loss;
+                cd += (double)st.dlse;
+                v[k] = st.dpos;                            // the cell's value has served: the write pass needs only this
+            }
+        cn = block_reduce_count(cn, reinterpret_cast<int*>(smf));
+        if (cn > 0) {                                      // workgroup-uniform
+            const double w = sup_weight(pw, nS, cn);
+            loss += w * block_reduce_sum(ct, smd);
+            dlse = (float)(dlse_s + w * block_reduce_sum(cd, smd)) * invB;
+            wB = (float)w * invB;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < CK; ++k) {
         const int e = threadIdx.x + k * 1024;
-        if (e < total) dsim[off[k] & 0x7fffffffu] = (off[k] >> 31) ? 0.f : dlse * __expf(v[k] - lse);
+        if (e < total) {
+            float d = (off[k] >> 31) ? 0.f : dlse * __expf(v[k] - lse);
+            if constexpr (MASK == MASK_SUP)
+                if ((cell >> k) & 1u) d = wB * v[k];
+            dsim[off[k] & 0x7fffffffu] = d;
+        }
     }
     if (sp.circle) {                                       // the view that is no anchor: zero gradient row
         float* z = dsim + (size_t)(sp.ord(G - 1) * B + n) * J;
@@ -203,14 +261,14 @@ template <int MASK>
 __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__ sim, int G, int B, int Bk, int J,
                                                        const long long* __restrict__ order, int clip_offset,
                                                        float* __restrict__ dsim, double* __restrict__ part,
-                                                       const int* __restrict__ cls) {
+                                                       const int* __restrict__ cls, float pw) {
     __shared__ float smf[4];
     __shared__ double smd[4];
     const int circle = blockIdx.x >= (unsigned)B;
     const PairSpec sp(circle, circle ? blockIdx.x - B : blockIdx.x, G, B, Bk, J, clip_offset, order);
     const int n = sp.n, myclip = sp.myclip, nA = sp.nA, nS = sp.nS;
     int mycls = -1;
-    if constexpr (MASK == MASK_CLASS) mycls = cls[myclip];
+    if constexpr (MASK >= MASK_CLASS) mycls = cls[myclip];
     float mx = MASK == MASK_ZERO ? 0.f : -INFINITY;
     for (int i = 0; i < nA; ++i) {
         const float* row = sim + (size_t)(sp.row_block(i) * B + n) * J;
@@ -238,11 +296,40 @@ __global__ __launch_bounds__(256) void k_contrast_pair(const float* __restrict__
         dlse += st.dlse;
     }
     const float invB = 1.f / (float)B;
+    float wB = 0.f;                                        // MASK_SUP: w / B, the factor on a class cell's dpos
+    if constexpr (MASK == MASK_SUP) {                      // the class cells (see MASK_SUP above): one more strided pass
+        int cn = 0;
+        double ct = 0, cd = 0;
+        if (mycls >= 0)                                    // workgroup-uniform
+            for (int i = 0; i < nA; ++i) {
+                const float* row = sim + (size_t)(sp.row_block(i) * B + n) * J;
+                for (int j = threadIdx.x; j < J; j += 256) {
+                    const int jm = j % Bk;
+                    if (jm == myclip || cls[jm] != mycls) continue;
+                    const SlotTerm st = slot_term(row[j], lse);
+                    ++cn;
+                    ct += (double)st.loss;
+                    cd += (double)st.dlse;
+                }
+            }
+        cn = block_reduce_count(cn, reinterpret_cast<int*>(smf));
+        if (cn > 0) {                                      // workgroup-uniform
+            const double w = sup_weight(pw, nS, cn);
+            loss += w * block_reduce_sum(ct, smd);
+            dlse = (float)((double)dlse + w * block_reduce_sum(cd, smd));
+            wB = (float)w * invB;
+        }
+    }
     dlse *= invB;
     for (int i = 0; i < nA; ++i) {
         const size_t ro = (size_t)(sp.row_block(i) * B + n) * J;
-        for (int j = threadIdx.x; j < J; j += 256)
-            dsim[ro + j] = col_masked<MASK>(j % Bk, myclip, mycls, cls) ? 0.f : dlse * __expf(sim[ro + j] - lse);
+        for (int j = threadIdx.x; j < J; j += 256) {
+            const int jm = j % Bk;
+            float d = col_masked<MASK>(jm, myclip, mycls, cls) ? 0.f : dlse * __expf(sim[ro + j] - lse);
+            if constexpr (MASK == MASK_SUP)
+                if (jm != myclip && mycls >= 0 && cls[jm] == mycls) d = wB * slot_term(sim[ro + j], lse).dpos;
+            dsim[ro + j] = d;
+        }
     }
     if (sp.circle) {
         float* z = dsim + (size_t)(sp.ord(G - 1) * B + n) * J;
@@ -345,12 +432,12 @@ int finish_losses(const void* part, int B, double* losses, float* losses32, hipS
     return facl_launch_status();
 }
 
-// The shapes every pair entry takes.  have_ids: the class ids MASK_CLASS reads were passed; the entries with a mask_mode argument
-// pass none, so mode 2 is no mode of theirs.
+// The shapes every pair entry takes.  have_ids: the class ids MASK_CLASS / MASK_SUP read were passed; the entries with a
+// mask_mode argument pass none, so modes 2 and 3 are no modes of theirs.
 bool pair_shape_ok(int G, int B, int Bk, int J, int clip_offset, int mask_mode, bool have_ids) {
     if (G < 2 || B < 1 || Bk < 1 || J != G * Bk) return false;
     if (clip_offset < 0 || clip_offset + B > Bk) return false;               // the local clips must be columns of the keys
-    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !(mask_mode == MASK_CLASS && have_ids)) return false;
+    if (mask_mode != MASK_ZERO && mask_mode != MASK_EXCLUDE && !((mask_mode == MASK_CLASS || mask_mode == MASK_SUP) && have_ids)) return false;
     return mask_mode == MASK_ZERO || Bk >= 2;                                // one key clip: no negative exists
 }
 
@@ -359,32 +446,36 @@ template <class F>
 void with_mask(int mask_mode, F&& f) {
     if (mask_mode == MASK_ZERO) f(std::integral_constant<int, MASK_ZERO>{});
     else if (mask_mode == MASK_EXCLUDE) f(std::integral_constant<int, MASK_EXCLUDE>{});
-    else f(std::integral_constant<int, MASK_CLASS>{});
+    else if (mask_mode == MASK_CLASS) f(std::integral_constant<int, MASK_CLASS>{});
+    else f(std::integral_constant<int, MASK_SUP>{});
 }
+
+// the weight of MASK_SUP's class cells: finite and > 0
+inline bool pos_weight_ok(float pw) { return pw > 0.f && pw <= 3.402823466e38f; }
 
 // shape checks and launch of the pair kernels: per-clip partial losses [loss_c, loss_circle] into ws, d/dsim into dsim
 int launch_pair(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, float* dsim,
-                void* ws, hipStream_t st, const int32_t* cls = nullptr) {
+                void* ws, hipStream_t st, const int32_t* cls = nullptr, float pw = 0.f) {
     if (!pair_shape_ok(G, B, Bk, J, clip_offset, mask_mode, cls != nullptr)) return FACL_E_SHAPE;
     const bool reg = (long long)(G - 1) * J <= (long long)CK * 1024 && G <= 1024 && (long long)(G + 1) * B * J < 0x7fffffffLL;
     with_mask(mask_mode, [&](auto m) {
         constexpr int MASK = decltype(m)::value;
         if (reg)
             hipLaunchKernelGGL(k_contrast_pair_reg<MASK>, dim3(2 * B), dim3(1024), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                               clip_offset, dsim, (double*)ws, (const int*)cls);
+                               clip_offset, dsim, (double*)ws, (const int*)cls, pw);
         else
             hipLaunchKernelGGL(k_contrast_pair<MASK>, dim3(2 * B), dim3(256), 0, st, sim, G, B, Bk, J, (const long long*)order,
-                               clip_offset, dsim, (double*)ws, (const int*)cls);
+                               clip_offset, dsim, (double*)ws, (const int*)cls, pw);
     });
     return facl_launch_status();
 }
 
-// facl_contrast_pair_sum_mask / _cls behind their NULL checks
+// facl_contrast_pair_sum_mask / _cls / _sup behind their NULL checks
 int pair_sum(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset, int mask_mode, const int32_t* cls,
-             float* dsim, double* losses, float* losses32, void* ws, void* stream) {
+             float* dsim, double* losses, float* losses32, void* ws, void* stream, float pw = 0.f) {
     if (!sim || !order || !dsim || !losses || !losses32 || !ws) return FACL_E_NULL;
     hipStream_t st = (hipStream_t)stream;
-    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, mask_mode, dsim, ws, st, cls);
+    int rc = launch_pair(sim, G, B, Bk, J, order, clip_offset, mask_mode, dsim, ws, st, cls, pw);
     return rc ? rc : finish_losses(ws, B, losses, losses32, st);
 }
 
@@ -467,6 +558,8 @@ extern "C" int facl_scale_rows2(const float* src, float* dst, int64_t R1, int64_
 //   k_contrast_queue_write  every workgroup combines the partials of its clip's block in the same fixed order (the same lse
 //                           bits in all of them, no atomic), evaluates the positives' terms and writes its chunk of dsim /
 //                           dsim_q; the workgroup of (slot 0 | slot G, chunk 0) stores the clip's loss.
+// MASK_SUP runs a third launch between the two, k_contrast_queue_pos (below): a clip's class cells are spread over the chunks and
+// need lse, and the coefficient of the negatives needs their sums over all chunks.
 // The chunk is held in registers inside each kernel (QC / QT values per thread); the same-clip column index advances by
 // increments (one division per thread, see k_contrast_pair_reg).  V = 4: 16-byte loads and stores (J % 4 == L % 4 == 0).
 namespace {
@@ -514,9 +607,11 @@ __device__ __forceinline__ QUnit q_unit(int G, int B, int Bk, int J, int L, cons
 // MASK_CLASS: ids = cls (Bk) for a chunk of sim, looked up through the same-clip column index, or qcls (L) for a chunk of sim_q,
 // read beside the values (V = 4: one 16-byte load, the launcher checks qcls's alignment); a queue column is masked iff the
 // anchor's class is known and equals the column's.  Ids of dead lanes (columns >= valid) are never looked at.
+// MASK_SUP: bit i of `*cell`: value i is a class cell (live, masked for its class and not for being the own clip); its value is
+// kept in x[] although it is no member and has no bit in `grad`.
 template <int MASK, int V>
 __device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__ m, float (&x)[QN], unsigned& mem, unsigned& grad,
-                                       const int* __restrict__ ids = nullptr, int mycls = -1) {
+                                       const int* __restrict__ ids = nullptr, int mycls = -1, unsigned* cell = nullptr) {
     const float* src = m + u.base;
     const int Bk = u.sp.Bk;
     int jm = 0, step = 0;
@@ -536,7 +631,7 @@ __device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__
             } else {
                 v[0] = src[e];
             }
-            if constexpr (MASK == MASK_CLASS) {
+            if constexpr (MASK >= MASK_CLASS) {
                 if (!u.in_sim && mycls >= 0) {             // workgroup-uniform
                     if constexpr (V == 4) {
                         const int4 q = *reinterpret_cast<const int4*>(ids + u.c0 + e);
@@ -551,12 +646,18 @@ __device__ __forceinline__ void q_load(const QUnit& u, const float* __restrict__
         for (int c = 0; c < V; ++c) {
             const bool live = e + c < u.len;
             bool masked = u.in_sim && jm == u.sp.myclip;
-            if constexpr (MASK == MASK_CLASS) {
+            if constexpr (MASK >= MASK_CLASS) {
                 if (u.in_sim) masked = live && col_masked<MASK>(jm, u.sp.myclip, mycls, ids);
                 else masked = mycls >= 0 && id[c] == mycls;
             }
             const bool g = live && !masked;
-            x[k * V + c] = g ? v[c] : 0.f;
+            bool keep = g;
+            if constexpr (MASK == MASK_SUP) {
+                const bool cc = live && masked && !(u.in_sim && jm == u.sp.myclip);
+                *cell |= (unsigned)cc << (k * V + c);
+                keep = g || cc;
+            }
+            x[k * V + c] = keep ? v[c] : 0.f;
             grad |= (unsigned)g << (k * V + c);
             mem |= (unsigned)(MASK == MASK_ZERO ? live : g) << (k * V + c);
             if (u.in_sim && ++jm == Bk) jm = 0;
@@ -570,14 +671,15 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_part(const float* __restr
                                                             int B, int Bk, int J, int L, const long long* __restrict__ order,
                                                             int clip_offset, const int* __restrict__ qstate,
                                                             float* __restrict__ pm, double* __restrict__ ps,
-                                                            const int* __restrict__ cls, const int* __restrict__ qcls) {
+                                                            const int* __restrict__ cls, const int* __restrict__ qcls,
+                                                            int* __restrict__ pc) {
     __shared__ float smf[QT / 64];
     __shared__ double smd[QT / 64];
     const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
     if (u.slot == G - 1) return;                           // no anchor: no member of any log-sum-exp
     float x[QN];
-    unsigned mem, grad;
-    if constexpr (MASK == MASK_CLASS) q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[u.sp.myclip]);
+    unsigned mem, grad, cell = 0u;
+    if constexpr (MASK >= MASK_CLASS) q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[u.sp.myclip], &cell);
     else q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);
     float mx = -INFINITY;                                  // a chunk without a member: (-inf, 0), skipped by the combination
 #pragma unroll
@@ -590,6 +692,60 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_part(const float* __restr
         if ((mem >> i) & 1u) se += (double)__expf(x[i] - mx);
     se = block_reduce_sum(se, smd);
     if (threadIdx.x == 0) { pm[blockIdx.x] = mx; ps[blockIdx.x] = se; }
+    if constexpr (MASK == MASK_SUP) {                      // the chunk's class cells, counted
+        const int cn = block_reduce_count(__popc(cell), reinterpret_cast<int*>(smf));
+        if (threadIdx.x == 0) pc[blockIdx.x] = cn;
+    }
+}
+
+// The log-sum-exp of a clip's block from its nA * nch chunk partials, which start at p0 (circle: slots 0..G-2 are adjacent
+// units): every workgroup of the block combines them in the same fixed order -- the same lse bits in all of them, no atomic.
+__device__ __forceinline__ float q_lse(const float* __restrict__ pm, const double* __restrict__ ps, size_t p0, int np, float* smf,
+                                       double* smd) {
+    float M = -INFINITY;
+    for (int p = threadIdx.x; p < np; p += QT)
+        if (ps[p0 + p] != 0) M = fmaxf(M, pm[p0 + p]);     // != 0, not > 0: a NaN partial (a NaN / inf similarity) is no empty chunk
+    M = block_reduce_max(M, smf);
+    double S = 0;
+    for (int p = threadIdx.x; p < np; p += QT) {
+        const double s = ps[p0 + p];
+        if (s != 0) S += s * exp((double)pm[p0 + p] - (double)M);
+    }
+    S = block_reduce_sum(S, smd);
+    return M + (float)log(S);
+}
+
+// MASK_SUP only, between the two launches above, on the same grid and units: lse as the write kernel forms it, then the chunk's
+// class cells as positive slots against it; per chunk (sum of terms, sum of dlse shares) in fp64 into pt / pd.
+template <int V>
+__global__ __launch_bounds__(QT) void k_contrast_queue_pos(const float* __restrict__ sim, const float* __restrict__ sim_q, int G,
+                                                           int B, int Bk, int J, int L, const long long* __restrict__ order,
+                                                           int clip_offset, const int* __restrict__ qstate,
+                                                           const float* __restrict__ pm, const double* __restrict__ ps,
+                                                           const int* __restrict__ cls, const int* __restrict__ qcls,
+                                                           const int* __restrict__ pc, double* __restrict__ pt,
+                                                           double* __restrict__ pd) {
+    __shared__ float smf[QT / 64];
+    __shared__ double smd[QT / 64];
+    const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
+    const PairSpec& sp = u.sp;
+    if (u.slot == G - 1) return;                           // no anchor
+    if (pc[blockIdx.x] == 0) return;                       // workgroup-uniform; the write kernel reads no sums of such a chunk
+    float x[QN];
+    unsigned mem, grad, cell = 0u;
+    q_load<MASK_SUP, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[sp.myclip], &cell);
+    const float lse = q_lse(pm, ps, ((size_t)sp.n * (G + 1) + (sp.circle ? 0 : G)) * u.nch, sp.nA * u.nch, smf, smd);
+    double ct = 0, cd = 0;
+#pragma unroll
+    for (int i = 0; i < QN; ++i)
+        if ((cell >> i) & 1u) {
+            const SlotTerm st = slot_term(x[i], lse);
+            ct += (double)st.loss;
+            cd += (double)st.dlse;
+        }
+    ct = block_reduce_sum(ct, smd);
+    cd = block_reduce_sum(cd, smd);
+    if (threadIdx.x == 0) { pt[blockIdx.x] = ct; pd[blockIdx.x] = cd; }
 }
 
 template <int MASK, int V>
@@ -599,35 +755,26 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
                                                              const float* __restrict__ pm, const double* __restrict__ ps,
                                                              float* __restrict__ dsim, float* __restrict__ dsim_q,
                                                              double* __restrict__ part, const int* __restrict__ cls,
-                                                             const int* __restrict__ qcls) {
+                                                             const int* __restrict__ qcls, const int* __restrict__ pc,
+                                                             const double* __restrict__ pt, const double* __restrict__ pd,
+                                                             float pw) {
     __shared__ float smf[QT / 64];
     __shared__ double smd[QT / 64];
     const QUnit u = q_unit(G, B, Bk, J, L, order, clip_offset, qstate);
     const PairSpec& sp = u.sp;
     float* dst = (u.in_sim ? dsim : dsim_q) + u.base;
     float x[QN];
-    unsigned mem = 0u, grad = 0u;
-    float lse = 0.f, dlse = 0.f;
+    unsigned mem = 0u, grad = 0u, cell = 0u;
+    float lse = 0.f, dlse = 0.f, wB = 0.f;                 // wB (MASK_SUP): w / B, the factor on a class cell's dpos
     double loss = 0;
     const float invB = 1.f / (float)B;
     if (u.slot != G - 1) {                                 // workgroup-uniform
         // requested ahead of the reductions below
-        if constexpr (MASK == MASK_CLASS) q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[sp.myclip]);
+        if constexpr (MASK >= MASK_CLASS) q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad, u.in_sim ? cls : qcls, cls[sp.myclip], &cell);
         else q_load<MASK, V>(u, u.in_sim ? sim : sim_q, x, mem, grad);
-        // the log-sum-exp of the clip's block from its nA * nch chunk partials (circle: slots 0..G-2 are adjacent units)
         const int np = sp.nA * u.nch;
         const size_t p0 = ((size_t)sp.n * (G + 1) + (sp.circle ? 0 : G)) * u.nch;
-        float M = -INFINITY;
-        for (int p = threadIdx.x; p < np; p += QT)
-            if (ps[p0 + p] != 0) M = fmaxf(M, pm[p0 + p]);     // != 0, not > 0: a NaN partial (a NaN / inf similarity) is no empty chunk
-        M = block_reduce_max(M, smf);
-        double S = 0;
-        for (int p = threadIdx.x; p < np; p += QT) {
-            const double s = ps[p0 + p];
-            if (s != 0) S += s * exp((double)pm[p0 + p] - (double)M);
-        }
-        S = block_reduce_sum(S, smd);
-        lse = M + (float)log(S);
+        lse = q_lse(pm, ps, p0, np, smf, smd);
         double loss_t = 0, dlse_t = 0;
         for (int s = threadIdx.x; s < sp.nS; s += QT) {
             const SlotTerm st = slot_term(sim[sp.pos_index(s)], lse);
@@ -635,7 +782,23 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
             dlse_t += (double)st.dlse;
         }
         loss = block_reduce_sum(loss_t, smd);
-        dlse = (float)block_reduce_sum(dlse_t, smd) * invB;
+        const double dlse_s = block_reduce_sum(dlse_t, smd);
+        dlse = (float)dlse_s * invB;
+        if constexpr (MASK == MASK_SUP) {                  // the block's class cells from their chunk partials, the same fixed order
+            int cn = 0;
+            double ct = 0, cd = 0;
+            for (int p = threadIdx.x; p < np; p += QT) {
+                const int c = pc[p0 + p];
+                if (c > 0) { cn += c; ct += pt[p0 + p]; cd += pd[p0 + p]; }
+            }
+            cn = block_reduce_count(cn, reinterpret_cast<int*>(smf));
+            if (cn > 0) {                                  // workgroup-uniform
+                const double w = sup_weight(pw, sp.nS, cn);
+                loss += w * block_reduce_sum(ct, smd);
+                dlse = (float)(dlse_s + w * block_reduce_sum(cd, smd)) * invB;
+                wB = (float)w * invB;
+            }
+        }
     }
 #pragma unroll
     for (int k = 0; k < QN / V; ++k) {
@@ -643,7 +806,11 @@ __global__ __launch_bounds__(QT) void k_contrast_queue_write(const float* __rest
         if (e < u.wlen) {
             float d[V];
 #pragma unroll
-            for (int c = 0; c < V; ++c) d[c] = ((grad >> (k * V + c)) & 1u) ? dlse * __expf(x[k * V + c] - lse) : 0.f;
+            for (int c = 0; c < V; ++c) {
+                d[c] = ((grad >> (k * V + c)) & 1u) ? dlse * __expf(x[k * V + c] - lse) : 0.f;
+                if constexpr (MASK == MASK_SUP)
+                    if ((cell >> (k * V + c)) & 1u) d[c] = wB * slot_term(x[k * V + c], lse).dpos;
+            }
             if constexpr (V == 4) *reinterpret_cast<float4*>(dst + e) = make_float4(d[0], d[1], d[2], d[3]);
             else dst[e] = d[0];
         }
@@ -686,22 +853,28 @@ __global__ __launch_bounds__(64) void k_queue_advance(int* __restrict__ qstate, 
     }
 }
 
-// cls / qcls: the class ids of MASK_CLASS; the entry with a mask_mode argument passes none, and mode 2 is no mode of its
+// cls / qcls: the class ids of MASK_CLASS / MASK_SUP; the entry with a mask_mode argument passes none, and modes 2 and 3 are no
+// modes of its.  pw: MASK_SUP's weight.
 int pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order, int clip_offset,
                int mask_mode, const int32_t* cls, const int32_t* qcls, const int32_t* qstate, float* dsim, float* dsim_q,
-               double* losses, float* losses32, void* ws, void* stream) {
+               double* losses, float* losses32, void* ws, void* stream, float pw = 0.f) {
     if (!sim || !sim_q || !order || !qstate || !dsim || !dsim_q || !losses || !losses32 || !ws) return FACL_E_NULL;
     // Bk >= 2 outside `zero` here too: the queue may be empty
     if (!pair_shape_ok(G, B, Bk, J, clip_offset, mask_mode, cls && qcls) || L < 1) return FACL_E_SHAPE;
     if (J > 0x7fffffff - QC || L > 0x7fffffff - QC) return FACL_E_SHAPE;      // the kernels round both up to chunks in int
     const long long nch = (J + QC - 1) / QC + (L + QC - 1) / QC, units = (long long)(G + 1) * B * nch;
     if (units > 0x7fffffffLL) return FACL_E_SHAPE;
-    // workspace: [per-clip losses (2B doubles) | chunk sums (units doubles) | chunk maxima (units floats)]
-    if ((size_t)(2 * (long long)B + units) * sizeof(double) + (size_t)units * sizeof(float) >
+    // workspace: [per-clip losses (2B doubles) | chunk sums (units doubles) | chunk maxima (units floats)]; MASK_SUP: the
+    // doubles grow by the chunks' class-cell terms and dlse shares (units each), and the cell counts (units ints) follow the maxima
+    const size_t nd = mask_mode == MASK_SUP ? 3 : 1, ni = mask_mode == MASK_SUP ? 1 : 0;
+    if ((size_t)(2 * (long long)B + nd * units) * sizeof(double) + (size_t)units * (sizeof(float) + ni * sizeof(int)) >
         (size_t)facl_ws_bytes()) return FACL_E_SHAPE;
     double* part = (double*)ws;
     double* ps = part + 2 * (size_t)B;
-    float* pm = (float*)(ps + units);
+    double* pt = ps + units;                               // MASK_SUP only, as pd and pc
+    double* pd = pt + units;
+    float* pm = (float*)(ps + nd * units);
+    int* pc = (int*)(pm + units);
     hipStream_t st = (hipStream_t)stream;
     const bool vec = J % 4 == 0 && L % 4 == 0 && !(((uintptr_t)sim | (uintptr_t)sim_q | (uintptr_t)dsim | (uintptr_t)dsim_q) & 15);
     with_mask(mask_mode, [&](auto m) {
@@ -709,13 +882,17 @@ int pair_queue(const float* sim, const float* sim_q, int G, int B, int Bk, int J
         auto launch = [&](auto v) {
             constexpr int V = decltype(v)::value;
             hipLaunchKernelGGL((k_contrast_queue_part<MASK, V>), dim3((unsigned)units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
-                               (const long long*)order, clip_offset, (const int*)qstate, pm, ps, (const int*)cls, (const int*)qcls);
+                               (const long long*)order, clip_offset, (const int*)qstate, pm, ps, (const int*)cls, (const int*)qcls, pc);
+            if constexpr (MASK == MASK_SUP)
+                hipLaunchKernelGGL((k_contrast_queue_pos<V>), dim3((unsigned)units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
+                                   (const long long*)order, clip_offset, (const int*)qstate, (const float*)pm, (const double*)ps,
+                                   (const int*)cls, (const int*)qcls, (const int*)pc, pt, pd);
             hipLaunchKernelGGL((k_contrast_queue_write<MASK, V>), dim3((unsigned)units), dim3(QT), 0, st, sim, sim_q, G, B, Bk, J, L,
                                (const long long*)order, clip_offset, (const int*)qstate, (const float*)pm, (const double*)ps, dsim,
-                               dsim_q, part, (const int*)cls, (const int*)qcls);
+                               dsim_q, part, (const int*)cls, (const int*)qcls, (const int*)pc, (const double*)pt, (const double*)pd, pw);
         };
-        // MASK_CLASS reads qcls beside the values: 16-byte loads need it aligned too
-        if (vec && (MASK != MASK_CLASS || !((uintptr_t)qcls & 15))) launch(std::integral_constant<int, 4>{});
+        // MASK_CLASS / MASK_SUP read qcls beside the values: 16-byte loads need it aligned too
+        if (vec && (MASK < MASK_CLASS || !((uintptr_t)qcls & 15))) launch(std::integral_constant<int, 4>{});
         else launch(std::integral_constant<int, 1>{});
     });
     int rc = facl_launch_status();
@@ -752,6 +929,25 @@ extern "C" int facl_contrast_pair_queue_cls(const float* sim, const float* sim_q
     if (!cls || !qcls) return FACL_E_NULL;
     return pair_queue(sim, sim_q, G, B, Bk, J, L, order, clip_offset, MASK_CLASS, cls, qcls, qstate, dsim, dsim_q, losses, losses32,
                       ws, stream);
+}
+
+// class-mates as extra positives (MASK_SUP above), weight pos_weight
+extern "C" int facl_contrast_pair_sum_sup(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                                          const int32_t* cls, float pos_weight, float* dsim, double* losses, float* losses32,
+                                          void* ws, void* stream) {
+    if (!cls) return FACL_E_NULL;
+    if (!pos_weight_ok(pos_weight)) return FACL_E_SHAPE;
+    return pair_sum(sim, G, B, Bk, J, order, clip_offset, MASK_SUP, cls, dsim, losses, losses32, ws, stream, pos_weight);
+}
+
+extern "C" int facl_contrast_pair_queue_sup(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L,
+                                            const int64_t* order, int clip_offset, const int32_t* cls, const int32_t* qcls,
+                                            const int32_t* qstate, float pos_weight, float* dsim, float* dsim_q, double* losses,
+                                            float* losses32, void* ws, void* stream) {
+    if (!cls || !qcls) return FACL_E_NULL;
+    if (!pos_weight_ok(pos_weight)) return FACL_E_SHAPE;
+    return pair_queue(sim, sim_q, G, B, Bk, J, L, order, clip_offset, MASK_SUP, cls, qcls, qstate, dsim, dsim_q, losses, losses32,
+                      ws, stream, pos_weight);
 }
 
 extern "C" int facl_queue_push_ids(const int32_t* ids, int P, int32_t* qcls, int L, const int32_t* qstate, void* stream) {

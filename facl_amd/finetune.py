@@ -139,6 +139,8 @@ def check_finetune_flags(opt, world=None):
     if opt.loss_normalize or opt.loss_temperature != 1.0 or opt.loss_mask != 'zero':
         raise RuntimeError("--loss_normalize / --loss_temperature / --loss_mask shape the contrastive loss: fine-tuning has the "
                            "cross-entropy only")
+    if opt.class_positives:
+        raise RuntimeError("--class_positives adds positives to the contrastive loss: fine-tuning has the cross-entropy only")
     if opt.neg_queue:
         raise RuntimeError("--neg_queue holds negatives of the contrastive loss: fine-tuning has the cross-entropy only")
     if opt.key_encoder:

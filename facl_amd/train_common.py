@@ -12,7 +12,7 @@ import torch
 
 from . import cn3d_model_conbag as MODELL
 from . import dist as fdist
-from .utils_my import check_loss_mode, contrastive_losses_stacked, group_points_3DV, is_default_loss_mode, knn_radius_group
+from .utils_my import check_class_positives, check_loss_mode, contrastive_losses_stacked, group_points_3DV, is_default_loss_mode, knn_radius_group
 
 
 def build_parser(default_branch):
@@ -112,6 +112,10 @@ def build_parser(default_branch):
                         'softmax as exp(0) (the reference); exclude = taken out of the log-sum-exp (negatives only); class '
                         '(--synthetic 0, one rank) = exclude, and the keys and queue rows of clips known to share the '
                         'anchor\'s action leave it too; --label_fraction of the train clips are "known"')
+    p.add_argument('--class_positives', type=float, default=0.0,
+                   help='NEW (--loss_mask class): lambda > 0 = the keys and queue rows that the class mask removes for sharing '
+                        'the anchor\'s action are extra positives of the global / circle losses, through their mean term and '
+                        'with weight lambda against the clip\'s own positives; 0 = off')
     p.add_argument('--label_fraction', type=float, default=1.0,
                    help='NEW: 0 < f <= 1, the stratified fraction of the train split whose labels are used (label_subset)')
     p.add_argument('--label_seed', type=int, default=0, help='NEW: seed of the per-class permutations of --label_fraction')
@@ -267,6 +271,8 @@ class ContrastiveStep:
         self.key_encoder = None
         if self.key_momentum is not None and not self.neg_queue:
             raise RuntimeError("the key encoder supplies the rows of the negative queue: it needs neg_queue > 0")
+        # class-mates as extra positives (utils_my: class_positives); beside loss_mode, which stays the dict of the three modes
+        self.class_positives = check_class_positives(getattr(opt, "class_positives", 0.0), self.loss_mode["mask"])
         self.rank = torch.distributed.get_rank() if fdist.is_distributed() else 0
         self.grad_sync = fdist.GradSync(list(netR.named_parameters())) if fdist.is_distributed() else None
 
@@ -383,6 +389,7 @@ class ContrastiveStep:
                                                                    clip_offset=off, with_sum=True, **self.loss_mode,
                                                                    **({} if self.queue is None else {"queue": self.queue}),
                                                                    **({} if self.clip_classes is None else {"classes": self.clip_classes}),
+                                                                   **({} if not self.class_positives else {"class_positives": self.class_positives}),
                                                                    **({} if key_rows is None else {"queue_rows": key_rows}))
         # loss = loss_circle + loss_c (:329; swa, CLD terms are 0 ...): the fp32 sum comes out of the loss launch itself
         if self.swa_if:                                                            # ... unless switched on: :239-263
@@ -801,8 +808,12 @@ def check_loss_flags(opt, world=None):
 
 
 def check_class_mask_flags(opt, world=None):
-    """--loss_mask class: one rank, labelled clips (--synthetic 0) and 0 < --label_fraction <= 1.  Raises before the device is
-    touched (`world` None: the launcher's WORLD_SIZE)."""
+    """--loss_mask class: one rank, labelled clips (--synthetic 0) and 0 < --label_fraction <= 1; --class_positives finite, >= 0
+    and > 0 only with that mask.  Raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
+    try:
+        check_class_positives(getattr(opt, "class_positives", 0.0), opt.loss_mask)
+    except ValueError as e:
+        raise RuntimeError("--class_positives: %s" % e) from None
     if opt.loss_mask != 'class':
         return
     world = fdist.env_world_size() if world is None else world
@@ -1037,6 +1048,8 @@ def run(default_branch, ckpt_pattern, args=None):
         ids = split_class_ids([source.index.label(int(v)) for v in source.split], opt.label_fraction, opt.label_seed)
         class_of = {source.index.v_name(int(v)): int(c) for v, c in zip(source.split, ids)}
         print('class mask: %d of %d train clips labelled, %d classes' % (int((ids >= 0).sum()), len(ids), len(np.unique(ids[ids >= 0]))))
+        if opt.class_positives:
+            print('class positives: weight %g' % opt.class_positives)
 
     def next_batch(disk, epoch, i):
         if opt.synthetic == 0:

@@ -21,15 +21,16 @@ TRAJECTORY_FLAGS = ("batchSize", "num_crop", "SAMPLE_NUM", "INPUT_FEATURE_NUM", 
                     "Num_Class", "swa_if", "cld_if", "loss_normalize", "loss_temperature", "loss_mask", "neg_queue", "key_encoder",
                     "key_momentum", "adamw_decay", "clip_grad_norm", "lr_schedule", "warmup_steps", "lr_decay_epochs", "lr_min",
                     "view_kinds", "jitter_sigma", "jitter_clip", "rot_range", "scale_lo", "scale_hi", "tilt_angle",
-                    "label_fraction", "label_seed")
+                    "label_fraction", "label_seed", "class_positives")
 
 # the optimizer-recipe flags and the view-recipe flags came after the first states were written: a state without them ran with
 # the recipe off / with the reference's ten views at its strengths, which is what these defaults (the parser's) say; so did the
-# labelled fraction of the class-aware loss mask (every label, seed 0: the mask itself did not exist).  Every other flag must
-# be in the file.
+# labelled fraction of the class-aware loss mask (every label, seed 0: the mask itself did not exist) and the weight of
+# class-mates as extra positives (0: off).  Every other flag must be in the file.
 LATER_FLAG_DEFAULTS = {"adamw_decay": 0.0, "clip_grad_norm": 0.0, "lr_schedule": "step", "warmup_steps": 0, "lr_decay_epochs": 0,
                        "lr_min": 0.0, "view_kinds": "reference", "jitter_sigma": 0.01, "jitter_clip": 0.05, "rot_range": 0.8,
-                       "scale_lo": 0.5, "scale_hi": 1.5, "tilt_angle": 0.25, "label_fraction": 1.0, "label_seed": 0}
+                       "scale_lo": 0.5, "scale_hi": 1.5, "tilt_angle": 0.25, "label_fraction": 1.0, "label_seed": 0,
+                       "class_positives": 0.0}
 
 _STATE_NAME = re.compile(r"^state_(\d+)\.pth$")
 

@@ -108,7 +108,23 @@ def group_points(points, opt):
 #                j of anchor clip c is masked iff clip(j) == c or (id[c] >= 0 and id[clip(j)] == id[c]); a queue row with the id
 #                q of the clip that pushed it iff id[c] >= 0 and q == id[c].  Positives stay the clip's own views.  A clip may
 #                be left without a negative: its log-sum-exp is -inf, its terms and gradients are exactly 0
+#   class_positives  (mask 'class' only) lambda > 0: the cells that mask 'class' removes for a reason other than "own clip" -- key
+#                columns of OTHER clips with the anchor's known class, queue rows with it: the clip's class cells C -- are
+#                positive slots against the same log-sum-exp as well, through their mean term:
+#                loss_n = sum_s term(pos_s) + (lambda nS / |C|) sum_{c in C} term(sim_c), term(p) = logaddexp(p, lse) - p, nS the
+#                clip's own slots (G resp. G-1); nothing is added when |C| = 0, and |C| is a count (not differentiated).  0 = off
 MASK_MODES = {"zero": 0, "exclude": 1, "class": 2}
+
+
+def check_class_positives(class_positives, mask):
+    """The weight of the class cells as a float: finite and >= 0, and > 0 only with mask 'class'; ValueError otherwise."""
+    w = float(class_positives)
+    if not (w >= 0.0 and w < float("inf")):
+        raise ValueError("class_positives must be finite and >= 0 (got %r)" % (class_positives,))
+    if w > 0.0 and mask != "class":
+        raise ValueError("class_positives adds the keys that mask 'class' removes as positives: it needs mask 'class' "
+                         "(got mask %r)" % (mask,))
+    return w
 
 
 def loss_scale(temperature):
@@ -211,12 +227,37 @@ def _pair_terms(pos, lse):
     return torch.where(empty, zero, t).mean(dim=1).sum()
 
 
+def _class_cell_terms(anchors, keys, anchor_clip, key_clip, kc, queue, qc, nA, lse, nS, weight):
+    """The class cells' share of a loss: sum over the B clips of (weight nS / |C_n|) sum_{c in C_n} term(v_c, lse_n), divided by
+    B.  ``anchors``: nA * B rows, row i * B + n an anchor row of local clip n.  A clip with lse = -inf contributes exactly 0 and
+    no gradient (treated explicitly, as in _pair_terms); so does a clip without a class cell.  None when no clip has one."""
+    B = anchors.shape[0] // nA
+    kc = kc.to(anchors.device)
+    a_cls = kc[anchor_clip]
+    vals = anchors @ keys.t()
+    cell = (a_cls[:, None] >= 0) & (a_cls[:, None] == kc[key_clip][None, :]) & (anchor_clip[:, None] != key_clip[None, :])
+    if queue is not None and queue.shape[0]:
+        vals = torch.cat((vals, anchors @ queue.to(device=anchors.device, dtype=anchors.dtype).t()), dim=1)
+        cell = torch.cat((cell, (a_cls[:, None] >= 0) & (a_cls[:, None] == qc.to(anchors.device)[None, :])), dim=1)
+    vals = vals.view(nA, B, -1).permute(1, 0, 2).reshape(B, -1)
+    cell = cell.view(nA, B, -1).permute(1, 0, 2).reshape(B, -1)
+    count = cell.sum(dim=1)
+    if not bool(count.any()):
+        return None
+    use = cell & (lse != float("-inf"))[:, None]
+    zero = torch.zeros((), dtype=vals.dtype, device=vals.device)
+    v, l = torch.where(use, vals, zero), torch.where(use, lse[:, None].expand_as(vals), zero)
+    terms = torch.where(use, torch.logaddexp(v, l) - v, zero).sum(dim=1)
+    w = weight * nS / count.clamp_min(1).to(vals.dtype)
+    return (torch.where(count > 0, w * terms, zero)).sum() / B
+
+
 def _clip_ids(G, B, device, offset=0):
     return (torch.arange(B, device=device) + offset).repeat(G)     # row g*B+b -> clip id b
 
 
 def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, clip_offset=0, normalize=False, temperature=1.0,
-                    mask='zero', queue=None, key_classes=None, queue_classes=None):
+                    mask='zero', queue=None, key_classes=None, queue_classes=None, class_positives=0.0):
     """utils_my.py:53-83.  loss_c = sum_g CE([<xg_n, x_{gB+n}> | (xg @ x^T)*mask], 0), CE = mean over B.
     The (G,B,1+GB) logits tensor and its ``repeat`` are never built: every g shares the negatives, so
     CE_g[n] = logaddexp(pos[g,n], LSE_n) - pos[g,n].
@@ -231,8 +272,11 @@ def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, cli
     clip.  They carry no clip identity (masks 'zero' and 'exclude' do not touch them) and are used as stored.
 
     ``key_classes`` (Bk,) / ``queue_classes`` (Q,): the class ids of mask 'class' (see the loss modes above), integer tensors;
-    required with that mask (the queue's whenever the queue has rows), refused with any other."""
+    required with that mask (the queue's whenever the queue has rows), refused with any other.
+
+    ``class_positives``: the weight of the class cells as extra positives (the loss modes above); mask 'class' only."""
     B, G = x_global.shape[0], num_crop
+    cp = check_class_positives(class_positives, mask)
     check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     x_global, x = _loss_rows_torch(x_global, normalize, temperature), _loss_rows_torch(x, normalize, temperature)
     keys = x if x_keys is None else _loss_rows_torch(x_keys, normalize, temperature)
@@ -246,16 +290,19 @@ def global_contrast(num_crop, x_global, x, opt, criterion=None, x_keys=None, cli
     lse = _lse_rows(neg, mask)
     pos = (x_global.unsqueeze(0) * x.view(G, B, -1)).sum(-1)                   # (G,B)
     if mask == "class":
-        return _pair_terms(pos, lse)
+        extra = None if not cp else _class_cell_terms(x_global, keys, a_clip, _clip_ids(G, Bk, x.device), kc, queue, qc, 1, lse, G, cp)
+        return _pair_terms(pos, lse) if extra is None else _pair_terms(pos, lse) + extra
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
 
 def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=None, clip_offset=0, normalize=False,
-                    temperature=1.0, mask='zero', queue=None, key_classes=None, queue_classes=None):
+                    temperature=1.0, mask='zero', queue=None, key_classes=None, queue_classes=None, class_positives=0.0):
     """utils_my.py:85-116.  ``order`` replaces the reference's np.random.shuffle(arange(num_crop)) (:96-97);
     when omitted it is drawn from NumPy's global RNG like the reference.  Loss modes, ``queue`` and the class ids: as in
-    global_contrast (the shared negative set of a clip becomes the (G-1) x (J + Q) block)."""
+    global_contrast (the shared negative set of a clip becomes the (G-1) x (J + Q) block); ``class_positives``: the class cells
+    of that block, against nS = G-1 own slots."""
     G, B = num_crop, batchSize
+    cp = check_class_positives(class_positives, mask)
     check_loss_mode(temperature, mask, (x if x_keys is None else x_keys).shape[0] // G)
     if order is None:
         order = np.arange(0, G, 1)
@@ -276,7 +323,9 @@ def circle_contrast(num_crop, x, batchSize, criterion=None, order=None, x_keys=N
         neg = torch.cat((neg, neg_q.view(G - 1, B, -1).permute(1, 0, 2).reshape(B, -1)), dim=1)
     lse = _lse_rows(neg, mask)
     if mask == "class":
-        return _pair_terms(pos, lse)
+        extra = None if not cp else _class_cell_terms(anchors.reshape((G - 1) * B, -1), keys, a_clip, _clip_ids(G, Bk, x.device), kc,
+                                                      queue, qc, G - 1, lse, G - 1, cp)
+        return _pair_terms(pos, lse) if extra is None else _pair_terms(pos, lse) + extra
     return (torch.logaddexp(pos, lse.unsqueeze(0)) - pos).mean(dim=1).sum()
 
 
@@ -293,10 +342,11 @@ class _ContrastivePair(torch.autograd.Function):
     dsim_q @ queue to d stacked.  The queue itself gets no gradient and is not written here.
 
     ``classes`` (mask mode 2, `class`): the int32 class ids of the Bk key clips on the device; the launches are
-    facl_contrast_pair_sum_cls resp. facl_contrast_pair_queue_cls with the queue's own ``ids``."""
+    facl_contrast_pair_sum_cls resp. facl_contrast_pair_queue_cls with the queue's own ``ids``; with ``class_positives`` > 0
+    facl_contrast_pair_sum_sup resp. facl_contrast_pair_queue_sup."""
 
     @staticmethod
-    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0, queue=None, classes=None):
+    def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0, queue=None, classes=None, class_positives=0.0):
         from . import tail as _tail
         from .sa_mlp import _Workspace
         lib = _lib.load_library()
@@ -327,7 +377,14 @@ class _ContrastivePair(torch.autograd.Function):
                                  % (Bk, dev, classes.dtype, tuple(classes.shape), classes.device))
             if queue is not None and getattr(queue, "ids", None) is None:
                 raise ValueError("mask 'class' needs a queue that keeps the class ids of its rows: NegativeQueue(..., with_ids=True)")
-        if queue is None and classes is not None:
+        if class_positives and classes is None:
+            raise ValueError("class_positives needs mask 'class' and the class ids of the key clips")
+        if queue is None and class_positives:
+            _lib.check(lib.facl_contrast_pair_sum_sup(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, _lib.ptr(classes),
+                                                      float(class_positives), _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32),
+                                                      _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_sum_sup")
+            ctx.save_for_backward(stacked, keys, dsim)
+        elif queue is None and classes is not None:
             _lib.check(lib.facl_contrast_pair_sum_cls(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, _lib.ptr(classes),
                                                       _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
                        "facl_contrast_pair_sum_cls")
@@ -345,7 +402,12 @@ class _ContrastivePair(torch.autograd.Function):
             ctx.mfma_q = (L % 4 == 0 and C % 4 == 0)
             sim_q = _tail.gemm_fwd(stacked, queue.buf, None, prec=ctx.prec)[0] if ctx.mfma_q else stacked @ queue.buf.t()
             dsim_q = _lib.empty_like(sim_q)
-            if classes is not None:
+            if class_positives:
+                _lib.check(lib.facl_contrast_pair_queue_sup(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order),
+                                                            clip_offset, _lib.ptr(classes), _lib.ptr(queue.ids), _lib.ptr(queue.state),
+                                                            float(class_positives), _lib.ptr(dsim), _lib.ptr(dsim_q), _lib.ptr(out),
+                                                            _lib.ptr(out32), _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_queue_sup")
+            elif classes is not None:
                 _lib.check(lib.facl_contrast_pair_queue_cls(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order),
                                                             clip_offset, _lib.ptr(classes), _lib.ptr(queue.ids), _lib.ptr(queue.state),
                                                             _lib.ptr(dsim), _lib.ptr(dsim_q), _lib.ptr(out), _lib.ptr(out32),
@@ -374,7 +436,7 @@ class _ContrastivePair(torch.autograd.Function):
             return g if g_s is None else g + g_s.float()
         g_c, g_o = tot(g_c), tot(g_o)
         if g_c is None and g_o is None:
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         zero = None
         if g_c is None or g_o is None:
             zero = torch.zeros((), dtype=torch.float32, device=dsim.device)
@@ -401,14 +463,14 @@ class _ContrastivePair(torch.autograd.Function):
                 rc = lib.facl_gemm_wgrad_acc(_lib.ptr(ds), _lib.ptr(stacked), M_, N_, K_, stacked.stride(0), _lib.ptr(d_stacked), pc,
                                              _lib.stream())
             if rc == 0:
-                return d_stacked, None, None, None, None, None, None, None
+                return d_stacked, None, None, None, None, None, None, None, None
             if rc != -4:
                 _lib.check(rc, "facl_gemm_wgrad_acc")
         d_keys = _tail.gemm_wgrad(ds, stacked, prec=bp) if ctx.mfma else ds.t() @ stacked
         if ctx.own_keys:
             d_stacked[:ctx.GB] += d_keys
             d_keys = None
-        return d_stacked, d_keys, None, None, None, None, None, None
+        return d_stacked, d_keys, None, None, None, None, None, None, None
 
 
 class _LossRows(torch.autograd.Function):
@@ -459,7 +521,7 @@ def _check_order(order, G):
 
 
 def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offset=0, with_sum=False, normalize=False,
-                               temperature=1.0, mask='zero', queue=None, queue_rows=None, classes=None):
+                               temperature=1.0, mask='zero', queue=None, queue_rows=None, classes=None, class_positives=0.0):
     """(loss_c, loss_circle) from the model's stacked output [x ; x_global] (facl_amd.cn3d_model_conbag: ``_stacked``);
     with_sum: also `loss_circle + loss_c` (fp32, cn3d_train_motion_GL.py:329) as a third output of the same launch.
 
@@ -477,7 +539,11 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
 
     ``classes``: mask 'class' only, and required there -- the int32 device tensor of the Bk key clips' class ids (< 0: unknown).
     With a queue (created ``with_ids``) the ids of this rank's clips, classes[clip_offset : clip_offset + B], are staged beside
-    the rows.  The tensor is read by the launches, not copied: a captured step sees what it holds at replay."""
+    the rows.  The tensor is read by the launches, not copied: a captured step sees what it holds at replay.
+
+    ``class_positives``: lambda > 0 (mask 'class' only) makes the class cells extra positives of weight lambda (the loss modes,
+    see global_contrast): the launch is facl_contrast_pair_sum_sup / _queue_sup.  0: today's launches."""
+    cp = check_class_positives(class_positives, mask)
     if (mask == "class") != (classes is not None):
         raise ValueError("mask 'class' needs classes=, the class ids of the key clips, and no other mask takes them "
                          "(got mask %r %s classes)" % (mask, "without" if classes is None else "with"))
@@ -510,12 +576,12 @@ def contrastive_losses_stacked(num_crop, stacked, order, x_keys=None, clip_offse
         _check_order(order, G)
         order = torch.as_tensor(order, device=stacked.device, dtype=torch.long)
     if queue is None:
-        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, None, classes)
+        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, None, classes, cp)
     else:
         rows = stacked.detach()[GB:] if queue_rows is None else queue_rows
         if classes is None:
             queue.stage(rows)
         else:
             queue.stage(rows, ids=classes[clip_offset:clip_offset + rows.shape[0]])
-        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, queue, classes)
+        out = _ContrastivePair.apply(stacked, x_keys, order.contiguous(), G, clip_offset, mask_mode, queue, classes, cp)
     return out if with_sum else out[:2]

@@ -524,6 +524,29 @@ int facl_contrast_pair_sum_cls(const float* sim, int G, int B, int Bk, int J, co
 int facl_contrast_pair_queue_cls(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order,
                                  int clip_offset, const int32_t* cls, const int32_t* qcls, const int32_t* qstate, float* dsim,
                                  float* dsim_q, double* losses, float* losses32, void* ws, void* stream);
+/* Class-mates as extra positives: facl_contrast_pair_sum_cls, and the cells it masks for a reason other than "own clip" -- the
+ * clip's class cells C: (r, j) with r an anchor row of the clip, j % Bk != myclip, cls[myclip] >= 0 and cls[j % Bk] ==
+ * cls[myclip] -- are positive slots against the same lse as well.  With term(p) = logaddexp(p, lse) - p and nS the clip's own
+ * slots (G global, G-1 circle):  loss_n = sum_s term(pos_s) + w sum_{c in C} term(sim_c),  w = pos_weight * nS / |C| (nothing
+ * added when |C| = 0).  dsim of a class cell is w * dterm/dp / B; the cells' dlse shares, times w, join the own slots' in the
+ * coefficient of the negatives; |C| is not differentiated.  Own-clip columns that are no positive keep exactly 0.  Without a
+ * class cell anywhere (every id < 0, or all distinct) all outputs equal mode 1's bit for bit; a clip without a negative has
+ * exact zeros, class cells included.  A NULL cls: FACL_E_NULL; the shapes of facl_contrast_pair_sum_cls and a pos_weight that
+ * is finite and > 0, else FACL_E_SHAPE; every refusal before any launch. */
+int facl_contrast_pair_sum_sup(const float* sim, int G, int B, int Bk, int J, const int64_t* order, int clip_offset,
+                               const int32_t* cls, float pos_weight, float* dsim, double* losses, float* losses32, void* ws,
+                               void* stream);
+/* The same on facl_contrast_pair_queue_cls: column k < valid of sim_q with cls[myclip] >= 0 && qcls[k] == cls[myclip] is a class
+ * cell too (dsim_q = w * dterm/dp / B there; queue rows carry no gradient, so it moves the anchor only); columns >= valid are
+ * ignored whatever qcls holds.  Three launches on one grid (chunk partials and cell counts; the cells' terms against lse; the
+ * write), combined in a fixed order: same bits every run, no atomics.  With an empty queue the register-kernel shapes give
+ * facl_contrast_pair_sum_sup's bits; with every id < 0 the outputs are facl_contrast_pair_queue(mode 1)'s.  Domain of
+ * facl_contrast_pair_queue_cls, with 32 bytes per chunk partial instead of 12 in the workspace check; pos_weight finite and
+ * > 0, else FACL_E_SHAPE. */
+int facl_contrast_pair_queue_sup(const float* sim, const float* sim_q, int G, int B, int Bk, int J, int L, const int64_t* order,
+                                 int clip_offset, const int32_t* cls, const int32_t* qcls, const int32_t* qstate,
+                                 float pos_weight, float* dsim, float* dsim_q, double* losses, float* losses32, void* ws,
+                                 void* stream);
 /* Writes ids (P int32) into the slots [head, head + P) of qcls (L int32), head clamped as in facl_queue_push.  The state is
  * only read: the caller launches this BEFORE facl_queue_push in stream order, so that both see the same head.  L % P == 0, else
  * FACL_E_SHAPE (checked first); a NULL pointer: FACL_E_NULL. */

@@ -1,9 +1,8 @@
 // The philox views of clips that are RESIDENT in device memory (--resident 1): the whole training split is loaded once
 // into a pool, and a batch is B table positions.  No file is read, nothing is packed and no clip data crosses to the
-// device per step.  The views equal csrc/views_philox.hip's bit for bit: the draw recipe and the per-point arithmetic are
-// the same code (views_philox_point.inc); only the way a drawn position becomes a source row differs.  G views of P
-// points per clip, by the recipe in the header of views_philox.hip (default: kind v % 10, round v / 10, slots + 32 * round;
-// any other list of kinds and strengths through the same ViewRecipe, passed by value).
+// device per step.  The views equal csrc/views_philox.hip's bit for bit: the draws, the per-point arithmetic and the kernel
+// body are the same code (views_point.inc, where the recipe is written out); only the way a drawn position becomes a source
+// row differs (FromPool), and source rows are int64.
 //
 // Pool (device memory owned by facl_amd/resident.py):
 //   src    (rows_total, 8) in the dataset's one dtype: the clips back to back, each as its four clouds in pack_clips' order
@@ -22,7 +21,7 @@
 
 namespace {
 
-#include "views_philox_point.inc"
+#include "views_point.inc"
 
 constexpr int REC = FACL_RESIDENT_REC, RC = 8;      // int64 words per table record; channels per pool row
 
@@ -51,8 +50,30 @@ __global__ __launch_bounds__(TR_THREADS) void k_resident_temporal_rows(const S* 
     }
 }
 
-// workgroup = one (clip of the batch, view, chunk of up to 512 points); thread = one point.  idx_out (B, G, P) int64,
-// optional: the pool row of every point.  REF: the default recipe folded into the code (views_philox_point.inc).
+// how a drawn position becomes a row of the pool (build_view's `from`): through the table record of the selected clip
+struct FromPool {
+    const int64_t* table;
+    const int32_t *lists, *sel;
+    int n_clips;
+    int32_t* err;
+    const int64_t* m;                                              // the clip's table record, set by clip()
+    __device__ bool clip(int b, bool first) {
+        const int pos = sel[b];
+        if (pos < 0 || pos >= n_clips) {                           // not a clip of the pool: no pool memory is touched
+            if (first) atomicOr(err, 2);
+            return false;
+        }
+        m = table + (int64_t)pos * REC;
+        return true;
+    }
+    __device__ uint32_t cid() const { return (uint32_t)m[8]; }
+    __device__ int temporal_count(int t) const { return (int)m[10 + t]; }      // 0: the ingest raised err for this clip
+    __device__ int64_t temporal_row(int t, int k) const { return m[0] + lists[2 * m[9] + t * m[4] + k]; }
+    __device__ int64_t cloud_row(int s, uint32_t word) const { return m[s] + draw_row(word, (int)m[4 + s]); }
+    __device__ int64_t channels() const { return RC; }
+};
+
+// build_view on the pool.  idx_out (B, G, P) int64, optional: the pool row of every point.
 template <typename S, bool REF>
 __global__ __launch_bounds__(CHUNK) void k_build_views_resident(const S* __restrict__ src, const int64_t* __restrict__ table,
                                                                 const int32_t* __restrict__ lists, int n_clips,
@@ -60,39 +81,7 @@ __global__ __launch_bounds__(CHUNK) void k_build_views_resident(const S* __restr
                                                                 int chunks, int64_t seed, int epoch, float* __restrict__ out,
                                                                 int64_t* __restrict__ idx_out, int32_t* __restrict__ err,
                                                                 const ViewRecipe rc) {
-    const ViewAt at = REF ? view_at_reference(G, chunks) : view_at(rc, G, chunks);
-    const int b = at.b, n = at.n;
-    if (n >= P) return;                                            // the ragged last chunk of a view
-    float* dst = out + (((size_t)at.v * B + b) * P + n) * 4;
-    int64_t* io = idx_out ? idx_out + ((size_t)b * G + at.v) * P + n : nullptr;
-    const int pos = sel[b];
-    if (pos < 0 || pos >= n_clips) {                               // not a clip of the pool: no pool memory is touched
-        if (n == 0 && at.v == 0) atomicOr(err, 2);
-        view_void(dst);
-        if (io) *io = -1;
-        return;
-    }
-    const ViewPos d = REF ? ViewPos{} : rc.pos[at.k];
-    const int64_t* m = table + (int64_t)pos * REC;
-    const ViewDraw q = view_draw(seed, (uint32_t)m[8], epoch);
-    const int src_of = REF ? view_source_reference(at.k) : (int)d.src;
-    const uint32_t word = REF ? view_row_word_reference(q, at.k, at.slot0, n) : view_row_word(q, d, at.slot0, n);
-    int64_t row;
-    if (src_of >= SRC_T4) {
-        const int t = src_of - SRC_T4;
-        const int cnt = (int)m[10 + t];
-        if (cnt == 0) {                                            // the ingest raised err for this clip: void views
-            view_void(dst);
-            if (io) *io = -1;
-            return;
-        }
-        row = m[0] + lists[2 * m[9] + t * m[4] + draw_row(word, cnt)];
-    } else {
-        row = m[src_of] + draw_row(word, (int)m[4 + src_of]);
-    }
-    if (io) *io = row;
-    if (REF) view_point_reference<S>(src + row * RC, q, at.k, at.slot0, n, dst);
-    else view_point<S>(src + row * RC, q, rc, d, at.slot0, n, dst);
+    build_view<S, REF>(src, FromPool{table, lists, sel, n_clips, err, nullptr}, B, G, P, chunks, seed, epoch, out, idx_out, rc);
 }
 
 }  // namespace
@@ -111,26 +100,12 @@ template <typename S>
 static int launch_views_resident(const S* src, const int64_t* table, const int32_t* lists, int n_clips, const int32_t* sel,
                                  int B, int G, int P, int64_t seed, int epoch, float* out, int64_t* idx_out, int32_t* err,
                                  const ViewRecipe& rc, void* stream) {
-    if (!src || !table || !lists || !sel || !out || !err) return FACL_E_NULL;
-    if (n_clips < 1 || B < 1 || B > (1 << 20) || !views_gp_ok(G, P)) return FACL_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(out) % 16) return FACL_E_ALIGN;
-    const ViewGrid g = view_grid(P);
-    const auto kernel = view_recipe_is_default(rc) ? k_build_views_resident<S, true> : k_build_views_resident<S, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B * G * g.chunks), dim3(g.threads), 0, (hipStream_t)stream, src, table, lists,
-                       n_clips, sel, B, G, P, g.chunks, seed, epoch, out, idx_out, err, rc);
-    return facl_launch_status();
-}
-
-// the recipe entries: the caller's HOST arrays are checked and turned into the recipe first (no launch on a refusal)
-template <typename S>
-static int launch_views_resident_recipe(const S* src, const int64_t* table, const int32_t* lists, int n_clips,
-                                        const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
-                                        int64_t* idx_out, int32_t* err, const int32_t* kinds, int n_kinds,
-                                        const double* strengths, void* stream) {
-    ViewRecipe rc;
-    const int e = view_recipe_make(kinds, n_kinds, strengths, &rc);
-    if (e != 0) return e;
-    return launch_views_resident<S>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, rc, stream);
+    const int own = (!src || !table || !lists || !sel || !out || !err) ? FACL_E_NULL : n_clips < 1 ? FACL_E_SHAPE : 0;
+    return view_launch(own, k_build_views_resident<S, true>, k_build_views_resident<S, false>, B, G, P, out, rc,
+                       [&](auto kernel, dim3 grid, dim3 threads, int chunks) {
+                           hipLaunchKernelGGL(kernel, grid, threads, 0, (hipStream_t)stream, src, table, lists, n_clips, sel,
+                                              B, G, P, chunks, seed, epoch, out, idx_out, err, rc);
+                       });
 }
 
 extern "C" int facl_resident_temporal_rows_f32(const float* src, int64_t* table, int32_t* lists, int first, int count,
@@ -175,14 +150,16 @@ extern "C" int facl_build_views_resident_recipe_f32(const float* src, const int6
                                                     const int32_t* sel, int B, int G, int P, int64_t seed, int epoch,
                                                     float* out, int64_t* idx_out, int32_t* err, const int32_t* kinds,
                                                     int n_kinds, const double* strengths, void* stream) {
-    return launch_views_resident_recipe<float>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, kinds,
-                                               n_kinds, strengths, stream);
+    return with_view_recipe(kinds, n_kinds, strengths, [&](const ViewRecipe& rc) {
+        return launch_views_resident<float>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, rc, stream);
+    });
 }
 
 extern "C" int facl_build_views_resident_recipe_f64(const double* src, const int64_t* table, const int32_t* lists, int n_clips,
                                                     const int32_t* sel, int B, int G, int P, int64_t seed, int epoch,
                                                     float* out, int64_t* idx_out, int32_t* err, const int32_t* kinds,
                                                     int n_kinds, const double* strengths, void* stream) {
-    return launch_views_resident_recipe<double>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err,
-                                                kinds, n_kinds, strengths, stream);
+    return with_view_recipe(kinds, n_kinds, strengths, [&](const ViewRecipe& rc) {
+        return launch_views_resident<double>(src, table, lists, n_clips, sel, B, G, P, seed, epoch, out, idx_out, err, rc, stream);
+    });
 }

@@ -4,7 +4,7 @@ The philox views of a clip depend on (seed, epoch, dataset index) and on nothing
 in the HBM of one device, so the per-batch host work of `dataset.DiskBatches` (np.load of 4 B files, packing, pinning, the
 copy) happens ONCE, at the ingest.  After it a training step needs from the host only B table positions: one (B,) int32
 copy and one launch (csrc/views_resident.hip).  The views are `DiskBatches(..., 'philox', ...)`'s bit for bit: both
-kernels run one shared implementation of the draws and the arithmetic (csrc/views_philox_point.inc).
+kernels run one shared implementation of the draws and the arithmetic (csrc/views_point.inc).
 
 Pool layout (include/facl_hip.h): `src` (rows_total, 8), `table` (n_clips, 12) int64, `lists` (2 * point-cloud rows,)
 int32, `err` (2,) int32.  The header pass and the table builder below are pure NumPy (tests/test_resident_cpu.py).
@@ -268,20 +268,15 @@ def build_views_resident(res, sel, seed, epoch, return_idx=False, num_crop=V.NUM
     from . import _lib
     V.check_view_size(num_crop, num_point)
     G, P = int(num_crop), int(num_point)
-    lib = _lib.load_library()
     B = sel.shape[0]
     if sel.dtype != torch.int32 or sel.dim() != 1 or not sel.is_contiguous():
         raise TypeError("sel must be a contiguous (B,) int32 tensor")
     _lib.require_cuda(sel, res.src)
     out = _lib.empty((G * B, P, 4), dtype=torch.float32, device=res.dev)
     idx = _lib.empty((B, G, P), dtype=torch.int64, device=res.dev) if return_idx else None
-    name = "facl_build_views_resident_%s_%s" % ("gp" if recipe is None else "recipe", "f64" if res.dtype == np.float64 else "f32")
-    keep, extra = ((), ()) if recipe is None else V.recipe_args(recipe)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.check(getattr(lib, name)(_lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B, G, P,
-                                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), _lib.ptr(out), _lib.ptr(idx),
-                                  _lib.ptr(res.err), *extra, _lib.stream()), name)
-    del keep
+    V._call_view_entry("resident", res.dtype == np.float64, recipe, seed, lambda sd: (
+        _lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B, G, P, sd, int(epoch), _lib.ptr(out),
+        _lib.ptr(idx), _lib.ptr(res.err)))
     return (out, idx) if return_idx else out
 
 

@@ -207,6 +207,19 @@ def recipe_args(recipe):
     return (kinds, strengths), (kinds.ctypes.data, int(kinds.shape[0]), strengths.ctypes.data)
 
 
+def _call_view_entry(stem, f64, recipe, seed, args):
+    """What the philox entries' callers share (build_views_philox, resident.build_views_resident): calls
+    facl_build_views_<stem>_{gp | recipe}_{f32 | f64} on the current stream.  `args(seed)` gives the entry's arguments up to the
+    recipe's, with the seed as the signed 64-bit integer the C ABI takes; the recipe's host arrays follow and stay alive over
+    the call."""
+    name = "facl_build_views_%s_%s_%s" % (stem, "gp" if recipe is None else "recipe", "f64" if f64 else "f32")
+    keep, extra = ((), ()) if recipe is None else recipe_args(recipe)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    _lib.check(getattr(_lib.load_library(), name)(*args(seed - (1 << 64) if seed >= 1 << 63 else seed), *extra, _lib.stream()),
+               name)
+    del keep
+
+
 def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NUM_CROP, num_point=NUM_POINT, recipe=None):
     """Device half of the philox mode: src (rows, 8) and meta (B, 9) int32 on the device (pack_clips' layout, temporal
     rows already checked).  Two launches on the current stream: the temporal-row compaction, then the views.
@@ -227,13 +240,9 @@ def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NU
     rt = lib.facl_views_temporal_rows_f64 if f64 else lib.facl_views_temporal_rows_f32
     _lib.check(rt(_lib.ptr(src), rows, 8, _lib.ptr(meta), B, _lib.ptr(lists), _lib.ptr(counts), _lib.ptr(err),
                   _lib.stream()), "facl_views_temporal_rows")
-    name = "facl_build_views_philox_%s_%s" % ("gp" if recipe is None else "recipe", "f64" if f64 else "f32")
-    keep, extra = ((), ()) if recipe is None else recipe_args(recipe)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.check(getattr(lib, name)(_lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts),
-                                  seed - (1 << 64) if seed >= 1 << 63 else seed, int(epoch), B, G, P, _lib.ptr(out),
-                                  _lib.ptr(idx), *extra, _lib.stream()), name)
-    del keep
+    _call_view_entry("philox", f64, recipe, seed, lambda sd: (
+        _lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts), sd, int(epoch), B, G, P, _lib.ptr(out),
+        _lib.ptr(idx)))
     return (out, idx, err) if return_idx else out
 
 

@@ -729,7 +729,7 @@ int facl_build_views_resident_gp_f64(const double* src, const int64_t* table, co
                                      const int32_t* sel, int B, int G, int P, int64_t seed, int epoch, float* out,
                                      int64_t* idx_out, int32_t* err, void* stream);
 
-/* ---- the philox views by a RECIPE: which kinds a round holds and how strongly they are augmented (csrc/views_philox_point.inc;
+/* ---- the philox views by a RECIPE: which kinds a round holds and how strongly they are augmented (csrc/views_point.inc;
  * restated by facl_amd/philox.py's Recipe).  A recipe is a list of 1..FACL_VIEW_POS_MAX kind codes, the positions of a round,
  * and FACL_VIEW_NSTRENGTH strengths.  View v is of the kind at position v % n_kinds in round v / n_kinds.
  *   kinds      RAW, MIRROR, KEY, KEY_MIRROR, ROT, T4, T7, RES30, RES10: the reference's views (the default list is RAW, MIRROR,

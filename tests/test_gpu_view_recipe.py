@@ -1,4 +1,4 @@
-"""The view recipe on the device (csrc/views_philox_point.inc through csrc/views_philox.hip and csrc/views_resident.hip; the
+"""The view recipe on the device (csrc/views_point.inc through csrc/views_philox.hip and csrc/views_resident.hip; the
 rule and the arithmetic are restated by facl_amd/philox.py): the default recipe is the _gp entries' output bit for bit, every
 kind equals the NumPy restatement, the new kinds have the properties their definitions promise without leaning on it, a clip's
 views stay local to (seed, epoch, clip id), every refusal comes without a launch, a temporal kind is void at any position,
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from helpers import synth_clip
-from test_gpu_views_sizes import _Packed, _index, _signed, _train_args, _tree
+from view_helpers import _Packed, _Pool, _call, _clips, _host, _index, _train_args, _tree
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,72 +25,9 @@ B_STRENGTHS = dict(jitter_sigma=0.02, jitter_clip=0.03, rot_range=2.0, scale_lo=
 C = "res10,t4,key,raw,res30"
 
 
-def _clips(dt):
-    return [synth_clip(1, dt), synth_clip(2, dt, 777, 513, 400, 64), synth_clip(3, dt, 2048, 1024, 600, 300)]
-
-
 def _recipe(kinds="reference", **kw):
     from facl_amd.philox import Recipe
     return Recipe.parse(kinds, **kw)
-
-
-def _host(recipe, kinds=None, n_kinds=None, strengths=None):
-    """The three host arguments of a recipe entry (overridable, for the refusals) and the arrays that back them."""
-    k = recipe.codes() if kinds is None else np.asarray(kinds, dtype=np.int32)
-    s = recipe.strengths() if strengths is None else np.asarray(strengths, dtype=np.float64)
-    return (k, s), (k.ctypes.data if k.size or kinds is None else None, len(k) if n_kinds is None else n_kinds, s.ctypes.data)
-
-
-def _call(pk, recipe, seed, epoch, G, P, out=None, idx=None, host=None):
-    """facl_build_views_philox_recipe_* on a packed batch; (rc, out (G,B,P,4), idx (B,G,P)) as NumPy."""
-    from facl_amd import _lib
-    if out is None:
-        out = torch.full((G * pk.B, P, 4), float("nan"), dtype=torch.float32, device=DEV)
-        idx = torch.full((pk.B, G, P), -7, dtype=torch.int32, device=DEV)
-    keep, extra = _host(recipe) if host is None else host
-    rc = getattr(pk.lib, "facl_build_views_philox_recipe_" + ("f64" if pk.f64 else "f32"))(
-        _lib.ptr(pk.src), pk.rows, 8, _lib.ptr(pk.meta), _lib.ptr(pk.lists), _lib.ptr(pk.counts), _signed(seed), int(epoch),
-        pk.B, G, P, _lib.ptr(out), _lib.ptr(idx), *extra, _lib.stream())
-    torch.cuda.synchronize()
-    if rc != 0:
-        return rc, out.cpu().numpy(), idx.cpu().numpy()
-    return rc, out.cpu().numpy().reshape(G, pk.B, P, 4), idx.cpu().numpy()
-
-
-class _Pool:
-    """The same clips as a resident pool (build_table's layout), their temporal rows compacted."""
-
-    def __init__(self, clips, ids):
-        from facl_amd import _lib
-        from facl_amd.resident import build_table
-        self.lib = _lib.load_library()
-        self.f64 = clips[0][0].dtype == np.float64
-        rows = np.array([[a.shape[0] for a in c] for c in clips])
-        self.table_np, total, total0 = build_table(rows, ids)
-        self.n = len(clips)
-        self.src = torch.from_numpy(np.concatenate([a[:, :8] for c in clips for a in c])).to(DEV)
-        self.tab = torch.from_numpy(self.table_np).to(DEV)
-        self.lists = torch.empty((2 * total0,), dtype=torch.int32, device=DEV)
-        self.err = torch.tensor([0, 2 ** 31 - 1], dtype=torch.int32, device=DEV)
-        fn = self.lib.facl_resident_temporal_rows_f64 if self.f64 else self.lib.facl_resident_temporal_rows_f32
-        _lib.check(fn(_lib.ptr(self.src), _lib.ptr(self.tab), _lib.ptr(self.lists), 0, self.n, _lib.ptr(self.err),
-                      _lib.stream()), "facl_resident_temporal_rows")
-
-    def call(self, recipe, seed, epoch, G, P, sel=None, out=None, idx=None, host=None, entry="recipe"):
-        from facl_amd import _lib
-        sel = torch.arange(self.n, dtype=torch.int32, device=DEV) if sel is None else sel
-        Bn = sel.shape[0]
-        if out is None:
-            out = torch.full((G * Bn, P, 4), float("nan"), dtype=torch.float32, device=DEV)
-            idx = torch.full((Bn, G, P), -7, dtype=torch.int64, device=DEV)
-        keep, extra = ((), ()) if entry == "gp" else (_host(recipe) if host is None else host)
-        rc = getattr(self.lib, "facl_build_views_resident_%s_%s" % (entry, "f64" if self.f64 else "f32"))(
-            _lib.ptr(self.src), _lib.ptr(self.tab), _lib.ptr(self.lists), self.n, _lib.ptr(sel), Bn, G, P, _signed(seed),
-            int(epoch), _lib.ptr(out), _lib.ptr(idx), _lib.ptr(self.err), *extra, _lib.stream())
-        torch.cuda.synchronize()
-        if rc != 0:
-            return rc, out.cpu().numpy(), idx.cpu().numpy()
-        return rc, out.cpu().numpy().reshape(G, Bn, P, 4), idx.cpu().numpy()
 
 
 def _c_table(recipe):

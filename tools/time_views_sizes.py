@@ -11,7 +11,8 @@
 3. End to end: clips/s of the training entry at --num_crop 24 --SAMPLE_NUM 2048 --resident 1 --graph 1 on a synthetic tree
    (tools/time_disk_entry.make_dataset), from disk (--resident 0), and on the synthetic iid input of the same size.
 With --sizes_every_round 1 the _gp sizes are timed in EVERY round and library (medians and spread per library), and, where
-   the library has the recipe entries, a non-default view recipe (scale,tilt_neg,tilt_pos,jitter,rot,mirror,t7) next to them.
+   the library has the recipe entries, a non-default view recipe (scale,tilt_neg,tilt_pos,jitter,rot,mirror,t7) next to them,
+   per library as well; with a baseline, rule 1 is then applied to every cell at 10 x 512 and 24 x 2048 (no_regression_sizes).
 A child that fails ends the measurement at once.  Prints one JSON line (and writes it to --out).
 
     python tools/time_views_sizes.py [--baseline_lib PATH] [--out profiles/views_sizes.json]
@@ -194,7 +195,7 @@ def main():
         libs["baseline"] = os.path.abspath(a.baseline_lib)
     common = ["--B", str(a.B), "--reps", str(a.reps), "--launches", str(a.launches)]
     runs = {k: [] for k in libs}
-    size_runs, recipe_runs = {k: [] for k in libs}, []
+    size_runs, recipe_runs = {k: [] for k in libs}, {k: [] for k in libs}
     sizes = None
     for i in range(a.rounds):
         for k in sorted(libs):                                      # baseline, this, baseline, this, ...
@@ -207,7 +208,7 @@ def main():
             if "sizes_us" in res:
                 size_runs[k].append(res["sizes_us"])
             if "recipe_us" in res:
-                recipe_runs.append(res["recipe_us"])
+                recipe_runs[k].append(res["recipe_us"])
             print("%s round %d: %s %s" % (k, i, res["old_entries_us"], res.get("sizes_us", {}).get("24x2048", "")),
                   file=sys.stderr, flush=True)
     out = {"B": a.B, "launches_per_window": a.launches, "windows_per_run": a.reps, "rounds": a.rounds, "process_per_run": True,
@@ -227,10 +228,20 @@ def main():
     if a.sizes_every_round:                                          # the _gp entries per library and round, and a recipe's time
         out["sizes_us_by_library"] = {k: {gp: {p: spread([r[gp][p] for r in v]) for p in ("disk", "resident")} for gp in v[0]}
                                       for k, v in size_runs.items() if v}
-        if recipe_runs:
+        if any(recipe_runs.values()):
             out["recipe_us"] = {"kinds": "scale,tilt_neg,tilt_pos,jitter,rot,mirror,t7",
-                                **{gp: {p: spread([r[gp][p] for r in recipe_runs]) for p in ("disk", "resident")}
-                                   for gp in recipe_runs[0]}}
+                                **{k: {gp: {p: spread([r[gp][p] for r in v]) for p in ("disk", "resident")} for gp in v[0]}
+                                   for k, v in recipe_runs.items() if v}}
+        if "baseline" in out["sizes_us_by_library"]:                 # the rule of 1., for every cell both libraries have
+            cells = {"default " + gp: (out["sizes_us_by_library"]["this"][gp], out["sizes_us_by_library"]["baseline"][gp])
+                     for gp in ("10x512", "24x2048")}
+            if "baseline" in out.get("recipe_us", {}):
+                cells.update({"recipe " + gp: (out["recipe_us"]["this"][gp], out["recipe_us"]["baseline"][gp])
+                              for gp in out["recipe_us"]["this"]})
+            out["no_regression_sizes"] = {c: {p: {"this_minus_baseline_us": t[p]["median"] - b[p]["median"],
+                                                  "baseline_spread_us": b[p]["spread"],
+                                                  "holds": t[p]["median"] - b[p]["median"] <= b[p]["spread"]}
+                                              for p in ("disk", "resident")} for c, (t, b) in cells.items()}
     out["sizes"] = {k: {p: {"us_per_launch": us, "points_per_s": a.B * int(k.split("x")[0]) * int(k.split("x")[1]) / (us * 1e-6)}
                         for p, us in v.items()} for k, v in (sizes or {}).items()}
     if a.entries:

@@ -168,8 +168,11 @@ SIGNATURES = {
     "facl_softmax_ce": [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     "facl_cls_probs_acc": [c_p, c_i, c_i, c_i, c_p, c_i, c_p],
     "facl_cls_topk": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "facl_cluster_ws_bytes": [c_i, c_i, c_i],
+    "facl_cluster_row_inv": [c_p, c_i, c_i, c_i, c_p, c_p],
+    "facl_cluster_sums": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
 }
-RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes"}
+RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes", "facl_cluster_ws_bytes"}
 
 
 def lib_path():

@@ -119,6 +119,16 @@ def build_parser(default_branch):
     p.add_argument('--label_fraction', type=float, default=1.0,
                    help='NEW: 0 < f <= 1, the stratified fraction of the train split whose labels are used (label_subset)')
     p.add_argument('--label_seed', type=int, default=0, help='NEW: seed of the per-class permutations of --label_fraction')
+    p.add_argument('--class_ids', type=str, default='labels', choices=('labels', 'cluster'),
+                   help='NEW (--loss_mask class): labels = the class ids are the action labels of --label_fraction of the clips; '
+                        'cluster = no label is read: after every --cluster_every-th epoch the train split is extracted in memory '
+                        'and clustered by spherical k-means (facl_amd/cluster.py), and the cluster ids are the class ids; every '
+                        'clip is unknown until the first clustering')
+    p.add_argument('--clusters', type=int, default=0, help='NEW (--class_ids cluster): K of the k-means, 2..1024')
+    p.add_argument('--cluster_every', type=int, default=0, help='NEW (--class_ids cluster): re-cluster after every E-th epoch, E >= 1')
+    p.add_argument('--cluster_iters', type=int, default=50, help='NEW (--class_ids cluster): centroid updates per restart at most')
+    p.add_argument('--cluster_restarts', type=int, default=1, help='NEW (--class_ids cluster): restarts of every clustering')
+    p.add_argument('--cluster_seed', type=int, default=0, help='NEW (--class_ids cluster): the clustering after epoch e draws its initial rows with seed + e')
     p.add_argument('--neg_queue', type=int, default=0,
                    help='NEW (one rank): L > 0 = the global / circle losses also see the x_global rows of the last L clips as '
                         'negatives (a device-side ring buffer, facl_amd/neg_queue.py); a multiple of --batchSize; 0 = off')
@@ -814,6 +824,7 @@ def check_class_mask_flags(opt, world=None):
         check_class_positives(getattr(opt, "class_positives", 0.0), opt.loss_mask)
     except ValueError as e:
         raise RuntimeError("--class_positives: %s" % e) from None
+    check_cluster_id_flags(opt, world)
     if opt.loss_mask != 'class':
         return
     world = fdist.env_world_size() if world is None else world
@@ -824,6 +835,36 @@ def check_class_mask_flags(opt, world=None):
                            "(got --synthetic %d, which has no labelled clips)" % opt.synthetic)
     if not 0.0 < opt.label_fraction <= 1.0:                  # NaN fails both comparisons
         raise RuntimeError("--label_fraction must be in (0, 1] (got %r)" % opt.label_fraction)
+
+
+def check_cluster_id_flags(opt, world=None):
+    """--class_ids cluster: the class ids of --loss_mask class are k-means cluster ids of the train split on disk.  Needs that
+    mask, --synthetic 0, one rank, 2 <= --clusters <= 1024, --cluster_every >= 1; reads no label, so --label_fraction /
+    --label_seed stay at their defaults; the ids are not in a state file, so neither --save_state_every nor --resume.  Raises
+    before the device is touched (`world` None: the launcher's WORLD_SIZE); namespaces from before the flag hold `labels`."""
+    if getattr(opt, "class_ids", "labels") != 'cluster':
+        return
+    if opt.loss_mask != 'class':
+        raise RuntimeError("--class_ids cluster supplies the ids of --loss_mask class (got --loss_mask %s): nothing else reads them"
+                           % opt.loss_mask)
+    if opt.synthetic != 0:
+        raise RuntimeError("--class_ids cluster extracts and clusters the train split of --data_root: it needs --synthetic 0 "
+                           "(got --synthetic %d, which has no clips on disk)" % opt.synthetic)
+    world = fdist.env_world_size() if world is None else world
+    if world > 1:
+        raise RuntimeError("--class_ids cluster runs on one rank only (got %d ranks): the sharded extraction is not implemented" % world)
+    if not 2 <= opt.clusters <= 1024:
+        raise RuntimeError("--class_ids cluster needs --clusters K in 2..1024 (got %d)" % opt.clusters)
+    if opt.cluster_every < 1:
+        raise RuntimeError("--class_ids cluster needs --cluster_every E >= 1 (got %d)" % opt.cluster_every)
+    if opt.cluster_iters < 1 or opt.cluster_restarts < 1:
+        raise RuntimeError("--cluster_iters and --cluster_restarts must be >= 1 (got %d, %d)" % (opt.cluster_iters, opt.cluster_restarts))
+    if opt.label_fraction != 1.0 or opt.label_seed != 0:
+        raise RuntimeError("--class_ids cluster reads no label: --label_fraction %r / --label_seed %d select labels and have "
+                           "nothing to act on" % (opt.label_fraction, opt.label_seed))
+    if opt.save_state_every or opt.resume:
+        raise RuntimeError("--class_ids cluster with --save_state_every / --resume: the cluster ids of the clips are not part "
+                           "of a state file, so a resumed run could not continue with them")
 
 
 def split_class_ids(labels, fraction, seed):
@@ -849,26 +890,54 @@ def eval_mode(netR):
         netR.train(was_training)
 
 
-def knn_monitor(netR, opt, device):
-    """Weighted-kNN test top-1 (%) of the model as it stands: both splits of <data_root>/raw extracted in memory exactly as
-    facl_amd.extract_common.run_disk extracts them (eval(), its own view seed 2000 and generator), test against the train
-    bank.  Reads no training RNG stream and, in eval(), updates no running statistic; runs on ordinary eager launches, so
-    its tensors come from the default allocator pool, never from a captured step's.  The model returns to train()."""
+def extract_monitor_splits(netR, opt, device, test=True, what="--knn_every"):
+    """[(features, labels, v_names)] of the train split and, with `test`, the test split of <data_root>/raw, extracted in memory
+    exactly as facl_amd.extract_common.run_disk extracts them (eval(), its own view seed 2000 and generator, train first: the
+    train features do not depend on `test`).  Reads no training RNG stream and, in eval(), updates no running statistic; runs on
+    ordinary eager launches, so its tensors come from the default allocator pool, never from a captured step's.  The model
+    returns to the mode it was in."""
     from . import dataset as fds
     from .extract_common import extract_split
-    from .knn_eval import knn_top1
     index = fds.ClipIndex.from_dir(os.path.join(opt.data_root, fds.EXTRACT_LIST_DIR), opt.dataset)
     rng = np.random.RandomState(2000)
+    splits = [index.select(opt.split, full_train=bool(opt.full_train))] + ([index.select(opt.split, test=True)] if test else [])
     with eval_mode(netR):
         data = []
-        for split in (index.select(opt.split, full_train=bool(opt.full_train)), index.select(opt.split, test=True)):
+        for split in splits:
             if not len(split):
-                raise RuntimeError("--knn_every: a split of %s has no clips" % opt.data_root)
+                raise RuntimeError("%s: a split of %s has no clips" % (what, opt.data_root))
             f = extract_split(netR, opt, device, index, split, rng)
             y = torch.as_tensor([index.label(v) for v in split], dtype=torch.int64, device=device)
-            data.append((f, y))
-        (ftr, ytr), (fte, yte) = data
-        return knn_top1(fte, yte, ftr, ytr, k=opt.knn_k, T=opt.knn_T)
+            data.append((f, y, [index.v_name(v) for v in split]))
+    return data
+
+
+def knn_monitor(netR, opt, device, data=None):
+    """Weighted-kNN test top-1 (%) of the model as it stands, test against the train bank; `data`: what
+    `extract_monitor_splits` returned for both splits (None: extracted here)."""
+    from .knn_eval import knn_top1
+    (ftr, ytr, _), (fte, yte, _) = extract_monitor_splits(netR, opt, device) if data is None else data
+    return knn_top1(fte, yte, ftr, ytr, k=opt.knn_k, T=opt.knn_T)
+
+
+def recluster(step, class_of, feats, names, K, iters=50, restarts=1, seed=0):
+    """--class_ids cluster: spherical k-means of the global chunk (the last 512 columns) of the extracted train features
+    `feats` (clips, (num_crop+1)*512); `class_of` {v_name: id} is replaced IN PLACE by the cluster ids of `names` (-1 for a clip
+    that was not extracted).  Cluster numbers of two clusterings are unrelated, so the id ring of the step's queue goes back to
+    unknown: stale ids would mask or attract the wrong rows, unknown ones leave them ordinary negatives until fresh pushes
+    replace them; the rows and {head, valid} stay.  Returns (labels as a host array, info of facl_amd.cluster.kmeans)."""
+    from . import cluster as fcl
+    labels, _, info = fcl.kmeans(feats[:, feats.shape[1] - 512:], K, iters=iters, restarts=restarts, seed=seed)
+    ids = labels.cpu().numpy()
+    for n in class_of:
+        class_of[n] = -1
+    for n, c in zip(names, ids):
+        if n in class_of:
+            class_of[n] = int(c)
+    queue = getattr(step, "queue", None)
+    if queue is not None and queue.ids is not None:
+        queue.ids.fill_(-1)
+    return ids, info
 
 
 def setup_run(opt):
@@ -1043,7 +1112,14 @@ def run(default_branch, ckpt_pattern, args=None):
     gen.manual_seed(1000 + rank)
     view_rng = np.random.RandomState(2000 + rank)         # --synthetic 2: the generator the view construction draws from
     class_of = None
-    if opt.loss_mask == 'class':
+    if opt.loss_mask == 'class' and opt.class_ids == 'cluster':
+        # no label is read: every clip is unknown (the class mask is then the exclude mask) until the first clustering
+        class_of = {source.index.v_name(int(v)): -1 for v in source.split}
+        print('class mask: cluster ids, %d clusters, every %d epoch(s); %d train clips unknown until the first clustering'
+              % (opt.clusters, opt.cluster_every, len(class_of)))
+        if opt.class_positives:
+            print('class positives: weight %g' % opt.class_positives)
+    elif opt.loss_mask == 'class':
         # every clip trains; the stratified subset keeps its label as class id, every other clip is unknown (-1)
         ids = split_class_ids([source.index.label(int(v)) for v in source.split], opt.label_fraction, opt.label_seed)
         class_of = {source.index.v_name(int(v)): int(c) for v, c in zip(source.split, ids)}
@@ -1077,8 +1153,26 @@ def run(default_branch, ckpt_pattern, args=None):
         logging.info('{} --epoch{} ==Average loss:{}'.format('Valid', epoch, mean_loss))
         if rank == 0:
             print('epoch:', epoch, 'loss mode is :', 1, '--loss:', mean_loss, '| clips/s: %.1f%s' % (clips, grad_norms))
-        if opt.knn_every and (epoch + 1) % opt.knn_every == 0:
-            top1 = knn_monitor(netR, opt, device)
+        knn_now = bool(opt.knn_every) and (epoch + 1) % opt.knn_every == 0
+        cluster_now = opt.class_ids == 'cluster' and (epoch + 1) % opt.cluster_every == 0
+        data = None
+        if cluster_now:                                      # the train split is extracted once for both monitors
+            data = extract_monitor_splits(netR, opt, device, test=knn_now, what="--class_ids cluster")
+            ftr, ytr, names = data[0]
+            ids, info = recluster(step, class_of, ftr, names, opt.clusters, opt.cluster_iters, opt.cluster_restarts,
+                                  opt.cluster_seed + epoch)
+            # the split is labelled on disk anyway: acc / nmi against the true labels are printed as a monitor ONLY -- the
+            # training never sees those labels, its class ids are the cluster numbers above
+            from . import cluster as fcl
+            table = fcl.contingency(ids, ytr.cpu().numpy())
+            sizes = np.sort(info['sizes'])
+            line = ('clusters: %d objective: %.6f iters: %d sizes min/median/max: %d/%g/%d | acc: %.2f nmi: %.4f'
+                    % (opt.clusters, info['objective'], info['n_iter'], sizes[0], float(np.median(sizes)), sizes[-1],
+                       fcl.matched_accuracy(table), fcl.nmi(table)))
+            logging.info('{} --epoch{} =={}'.format('Valid', epoch, line))
+            print('epoch:', epoch, line)
+        if knn_now:
+            top1 = knn_monitor(netR, opt, device, data)
             logging.info('{} --epoch{} ==knn top1:{}'.format('Valid', epoch, top1))
             print('epoch:', epoch, 'knn top1:', top1)
         if rank == 0 and epoch % 5 == 0:

@@ -930,6 +930,37 @@ int facl_cls_probs_acc(const float* logits, int ld, int R, int ncls, double* acc
 int facl_cls_topk(const double* acc, int R, int ncls, int ndraws, int k, const int32_t* labels, float* top_p, int32_t* top_c,
                   int32_t* rank, void* stream);
 
+/* ---- spherical k-means over frozen features: the centroid update (csrc/cluster.hip) ----------------------------
+ * The reference has no counterpart: clustering accuracy / NMI / ARI are the standard label-free complement of its linear probe,
+ * and cluster ids stand in for action labels in the class-aware loss modes.  The ASSIGNMENT step of a Lloyd iteration is
+ * facl_knn_topk with q = x, the centroids as the bank, k = 1 and self_idx = NULL; these entries are the UPDATE step.
+ *   x (n, C) fp32 rows ldx floats apart (a column slice of a wider matrix is read in place)
+ *
+ * facl_cluster_row_inv: inv[i] = fp32(1 / max(||x_i||, 1e-12)), the sum of squares in fp64 in a fixed order (one wave per row).
+ * Run once per clustering.  Domain: n >= 1; C a positive multiple of 64; ldx >= C and a multiple of 4; else FACL_E_SHAPE.  NULL x /
+ * inv: FACL_E_NULL.  x not 16-byte aligned: FACL_E_ALIGN.
+ *
+ * facl_cluster_sums: for every cluster c with offs[c+1] > offs[c]
+ *     cent[c][j] = fp32( sum over r = offs[c] .. offs[c+1]-1, in that order, of double(x[order[r]][j]) * double(inv[order[r]]) ),
+ * the UN-normalised sum (facl_knn_topk normalises bank rows itself).  A cluster without rows leaves its row of cent untouched.
+ *   order  int32 (n): the row indices sorted by label, ascending row index inside a label
+ *   offs   int32 (K+1): the label boundaries, 0 = offs[0] <= offs[1] <= ... <= offs[K] = n
+ *   cent   (K, C) fp32 contiguous
+ *   err    one int32 of flags, only ever raised: 1 an entry of order outside [0, n) -- that row is skipped and never
+ *          dereferenced; 2 boundaries that are not as above -- then no row is read and cent is left as it is
+ *   ws     facl_cluster_ws_bytes(n, K, C) bytes, 16-byte aligned; contents are scratch
+ * A cluster is cut into segments of 128 rows of order; a first launch writes each segment's fp64 partial sums to ws, a second
+ * adds a cluster's segments in segment order and rounds once.  No floating-point atomic takes part and the order of every sum
+ * is fixed by (n, order, offs): the same bits every run.
+ * Domain: n >= 1; 1 <= K <= 1024 (facl_knn_vote's class limit); C, ldx as above; else FACL_E_SHAPE.  A NULL pointer:
+ * FACL_E_NULL.  x, cent or ws not 16-byte aligned: FACL_E_ALIGN.  Every refusal comes before any launch.
+ * facl_cluster_ws_bytes: 4 (K + 1) bytes of segment offsets, rounded up to 256, + 8 C (n / 128 + K) bytes of partial sums.
+ * FACL_E_SHAPE outside the domain of (n, K, C). */
+int64_t facl_cluster_ws_bytes(int n, int K, int C);
+int facl_cluster_row_inv(const float* x, int n, int ldx, int C, float* inv, void* stream);
+int facl_cluster_sums(const float* x, int n, int ldx, int C, const float* inv, const int32_t* order, const int32_t* offs, int K,
+                      float* cent, int32_t* err, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,8 +171,11 @@ SIGNATURES = {
     "facl_cluster_ws_bytes": [c_i, c_i, c_i],
     "facl_cluster_row_inv": [c_p, c_i, c_i, c_i, c_p, c_p],
     "facl_cluster_sums": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
+    "facl_proto_nce_ws_bytes": [c_i],
+    "facl_proto_nce": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
 }
-RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes", "facl_cluster_ws_bytes"}
+RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes", "facl_cluster_ws_bytes",
+               "facl_proto_nce_ws_bytes"}
 
 
 def lib_path():

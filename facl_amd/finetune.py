@@ -143,6 +143,8 @@ def check_finetune_flags(opt, world=None):
         raise RuntimeError("--class_positives adds positives to the contrastive loss: fine-tuning has the cross-entropy only")
     if getattr(opt, "class_ids", "labels") != 'labels':
         raise RuntimeError("--class_ids supplies the class ids of the contrastive loss's mask: fine-tuning has the cross-entropy only")
+    if getattr(opt, "proto_weight", 0.0):
+        raise RuntimeError("--proto_weight adds the prototype term to the contrastive loss: fine-tuning has the cross-entropy only")
     if opt.neg_queue:
         raise RuntimeError("--neg_queue holds negatives of the contrastive loss: fine-tuning has the cross-entropy only")
     if opt.key_encoder:

@@ -3,6 +3,7 @@ lines: default ``branch_choose``, data root and checkpoint file name -- cn3d_tra
 import argparse
 import contextlib
 import logging
+import math
 import os
 import random
 import time
@@ -129,6 +130,16 @@ def build_parser(default_branch):
     p.add_argument('--cluster_iters', type=int, default=50, help='NEW (--class_ids cluster): centroid updates per restart at most')
     p.add_argument('--cluster_restarts', type=int, default=1, help='NEW (--class_ids cluster): restarts of every clustering')
     p.add_argument('--cluster_seed', type=int, default=0, help='NEW (--class_ids cluster): the clustering after epoch e draws its initial rows with seed + e')
+    p.add_argument('--proto_weight', type=float, default=0.0,
+                   help='NEW (--class_ids cluster): w > 0 = add w x the prototype contrastive term (ProtoNCE, facl_amd/proto.py) on '
+                        'the centroids of the last clustering: every row of the stacked output against its clip\'s own centroid and '
+                        'the other K - 1; zero until the first clustering; 0 = off')
+    p.add_argument('--proto_temperature', type=float, default=0.2,
+                   help='NEW (--proto_weight): the mean of the per-cluster temperatures phi_k (the temperature itself under fixed)')
+    p.add_argument('--proto_concentration', type=str, default='cluster', choices=('cluster', 'fixed'),
+                   help='NEW (--proto_weight): cluster = phi_k from the cluster\'s own concentration (PCL: mean distance to the '
+                        'centroid / log(size + 10), clipped to the 10th..90th percentile, mean = --proto_temperature); fixed = '
+                        'every phi_k = --proto_temperature')
     p.add_argument('--neg_queue', type=int, default=0,
                    help='NEW (one rank): L > 0 = the global / circle losses also see the x_global rows of the last L clips as '
                         'negatives (a device-side ring buffer, facl_amd/neg_queue.py); a multiple of --batchSize; 0 = off')
@@ -283,8 +294,33 @@ class ContrastiveStep:
             raise RuntimeError("the key encoder supplies the rows of the negative queue: it needs neg_queue > 0")
         # class-mates as extra positives (utils_my: class_positives); beside loss_mode, which stays the dict of the three modes
         self.class_positives = check_class_positives(getattr(opt, "class_positives", 0.0), self.loss_mode["mask"])
+        # prototype contrastive term (facl_amd/proto.py): static tensors that the caller fills in place after every clustering
+        # (set_prototypes), so that a replayed graph reads the current centroids; zeros / ones do nothing while every id is -1
+        self.proto_weight = float(getattr(opt, "proto_weight", 0.0))
+        self.prototypes = self.proto_inv = self.proto_scale = self.proto_err = None
+        if self.proto_weight > 0:
+            if self.clip_classes is None:
+                raise RuntimeError("the prototype term reads the clips' cluster ids: it needs the class-aware loss mask")
+            from .cls_head import FEATURE_DIM
+            dev, K = self.clip_classes.device, int(opt.clusters)
+            self.prototypes = torch.zeros((K, FEATURE_DIM), dtype=torch.float32, device=dev)
+            self.proto_inv = torch.ones((K,), dtype=torch.float32, device=dev)
+            self.proto_scale = torch.ones((K,), dtype=torch.float32, device=dev)
         self.rank = torch.distributed.get_rank() if fdist.is_distributed() else 0
         self.grad_sync = fdist.GradSync(list(netR.named_parameters())) if fdist.is_distributed() else None
+
+    def set_prototypes(self, centroids, scale):
+        """After a clustering: the (K, 512) centroids and their (K,) scales 1 / phi_k go IN PLACE into the step's static tensors."""
+        from .cluster import row_inv
+        self.prototypes.copy_(centroids)
+        self.proto_inv.copy_(row_inv(self.prototypes))
+        self.proto_scale.copy_(torch.as_tensor(scale, dtype=torch.float32))
+
+    def check_proto_err(self):
+        """Outside the step (a host read-back): raises when a clip's id was >= K since the last check."""
+        if self.proto_err is not None:
+            from .proto import raise_if_err
+            raise_if_err(self.proto_err, self.prototypes.shape[0], "--proto_weight")
 
     def group(self, data1):
         return group_views(data1, self.opt, self.r2)
@@ -411,6 +447,10 @@ class ContrastiveStep:
         if self.cld_if:                                                            # :319-326
             from . import swav_cld
             loss = loss + swav_cld.cld_loss(x_nor, B, G)
+        if self.proto_weight > 0:                                                  # no counterpart in the reference
+            from .proto import proto_nce_raw
+            loss_p, self.proto_err = proto_nce_raw(netR._stacked, self.clip_classes, self.prototypes, self.proto_inv, self.proto_scale)
+            loss = loss + self.proto_weight * loss_p
         self.optimizer.zero_grad(set_to_none=True)
         if self._one is None or self._one.device != loss.device:
             self._one = torch.ones((), dtype=torch.float32, device=loss.device)    # the seed of backward(): no fill launch per step
@@ -867,6 +907,21 @@ def check_cluster_id_flags(opt, world=None):
                            "of a state file, so a resumed run could not continue with them")
 
 
+def check_proto_flags(opt, world=None):
+    """--proto_weight w: finite and >= 0, and w > 0 only with --class_ids cluster, whose centroids are the prototypes (that flag
+    already implies one rank, --synthetic 0, --loss_mask class and no state files); --proto_temperature finite and > 0.  Raises
+    before the device is touched; namespaces from before the flags hold the defaults."""
+    w, t = float(getattr(opt, "proto_weight", 0.0)), float(getattr(opt, "proto_temperature", 0.2))
+    if not (w >= 0.0 and math.isfinite(w)):                  # NaN fails the comparison
+        raise RuntimeError("--proto_weight must be finite and >= 0 (got %r)" % w)
+    if not (t > 0.0 and math.isfinite(t)):
+        raise RuntimeError("--proto_temperature must be finite and > 0 (got %r)" % t)
+    if w > 0 and getattr(opt, "class_ids", "labels") != 'cluster':
+        raise RuntimeError("--proto_weight %g needs --class_ids cluster: the prototypes are the centroids of its k-means" % w)
+    if w > 0:
+        check_cluster_id_flags(opt, world)
+
+
 def split_class_ids(labels, fraction, seed):
     """The class id of every clip of a labelled split as the class-aware mask sees it: the clip's label inside the stratified
     `label_subset` (facl_amd/finetune.py: nested in `fraction` for one seed), -1 outside.  (N,) int32; pure host code."""
@@ -925,9 +980,11 @@ def recluster(step, class_of, feats, names, K, iters=50, restarts=1, seed=0):
     `feats` (clips, (num_crop+1)*512); `class_of` {v_name: id} is replaced IN PLACE by the cluster ids of `names` (-1 for a clip
     that was not extracted).  Cluster numbers of two clusterings are unrelated, so the id ring of the step's queue goes back to
     unknown: stale ids would mask or attract the wrong rows, unknown ones leave them ordinary negatives until fresh pushes
-    replace them; the rows and {head, valid} stay.  Returns (labels as a host array, info of facl_amd.cluster.kmeans)."""
+    replace them; the rows and {head, valid} stay.  Returns (labels as a host array, info of facl_amd.cluster.kmeans); the
+    (K, 512) un-normalised centroids that produced the labels ride along as info["centroids"] (the prototypes of --proto_weight)."""
     from . import cluster as fcl
-    labels, _, info = fcl.kmeans(feats[:, feats.shape[1] - 512:], K, iters=iters, restarts=restarts, seed=seed)
+    labels, cent, info = fcl.kmeans(feats[:, feats.shape[1] - 512:], K, iters=iters, restarts=restarts, seed=seed)
+    info["centroids"] = cent
     ids = labels.cpu().numpy()
     for n in class_of:
         class_of[n] = -1
@@ -1080,6 +1137,7 @@ def run(default_branch, ckpt_pattern, args=None):
     check_knn_flags(opt)
     check_loss_flags(opt)
     check_class_mask_flags(opt)
+    check_proto_flags(opt)
     check_queue_flags(opt)
     check_key_flags(opt)
     check_state_flags(opt)
@@ -1171,6 +1229,18 @@ def run(default_branch, ckpt_pattern, args=None):
                        fcl.matched_accuracy(table), fcl.nmi(table)))
             logging.info('{} --epoch{} =={}'.format('Valid', epoch, line))
             print('epoch:', epoch, line)
+            if step.proto_weight > 0:
+                # the ids a step saw so far came from the previous clustering (or were -1): any of them >= K raises here
+                step.check_proto_err()
+                from .knn_eval import knn_topk
+                from .proto import concentrations
+                cos_own = knn_topk(ftr[:, ftr.shape[1] - 512:], info["centroids"], 1)[0][:, 0]
+                scale = concentrations(cos_own.cpu().numpy(), ids, opt.clusters, opt.proto_temperature, opt.proto_concentration)
+                step.set_prototypes(info["centroids"], scale)
+                phi = 1.0 / scale.astype(np.float64)
+                line = 'prototypes: %d concentration min/mean/max: %.6g/%.6g/%.6g' % (opt.clusters, phi.min(), phi.mean(), phi.max())
+                logging.info('{} --epoch{} =={}'.format('Valid', epoch, line))
+                print('epoch:', epoch, line)
         if knn_now:
             top1 = knn_monitor(netR, opt, device, data)
             logging.info('{} --epoch{} ==knn top1:{}'.format('Valid', epoch, top1))

@@ -961,6 +961,31 @@ int facl_cluster_row_inv(const float* x, int n, int ldx, int C, float* inv, void
 int facl_cluster_sums(const float* x, int n, int ldx, int C, const float* inv, const int32_t* order, const int32_t* offs, int K,
                       float* cent, int32_t* err, void* ws, void* stream);
 
+/* ---- prototype contrastive term on the k-means centroids (csrc/proto.hip) ------------------------------------------
+ * The reference has no counterpart: ProtoNCE (Li et al. 2021, "Prototypical Contrastive Learning") on the centroids that
+ * --class_ids cluster computes anyway.  With z_r = x_r / max(||x_r||, 1e-12), p_k = c_k proto_inv_k, l_rk = scale_k <z_r, p_k> and
+ * s_r = classes[r % B]:
+ *   loss     = (1/M) sum over the rows with 0 <= s_r < K of [logsumexp_k l_rk - l_{r,s_r}]      (the division is by M: a row of
+ *              unknown class adds nothing and still counts, facl_softmax_ce's convention)
+ *   dstacked = d loss / d stacked: row r = inv_r (dz_r - z_r <dz_r, z_r>) with dz_r = sum_k (softmax_k(l_r.) - [k = s_r]) / M scale_k p_k,
+ *              exact zeros in the other rows.  The prototypes are constants: they get no gradient.
+ *   stacked   (M, C) float32, row stride ld; row r belongs to clip r % B (view-major rows, the clips' global rows last)
+ *   classes   (B) int32; < 0: unknown.  An id >= K raises bit 0 of err[0] (an integer OR: the caller zeroes err once and may
+ *             read it whenever it likes); the row is treated as unknown and the id indexes nothing
+ *   protos    (K, C) float32 contiguous, un-normalised;  proto_inv (K) = 1 / max(||c_k||, 1e-12);  scale (K) = 1 / phi_k > 0
+ *   loss      (1) float32;  dstacked (M, C) float32 contiguous;  ws facl_proto_nce_ws_bytes(M) bytes, contents are scratch
+ * One launch does everything per tile of 16 rows on the exact f32-input MFMA (sums of squares, sum of exp and the projection
+ * in fp64), a second one (one wave) adds the tiles' loss sums in a fixed order.  No floating-point atomic: equal inputs give
+ * equal bits.  With every class unknown the loss is +0.0 and dstacked all zero bits.
+ * Domain: M >= 1, B >= 1, M % B == 0; 1 <= K <= 1024; C a multiple of 64 in 64..512; ld >= C and a multiple of 4; else
+ * FACL_E_SHAPE.  A NULL pointer: FACL_E_NULL.  stacked, protos, proto_inv, scale, dstacked or ws not 16-byte aligned:
+ * FACL_E_ALIGN.  Every refusal comes before any launch.
+ * facl_proto_nce_ws_bytes: 8 ceil(M / 16) bytes, rounded up to 256; FACL_E_SHAPE for M < 1. */
+int64_t facl_proto_nce_ws_bytes(int M);
+int facl_proto_nce(const float* stacked, int M, int ld, int C, int B, const int32_t* classes, const float* protos,
+                   const float* proto_inv, const float* scale, int K, float* loss, float* dstacked, int32_t* err, void* ws,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

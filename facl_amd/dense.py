@@ -19,7 +19,6 @@ What the reference holds for it: the second-level groupers ``group_points_2`` / 
     accumulation;
   * ``DenseStep`` (grouping -> forward -> global + circle loss -> backward -> optimizer) and the bench hook.
 """
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -28,6 +27,7 @@ from . import dist as fdist
 from . import sa_mlp
 from . import tail as _tail
 from .cn3d_model_conbag import _Affine, _BatchNormState, _Slots, _conv_stack, nstates_plus_1, nstates_plus_2, nstates_plus_3
+from .train_step import GraphedStep, TrainStep
 from .utils_my import contrastive_losses_stacked, knn_radius_group
 
 
@@ -170,23 +170,9 @@ class PointNet_Plus_dense(nn.Module):
         return x, code, x_nor, x_global
 
 
-class DenseStep:
+class DenseStep(TrainStep):
     """One training iteration of the dense configuration: the loop body of cn3d_train_motion_GL.py:224-335 with the
     3-level encoder (grouping happens inside the model)."""
-
-    def __init__(self, netR, optimizer, num_crop):
-        self.netR, self.optimizer, self.G = netR, optimizer, num_crop
-        self.rank = torch.distributed.get_rank() if fdist.is_distributed() else 0
-        self.grad_sync = fdist.GradSync(list(netR.named_parameters()), early_prefixes=("net3DV_3.", "netR_FC.")) \
-            if fdist.is_distributed() else None
-
-    def __call__(self, out_points, epoch=0, order=None):
-        if order is None:
-            order = np.arange(0, self.G, 1)
-            np.random.shuffle(order)
-        if not torch.is_tensor(order):
-            order = torch.as_tensor(np.asarray(order), dtype=torch.long).to(out_points.device)
-        return self.run(out_points, order)
 
     def run(self, out_points, order):
         netR, G = self.netR, self.G
@@ -196,11 +182,7 @@ class DenseStep:
         loss_c, loss_circle = contrastive_losses_stacked(G, netR._stacked, order, x_keys=None if x_keys is x else x_keys,
                                                          clip_offset=self.rank * B)
         loss = loss_circle + loss_c
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        if self.grad_sync is not None:
-            self.grad_sync.finish()
-        self.optimizer.step()
+        self.backward_and_update(loss)
         return loss, loss_c, loss_circle
 
 
@@ -223,7 +205,6 @@ def make_bench_step(a, dev, rank, world):
             "dgrad/wgrad), fp32 accumulation and storage; level-1 first layers and level-1 backward fp32-grade")
     mode, run_step = "eager", step
     if world == 1 and getattr(a, "graph", 1):
-        from .train_common import GraphedStep
         try:
             run_step = GraphedStep(step, batches[0], a.T)           # the whole iteration replayed as one HIP graph
             mode = "hipgraph"

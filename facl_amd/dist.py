@@ -14,14 +14,11 @@ import os
 import torch
 import torch.distributed as dist
 
+from .train_flags import env_world_size  # noqa: F401  (the flag checks read it without importing torch)
+
 
 def is_distributed():
     return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-
-
-def env_world_size():
-    """The launcher's WORLD_SIZE (torch.distributed.run); 1 without a launcher."""
-    return int(os.environ.get("WORLD_SIZE", "1"))
 
 
 def init_from_env(backend=None):
@@ -48,7 +45,7 @@ def full_graph_env():
     """OPT-IN FACL_DP_GRAPH=full only (call before the process group exists).  Observed once in ~10 one-rank rehearsals of that mode
     (gpurun_out/r04_evidence.log, round 4): the process group's watchdog thread queried an event `last recorded in a capturing
     stream` (hipErrorCapturedEvent) and tore the process down with SIGABRT.  Two precautions, neither proven sufficient: no
-    re-use of the process group's events through its cache, and (train_common.GraphedStep) a pause between the eager warm-up and
+    re-use of the process group's events through its cache, and (train_step.GraphedStep) a pause between the eager warm-up and
     the capture so that the watchdog has retired every eager collective before the first captured one is issued."""
     if os.environ.get("FACL_DP_GRAPH", "segments") == "full":
         os.environ.setdefault("TORCH_NCCL_CUDA_EVENT_CACHE", "0")
@@ -86,7 +83,7 @@ class GraphSegments:
 
     Failure protocol (a capture that fails on ONE rank must not leave the others replaying segments against its eager
     launches: mismatched collectives = a hang).  While capturing, every cut and the end of the capture carry one extra
-    tiny collective, a `vote`: a rank whose segment raised votes "failed" exactly once (train_common.GraphedStep does, from
+    tiny collective, a `vote`: a rank whose segment raised votes "failed" exactly once (train_step.GraphedStep does, from
     its handler), which pairs with the others' next vote; they raise CaptureAborted there.  Up to that vote every rank has
     issued the same collectives, so all ranks leave the capture at the same point of the collective sequence and can
     continue TOGETHER on eager launches.  A failure inside a collective itself cannot be voted on: the process-group

@@ -8,7 +8,9 @@ import numpy as np
 import torch
 
 from . import cn3d_model_conbag as MM
-from .train_common import build_parser, check_view_flags, group_views, synthetic_batch, view_recipe
+from .train_common import synthetic_batch
+from .train_flags import build_parser, check_view_flags, view_recipe
+from .train_step import group_views
 
 
 def save_single_feature(feature, save_path, name, num_crop=11):

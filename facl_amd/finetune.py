@@ -5,7 +5,7 @@ From a pre-trained checkpoint, from scratch (no checkpoint), or on a stratified 
     python -m facl_amd.finetune --synthetic 0 --data_root ../ntu/3DV_ntu60 --checkpoint corr_GL_95.pth --label_fraction 0.1
 
 The head is the reference's probe head ``Final_FC`` (linear_classify/fc_model.py:12-25) reading the encoder's stacked
-output in place (facl_amd/cls_head.py, csrc/cls.hip); the step replays as one HIP graph through ``train_common.GraphedStep``."""
+output in place (facl_amd/cls_head.py, csrc/cls.hip); the step replays as one HIP graph through ``train_step.GraphedStep``."""
 import logging
 import math
 import os
@@ -14,12 +14,11 @@ import numpy as np
 import torch
 
 from . import cn3d_model_conbag as MODELL
-from . import dist as fdist
 from .cls_head import ClipClassifier
 from .extract_common import ordered_views
-from .train_common import (ContrastiveStep, TrainBatches, build_parser, check_optim_flags, check_resident_flags,
-                           check_view_flags, eval_mode, optim_recipe, setup_run, synthetic_batch, train_epochs,
-                           view_recipe)
+from .train_common import TrainBatches, eval_mode, setup_run, synthetic_batch, train_epochs
+from .train_flags import check_finetune_flags, check_finetune_train_flags, finetune_parser, optim_recipe, view_recipe  # noqa: F401
+from .train_step import GroupedStep
 
 HEAD_PREFIX = "head."
 
@@ -51,8 +50,8 @@ class FineTuneNet(MODELL.PointNet_Plus):
                                % (missing, list(res.unexpected_keys)))
 
 
-class FineTuneStep(ContrastiveStep):
-    """One supervised iteration: grouping (ContrastiveStep.group) -> encoder forward -> head -> cross-entropy -> backward
+class FineTuneStep(GroupedStep):
+    """One supervised iteration: grouping (GroupedStep.grouped) -> encoder forward -> head -> cross-entropy -> backward
     -> FusedAdam, with no host round trip (`run` is what GraphedStep captures).  The labels come from the static int32
     device tensor ``self.labels`` (batch,), which the caller fills in place before each call; `order` is ignored.
 
@@ -62,8 +61,7 @@ class FineTuneStep(ContrastiveStep):
 
     def __init__(self, netR, optimizer, opt, num_crop, group_radius=None, fps_reorder=False, freeze_bn=False):
         super().__init__(netR, optimizer, opt, num_crop, group_radius, fps_reorder)
-        dev = next(netR.parameters()).device
-        self.labels = torch.zeros(opt.batchSize, dtype=torch.int32, device=dev)
+        self.labels = torch.zeros(opt.batchSize, dtype=torch.int32, device=next(netR.parameters()).device)
         self.freeze_bn = bool(freeze_bn)
 
     def run(self, out_points, order):
@@ -71,20 +69,14 @@ class FineTuneStep(ContrastiveStep):
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("a step with frozen BatchNorm (model in eval()) runs eager: it is not captured into a graph")
             self.netR.eval()                                # the epoch loop switches to train() at the start of every epoch
-        return super().run(out_points, order)
-
-    def _encode_and_step(self, xt, yt, B, order):
-        netR, G = self.netR, self.G
+        netR = self.netR
+        xt, yt, B = self.grouped(out_points)
         if B > self.labels.shape[0]:
             raise RuntimeError("a batch of %d clips, the step holds %d labels" % (B, self.labels.shape[0]))
         netR(xt, yt, 1)
-        logits = netR.head(netR._stacked, G, B)
+        logits = netR.head(netR._stacked, self.G, B)
         loss, stats = netR.head.loss(logits, self.labels[:B])
-        self.optimizer.zero_grad(set_to_none=True)
-        if self._one is None or self._one.device != loss.device:
-            self._one = torch.ones((), dtype=torch.float32, device=loss.device)    # the seed of backward(): no fill launch per step
-        loss.backward(self._one)
-        self.optimizer.step()
+        self.backward_and_update(loss)
         return loss, logits, stats
 
 
@@ -104,60 +96,6 @@ def label_subset(labels, fraction, seed):
         perm = rs.permutation(len(idx))
         keep.append(idx[perm[:max(1, int(math.ceil(fraction * len(idx))))]])
     return np.sort(np.concatenate(keep)) if keep else np.zeros((0,), dtype=np.int64)
-
-
-def finetune_parser():
-    p = build_parser('0')
-    p.description = "Supervised fine-tuning"
-    p.add_argument('--checkpoint', type=str, default='', help='NEW: encoder state_dict to start from; empty = from scratch')
-    p.add_argument('--num_class', type=int, default=0, help='NEW: classes of the head (0 = 60 for ntu60, 120 for ntu120)')
-    # --label_fraction / --label_seed: build_parser's (the pre-training entries read them for --loss_mask class); here they
-    # narrow the train split to the labelled subset
-    p.add_argument('--eval_every', type=int, default=1, help='NEW (--synthetic 0): test top-1 after every E-th epoch; 0 = off')
-    p.add_argument('--freeze_bn', type=int, default=0, choices=(0, 1),
-                   help='NEW: 1 = fine-tune with frozen BatchNorm: the model stays in eval() for the training step, the running '
-                        'statistics of --checkpoint (required) are kept, all weights train; the step runs eager')
-    return p
-
-
-def check_finetune_flags(opt, world=None):
-    """One rank, labelled clips or synthetic ones; raises before the device is touched (`world` None: the launcher's WORLD_SIZE)."""
-    world = fdist.env_world_size() if world is None else world
-    if world > 1:
-        raise RuntimeError("fine-tuning runs on one rank only (got %d ranks): data-parallel fine-tuning is not implemented" % world)
-    if opt.synthetic not in (0, 1):
-        raise RuntimeError("fine-tuning reads the labelled clips of --data_root (--synthetic 0) or synthetic clouds with "
-                           "random labels (--synthetic 1); got --synthetic %d" % opt.synthetic)
-    if not 0.0 < opt.label_fraction <= 1.0:
-        raise RuntimeError("--label_fraction must be in (0, 1] (got %r)" % opt.label_fraction)
-    if opt.eval_every < 0:
-        raise RuntimeError("--eval_every must be >= 0 (got %d)" % opt.eval_every)
-    if opt.knn_every:
-        raise RuntimeError("--knn_every belongs to the pre-training entries; fine-tuning reports its own test top-1 (--eval_every)")
-    if opt.swa_if or opt.cld_if:
-        raise RuntimeError("--swa_if / --cld_if are terms of the contrastive loss: fine-tuning has the cross-entropy only")
-    if opt.loss_normalize or opt.loss_temperature != 1.0 or opt.loss_mask != 'zero':
-        raise RuntimeError("--loss_normalize / --loss_temperature / --loss_mask shape the contrastive loss: fine-tuning has the "
-                           "cross-entropy only")
-    if opt.class_positives:
-        raise RuntimeError("--class_positives adds positives to the contrastive loss: fine-tuning has the cross-entropy only")
-    if getattr(opt, "class_ids", "labels") != 'labels':
-        raise RuntimeError("--class_ids supplies the class ids of the contrastive loss's mask: fine-tuning has the cross-entropy only")
-    if getattr(opt, "proto_weight", 0.0):
-        raise RuntimeError("--proto_weight adds the prototype term to the contrastive loss: fine-tuning has the cross-entropy only")
-    if opt.neg_queue:
-        raise RuntimeError("--neg_queue holds negatives of the contrastive loss: fine-tuning has the cross-entropy only")
-    if opt.key_encoder:
-        raise RuntimeError("--key_encoder fills the negative queue of the contrastive loss: fine-tuning has the cross-entropy only")
-    if not opt.num_class:
-        opt.num_class = 60 if opt.dataset == 'ntu60' else 120
-    if not 2 <= opt.num_class <= 1024 or opt.num_class % 4:
-        raise RuntimeError("--num_class must be a multiple of 4 in 2..1024 (got %d)" % opt.num_class)
-    if not 1 <= opt.num_crop <= 64:
-        raise RuntimeError("--num_crop must be in 1..64 (got %d)" % opt.num_crop)
-    if getattr(opt, "freeze_bn", 0) and not opt.checkpoint:
-        raise RuntimeError("--freeze_bn 1 keeps the running statistics of a pre-trained encoder: it needs --checkpoint (the "
-                           "initial statistics, mean 0 and variance 1, describe no data)")
 
 
 def _raise_bad_labels(bad, num_class, where):
@@ -191,12 +129,9 @@ def main(args=None):
     """Returns the last test top-1 (%), or None when no evaluation ran."""
     opt = finetune_parser().parse_args(args)
     print(opt)
-    check_finetune_flags(opt)
-    check_resident_flags(opt)
-    check_view_flags(opt)
+    check_finetune_train_flags(opt)
     if opt.synthetic != 1:
         print(view_recipe(opt).describe())
-    check_optim_flags(opt, world=1)
     torch.cuda.set_device(opt.main_gpu)
     device = torch.device("cuda", opt.main_gpu)
     setup_run(opt)

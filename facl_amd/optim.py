@@ -103,7 +103,7 @@ class FusedAdam:
     def sync_lr(self):
         """Host -> device copy of ``param_groups[0]["lr"]`` when a schedule changed it.  step() calls it; a captured
         HIP graph holds no such fill, so whoever REPLAYS a graph with this optimizer inside must call it before each
-        replay (train_common.GraphedStep does): the fill lands on the replay stream, ahead of the graph."""
+        replay (train_step.GraphedStep does): the fill lands on the replay stream, ahead of the graph."""
         lr = float(self.param_groups[0]["lr"])
         if lr != self._lr_host:                              # host -> device only when the schedule changed it
             self._lr.fill_(lr)

@@ -20,7 +20,8 @@ import torch
 from . import _lib
 from . import cls_head
 from . import dist as fdist
-from .train_common import build_parser, check_view_flags, group_views, view_recipe
+from .train_flags import build_parser, check_view_flags, view_recipe
+from .train_step import group_views
 
 MAX_TOPK = 64              # facl_cls_topk: one list entry per lane
 

@@ -16,7 +16,7 @@ C_MAX = 512
 
 # (device, stream, M, C, K) -> (dstacked, loss, ws, err): allocated once and reused, so that a captured step replays against static
 # memory.  NOT the stream's shared scratch workspace: the query forward leaves there what its backward reads
-# (train_common.ContrastiveStep._encode_and_step), and this term runs between the two.
+# (train_step.ContrastiveStep._encode_and_step), and this term runs between the two.
 _BUFFERS = {}
 
 

@@ -140,12 +140,12 @@ def test_path_helpers_follow_the_launcher():
     assert nq.vectorised(24, 12, m, m[4:]) and not nq.vectorised(24, 12, m, m[1:])
 
 
-class _PlainStep:
-    """A step object of the shape GraphedStep wraps, WITHOUT a ``queue`` attribute (dense.DenseStep has none)."""
-
-    def __init__(self):
-        self.netR = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2))
-        self.optimizer = torch.optim.SGD(self.netR.parameters(), lr=0.1)
+def _PlainStep():
+    """A step object of the shape GraphedStep wraps, WITHOUT a ``queue`` attribute (dense.DenseStep has none): the base class,
+    which carries no state besides model and optimizer."""
+    from facl_amd.train_step import TrainStep
+    net = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2))
+    return TrainStep(net, torch.optim.SGD(net.parameters(), lr=0.1), 2)
 
 
 def test_graphed_step_state_of_a_step_without_a_queue_attribute():

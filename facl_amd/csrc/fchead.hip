@@ -69,7 +69,7 @@ __device__ __forceinline__ void fc_slice_sums(const double* __restrict__ part, i
 
 // Both segments' train-mode BatchNorm constants bnc2 (2, 5, C) = (mean, invstd, scale, shift, sign) from the slice sums,
 // and the module's running statistics updated TWICE, segment a (the view rows, :228) first, segment b (the clip rows,
-// :229) second: the same arithmetic as two facl_bn_finalize calls (the buffers round to fp32 in between).
+// :229) second: the pieces of k_bn_finalize (bn_consts.h), so two facl_bn_finalize calls (the buffers round to fp32 in between).
 __global__ __launch_bounds__(256) void k_fc_finalize(const double* __restrict__ part, int na, int nb, int C, double count_a,
                                                      double count_b, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      float eps, float momentum, float* __restrict__ running_mean,
@@ -84,21 +84,10 @@ __global__ __launch_bounds__(256) void k_fc_finalize(const double* __restrict__ 
     float rm = running_mean ? running_mean[c] : 0.f, rv = running_var ? running_var[c] : 0.f;
 #pragma unroll
     for (int seg = 0; seg < 2; ++seg) {
-        const double s = acc[2 * seg], q = acc[2 * seg + 1];
         const double count = seg ? count_b : count_a;
-        const double mean = s / count;
-        double var = q / count - mean * mean;
-        if (var < 0) var = 0;
-        const double invstd = 1.0 / sqrt(var + (double)eps);
-        float* o = bnc2 + (size_t)seg * 5 * C;
-        o[c] = (float)mean;
-        o[C + c] = (float)invstd;
-        o[2 * C + c] = (float)(g * invstd);
-        o[3 * C + c] = (float)(b - mean * g * invstd);
-        o[4 * C + c] = g < 0 ? -1.0f : 1.0f;
-        const double unb = count > 1 ? var * count / (count - 1) : var;
-        rm = (float)((1.0 - momentum) * rm + momentum * mean);
-        rv = (float)((1.0 - momentum) * rv + momentum * unb);
+        const BnStats st = bn_train_stats(acc[2 * seg], acc[2 * seg + 1], count, eps);
+        bn_store_consts(bn_segment(bnc2, C, seg), C, c, (float)st.mean, st.mean, st.invstd, g, b, gamma[c]);
+        bn_running_step(rm, rv, momentum, st.mean, st.var, count);
     }
     if (running_mean) { running_mean[c] = rm; running_var[c] = rv; }
 }
@@ -109,8 +98,8 @@ __global__ __launch_bounds__(256) void k_fc_apply(const float* __restrict__ y, i
     const int c4 = blockIdx.x * 256 + threadIdx.x;
     if (c4 >= C4) return;
     const int C = 4 * C4;
-    const float4 sa = reinterpret_cast<const float4*>(bnc2 + 2 * C)[c4], ta = reinterpret_cast<const float4*>(bnc2 + 3 * C)[c4];
-    const float4 sb = reinterpret_cast<const float4*>(bnc2 + 7 * C)[c4], tb = reinterpret_cast<const float4*>(bnc2 + 8 * C)[c4];
+    const float4 sa = reinterpret_cast<const float4*>(bn_row(bnc2, C, BN_SCALE, 0))[c4], ta = reinterpret_cast<const float4*>(bn_row(bnc2, C, BN_SHIFT, 0))[c4];
+    const float4 sb = reinterpret_cast<const float4*>(bn_row(bnc2, C, BN_SCALE, 1))[c4], tb = reinterpret_cast<const float4*>(bn_row(bnc2, C, BN_SHIFT, 1))[c4];
     for (int r = blockIdx.y; r < R; r += gridDim.y) {
         const float4 sc = r < M ? sa : sb, sh = r < M ? ta : tb;
         reinterpret_cast<float4*>(out)[(size_t)r * C4 + c4] = lane_map<4>(bn_relu, sc, reinterpret_cast<const float4*>(y)[(size_t)r * C4 + c4], sh);
@@ -127,7 +116,7 @@ __global__ __launch_bounds__(256) void k_fc_bwd_stats(const float* __restrict__ 
     int r0, r1, seg;
     fc_slice(blockIdx.y, M, R, na, r0, r1, seg);
     double acc[8] = {};
-    if (c4 < C4) bn_bwd_stats_rows<4>(dout, y, C4, c4, bnc2 + (size_t)seg * 20 * C4, r0 + ph, r1, 4, acc);
+    if (c4 < C4) bn_bwd_stats_rows<4>(dout, y, C4, c4, bn_segment(bnc2, 4 * C4, seg), r0 + ph, r1, 4, acc);
     if (phase_sum(acc, red, lane, ph, c4 < C4)) {
         double* pr = part + (size_t)blockIdx.y * 8 * C4 + 8 * c4;
 #pragma unroll
@@ -153,9 +142,7 @@ __global__ __launch_bounds__(256) void k_fc_bwd_consts(const double* __restrict_
     for (int seg = 0; seg < 2; ++seg) {
         const double g0 = sums_g ? sums_g[(size_t)seg * V + 2 * c] : acc[2 * seg];
         const double g1 = sums_g ? sums_g[(size_t)seg * V + 2 * c + 1] : acc[2 * seg + 1];
-        const float inv = (float)(1.0 / (seg ? count_b : count_a));         // fp32 sum times fp32 reciprocal count (k_bn_bwd_consts)
-        kk2[(size_t)seg * V + c] = (float)g0 * inv;
-        kk2[(size_t)seg * V + C + c] = (float)g1 * inv;
+        bn_bwd_kk(g0, g1, seg ? count_b : count_a, kk2[(size_t)seg * V + c], kk2[(size_t)seg * V + C + c]);
     }
     dbeta[c] = (float)acc[0] + (float)acc[2];
     dgamma[c] = (float)acc[1] + (float)acc[3];
@@ -168,7 +155,7 @@ __global__ __launch_bounds__(256) void k_fc_bwd_apply(const float* __restrict__ 
     const int c4 = blockIdx.x * 256 + threadIdx.x;
     if (c4 >= C4) return;
     const int C = 4 * C4;
-    const BnLanes<4> q[2] = {bn_lanes<4>(bnc2, C, c4), bn_lanes<4>(bnc2 + 5 * C, C, c4)};
+    const BnLanes<4> q[2] = {bn_lanes<4>(bn_segment(bnc2, C, 0), C, c4), bn_lanes<4>(bn_segment(bnc2, C, 1), C, c4)};
     const KkLanes<4> k[2] = {kk_lanes<4>(kk2, C, c4), kk_lanes<4>(kk2 + 2 * C, C, c4)};
     for (int r = blockIdx.y; r < R; r += gridDim.y) {
         const int s = r < M ? 0 : 1;

@@ -1,8 +1,6 @@
 // Small fp64 "finalize" kernels between the passes of the train-mode BatchNorm pipeline:
-// partial-sum reduction, BN statistics -> (mean, invstd, scale, shift, sign), running-stat update.
-// BN semantics: cn3d_model_conbag.py:46,50,54,64,68,72,84 (nn.BatchNorm2d/1d defaults: eps 1e-5,
-// momentum 0.1, biased variance to normalise, unbiased for the running buffer).
-#include "common.h"
+// partial-sum reduction, BN statistics -> (mean, invstd, scale, shift, sign), running-stat update (the arithmetic: bn_consts.h).
+#include "bn_consts.h"
 #include <stdlib.h>
 
 extern "C" int64_t facl_ws_bytes(void);
@@ -39,11 +37,6 @@ __global__ __launch_bounds__(1024) void k_reduce_rows(const T* __restrict__ part
     }
 }
 
-// One workgroup: channels strided over the threads.  `aamax` (or null): FACL_AMAX_WORDS uint32 that receive -- in every one of
-// the FACL_AMAX_SLOTS slots -- the bits of a BOUND of max|gamma (y - mean) invstd + beta| over the batch these statistics were
-// taken on: Samuelson's inequality, |y_i - mean| <= sigma sqrt(n - 1) for ANY n numbers, gives
-// |.| <= |gamma| sqrt(n - 1) sigma invstd + |beta| (sigma invstd = sqrt(var / (var + eps)) <= 1).  It is the fp16x3 scale of the
-// layer's activation (common.h) -- rigorous, no pass over the data, and within a few octaves of the true maximum.
 // `prev` (or null): `nprev` floats that the INPUT of this layer was computed with -- the (scale | shift) rows of the previous
 // layer's constants.  The heavy passes apply the previous layer's ReLU as fmaxf(v, 0), which turns a NaN activation into a clean
 // zero, so a NaN / inf there never reaches this layer's sums; the reference's nn.ReLU keeps it and the next convolution spreads it
@@ -62,55 +55,46 @@ __device__ __forceinline__ bool block_any_nonfinite(const float* __restrict__ pr
     return !(z == 0.f);
 }
 
+// One workgroup: channels strided over the threads; the pieces are bn_consts.h's.  `aamax` (or null): FACL_AMAX_WORDS uint32 that
+// receive -- in every one of the FACL_AMAX_SLOTS slots -- the bits of bn_act_bound's maximum over the channels.  `zamax` (or
+// null): a buffer the launch zeroes.  `prev`: see block_any_nonfinite.
 __global__ __launch_bounds__(1024) void k_bn_finalize(const double* __restrict__ sums, int C, double count,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                       float momentum, float* __restrict__ running_mean,
                                                       float* __restrict__ running_var, float* __restrict__ bnc,
                                                       unsigned* __restrict__ aamax, unsigned* __restrict__ zamax,
                                                       const float* __restrict__ prev, int nprev) {
-    __shared__ float red[16];
     float bound = 0.f;
     const bool poisoned = prev ? block_any_nonfinite(prev, nprev) : false;                // uniform over the workgroup
     if (zamax)
         for (int i = threadIdx.x; i < FACL_AMAX_WORDS; i += blockDim.x) zamax[i] = 0u;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        double mean = sums[2 * c] / count;
-        if (poisoned) mean = __builtin_nan("");           // (the bound below is NaN too and fmaxf drops it: `aamax` then holds 0, a
-                                                          // meaningless scale -- harmless, every constant in bnc is NaN and decides)
-        double var = sums[2 * c + 1] / count - mean * mean;
-        if (var < 0) var = 0;
-        const double invstd = 1.0 / sqrt(var + (double)eps);
+        // poisoned: a NaN sum makes the mean and with it every constant NaN (the bound is NaN too and fmaxf drops it: `aamax` then
+        // holds 0, a meaningless scale -- harmless, the constants decide)
+        const BnStats st = bn_train_stats(poisoned ? __builtin_nan("") : sums[2 * c], sums[2 * c + 1], count, eps);
         const double g = gamma[c], b = beta[c];
-        bnc[0 * C + c] = (float)mean;
-        bnc[1 * C + c] = (float)invstd;
-        bnc[2 * C + c] = (float)(g * invstd);
-        bnc[3 * C + c] = (float)(b - mean * g * invstd);
-        bnc[4 * C + c] = g < 0 ? -1.0f : 1.0f;
-        if (running_mean) {
-            const double unb = count > 1 ? var * count / (count - 1) : var;
-            running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-        }
-        const double bd = (fabs(g) * sqrt((count > 1 ? count - 1 : 1) * var) * invstd + fabs(b)) * 1.001;   // 1.001: fp32 rounding of the constants
-        bound = fmaxf(bound, (float)bd);
+        bn_store_consts(bnc, C, c, (float)st.mean, st.mean, st.invstd, g, b, gamma[c]);
+        if (running_mean) bn_running_step(running_mean[c], running_var[c], momentum, st.mean, st.var, count);
+        bound = fmaxf(bound, bn_act_bound(g, b, st.var, st.invstd, count));
     }
-    if (!aamax) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bound = fmaxf(bound, __shfl_xor(bound, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bound;
-    __syncthreads();
-    if (threadIdx.x < FACL_AMAX_SLOTS) {
-        float m = red[0];
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmaxf(m, red[w]);
-        aamax[threadIdx.x * FACL_AMAX_STRIDE] = __float_as_uint(m);
+    if (aamax) bn_store_bound_in_slots<false>(bound, aamax);
+}
+
+// the wave's maximum RAISED into the slot of `amax` that its global wave id hashes to (one atomic per wave, non-negative floats
+// order like unsigned integers; 256-thread workgroups); `any_bad`: the flag word FACL_AMAX_FLAG_WORD raised to NaN bits as well
+__device__ __forceinline__ void raise_wave_slot(float m, unsigned* __restrict__ amax, bool any_bad = false) {
+    m = bn_wave_max(m);
+    if ((threadIdx.x & 63) == 0) {
+        const unsigned wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+        atomicMax(amax + (wave & (FACL_AMAX_SLOTS - 1)) * FACL_AMAX_STRIDE, __float_as_uint(m));
+        if (any_bad) atomicMax(amax + FACL_AMAX_FLAG_WORD, 0x7FC00000u);
     }
 }
 
-// max|x| over the FINITE elements of a contiguous fp32 array, RAISED into the FACL_AMAX_SLOTS slots of `amax` (zeroed by the caller,
-// or holding the maximum of another tensor that shares the scale): one atomic per wave, non-negative floats order like unsigned
-// integers.  A NaN / inf element does not enter the maximum -- one inf would otherwise push the operand scale of every OTHER row
-// out of the fp16 range (measured: an inf coordinate in one group left the features of all other groups 0.37 off) -- it raises
-// the flag word FACL_AMAX_FLAG_WORD of the buffer to NaN bits instead (a word no consumer of the scale reads: they take the slots).
+// max|x| over the FINITE elements of a contiguous fp32 array, raised into the slots of `amax` (zeroed by the caller, or holding the
+// maximum of another tensor that shares the scale).  A NaN / inf element does not enter the maximum -- one inf would otherwise push
+// the operand scale of every OTHER row out of the fp16 range (measured: an inf coordinate in one group left the features of all
+// other groups 0.37 off) -- it raises the flag word of the buffer instead (a word no consumer of the scale reads: they take the slots).
 __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, long long n, unsigned* __restrict__ amax) {
     float m = 0.f;
     bool bad = false;
@@ -121,18 +105,11 @@ __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, lon
         m = fmaxf(m, fin ? a : 0.f);
         bad |= !fin;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const bool any_bad = __ballot(bad) != 0ull;
-    if ((threadIdx.x & 63) == 0) {
-        const unsigned wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-        atomicMax(amax + (wave & (FACL_AMAX_SLOTS - 1)) * FACL_AMAX_STRIDE, __float_as_uint(m));
-        if (any_bad) atomicMax(amax + FACL_AMAX_FLAG_WORD, 0x7FC00000u);
-    }
+    raise_wave_slot(m, amax, __ballot(bad) != 0ull);
 }
 
 // max of relu(scale[c] y[r][c] + shift[c]) over a (R, C) row-major array: the measured activation maximum of an eval-mode
-// layer (running statistics give no bound on the data), raised into `amax` like k_absmax.  C % 4 == 0.
+// layer (running statistics give no bound on the data), raised into `amax` like k_absmax (no flag word).  C % 4 == 0.
 __global__ __launch_bounds__(256) void k_rows_act_amax(const float* __restrict__ y, long long n4, int C4,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
                                                        unsigned* __restrict__ amax) {
@@ -146,16 +123,12 @@ __global__ __launch_bounds__(256) void k_rows_act_amax(const float* __restrict__
         const float4 sc = reinterpret_cast<const float4*>(scale)[c4], sh = reinterpret_cast<const float4*>(shift)[c4];
         m = fmaxf(fmaxf(m, fmaxf(fmaf(sc.x, v.x, sh.x), fmaf(sc.y, v.y, sh.y))), fmaxf(fmaf(sc.z, v.z, sh.z), fmaf(sc.w, v.w, sh.w)));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) {
-        const unsigned wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-        atomicMax(amax + (wave & (FACL_AMAX_SLOTS - 1)) * FACL_AMAX_STRIDE, __float_as_uint(m));
-    }
+    raise_wave_slot(m, amax);
 }
 
-// `prev` (or null): as in k_bn_finalize -- `nprev` floats the layer's input depends on (the words of the amax buffer facl_absmax
-// measured x into: its flag word holds NaN bits when x held a NaN / inf); a non-finite one makes every constant NaN.
+// Eval mode: the constants from the running statistics.  `prev` (or null): as in k_bn_finalize -- `nprev` floats the layer's input
+// depends on (the words of the amax buffer facl_absmax measured x into: its flag word holds NaN bits when x held a NaN / inf); a
+// non-finite one makes scale and shift NaN.
 __global__ void k_bn_eval_consts(int C, const float* __restrict__ gamma, const float* __restrict__ beta,
                                  const float* __restrict__ rm, const float* __restrict__ rv, float eps,
                                  float* __restrict__ bnc, const float* __restrict__ prev, int nprev) {
@@ -163,39 +136,19 @@ __global__ void k_bn_eval_consts(int C, const float* __restrict__ gamma, const f
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const double invstd = 1.0 / sqrt((double)rv[c] + (double)eps);
-    const double g = poisoned ? __builtin_nan("") : (double)gamma[c];
-    bnc[0 * C + c] = rm[c];
-    bnc[1 * C + c] = (float)invstd;
-    bnc[2 * C + c] = (float)(g * invstd);
-    bnc[3 * C + c] = (float)((double)beta[c] - (double)rm[c] * g * invstd);
-    bnc[4 * C + c] = gamma[c] < 0 ? -1.0f : 1.0f;
+    bn_store_consts(bnc, C, c, rm[c], (double)rm[c], invstd, poisoned ? __builtin_nan("") : (double)gamma[c], (double)beta[c], gamma[c]);
 }
 
-// BN1 statistics analytically from the input moments: y1 = W1 x + b1  =>
-//   sum_p y1_c = W1_c . sx + P b1_c ;  sum_p y1_c^2 = W1_c X2 W1_c^T + 2 b1_c W1_c . sx + P b1_c^2
 __global__ void k_bn1_sums_from_moments(const double* __restrict__ mom, double count, int D,
                                         const float* __restrict__ W1, const float* __restrict__ b1, int C,
                                         double* __restrict__ sums) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const double* sx = mom;
-    const double* X2 = mom + D;
-    double ws = 0, q = 0;
-    for (int i = 0; i < D; ++i) {
-        const double wi = W1[c * D + i];
-        ws += wi * sx[i];
-        double t = 0;
-        for (int j = 0; j < D; ++j) t += X2[i * D + j] * (double)W1[c * D + j];
-        q += wi * t;
-    }
-    const double b = b1[c];
-    sums[2 * c] = ws + count * b;
-    sums[2 * c + 1] = q + 2.0 * b * ws + count * b * b;
+    if (c < C) bn1_moment_sums(mom, count, D, W1, b1, c, sums[2 * c], sums[2 * c + 1]);
 }
 
 // The three steps between the input moments and the layer-1 table in ONE single-wave launch (training, C = 64): the sums of
-// k_bn1_sums_from_moments, the constants / running statistics / activation bound of k_bn_finalize and the folded table of k_l1tab --
-// the same expressions in the same order, so every output is bit-identical to the three-launch chain (2 launches fewer per step).
+// k_bn1_sums_from_moments, the constants / running statistics / activation bound of k_bn_finalize and the folded table of k_l1tab,
+// composed of the same pieces, so every output is bit-identical to the three-launch chain (2 launches fewer per step).
 __global__ __launch_bounds__(64) void k_sa_bn1_chain(const double* __restrict__ mom, double count, int D,
                                                      const float* __restrict__ W1, const float* __restrict__ b1,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -204,74 +157,30 @@ __global__ __launch_bounds__(64) void k_sa_bn1_chain(const double* __restrict__ 
                                                      float* __restrict__ bnc, unsigned* __restrict__ aamax, float* __restrict__ tab) {
     constexpr int C = 64;
     const int c = threadIdx.x;
-    const double* sx = mom;
-    const double* X2 = mom + D;
-    double ws = 0, q = 0;
-    for (int i = 0; i < D; ++i) {
-        const double wi = W1[c * D + i];
-        ws += wi * sx[i];
-        double t = 0;
-        for (int j = 0; j < D; ++j) t += X2[i * D + j] * (double)W1[c * D + j];
-        q += wi * t;
-    }
-    const double bb = b1[c];
-    const double su = ws + count * bb, sq = q + 2.0 * bb * ws + count * bb * bb;
+    double su, sq;
+    bn1_moment_sums(mom, count, D, W1, b1, c, su, sq);
     sums[2 * c] = su;
     sums[2 * c + 1] = sq;
-    const double mean = su / count;
-    double var = sq / count - mean * mean;
-    if (var < 0) var = 0;
-    const double invstd = 1.0 / sqrt(var + (double)eps);
+    const BnStats st = bn_train_stats(su, sq, count, eps);
     const double g = gamma[c], b = beta[c];
-    const float scale = (float)(g * invstd), shift = (float)(b - mean * g * invstd);
-    bnc[0 * C + c] = (float)mean;
-    bnc[1 * C + c] = (float)invstd;
-    bnc[2 * C + c] = scale;
-    bnc[3 * C + c] = shift;
-    bnc[4 * C + c] = g < 0 ? -1.0f : 1.0f;
-    if (running_mean) {
-        const double unb = count > 1 ? var * count / (count - 1) : var;
-        running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-        running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-    }
-    if (aamax) {
-        const double bd = (fabs(g) * sqrt((count > 1 ? count - 1 : 1) * var) * invstd + fabs(b)) * 1.001;
-        float bound = (float)bd;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) bound = fmaxf(bound, __shfl_xor(bound, o, 64));
-        if (threadIdx.x < FACL_AMAX_SLOTS) aamax[threadIdx.x * FACL_AMAX_STRIDE] = __float_as_uint(bound);
-    }
-    const int L = FACL_SA_L1_COLS(D);                                  // row width (include/facl_hip.h): 8, or 12 for D > 4
-    for (int i = 0; i < L - 4; ++i) tab[c * L + i] = i < D ? scale * W1[c * D + i] : 0.0f;
-    tab[c * L + L - 4] = scale * b1[c] + shift;
-    tab[c * L + L - 3] = tab[c * L + L - 2] = tab[c * L + L - 1] = 0.0f;
+    const BnAffine a = bn_store_consts(bnc, C, c, (float)st.mean, st.mean, st.invstd, g, b, gamma[c]);
+    if (running_mean) bn_running_step(running_mean[c], running_var[c], momentum, st.mean, st.var, count);
+    if (aamax) bn_store_bound_in_slots<true>(bn_act_bound(g, b, st.var, st.invstd, count), aamax);
+    l1tab_row(W1, b1, D, c, a.scale, a.shift, tab);
 }
 
-// Fold BN1 into the first 1x1 conv: a1 = relu((scale*W1) x + (scale*b1 + shift)); rows of FACL_SA_L1_COLS(D) floats.
+// The folded layer-1 table (l1tab_row) for given constants (null: scale 1, shift 0); one wave, thread = channel.
 // `xamax` -> `a1amax` (both or neither): with X = max|x| over all coordinates (facl_absmax), |a1_c| <= X sum_i |w'_ci| + |b'_c|:
 // the bound of the layer-1 activation for eval-mode constants (train mode takes BatchNorm's own bound, facl_bn_finalize).
 __global__ void k_l1tab(const float* __restrict__ W1, const float* __restrict__ b1, int D,
                         const float* __restrict__ scale, const float* __restrict__ shift, float* __restrict__ tab,
                         const unsigned* __restrict__ xamax, unsigned* __restrict__ a1amax) {
-    const int c = threadIdx.x;                                          // 64 threads = one wave
-    const float s = scale ? scale[c] : 1.0f, t = shift ? shift[c] : 0.0f;
-    const int L = FACL_SA_L1_COLS(D);
-    float l1 = 0.f;
-    for (int i = 0; i < L - 4; ++i) {
-        const float w = i < D ? s * W1[c * D + i] : 0.0f;
-        tab[c * L + i] = w;
-        l1 += fabsf(w);
-    }
-    const float b = s * b1[c] + t;
-    tab[c * L + L - 4] = b;
-    tab[c * L + L - 3] = tab[c * L + L - 2] = tab[c * L + L - 1] = 0.0f;
+    const int c = threadIdx.x;
+    const L1Row r = l1tab_row(W1, b1, D, c, scale ? scale[c] : 1.0f, shift ? shift[c] : 0.0f, tab);
     if (a1amax) {
         const float X = __uint_as_float(amax_bits(xamax));
-        float bd = fmaf(l1, X, fabsf(b)) * 1.001f;                       // 1.001: covers the fp32 roundings of the sum and of the
-                                                                         // (at most 8-term) layer-1 chain many times over
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) bd = fmaxf(bd, __shfl_xor(bd, o, 64));
-        a1amax[c * FACL_AMAX_STRIDE] = __float_as_uint(bd);
+        // 1.001: covers the fp32 roundings of the sum and of the (at most 8-term) layer-1 chain many times over
+        bn_store_bound_in_slots<true>(fmaf(r.l1, X, fabsf(r.bias)) * 1.001f, a1amax);
     }
 }
 
@@ -412,7 +321,7 @@ __global__ __launch_bounds__(256) void k_sa_bwd_consts3(const double* __restrict
     __shared__ double red[3][64];
     const int c = threadIdx.x;
     {
-        const double mean = bnc3[c], inv = bnc3[256 + c], sc = bnc3[512 + c];
+        const double mean = bn_row(bnc3, 256, BN_MEAN)[c], inv = bn_row(bnc3, 256, BN_INVSTD)[c], sc = bn_row(bnc3, 256, BN_SCALE)[c];
         const double gg = -(sc * sums0[2 * c + 1] * inv) / P;
         g[c] = gg;
         hc[c] = -(sc * sums0[2 * c]) / P + gg * ((double)b3[c] - mean);
@@ -442,11 +351,36 @@ __global__ void k_sa_bwd_consts2(const double* __restrict__ sums1, const float* 
                                  float* __restrict__ bw2) {
     const int c = threadIdx.x;
     if (c >= 64) return;
-    const double inv = bnc2[64 + c], sc = bnc2[128 + c];
+    const double inv = bn_row(bnc2, 64, BN_INVSTD)[c], sc = bn_row(bnc2, 64, BN_SCALE)[c];
     bw2[c] = (float)sc;
     bw2[64 + c] = (float)(-sc * sums1[2 * c] / P);
     bw2[128 + c] = (float)(-sc * inv * sums1[2 * c + 1] / P);
-    bw2[192 + c] = bnc2[c];
+    bw2[192 + c] = bn_row(bnc2, 64, BN_MEAN)[c];
+}
+
+// ---- the output walk of facl_sa_bwd_final and facl_sa_bwd_final_frozen: one thread per output, five segments -------------------
+// dW3[c][k] | (dbeta3, dgamma3[, db3]) of a channel | dW2 | (dbeta2, dgamma2[, db2]) of a channel | layer 1, one channel per thread
+enum SaFinalSeg { SA_DW3, SA_BN3, SA_DW2, SA_BN2, SA_L1, SA_FINAL_PAST };
+constexpr int SA_N_DW3 = 256 * 64, SA_N_BN3 = 256, SA_N_DW2 = 64 * 64, SA_N_BN2 = 64, SA_N_L1 = 64;
+constexpr int SA_FINAL_TOTAL = SA_N_DW3 + SA_N_BN3 + SA_N_DW2 + SA_N_BN2 + SA_N_L1;
+// output index o -> its segment, r = the index within it
+__device__ __forceinline__ SaFinalSeg sa_final_segment(int o, int& r) {
+    r = o;
+    if (r < SA_N_DW3) return SA_DW3;
+    if ((r -= SA_N_DW3) < SA_N_BN3) return SA_BN3;
+    if ((r -= SA_N_BN3) < SA_N_DW2) return SA_DW2;
+    if ((r -= SA_N_DW2) < SA_N_BN2) return SA_BN2;
+    return (r -= SA_N_BN2) < SA_N_L1 ? SA_L1 : SA_FINAL_PAST;
+}
+// (dbeta1, dgamma1) of channel c from R1 (FACL_SA_L1_COLS(D),64) = rows sum_p x_d dz1 (d < D), then sum_p dz1 -- the tail of
+// facl_sa_bwd2's output: dgamma1 = sum_p dz1 (y1 - mean) invstd with y1 = W1 x + b1; bmm = b1 - mean
+struct L1Grads { double dbeta, dgamma; };
+__device__ __forceinline__ L1Grads l1_bn_grads(const double* __restrict__ R1, const float* __restrict__ W1, int D, int c, double inv,
+                                               double bmm) {
+    double wr = 0;
+    for (int d = 0; d < D; ++d) wr += (double)W1[c * D + d] * R1[d * 64 + c];
+    const double dbe = R1[D * 64 + c];
+    return {dbe, inv * (wr + bmm * dbe)};
 }
 
 // parameter gradients of layers 3, 2 and 1 from the reduced partial sums
@@ -458,48 +392,41 @@ __global__ __launch_bounds__(256) void k_sa_bwd_final(
     const float* __restrict__ b1, int D, double P, float* __restrict__ dW3, float* __restrict__ dg3,
     float* __restrict__ dbe3, float* __restrict__ dW2, float* __restrict__ dg2, float* __restrict__ dbe2,
     float* __restrict__ dW1, float* __restrict__ dg1, float* __restrict__ dbe1) {
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    const double* sparse3 = out3;
-    const double* gram2 = out3 + 256 * 64;
-    const double* s2 = out3 + 256 * 64 + 64 * 64;
-    if (o < 16384) {                                            // dW3[c][k]
-        const int c = o >> 6, k = o & 63;
-        const double mean = bnc3[c], inv = bnc3[256 + c], sc = bnc3[512 + c];
+    int r;
+    switch (sa_final_segment(blockIdx.x * 256 + threadIdx.x, r)) {
+    case SA_DW3: {
+        const double* gram2 = out3 + SA_N_DW3;                  // out3 = [sparse3 (256,64) | sum_p a2^T a2 (64,64) | sum_p a2 (64)]
+        const double* s2 = gram2 + 64 * 64;
+        const int c = r >> 6, k = r & 63;
+        const double mean = bn_row(bnc3, 256, BN_MEAN)[c], inv = bn_row(bnc3, 256, BN_INVSTD)[c], sc = bn_row(bnc3, 256, BN_SCALE)[c];
         double wg = 0;
         for (int j = 0; j < 64; ++j) wg += (double)W3[c * 64 + j] * gram2[j * 64 + k];
         const double yhat_a2 = inv * (wg + ((double)b3[c] - mean) * s2[k]);       // sum_p yhat3[p,c] a2[p,k]
-        dW3[o] = (float)(sparse3[o] - (sc / P) * (sums0_g[2 * c] * s2[k] + sums0_g[2 * c + 1] * yhat_a2));
-        return;
+        dW3[r] = (float)(out3[r] - (sc / P) * (sums0_g[2 * c] * s2[k] + sums0_g[2 * c + 1] * yhat_a2));
+        break;
     }
-    int r = o - 16384;
-    if (r < 256) { dbe3[r] = (float)sums0_l[2 * r]; dg3[r] = (float)sums0_l[2 * r + 1]; return; }
-    r -= 256;
-    if (r < 4096) { dW2[r] = (float)out2[r]; return; }
-    r -= 4096;
-    if (r < 64) { dbe2[r] = (float)sums1_l[2 * r]; dg2[r] = (float)sums1_l[2 * r + 1]; return; }
-    r -= 64;
-    if (r < 64) {                                               // layer 1, channel c = r
+    case SA_BN3: bn_store_grads(sums0_l, r, dbe3, dg3); break;
+    case SA_DW2: dW2[r] = (float)out2[r]; break;
+    case SA_BN2: bn_store_grads(sums1_l, r, dbe2, dg2); break;
+    case SA_L1: {
         const int c = r;
-        const double* R1_l = out2 + 4096;                       // (FACL_SA_L1_COLS(D),64): rows x_d (d<D), then sum dz1
-        const double mean = bnc1[c], inv = bnc1[64 + c], sc = bnc1[128 + c];
+        const double* R1_l = out2 + SA_N_DW2;
+        const double mean = bn_row(bnc1, 64, BN_MEAN)[c], inv = bn_row(bnc1, 64, BN_INVSTD)[c], sc = bn_row(bnc1, 64, BN_SCALE)[c];
         const double bmm = (double)b1[c] - mean;
-        double wr_l = 0, wr_g = 0;
-        for (int d = 0; d < D; ++d) {
-            wr_l += (double)W1[c * D + d] * R1_l[d * 64 + c];
-            wr_g += (double)W1[c * D + d] * R1_g[d * 64 + c];
-        }
-        const double dbe_l = R1_l[D * 64 + c], dbe_g = R1_g[D * 64 + c];
-        const double dg_l = inv * (wr_l + bmm * dbe_l), dg_g = inv * (wr_g + bmm * dbe_g);
-        dbe1[c] = (float)dbe_l;
-        dg1[c] = (float)dg_l;
+        const L1Grads l = l1_bn_grads(R1_l, W1, D, c, inv, bmm), g = l1_bn_grads(R1_g, W1, D, c, inv, bmm);
+        dbe1[c] = (float)l.dbeta;
+        dg1[c] = (float)l.dgamma;
         const double* sx = mom_l;
         const double* X2 = mom_l + D;
         for (int d = 0; d < D; ++d) {
             double wx = 0;
             for (int j = 0; j < D; ++j) wx += (double)W1[c * D + j] * X2[j * D + d];
             const double yhat_x = inv * (wx + bmm * sx[d]);                           // sum_p yhat1[p,c] x[p,d]
-            dW1[c * D + d] = (float)(sc * (R1_l[d * 64 + c] - (dbe_g / P) * sx[d] - (dg_g / P) * yhat_x));
+            dW1[c * D + d] = (float)(sc * (R1_l[d * 64 + c] - (g.dbeta / P) * sx[d] - (g.dgamma / P) * yhat_x));
         }
+        break;
+    }
+    default: break;
     }
 }
 
@@ -519,12 +446,8 @@ __global__ void k_bn_bwd_consts(const double* __restrict__ sums_l, const double*
                                 float* __restrict__ dbeta, float* __restrict__ dgamma, float* __restrict__ kk) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    dbeta[c] = (float)sums_l[2 * c];
-    dgamma[c] = (float)sums_l[2 * c + 1];
-    // same arithmetic as the torch glue it replaces: fp32 sum times fp32 reciprocal count
-    const float inv = (float)(1.0 / P);
-    kk[c] = (float)sums_g[2 * c] * inv;
-    kk[C + c] = (float)sums_g[2 * c + 1] * inv;
+    bn_store_grads(sums_l, c, dbeta, dgamma);
+    bn_bwd_kk(sums_g[2 * c], sums_g[2 * c + 1], P, kk[c], kk[C + c]);
 }
 
 extern "C" int facl_bn_bwd_consts(const double* sums_local, const double* sums_global, int C, double P, float* dbeta,
@@ -552,8 +475,7 @@ extern "C" int facl_sa_bwd_final(const double* out3, const double* sums0_g, cons
         !b1 || !dW3 || !dg3 || !dbe3 || !dW2 || !dg2 || !dbe2 || !dW1 || !dg1 || !dbe1)
         return FACL_E_NULL;
     if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX || P < 1) return FACL_E_SHAPE;
-    const int total = 16384 + 256 + 4096 + 64 + 64;
-    hipLaunchKernelGGL(k_sa_bwd_final, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out3, sums0_g,
+    hipLaunchKernelGGL(k_sa_bwd_final, dim3((SA_FINAL_TOTAL + 255) / 256), dim3(256), 0, (hipStream_t)stream, out3, sums0_g,
                        sums0_l, bnc3, W3, b3, out2, sums1_l, R1_g, mom_l, bnc1, W1, b1, D, P, dW3, dg3, dbe3, dW2, dg2,
                        dbe2, dW1, dg1, dbe1);
     return facl_launch_status();
@@ -572,9 +494,8 @@ __global__ void k_bn_bwd_consts_frozen(const double* __restrict__ sums, const fl
                                        float* __restrict__ kk) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    dbeta[c] = (float)sums[2 * c];
-    dgamma[c] = (float)sums[2 * c + 1];
-    dbias[c] = (float)((double)bnc[2 * C + c] * sums[2 * c]);
+    bn_store_grads(sums, c, dbeta, dgamma);
+    dbias[c] = (float)((double)bn_row(bnc, C, BN_SCALE)[c] * sums[2 * c]);
     kk[c] = 0.f;
     kk[C + c] = 0.f;
 }
@@ -590,10 +511,10 @@ __global__ void k_sa_bwd_consts3_frozen(float* __restrict__ G3, float* __restric
 __global__ void k_sa_bwd_consts2_frozen(const float* __restrict__ bnc2, float* __restrict__ bw2) {
     const int c = threadIdx.x;
     if (c >= 64) return;
-    bw2[c] = bnc2[128 + c];
+    bw2[c] = bn_row(bnc2, 64, BN_SCALE)[c];
     bw2[64 + c] = 0.f;
     bw2[128 + c] = 0.f;
-    bw2[192 + c] = bnc2[c];
+    bw2[192 + c] = bn_row(bnc2, 64, BN_MEAN)[c];
 }
 
 // the twelve gradients of net3DV_1 (b1, b2, b3 among them) from the partial sums of the heavy passes: no Gram / sum a2 /
@@ -605,36 +526,30 @@ __global__ __launch_bounds__(256) void k_sa_bwd_final_frozen(
     float* __restrict__ dW3, float* __restrict__ dg3, float* __restrict__ dbe3, float* __restrict__ db3,
     float* __restrict__ dW2, float* __restrict__ dg2, float* __restrict__ dbe2, float* __restrict__ db2,
     float* __restrict__ dW1, float* __restrict__ dg1, float* __restrict__ dbe1, float* __restrict__ db1) {
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o < 16384) { dW3[o] = (float)out3[o]; return; }         // sum_g coef a2[arg]: coef = scale3 dz3 is dy3 at its one position
-    int r = o - 16384;
-    if (r < 256) {
-        dbe3[r] = (float)sums0[2 * r];
-        dg3[r] = (float)sums0[2 * r + 1];
-        db3[r] = (float)((double)bnc3[512 + r] * sums0[2 * r]);
-        return;
-    }
-    r -= 256;
-    if (r < 4096) { dW2[r] = (float)out2[r]; return; }
-    r -= 4096;
-    if (r < 64) {
-        dbe2[r] = (float)sums1[2 * r];
-        dg2[r] = (float)sums1[2 * r + 1];
-        db2[r] = (float)((double)bnc2[128 + r] * sums1[2 * r]);
-        return;
-    }
-    r -= 64;
-    if (r < 64) {                                               // layer 1, channel c = r
+    int r;
+    switch (sa_final_segment(blockIdx.x * 256 + threadIdx.x, r)) {
+    case SA_DW3: dW3[r] = (float)out3[r]; break;                // sum_g coef a2[arg]: coef = scale3 dz3 is dy3 at its one position
+    case SA_BN3:
+        bn_store_grads(sums0, r, dbe3, dg3);
+        db3[r] = (float)((double)bn_row(bnc3, 256, BN_SCALE)[r] * sums0[2 * r]);
+        break;
+    case SA_DW2: dW2[r] = (float)out2[r]; break;
+    case SA_BN2:
+        bn_store_grads(sums1, r, dbe2, dg2);
+        db2[r] = (float)((double)bn_row(bnc2, 64, BN_SCALE)[r] * sums1[2 * r]);
+        break;
+    case SA_L1: {
         const int c = r;
-        const double* R1 = out2 + 4096;                         // (FACL_SA_L1_COLS(D),64): rows x_d (d<D), then sum dz1
-        const double mean = bnc1[c], inv = bnc1[64 + c], sc = bnc1[128 + c];
-        double wr = 0;
-        for (int d = 0; d < D; ++d) wr += (double)W1[c * D + d] * R1[d * 64 + c];
-        const double dbe = R1[D * 64 + c];
-        dbe1[c] = (float)dbe;
-        dg1[c] = (float)(inv * (wr + ((double)b1[c] - mean) * dbe));      // sum_p dz1 (y1 - mean) invstd, y1 = W1 x + b1
-        db1[c] = (float)(sc * dbe);
+        const double* R1 = out2 + SA_N_DW2;
+        const double mean = bn_row(bnc1, 64, BN_MEAN)[c], inv = bn_row(bnc1, 64, BN_INVSTD)[c], sc = bn_row(bnc1, 64, BN_SCALE)[c];
+        const L1Grads l = l1_bn_grads(R1, W1, D, c, inv, (double)b1[c] - mean);
+        dbe1[c] = (float)l.dbeta;
+        dg1[c] = (float)l.dgamma;
+        db1[c] = (float)(sc * l.dbeta);
         for (int d = 0; d < D; ++d) dW1[c * D + d] = (float)(sc * R1[d * 64 + c]);
+        break;
+    }
+    default: break;
     }
 }
 
@@ -670,8 +585,7 @@ extern "C" int facl_sa_bwd_final_frozen(const double* out3, const double* sums0,
         !dW2 || !dg2 || !dbe2 || !db2 || !dW1 || !dg1 || !dbe1 || !db1)
         return FACL_E_NULL;
     if (D < FACL_SA_D_MIN || D > FACL_SA_D_MAX) return FACL_E_SHAPE;
-    const int total = 16384 + 256 + 4096 + 64 + 64;
-    hipLaunchKernelGGL(k_sa_bwd_final_frozen, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, out3, sums0, bnc3,
+    hipLaunchKernelGGL(k_sa_bwd_final_frozen, dim3((SA_FINAL_TOTAL + 255) / 256), dim3(256), 0, (hipStream_t)stream, out3, sums0, bnc3,
                        out2, sums1, bnc2, bnc1, W1, b1, D, dW3, dg3, dbe3, db3, dW2, dg2, dbe2, db2, dW1, dg1, dbe1, db1);
     return facl_launch_status();
 }

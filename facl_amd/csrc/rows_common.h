@@ -3,14 +3,14 @@
 // the max-pool compare and the max|dy| bookkeeping.  The library is built with -ffp-contract=off and the one fused operation is
 // an explicit fmaf, so an expression written here gives the same bits in every kernel it is inlined into.
 #pragma once
-#include "common.h"
+#include "bn_consts.h"
 
 // all pointers 16-byte aligned (the float4 forms need it)
 template <class... P>
 static inline bool aligned16(const P*... p) { return !((... | (uintptr_t)p) & 15); }
 
 // ---- BatchNorm + ReLU, forward and backward, per element -------------------------------------------------------------------
-// consts "bnc" (5,C) = mean, invstd, scale, shift, sgn (facl_bn_finalize);  kk (2,C): k1 = dbeta/P, k2 = dgamma/P
+// consts "bnc" (5,C) = mean, invstd, scale, shift, sgn (bn_consts.h: BnRow);  kk (2,C): k1 = dbeta/P, k2 = dgamma/P
 __device__ __forceinline__ float bn_relu(float scale, float y, float shift) { return relu_nan(fmaf(scale, y, shift)); }
 // dz = dout * [z > 0]: the edge z == 0 and a NaN z both close the gate
 __device__ __forceinline__ float bn_relu_dz(float scale, float y, float shift, float dout) { return fmaf(scale, y, shift) > 0.f ? dout : 0.f; }
@@ -47,8 +47,8 @@ template <int W> struct BnLanes { typename lanes<W>::F mean, inv, scale, shift; 
 template <int W>
 __device__ __forceinline__ BnLanes<W> bn_lanes(const float* bnc, int C, int cw) {
     using F = typename lanes<W>::F;
-    return {reinterpret_cast<const F*>(bnc)[cw], reinterpret_cast<const F*>(bnc + C)[cw], reinterpret_cast<const F*>(bnc + 2 * C)[cw],
-            reinterpret_cast<const F*>(bnc + 3 * C)[cw]};
+    return {reinterpret_cast<const F*>(bn_row(bnc, C, BN_MEAN))[cw], reinterpret_cast<const F*>(bn_row(bnc, C, BN_INVSTD))[cw],
+            reinterpret_cast<const F*>(bn_row(bnc, C, BN_SCALE))[cw], reinterpret_cast<const F*>(bn_row(bnc, C, BN_SHIFT))[cw]};
 }
 template <int W> struct KkLanes { typename lanes<W>::F k1, k2; };
 template <int W>

@@ -146,12 +146,14 @@ def _stats(y, ws):
     return sums
 
 
-def _bn_bwd_consts(sums, C, count, reduce_fn):
-    """(dbeta, dgamma) fp64 sums -> fp32 parameter gradients of THIS rank + kk (2,C) = SyncBN-reduced sums / P."""
+def _bn_bwd_consts(sums, C, count, reduce_fn, sums_g=None):
+    """(dbeta, dgamma) fp64 sums -> fp32 parameter gradients of THIS rank + kk (2,C) = SyncBN-reduced sums / P.
+    `sums_g`: the already reduced sums (a caller that all-reduces several layers' sums at once); `reduce_fn` is then not called."""
     lib = _lib.load_library()
     f32 = dict(dtype=torch.float32, device=sums.device)
     dbeta, dgamma, kk = _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty((2, C), **f32)
-    sums_g = reduce_fn(sums.clone()) if reduce_fn is not None else sums
+    if sums_g is None:
+        sums_g = reduce_fn(sums.clone()) if reduce_fn is not None else sums
     _lib.check(lib.facl_bn_bwd_consts(_lib.ptr(sums), _lib.ptr(sums_g), C, float(count), _lib.ptr(dbeta), _lib.ptr(dgamma),
                                       _lib.ptr(kk), _lib.stream()), "facl_bn_bwd_consts")
     return dbeta, dgamma, kk
@@ -496,15 +498,12 @@ class _FCHead(torch.autograd.Function):
                                                    _lib.ptr(sums2[i]), _lib.ptr(ws), _lib.stream()), "facl_rows_bwd_stats")
             frozen = not ctx.training                            # eval mode: both segments share the running statistics
             sums2_g = ctx.reduce_fn(sums2.clone()) if ctx.reduce_fn is not None and not frozen else sums2   # one all-reduce for the pair
-            dbe, dga, kk = _lib.empty((2, C), **f32), _lib.empty((2, C), **f32), _lib.empty((2, 2, C), **f32)
             parts = []
             for i, ((r0, r1), bnc, count) in enumerate(zip(ctx.segs, (bnc_a, bnc_b), ctx.counts)):
                 if frozen:
                     part = _bn_bwd_consts_mode(sums2[i], bnc, C, count, None, False)
                 else:
-                    _lib.check(lib.facl_bn_bwd_consts(_lib.ptr(sums2[i]), _lib.ptr(sums2_g[i]), C, float(count), _lib.ptr(dbe[i]),
-                                                      _lib.ptr(dga[i]), _lib.ptr(kk[i]), _lib.stream()), "facl_bn_bwd_consts")
-                    part = (dbe[i], dga[i], kk[i], None)
+                    part = _bn_bwd_consts(sums2[i], C, count, None, sums_g=sums2_g[i]) + (None,)
                 _lib.check(lib.facl_rows_bwd_apply(_lib.ptr(dact[r0:r1]), _lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(bnc),
                                                    _lib.ptr(part[2]), _lib.ptr(dy[r0:r1]), _lib.stream()), "facl_rows_bwd_apply")
                 parts.append(part)

@@ -19,160 +19,165 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_l = ctypes.c_longlong
 
+
+class c_s(ctypes.c_void_p):
+    """The `void* stream` slot that closes an entry's signature: `call` fills it with the current stream."""
+
+
 # name -> argtypes; every function returns int.  Kept in one table so tests can check that the
 # library exports every symbol the header declares.
 SIGNATURES = {
     "facl_version": [],
-    "facl_fps_f32": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_fps_f64": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_fps_reorder": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p],
-    "facl_group": [c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p],
-    "facl_group_clips": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p],
-    "facl_gather_rows": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_p],
-    "facl_scatter_rows": [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p],
-    "facl_sinkhorn": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_kmeans": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
-    "facl_adam_prep": [c_p, c_p, c_f, c_f, c_p, c_p],
-    "facl_adam_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_p],
+    "facl_fps_f32": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_fps_f64": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_fps_reorder": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_s],
+    "facl_group": [c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_s],
+    "facl_group_clips": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_s],
+    "facl_gather_rows": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_s],
+    "facl_scatter_rows": [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_s],
+    "facl_sinkhorn": [c_p, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_kmeans": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_s],
+    "facl_adam_prep": [c_p, c_p, c_f, c_f, c_p, c_s],
+    "facl_adam_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_s],
     "facl_ws_bytes": [],
-    "facl_bn_finalize": [c_p, c_i, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_bn_finalize_after": [c_p, c_i, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
-    "facl_bn_eval_consts_after": [c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_p],
-    "facl_absmax": [c_p, c_l, c_p, c_p],
-    "facl_rows_act_amax": [c_p, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_bn_eval_consts": [c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p],
-    "facl_sa_x_moments": [c_p, c_l, c_i, c_p, c_p, c_p],
-    "facl_bn1_sums_from_moments": [c_p, c_d, c_i, c_p, c_p, c_p, c_p],
-    "facl_sa_bn1_chain": [c_p, c_d, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_l1tab": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_fwd2": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_fwd3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_fwd3_h3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_fwd3_f16": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_pool": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_eval": [c_p, c_l, c_i] + [c_p] * 12,
-    "facl_rows_stats": [c_p, c_l, c_i, c_p, c_p, c_p],
-    "facl_rows_bn_relu": [c_p, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_rows_segmax": [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p],
-    "facl_rows_bwd_stats": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_rows_bwd_apply": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_rows_bwd_apply_amax": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_segmax_bwd_stats": [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p],
-    "facl_segmax_bwd_stats_ymax": [c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p],
-    "facl_segmax_bwd_apply": [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p],
-    "facl_segmax_bwd_apply_amax": [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_fwd": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
-    "facl_gemm_fwd_segmax": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_dgrad": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p],
-    "facl_gemm_wgrad": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_p],
-    "facl_gemm_fwd_f16": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
-    "facl_gemm_fwd_segmax_f16": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_dgrad_f16": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p],
-    "facl_gemm_wgrad_f16": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_p],
-    "facl_gemm_wgrad_pro": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p],
-    "facl_gemm_wgrad_pro_x3": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p],
-    "facl_gemm_wgrad_h3": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
+    "facl_bn_finalize": [c_p, c_i, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_bn_finalize_after": [c_p, c_i, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_s],
+    "facl_bn_eval_consts_after": [c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_s],
+    "facl_absmax": [c_p, c_l, c_p, c_s],
+    "facl_rows_act_amax": [c_p, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_bn_eval_consts": [c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_s],
+    "facl_sa_x_moments": [c_p, c_l, c_i, c_p, c_p, c_s],
+    "facl_bn1_sums_from_moments": [c_p, c_d, c_i, c_p, c_p, c_p, c_s],
+    "facl_sa_bn1_chain": [c_p, c_d, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_l1tab": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_fwd2": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_fwd3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_fwd3_h3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_fwd3_f16": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_pool": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_eval": [c_p, c_l, c_i] + [c_p] * 11 + [c_s],
+    "facl_rows_stats": [c_p, c_l, c_i, c_p, c_p, c_s],
+    "facl_rows_bn_relu": [c_p, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_rows_segmax": [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_s],
+    "facl_rows_bwd_stats": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_rows_bwd_apply": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_rows_bwd_apply_amax": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_segmax_bwd_stats": [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_s],
+    "facl_segmax_bwd_stats_ymax": [c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_s],
+    "facl_segmax_bwd_apply": [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_s],
+    "facl_segmax_bwd_apply_amax": [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_fwd": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_s],
+    "facl_gemm_fwd_segmax": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_dgrad": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_s],
+    "facl_gemm_wgrad": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_s],
+    "facl_gemm_fwd_f16": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_s],
+    "facl_gemm_fwd_segmax_f16": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_dgrad_f16": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_s],
+    "facl_gemm_wgrad_f16": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_s],
+    "facl_gemm_wgrad_pro": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_s],
+    "facl_gemm_wgrad_pro_x3": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_s],
+    "facl_gemm_wgrad_h3": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_s],
     "facl_gemm_rs_wgrad_slices": [c_l, c_i, c_i],
-    "facl_gemm_rs_wgrad": [c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "facl_gemm_rs_wgrad": [c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
     "facl_gemm_rs_planes_bytes": [c_i, c_i, c_i],
-    "facl_gemm_rs_planes": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p],
-    "facl_gemm_rs_planes_multi": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p],
+    "facl_gemm_rs_planes": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_s],
+    "facl_gemm_rs_planes_multi": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_s],
     "facl_gemm_rs_supported": [c_l, c_i, c_i],
-    "facl_gemm_rs_fwd": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_rs_dgrad": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p],
-    "facl_gemm_rs_dgrad_bnstats": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_fwd_x3": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
-    "facl_gemm_fwd_segmax_x3": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_dgrad_x3": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p],
-    "facl_gemm_wgrad_x3": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_p],
-    "facl_sa_fwd3_x3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_contrast_pair": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
-    "facl_normalize_map": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p],
-    "facl_scale_rows2": [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p],
-    "facl_build_views_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
-    "facl_build_views_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
-    "facl_views_temporal_rows_f32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
-    "facl_views_temporal_rows_f64": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
-    "facl_build_views_philox_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
-    "facl_build_views_philox_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
-    "facl_build_views_philox_gp_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_build_views_philox_gp_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_resident_temporal_rows_f32": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
-    "facl_resident_temporal_rows_f64": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
-    "facl_build_views_resident_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_build_views_resident_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_build_views_resident_gp_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_build_views_resident_gp_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_build_views_philox_recipe_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
-    "facl_build_views_philox_recipe_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
-    "facl_build_views_resident_recipe_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
-    "facl_build_views_resident_recipe_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
+    "facl_gemm_rs_fwd": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_rs_dgrad": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_s],
+    "facl_gemm_rs_dgrad_bnstats": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_fwd_x3": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_s],
+    "facl_gemm_fwd_segmax_x3": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_dgrad_x3": [c_p, c_l, c_i, c_p, c_i, c_i, c_p, c_s],
+    "facl_gemm_wgrad_x3": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_s],
+    "facl_sa_fwd3_x3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_contrast_pair": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
+    "facl_normalize_map": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_s],
+    "facl_scale_rows2": [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_s],
+    "facl_build_views_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_p, c_s],
+    "facl_build_views_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_p, c_s],
+    "facl_views_temporal_rows_f32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
+    "facl_views_temporal_rows_f64": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
+    "facl_build_views_philox_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_s],
+    "facl_build_views_philox_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_s],
+    "facl_build_views_philox_gp_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_build_views_philox_gp_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_resident_temporal_rows_f32": [c_p, c_p, c_p, c_i, c_i, c_p, c_s],
+    "facl_resident_temporal_rows_f64": [c_p, c_p, c_p, c_i, c_i, c_p, c_s],
+    "facl_build_views_resident_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_build_views_resident_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_build_views_resident_gp_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_build_views_resident_gp_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_build_views_philox_recipe_f32": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_s],
+    "facl_build_views_philox_recipe_f64": [c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_s],
+    "facl_build_views_resident_recipe_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_s],
+    "facl_build_views_resident_recipe_f64": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_s],
     "facl_view_recipe_table": [c_p, c_i, c_p, c_p],
-    "facl_sa_bwd0": [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_bwd1": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_bwd_w3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_bwd2": [c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_bwd_consts3": [c_p, c_p, c_p, c_p, c_d, c_p, c_p, c_p],
-    "facl_sa_bwd_consts2": [c_p, c_p, c_d, c_p, c_p],
-    "facl_bn_bwd_consts": [c_p, c_p, c_i, c_d, c_p, c_p, c_p, c_p],
-    "facl_rows_center_wgrad": [c_p, c_p, c_l, c_i, c_p, c_p, c_p],
-    "facl_viewmax_fwd": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_viewmax_bwd": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
-    "facl_viewmax_bwd_add": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
-    "facl_sa_bwd_final": [c_p] * 13 + [c_i, c_d] + [c_p] * 9 + [c_p],
-    "facl_bn_bwd_consts_frozen": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_sa_bwd_consts3_frozen": [c_p, c_p, c_p],
-    "facl_sa_bwd_consts2_frozen": [c_p, c_p, c_p],
-    "facl_sa_bwd_final_frozen": [c_p] * 9 + [c_i] + [c_p] * 12 + [c_p],
-    "facl_viewmax_stack": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_fc_bn_stats": [c_p, c_l, c_l, c_i, c_p, c_p, c_p],
-    "facl_fc_bn_apply": [c_p, c_l, c_l, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p],
-    "facl_fc_bn_bwd_stats": [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_p],
-    "facl_fc_bn_bwd_apply": [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_d, c_d, c_p, c_p, c_p, c_p, c_p],
-    "facl_col_sums": [c_p, c_l, c_i, c_p, c_p],
-    "facl_contrast_pair_sum": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_gemm_wgrad_acc": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_i, c_p],
-    "facl_contrast_pair_sum_mask": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_loss_rows_fwd": [c_p, c_l, c_i, c_i, c_f, c_p, c_p, c_p],
-    "facl_loss_rows_bwd": [c_p, c_p, c_p, c_l, c_i, c_i, c_f, c_p, c_p],
-    "facl_contrast_pair_queue": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_queue_push": [c_p, c_i, c_i, c_p, c_i, c_p, c_p],
-    "facl_contrast_pair_sum_cls": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_contrast_pair_queue_cls": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_queue_push_ids": [c_p, c_i, c_p, c_i, c_p, c_p],
-    "facl_contrast_pair_sum_sup": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_p],
-    "facl_contrast_pair_queue_sup": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
-    "facl_ema_apply": [c_i, c_p, c_p, c_p, c_f, c_p],
-    "facl_grad_sqnorm": [c_i, c_p, c_p, c_p, c_p],
-    "facl_adam_prep_ex": [c_p, c_p, c_f, c_f, c_p, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_p],
-    "facl_adamw_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_p],
+    "facl_sa_bwd0": [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_bwd1": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_bwd_w3": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_bwd2": [c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_bwd_consts3": [c_p, c_p, c_p, c_p, c_d, c_p, c_p, c_s],
+    "facl_sa_bwd_consts2": [c_p, c_p, c_d, c_p, c_s],
+    "facl_bn_bwd_consts": [c_p, c_p, c_i, c_d, c_p, c_p, c_p, c_s],
+    "facl_rows_center_wgrad": [c_p, c_p, c_l, c_i, c_p, c_p, c_s],
+    "facl_viewmax_fwd": [c_p, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_viewmax_bwd": [c_p, c_p, c_i, c_i, c_i, c_p, c_s],
+    "facl_viewmax_bwd_add": [c_p, c_p, c_i, c_i, c_i, c_p, c_s],
+    "facl_sa_bwd_final": [c_p] * 13 + [c_i, c_d] + [c_p] * 9 + [c_s],
+    "facl_bn_bwd_consts_frozen": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_sa_bwd_consts3_frozen": [c_p, c_p, c_s],
+    "facl_sa_bwd_consts2_frozen": [c_p, c_p, c_s],
+    "facl_sa_bwd_final_frozen": [c_p] * 9 + [c_i] + [c_p] * 12 + [c_s],
+    "facl_viewmax_stack": [c_p, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_fc_bn_stats": [c_p, c_l, c_l, c_i, c_p, c_p, c_s],
+    "facl_fc_bn_apply": [c_p, c_l, c_l, c_i, c_p, c_p, c_i, c_i, c_d, c_d, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_s],
+    "facl_fc_bn_bwd_stats": [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_s],
+    "facl_fc_bn_bwd_apply": [c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_d, c_d, c_p, c_p, c_p, c_p, c_s],
+    "facl_col_sums": [c_p, c_l, c_i, c_p, c_s],
+    "facl_contrast_pair_sum": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_gemm_wgrad_acc": [c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_i, c_s],
+    "facl_contrast_pair_sum_mask": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_loss_rows_fwd": [c_p, c_l, c_i, c_i, c_f, c_p, c_p, c_s],
+    "facl_loss_rows_bwd": [c_p, c_p, c_p, c_l, c_i, c_i, c_f, c_p, c_s],
+    "facl_contrast_pair_queue": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_queue_push": [c_p, c_i, c_i, c_p, c_i, c_p, c_s],
+    "facl_contrast_pair_sum_cls": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_contrast_pair_queue_cls": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_queue_push_ids": [c_p, c_i, c_p, c_i, c_p, c_s],
+    "facl_contrast_pair_sum_sup": [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_p, c_s],
+    "facl_contrast_pair_queue_sup": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_ema_apply": [c_i, c_p, c_p, c_p, c_f, c_s],
+    "facl_grad_sqnorm": [c_i, c_p, c_p, c_p, c_s],
+    "facl_adam_prep_ex": [c_p, c_p, c_f, c_f, c_p, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_s],
+    "facl_adamw_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_s],
     "facl_mailbox_bytes": [c_i, c_i],
     "facl_mailbox_alloc": [c_l, c_p, c_p],
     "facl_mailbox_open": [c_p, c_p],
     "facl_mailbox_close": [c_p],
     "facl_mailbox_free": [c_p],
-    "facl_mailbox_allreduce": [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p],
-    "facl_gen3dv_frames": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
-    "facl_gen3dv_voxelise": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_d, c_p, c_p, c_p, c_p, c_p],
-    "facl_gen3dv_volumes": [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_p],
-    "facl_gen3dv_filter": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p],
-    "facl_gen3dv_compact": [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_p],
-    "facl_gen3dv_sample": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "facl_mailbox_allreduce": [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_s],
+    "facl_gen3dv_frames": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_s],
+    "facl_gen3dv_voxelise": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_l, c_d, c_p, c_p, c_p, c_p, c_s],
+    "facl_gen3dv_volumes": [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_s],
+    "facl_gen3dv_filter": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_s],
+    "facl_gen3dv_compact": [c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_s],
+    "facl_gen3dv_sample": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_s],
     "facl_gen3dv_app": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_l, c_p, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_i, c_l, c_d,
-                        c_p, c_p, c_p, c_p, c_p],
+                        c_p, c_p, c_p, c_p, c_s],
     "facl_knn_ws_bytes": [c_i, c_i, c_i],
-    "facl_knn_topk": [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_knn_vote": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p],
-    "facl_cls_gather_norm_fwd": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
-    "facl_cls_gather_norm_bwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
-    "facl_softmax_ce": [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
-    "facl_cls_probs_acc": [c_p, c_i, c_i, c_i, c_p, c_i, c_p],
-    "facl_cls_topk": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "facl_knn_topk": [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_knn_vote": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_s],
+    "facl_cls_gather_norm_fwd": [c_p, c_i, c_i, c_i, c_p, c_p, c_s],
+    "facl_cls_gather_norm_bwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_s],
+    "facl_softmax_ce": [c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
+    "facl_cls_probs_acc": [c_p, c_i, c_i, c_i, c_p, c_i, c_s],
+    "facl_cls_topk": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
     "facl_cluster_ws_bytes": [c_i, c_i, c_i],
-    "facl_cluster_row_inv": [c_p, c_i, c_i, c_i, c_p, c_p],
-    "facl_cluster_sums": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
+    "facl_cluster_row_inv": [c_p, c_i, c_i, c_i, c_p, c_s],
+    "facl_cluster_sums": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_s],
     "facl_proto_nce_ws_bytes": [c_i],
-    "facl_proto_nce": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    "facl_proto_nce": [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_s],
 }
 RESTYPE_I64 = {"facl_ws_bytes", "facl_gemm_rs_planes_bytes", "facl_mailbox_bytes", "facl_knn_ws_bytes", "facl_cluster_ws_bytes",
                "facl_proto_nce_ws_bytes"}
@@ -202,13 +207,55 @@ def load_library():
     return lib
 
 
-_ERR = {-1: "unsupported shape", -2: "NULL pointer", -3: "misaligned pointer", -4: "unsupported configuration"}
+E_SHAPE, E_NULL, E_ALIGN, E_CONFIG = -1, -2, -3, -4          # include/facl_hip.h: FACL_E_<NAME>
+_ERR = {E_SHAPE: "unsupported shape", E_NULL: "NULL pointer", E_ALIGN: "misaligned pointer", E_CONFIG: "unsupported configuration"}
 
 
 def check(rc, what):
     if rc != 0:
         msg = _ERR.get(rc, f"hipError {rc}")
         raise RuntimeError(f"{what} failed: {msg} (code {rc})")
+
+
+def _invoke(name, args, stream_):
+    """The C entry `name` on `args`: tensors as their device pointers, the stream slot filled, the count checked against
+    SIGNATURES[name] (not fn.argtypes: a stand-in for the library need not carry them).  The function is looked up at call
+    time, so whatever `load_library` returns now serves the call."""
+    sig = SIGNATURES[name]
+    if stream_ is not None:
+        args += (stream_,)
+    elif len(args) == len(sig) - 1 and sig[-1] is c_s:
+        args += (stream(),)
+    if len(args) != len(sig):
+        raise TypeError("%s takes %d arguments%s, %d given"
+                        % (name, len(sig), " (the stream may be left out)" if sig and sig[-1] is c_s else "", len(args)))
+    return getattr(load_library(), name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args])
+
+
+def call(name, *args, stream=None, detail=None, accept=()):
+    """Launch the C entry `name`.  A tensor stands for its `data_ptr()`, None for NULL, everything else (numbers, the host arrays
+    of `ptr_array` / `int_array`, raw addresses) goes through as it is.  An entry whose last slot is the stream (c_s) gets the
+    current stream when that argument is left out; `stream=` names another one.  A non-zero return code raises through `check`
+    under the entry's name (`detail`: shapes to add to the message) unless it is listed in `accept`: then it is returned, 0 on
+    success -- `accept=(E_CONFIG,)` is how a caller learns that a fused kernel does not serve the shape and falls back."""
+    rc = _invoke(name, args, stream)
+    if rc != 0 and rc not in accept:
+        check(rc, name if detail is None else "%s(%s)" % (name, detail))
+    return rc
+
+
+def call_size(name, *args, detail=None):
+    """The value of an entry that returns a size or a count instead of a status (RESTYPE_I64, facl_gemm_rs_wgrad_slices,
+    facl_gemm_rs_supported); a negative one is its refusal and raises like `call`."""
+    n = _invoke(name, args, None)
+    if n < 0:
+        check(n, name if detail is None else "%s(%s)" % (name, detail))
+    return n
+
+
+def env_on(name, default="1"):
+    """A/B switch from the environment: on unless set to 0."""
+    return os.environ.get(name, default) != "0"
 
 
 AMAX_WORDS = 2048          # include/facl_hip.h: FACL_AMAX_WORDS

@@ -20,7 +20,6 @@ class _GatherNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, stacked, G, B):
-        lib = _lib.load_library()
         _lib.require_cuda(stacked)
         stacked = stacked.contiguous()
         R, C = stacked.shape
@@ -28,21 +27,18 @@ class _GatherNorm(torch.autograd.Function):
             raise ValueError("stacked has %d rows, expected G*B + B = %d" % (R, G * B + B))
         out = _lib.empty((B, (G + 1) * C), dtype=torch.float32, device=stacked.device)
         inv = _lib.empty((B,), dtype=torch.float32, device=stacked.device)
-        _lib.check(lib.facl_cls_gather_norm_fwd(_lib.ptr(stacked), G, B, C, _lib.ptr(out), _lib.ptr(inv), _lib.stream()),
-                   "facl_cls_gather_norm_fwd(G=%d, B=%d, C=%d)" % (G, B, C))
+        _lib.call("facl_cls_gather_norm_fwd", stacked, G, B, C, out, inv, detail="G=%d, B=%d, C=%d" % (G, B, C))
         ctx.save_for_backward(out, inv)
         ctx.dims = (G, B, C)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load_library()
         out, inv = ctx.saved_tensors
         G, B, C = ctx.dims
         dout = dout.contiguous()
         dstacked = _lib.empty((G * B + B, C), dtype=torch.float32, device=dout.device)
-        _lib.check(lib.facl_cls_gather_norm_bwd(_lib.ptr(dout), _lib.ptr(out), _lib.ptr(inv), G, B, C, _lib.ptr(dstacked),
-                                                _lib.stream()), "facl_cls_gather_norm_bwd(G=%d, B=%d, C=%d)" % (G, B, C))
+        _lib.call("facl_cls_gather_norm_bwd", dout, out, inv, G, B, C, dstacked, detail="G=%d, B=%d, C=%d" % (G, B, C))
         return dstacked, None, None
 
 
@@ -57,7 +53,6 @@ class _SoftmaxCE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels):
-        lib = _lib.load_library()
         _lib.require_cuda(logits, labels)
         if logits.dim() != 2 or logits.dtype != torch.float32:
             raise ValueError("logits must be a 2-D float32 tensor (got %s %s)" % (tuple(logits.shape), logits.dtype))
@@ -72,9 +67,8 @@ class _SoftmaxCE(torch.autograd.Function):
         stats = _lib.empty((2,), dtype=torch.int32, device=dev)
         want_grad = ctx.needs_input_grad[0]
         dlogits = _lib.empty((R, ncls), dtype=torch.float32, device=dev) if want_grad else None
-        _lib.check(lib.facl_softmax_ce(_lib.ptr(logits), logits.stride(0), _lib.ptr(labels), R, ncls, _lib.ptr(loss),
-                                       _lib.ptr(dlogits), _lib.ptr(stats), _lib.ptr(ws), _lib.stream()),
-                   "facl_softmax_ce(R=%d, ncls=%d)" % (R, ncls))
+        _lib.call("facl_softmax_ce", logits, logits.stride(0), labels, R, ncls, loss, dlogits, stats, ws,
+                  detail="R=%d, ncls=%d" % (R, ncls))
         ctx.has_grad = want_grad
         if want_grad:
             ctx.save_for_backward(dlogits)
@@ -98,7 +92,6 @@ def probs_acc(logits, acc=None, first=None):
     added to `acc` in place: the sum of the class probabilities over test-time draws.  `first` True with an `acc`: stored into
     it, whatever it held (the first draw into a preallocated tensor).  A row whose maximum is not finite becomes NaN.
     Returns `acc`."""
-    lib = _lib.load_library()
     _lib.require_cuda(logits, acc)
     if logits.dim() != 2 or logits.dtype != torch.float32:
         raise ValueError("logits must be a 2-D float32 tensor (got %s %s)" % (tuple(logits.shape), logits.dtype))
@@ -112,8 +105,7 @@ def probs_acc(logits, acc=None, first=None):
         acc = _lib.empty((R, ncls), dtype=torch.float64, device=logits.device)
     elif acc.dtype != torch.float64 or acc.shape != (R, ncls) or not acc.is_contiguous():
         raise ValueError("acc must be a contiguous float64 tensor of shape (%d, %d) (got %s %s)" % (R, ncls, tuple(acc.shape), acc.dtype))
-    _lib.check(lib.facl_cls_probs_acc(_lib.ptr(logits), logits.stride(0), R, ncls, _lib.ptr(acc), int(first), _lib.stream()),
-               "facl_cls_probs_acc(R=%d, ncls=%d)" % (R, ncls))
+    _lib.call("facl_cls_probs_acc", logits, logits.stride(0), R, ncls, acc, int(first), detail="R=%d, ncls=%d" % (R, ncls))
     return acc
 
 
@@ -121,7 +113,6 @@ def topk(acc, ndraws, k, labels=None):
     """The k classes of largest `acc` (R, ncls) float64 per row under (value descending, class ascending) -> (top_p (R, k)
     float32 = acc / ndraws, top_c (R, k) int32, rank (R,) int32 or None without `labels`): rank = the classes that precede the
     label in that order (0 = a top-1 hit), -1 in a NaN row, -2 for a label outside [0, ncls)."""
-    lib = _lib.load_library()
     _lib.require_cuda(acc, labels)
     if acc.dim() != 2 or acc.dtype != torch.float64 or not acc.is_contiguous():
         raise ValueError("acc must be a contiguous 2-D float64 tensor (got %s %s)" % (tuple(acc.shape), acc.dtype))
@@ -133,8 +124,8 @@ def topk(acc, ndraws, k, labels=None):
     top_p = _lib.empty((R, max(k, 0)), dtype=torch.float32, device=dev)
     top_c = _lib.empty((R, max(k, 0)), dtype=torch.int32, device=dev)
     rank = _lib.empty((R,), dtype=torch.int32, device=dev) if labels is not None else None
-    _lib.check(lib.facl_cls_topk(_lib.ptr(acc), R, ncls, ndraws, k, _lib.ptr(labels), _lib.ptr(top_p), _lib.ptr(top_c),
-                                 _lib.ptr(rank), _lib.stream()), "facl_cls_topk(R=%d, ncls=%d, ndraws=%d, k=%d)" % (R, ncls, ndraws, k))
+    _lib.call("facl_cls_topk", acc, R, ncls, ndraws, k, labels, top_p, top_c, rank,
+              detail="R=%d, ncls=%d, ndraws=%d, k=%d" % (R, ncls, ndraws, k))
     return top_p, top_c, rank
 
 

@@ -21,11 +21,9 @@ def row_inv(x):
     """(n,) float32: 1 / max(||x_i||, 1e-12) of every row, the sum of squares in fp64."""
     x = _rows(x, "features")
     n, C = x.shape
-    lib = _lib.load_library()
     with torch.cuda.device(x.device):
         inv = _lib.empty((n,), dtype=torch.float32, device=x.device)
-        _lib.check(lib.facl_cluster_row_inv(_lib.ptr(x), n, x.stride(0), C, _lib.ptr(inv), _lib.stream()),
-                   "facl_cluster_row_inv(n=%d, C=%d)" % (n, C))
+        _lib.call("facl_cluster_row_inv", x, n, x.stride(0), C, inv, detail="n=%d, C=%d" % (n, C))
     return inv
 
 
@@ -55,16 +53,12 @@ def cluster_sums(x, inv, order, offs, cent):
         if t.dtype != torch.int32 or tuple(t.shape) != (m,) or not t.is_contiguous():
             raise ValueError("%s must be contiguous int32 (%d,) (got %s %s)" % (what, m, t.dtype, tuple(t.shape)))
     dev = x.device
-    lib = _lib.load_library()
     with torch.cuda.device(dev):
-        nbytes = lib.facl_cluster_ws_bytes(n, K, C)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "facl_cluster_ws_bytes(n=%d, K=%d, C=%d)" % (n, K, C))
+        nbytes = _lib.call_size("facl_cluster_ws_bytes", n, K, C, detail="n=%d, K=%d, C=%d" % (n, K, C))
         ws = _lib.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
         err = torch.zeros((1,), dtype=torch.int32, device=dev)
-        _lib.check(lib.facl_cluster_sums(_lib.ptr(x), n, x.stride(0), C, _lib.ptr(inv), _lib.ptr(order), _lib.ptr(offs), K,
-                                         _lib.ptr(cent), _lib.ptr(err), _lib.ptr(ws), _lib.stream()),
-                   "facl_cluster_sums(n=%d, C=%d, K=%d)" % (n, C, K))
+        _lib.call("facl_cluster_sums", x, n, x.stride(0), C, inv, order, offs, K, cent, err, ws,
+                  detail="n=%d, C=%d, K=%d" % (n, C, K))
         e = int(err.item())
     if e:
         raise RuntimeError("facl_cluster_sums: %s (err %d)" % (" and ".join(

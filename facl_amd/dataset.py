@@ -243,11 +243,9 @@ class DiskBatches:
             return V.build_views_philox(d['src'], d['meta'], s.dt, self.seed, self.epoch, num_crop=self.num_crop,
                                         num_point=self.num_point, recipe=self.recipe)
         from . import _lib
-        lib = _lib.load_library()
         out = _lib.empty((V.NUM_CROP * B, V.NUM_POINT, 4), dtype=torch.float32, device=self.dev)
-        fn = lib.facl_build_views_f32 if s.dt == np.float32 else lib.facl_build_views_f64
-        _lib.check(fn(_lib.ptr(d['src']), d['src'].shape[0], 8, _lib.ptr(d['idx']), _lib.ptr(d['noise']), _lib.ptr(d['cs']),
-                      B, _lib.ptr(out), _lib.stream()), "facl_build_views")
+        _lib.call("facl_build_views_f32" if s.dt == np.float32 else "facl_build_views_f64", d['src'], d['src'].shape[0], 8, d['idx'],
+                  d['noise'], d['cs'], B, out)
         return out
 
     def __iter__(self):

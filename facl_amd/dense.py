@@ -37,27 +37,23 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, idx, S1):
-        lib = _lib.load_library()
         _lib.require_cuda(feat, idx)
         feat = feat.contiguous()
         M, S2, K = idx.shape
         C = feat.shape[1]
         out = _lib.empty((M * S2 * K, C), dtype=torch.float32, device=feat.device)
-        _lib.check(lib.facl_gather_rows(_lib.ptr(feat), C, M, S1, C, _lib.ptr(idx), S2 * K, None, _lib.ptr(out), C, 0,
-                                        _lib.stream()), "facl_gather_rows")
+        _lib.call("facl_gather_rows", feat, C, M, S1, C, idx, S2 * K, None, out, C, 0)
         ctx.save_for_backward(idx)
         ctx.dims = (M, S1, C, S2 * K)
         return out
 
     @staticmethod
     def backward(ctx, drows):
-        lib = _lib.load_library()
         idx, = ctx.saved_tensors
         M, S1, C, rpc = ctx.dims
         drows = drows.contiguous()
         dfeat = _lib.empty((M * S1, C), dtype=torch.float32, device=drows.device)
-        _lib.check(lib.facl_scatter_rows(_lib.ptr(drows), C, 0, M, S1, C, _lib.ptr(idx), rpc, _lib.ptr(dfeat), _lib.stream()),
-                   "facl_scatter_rows")
+        _lib.call("facl_scatter_rows", drows, C, 0, M, S1, C, idx, rpc, dfeat)
         return dfeat, None, None
 
 
@@ -75,7 +71,6 @@ def _group_points_2(points, sample_num_level2, K, r2):
     _lib.require_cuda(points)
     if points.dim() != 3 or points.shape[1] < 3:
         raise ValueError("points must be (B, 3+C, S1) channel-first")
-    lib = _lib.load_library()
     B, C3, S1 = points.shape
     S2 = int(sample_num_level2)
     rows = points.detach().float().transpose(1, 2).contiguous()                    # (B,S1,3+C); a no-copy if it was a view of this
@@ -84,8 +79,7 @@ def _group_points_2(points, sample_num_level2, K, r2):
     out = _lib.empty((B, S2, K, C3), dtype=torch.float32, device=points.device)
     xyz_g = xt.permute(0, 2, 3, 1).contiguous()
     if C3 > 3:
-        _lib.check(lib.facl_gather_rows(rows[:, :, 3:].data_ptr(), C3, B, S1, C3 - 3, _lib.ptr(idx), S2 * K, _lib.ptr(xyz_g),
-                                        _lib.ptr(out), C3, 3, _lib.stream()), "facl_gather_rows")
+        _lib.call("facl_gather_rows", rows[:, :, 3:], C3, B, S1, C3 - 3, idx, S2 * K, xyz_g, out, C3, 3)
     else:
         out.copy_(xyz_g)
     return out.permute(0, 3, 1, 2), points[:, 0:3, 0:S2].unsqueeze(3)              # (B,3+C,S2,K) view, (B,3,S2,1): :352

@@ -18,12 +18,11 @@ def farthest_point_sampling_batch(xyz, sample_num, start_idx):
     if start.numel() != M:
         raise ValueError("start_idx must have one entry per cloud")
     out = _lib.empty((M, sample_num), dtype=torch.int32, device=xyz.device)
-    lib = _lib.load_library()
-    fn = {torch.float32: lib.facl_fps_f32, torch.float64: lib.facl_fps_f64}.get(xyz.dtype)
+    fn = {torch.float32: "facl_fps_f32", torch.float64: "facl_fps_f64"}.get(xyz.dtype)
     if fn is None:
         raise TypeError("xyz must be float32 or float64")
     with _lib.timed("facl_fps"):
-        _lib.check(fn(_lib.ptr(xyz), M, N, ld, sample_num, _lib.ptr(start), _lib.ptr(out), _lib.stream()), "facl_fps")
+        _lib.call(fn, xyz, M, N, ld, sample_num, start, out)
     return out
 
 
@@ -39,9 +38,7 @@ def farthest_point_sampling_fast(pc, sample_num, start_idx=None):
 def _reorder(pts, picks, m):
     out = _lib.empty_like(pts)
     b, N, D = pts.shape
-    lib = _lib.load_library()
-    _lib.check(lib.facl_fps_reorder(_lib.ptr(pts), b, N, D, _lib.ptr(picks), m, _lib.ptr(out), _lib.stream()),
-               "facl_fps_reorder")
+    _lib.call("facl_fps_reorder", pts, b, N, D, picks, m, out)
     return out
 
 

@@ -166,14 +166,12 @@ def generate_clips(frames_list, names, rng=None, py_random=None, mode="numpy", s
         if mode == "numpy" and f.shape[0] > k and py_random is None:
             raise ValueError("clip %s has more than %d frames: mode numpy samples them from the random.Random it is given" % (n, k))
         chosen.append(choose_frames(f.shape[0], k, py_random, (seed, resolution, c) if mode == "philox" else None))
-    lib = _lib.load_library()
     with torch.cuda.device(dev):
-        return _run(lib, dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution, float(voxel_size), H, W, B,
+        return _run(dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution, float(voxel_size), H, W, B,
                     intermediates)
 
 
-def _run(lib, dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution, voxel, H, W, B, intermediates):
-    st = _lib.stream()
+def _run(dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution, voxel, H, W, B, intermediates):
     # frames: per clip its first file, then the chosen ones
     files = [[0] + c for c in chosen]
     first = np.cumsum([0] + [len(f) for f in files])               # frame offset of each clip
@@ -191,8 +189,7 @@ def _run(lib, dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution
     fcount = _lib.empty((NF,), dtype=torch.int32, device=dev)
     fext = _lib.empty((NF, 6), dtype=torch.float64, device=dev)
     with _lib.timed("gen3dv_frames"):
-        _lib.check(lib.facl_gen3dv_frames(_lib.ptr(frames), NF, H, W, _lib.ptr(fbox), _lib.ptr(fcount), _lib.ptr(fext), st),
-                   "facl_gen3dv_frames")
+        _lib.call("facl_gen3dv_frames", frames, NF, H, W, fbox, fcount, fext)
     h_box, h_cnt, h_ext = fbox.cpu().numpy(), fcount.cpu().numpy(), fext.cpu().numpy()      # first of two small copies back
 
     fmeta = np.zeros((NF, 4), dtype=np.int32)
@@ -227,19 +224,15 @@ def _run(lib, dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution
     keyf = _lib.empty((NV,), dtype=torch.int32, device=dev)
     lists = _lib.empty((12 * NV,), dtype=torch.int32, device=dev)
     counts = _lib.empty((B, 4), dtype=torch.int32, device=dev)
-    P = _lib.ptr
     with _lib.timed("gen3dv_voxelise"):
-        _lib.check(lib.facl_gen3dv_voxelise(P(frames), NF, H, W, P(fbox), P(d_fmeta), P(d_cmin), P(d_cgrid), B, maxF, maxvox, NV,
-                                            NP, voxel, P(occ[0]), P(occ[1]), P(pix), P(err), st), "facl_gen3dv_voxelise")
+        _lib.call("facl_gen3dv_voxelise", frames, NF, H, W, fbox, d_fmeta, d_cmin, d_cgrid, B, maxF, maxvox, NV, NP, voxel,
+                  occ[0], occ[1], pix, err)
     with _lib.timed("gen3dv_volumes"):
-        _lib.check(lib.facl_gen3dv_volumes(P(occ[0]), P(occ[1]), P(d_wtab), P(d_cgrid), B, maxvox, NV, P(vol), P(key), st),
-                   "facl_gen3dv_volumes")
+        _lib.call("facl_gen3dv_volumes", occ[0], occ[1], d_wtab, d_cgrid, B, maxvox, NV, vol, key)
     with _lib.timed("gen3dv_filter"):
-        _lib.check(lib.facl_gen3dv_filter(P(vol), P(key), P(d_cgrid), B, maxvox, NV, TH_ALL, TH_KEY, P(vol0f), P(keyf), st),
-                   "facl_gen3dv_filter")
+        _lib.call("facl_gen3dv_filter", vol, key, d_cgrid, B, maxvox, NV, TH_ALL, TH_KEY, vol0f, keyf)
     with _lib.timed("gen3dv_compact"):
-        _lib.check(lib.facl_gen3dv_compact(P(vol), P(vol0f), P(keyf), P(d_cgrid), B, maxvox, NV, P(lists), P(counts), st),
-                   "facl_gen3dv_compact")
+        _lib.call("facl_gen3dv_compact", vol, vol0f, keyf, d_cgrid, B, maxvox, NV, lists, counts)
     h_counts = counts.cpu().numpy()                                    # second small copy: the draws' sizes depend on it
     _raise_err(err, "voxelise")
     for b in range(B):
@@ -267,13 +260,11 @@ def _run(lib, dev, frames_list, names, crcs, chosen, rng, mode, seed, resolution
     out_app = _lib.empty((NA, SAMPLE, 4), dtype=torch.float64, device=dev)
     norm = _lib.empty((B, 14), dtype=torch.float64, device=dev)
     with _lib.timed("gen3dv_sample"):
-        _lib.check(lib.facl_gen3dv_sample(P(vol), P(vol0f), P(lists), P(counts), P(d_cgrid), B, maxvox, NV, P(d_idx), int(seed),
-                                          int(resolution), P(d_crc), P(out_raw), P(out_key), P(norm), P(err), st),
-                   "facl_gen3dv_sample")
+        _lib.call("facl_gen3dv_sample", vol, vol0f, lists, counts, d_cgrid, B, maxvox, NV, d_idx, int(seed), int(resolution),
+                  d_crc, out_raw, out_key, norm, err)
     with _lib.timed("gen3dv_app"):
-        _lib.check(lib.facl_gen3dv_app(P(frames), NF, H, W, P(d_fmeta), P(fcount), P(pix), NP, P(d_ameta), NA, P(d_aidx),
-                                       int(seed), int(resolution), P(d_crc), P(d_cmin), P(d_cgrid), B, maxvox, NV, voxel,
-                                       P(vol0f), P(norm), P(out_app), P(err), st), "facl_gen3dv_app")
+        _lib.call("facl_gen3dv_app", frames, NF, H, W, d_fmeta, fcount, pix, NP, d_ameta, NA, d_aidx, int(seed),
+                  int(resolution), d_crc, d_cmin, d_cgrid, B, maxvox, NV, voxel, vol0f, norm, out_app, err)
     raw, keyc, app = out_raw.cpu().numpy(), out_key.cpu().numpy(), out_app.cpu().numpy()
     _raise_err(err, "sample")
     a0 = np.cumsum([0] + [len(c) for c in app_choice])

@@ -55,9 +55,8 @@ class KeyEncoder:
 
     def update(self):
         """k <- m k + (1 - m) q over all parameters: one launch on the current stream."""
-        lib = _lib.load_library()
-        _lib.check(lib.facl_ema_apply(self.nt, self._pk, self._p, self._n, self.momentum, _lib.stream()),
-                   "facl_ema_apply(nt=%d, m=%r)" % (self.nt, self.momentum))
+        _lib.call("facl_ema_apply", self.nt, self._pk, self._p, self._n, self.momentum,
+                  detail="nt=%d, m=%r" % (self.nt, self.momentum))
 
     # ---- state: the copy's own, in the model's format
     def state_dict(self):

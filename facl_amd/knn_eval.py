@@ -45,17 +45,13 @@ def knn_topk(queries, bank, k, self_idx=None):
     k = int(k)
     dev = queries.device
     sidx = _int32(self_idx, nq, "self_idx", dev)
-    lib = _lib.load_library()
     with torch.cuda.device(dev):
-        nbytes = lib.facl_knn_ws_bytes(nq, nb, k)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "facl_knn_ws_bytes(nq=%d, nb=%d, k=%d)" % (nq, nb, k))
+        nbytes = _lib.call_size("facl_knn_ws_bytes", nq, nb, k, detail="nq=%d, nb=%d, k=%d" % (nq, nb, k))
         ws = _lib.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
         val = _lib.empty((nq, k), dtype=torch.float32, device=dev)
         idx = _lib.empty((nq, k), dtype=torch.int32, device=dev)
-        _lib.check(lib.facl_knn_topk(_lib.ptr(queries), nq, queries.stride(0), _lib.ptr(bank), nb, bank.stride(0), C, k,
-                                     _lib.ptr(sidx), _lib.ptr(val), _lib.ptr(idx), _lib.ptr(ws), _lib.stream()),
-                   "facl_knn_topk(nq=%d, nb=%d, C=%d, k=%d)" % (nq, nb, C, k))
+        _lib.call("facl_knn_topk", queries, nq, queries.stride(0), bank, nb, bank.stride(0), C, k, sidx, val, idx, ws,
+                  detail="nq=%d, nb=%d, C=%d, k=%d" % (nq, nb, C, k))
     return val, idx
 
 
@@ -69,13 +65,11 @@ def knn_vote(values, indices, bank_labels, num_class, T=0.1):
     indices = indices.to(torch.int32).contiguous()
     labels = bank_labels.to(device=dev, dtype=torch.int32).contiguous()
     num_class = int(num_class)
-    lib = _lib.load_library()
     with torch.cuda.device(dev):
         pred = _lib.empty((nq,), dtype=torch.int32, device=dev)
         scores = _lib.empty((nq, max(num_class, 0)), dtype=torch.float32, device=dev)
-        _lib.check(lib.facl_knn_vote(_lib.ptr(values), _lib.ptr(indices), _lib.ptr(labels), nq, labels.shape[0], k, num_class,
-                                     1.0 / T, _lib.ptr(pred), _lib.ptr(scores), _lib.stream()),
-                   "facl_knn_vote(nq=%d, k=%d, num_class=%d)" % (nq, k, num_class))
+        _lib.call("facl_knn_vote", values, indices, labels, nq, labels.shape[0], k, num_class, 1.0 / T, pred, scores,
+                  detail="nq=%d, k=%d, num_class=%d" % (nq, k, num_class))
     return pred, scores
 
 

@@ -19,14 +19,13 @@ class OneShotAllReduce:
     failed to post in time (device error word; reads back = synchronises: call it outside the hot loop)."""
 
     def __init__(self, group=None, n_max=4608):
-        lib = _lib.load_library()
-        self.lib, self.group, self.n_max = lib, group, int(n_max)
+        self.group, self.n_max = group, int(n_max)
         self.rank, self.R = dist.get_rank(group), dist.get_world_size(group)
         self.device = torch.device("cuda", torch.cuda.current_device())
-        nbytes = lib.facl_mailbox_bytes(self.R, self.n_max)
+        nbytes = _lib.call_size("facl_mailbox_bytes", self.R, self.n_max)
         own = ctypes.c_void_p()
         handle = (ctypes.c_char * 64)()
-        _lib.check(lib.facl_mailbox_alloc(nbytes, ctypes.byref(own), handle), "facl_mailbox_alloc")
+        _lib.call("facl_mailbox_alloc", nbytes, ctypes.byref(own), handle)
         self._own = own
         handles = [None] * self.R
         dist.all_gather_object(handles, bytes(handle.raw), group=group)
@@ -37,7 +36,7 @@ class OneShotAllReduce:
                 continue
             p = ctypes.c_void_p()
             buf = (ctypes.c_char * 64).from_buffer_copy(h)
-            _lib.check(lib.facl_mailbox_open(buf, ctypes.byref(p)), "facl_mailbox_open (peer %d)" % r)
+            _lib.call("facl_mailbox_open", buf, ctypes.byref(p), detail="peer %d" % r)
             ptrs.append(p.value)
             self._opened.append(p)
         self.boxes = torch.tensor(ptrs, dtype=torch.int64, device=self.device)          # device array of R pointers
@@ -49,9 +48,7 @@ class OneShotAllReduce:
     def __call__(self, t):
         if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() > self.n_max:
             raise RuntimeError("OneShotAllReduce takes contiguous fp64 CUDA tensors of at most %d elements" % self.n_max)
-        _lib.check(self.lib.facl_mailbox_allreduce(_lib.ptr(t), _lib.ptr(t), t.numel(), self.n_max, _lib.ptr(self.boxes), self.rank,
-                                                   self.R, _lib.ptr(self.seq), _lib.ptr(self.err), _lib.stream()),
-                   "facl_mailbox_allreduce")
+        _lib.call("facl_mailbox_allreduce", t, t, t.numel(), self.n_max, self.boxes, self.rank, self.R, self.seq, self.err)
         return t
 
     def check(self):
@@ -61,8 +58,8 @@ class OneShotAllReduce:
     def close(self):
         torch.cuda.synchronize()
         for p in self._opened:
-            self.lib.facl_mailbox_close(p)
+            _lib.call_size("facl_mailbox_close", p)       # teardown: the hipError_t it returns is not acted on
         self._opened = []
         if self._own is not None:
-            self.lib.facl_mailbox_free(self._own)
+            _lib.call_size("facl_mailbox_free", self._own)
             self._own = None

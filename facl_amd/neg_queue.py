@@ -48,15 +48,13 @@ class NegativeQueue:
         if (ids is not None) != (self.ids is not None):
             raise ValueError("a queue %s ids was pushed rows %s them" % (("without", "with") if self.ids is None else ("with", "without")))
         rows = rows.detach().contiguous()
-        lib = _lib.load_library()
         if ids is not None:
             _lib.require_cuda(ids)
             if ids.dtype != torch.int32 or tuple(ids.shape) != (self.P,) or not ids.is_contiguous():
                 raise ValueError("push takes contiguous int32 (%d,) ids, got %s %s" % (self.P, ids.dtype, tuple(ids.shape)))
-            _lib.check(lib.facl_queue_push_ids(_lib.ptr(ids), self.P, _lib.ptr(self.ids), self.L, _lib.ptr(self.state),
-                                               _lib.stream()), "facl_queue_push_ids(P=%d, L=%d)" % (self.P, self.L))
-        _lib.check(lib.facl_queue_push(_lib.ptr(rows), self.P, self.C, _lib.ptr(self.buf), self.L, _lib.ptr(self.state),
-                                       _lib.stream()), "facl_queue_push(P=%d, C=%d, L=%d)" % (self.P, self.C, self.L))
+            _lib.call("facl_queue_push_ids", ids, self.P, self.ids, self.L, self.state, detail="P=%d, L=%d" % (self.P, self.L))
+        _lib.call("facl_queue_push", rows, self.P, self.C, self.buf, self.L, self.state,
+                  detail="P=%d, C=%d, L=%d" % (self.P, self.C, self.L))
 
     def head_valid(self):
         """(head, valid) read back to the host (synchronises; tests and logs only)."""

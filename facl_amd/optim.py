@@ -124,12 +124,10 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self):
-        lib = _lib.load_library()
         self.sync_lr()
         act = [p for p in self.params if p.grad is not None]
         if not act:
             return
-        st = _lib.stream()
         nt = len(act)
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in act]
         P, G = _lib.ptr_array(act), _lib.ptr_array(grads)
@@ -137,22 +135,18 @@ class FusedAdam:
         V = _lib.ptr_array([self.state[p]["exp_avg_sq"] for p in act])
         N = _lib.int_array([p.numel() for p in act])
         if not self.recipe:
-            _lib.check(lib.facl_adam_prep(_lib.ptr(self._lr), _lib.ptr(self._step), self.betas[0], self.betas[1],
-                                          _lib.ptr(self._consts), st), "facl_adam_prep")
-            _lib.check(lib.facl_adam_apply(nt, P, G, M, V, N, _lib.ptr(self._consts), self.betas[0], self.betas[1], self.eps, st),
-                       "facl_adam_apply")
+            _lib.call("facl_adam_prep", self._lr, self._step, self.betas[0], self.betas[1], self._consts)
+            _lib.call("facl_adam_apply", nt, P, G, M, V, N, self._consts, self.betas[0], self.betas[1], self.eps)
             return
         npartial = 0
         if self.max_grad_norm:
             npartial = sum((p.numel() + CHUNK - 1) // CHUNK for p in act)
-            _lib.check(lib.facl_grad_sqnorm(nt, G, N, _lib.ptr(self._partial), st), "facl_grad_sqnorm")
-        _lib.check(lib.facl_adam_prep_ex(_lib.ptr(self._lr), _lib.ptr(self._step), self.betas[0], self.betas[1],
-                                         _lib.ptr(self._partial), npartial, self.max_grad_norm, SCHEDULES[self.schedule],
-                                         self.warmup_steps, self.decay_steps, self.lr_min, _lib.ptr(self._consts), st),
-                   "facl_adam_prep_ex")
+            _lib.call("facl_grad_sqnorm", nt, G, N, self._partial)
+        _lib.call("facl_adam_prep_ex", self._lr, self._step, self.betas[0], self.betas[1], self._partial, npartial,
+                  self.max_grad_norm, SCHEDULES[self.schedule], self.warmup_steps, self.decay_steps, self.lr_min, self._consts)
         D = _lib.int_array([self._decay[p] for p in act])
-        _lib.check(lib.facl_adamw_apply(nt, P, G, M, V, N, D, _lib.ptr(self._consts), self.betas[0], self.betas[1], self.eps,
-                                        self.weight_decay, st), "facl_adamw_apply")
+        _lib.call("facl_adamw_apply", nt, P, G, M, V, N, D, self._consts, self.betas[0], self.betas[1], self.eps,
+                  self.weight_decay)
 
     def state_dict(self):
         """torch.optim.Adam's layout (state by parameter index), so either optimizer can resume the other's run."""

@@ -26,10 +26,7 @@ def buffers(dev, M, C, K):
     key = (dev.index, _lib.stream(), M, C, K)
     buf = _BUFFERS.get(key)
     if buf is None:
-        lib = _lib.load_library()
-        nbytes = lib.facl_proto_nce_ws_bytes(M)
-        if nbytes < 0:
-            _lib.check(int(nbytes), "facl_proto_nce_ws_bytes(M=%d)" % M)
+        nbytes = _lib.call_size("facl_proto_nce_ws_bytes", M, detail="M=%d" % M)
         buf = (_lib.empty((M, C), dtype=torch.float32, device=dev), _lib.empty((1,), dtype=torch.float32, device=dev),
                _lib.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev))
         _BUFFERS[key] = buf
@@ -48,7 +45,6 @@ def raise_if_err(err, K, what="proto_nce"):
 class _ProtoNCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stacked, classes, protos, proto_inv, scale):
-        lib = _lib.load_library()
         _lib.require_cuda(stacked, classes, protos, proto_inv, scale)
         if stacked.dim() != 2 or stacked.dtype != torch.float32:
             raise ValueError("stacked must be a 2-D float32 tensor (got %s %s)" % (tuple(stacked.shape), stacked.dtype))
@@ -69,9 +65,8 @@ class _ProtoNCE(torch.autograd.Function):
         dev = stacked.device
         with torch.cuda.device(dev):
             dstacked, loss, ws, err = buffers(dev, M, C, K)
-            _lib.check(lib.facl_proto_nce(_lib.ptr(stacked), M, stacked.stride(0), C, B, _lib.ptr(classes), _lib.ptr(protos),
-                                          _lib.ptr(proto_inv), _lib.ptr(scale), K, _lib.ptr(loss), _lib.ptr(dstacked), _lib.ptr(err),
-                                          _lib.ptr(ws), _lib.stream()), "facl_proto_nce(M=%d, C=%d, B=%d, K=%d)" % (M, C, B, K))
+            _lib.call("facl_proto_nce", stacked, M, stacked.stride(0), C, B, classes, protos, proto_inv, scale, K, loss,
+                      dstacked, err, ws, detail="M=%d, C=%d, B=%d, K=%d" % (M, C, B, K))
         ctx.save_for_backward(dstacked)
         ctx.mark_non_differentiable(err)
         return loss.view(()), err

@@ -194,8 +194,7 @@ class ResidentClips:
         self._pos = {v: i for i, v in enumerate(self.vids)}
         self.n = len(self.vids)
         tdt = torch.float64 if self.dtype == np.float64 else torch.float32
-        lib = _lib.load_library()
-        rt = lib.facl_resident_temporal_rows_f64 if self.dtype == np.float64 else lib.facl_resident_temporal_rows_f32
+        rt = "facl_resident_temporal_rows_f64" if self.dtype == np.float64 else "facl_resident_temporal_rows_f32"
         chunks = chunk_ranges(rows, self.dtype.itemsize, chunk_clips)
         first_row = table[:, 0]
         end_row = np.append(first_row[1:], self.rows_total)
@@ -235,8 +234,7 @@ class ResidentClips:
                         list(ex.map(lambda i: load_into(host, r0, i), range(a, b)))
                         with torch.cuda.stream(side):
                             self.src[r0:r1].copy_(stage[s][:r1 - r0], non_blocking=True)
-                            _lib.check(rt(_lib.ptr(self.src), _lib.ptr(self.table), _lib.ptr(self.lists), a, b - a,
-                                          _lib.ptr(self.err), side.cuda_stream), "facl_resident_temporal_rows")
+                            _lib.call(rt, self.src, self.table, self.lists, a, b - a, self.err, stream=side.cuda_stream)
                             done[s] = torch.cuda.Event()
                             done[s].record(side)
             finally:
@@ -275,8 +273,7 @@ def build_views_resident(res, sel, seed, epoch, return_idx=False, num_crop=V.NUM
     out = _lib.empty((G * B, P, 4), dtype=torch.float32, device=res.dev)
     idx = _lib.empty((B, G, P), dtype=torch.int64, device=res.dev) if return_idx else None
     V._call_view_entry("resident", res.dtype == np.float64, recipe, seed, lambda sd: (
-        _lib.ptr(res.src), _lib.ptr(res.table), _lib.ptr(res.lists), res.n, _lib.ptr(sel), B, G, P, sd, int(epoch), _lib.ptr(out),
-        _lib.ptr(idx), _lib.ptr(res.err)))
+        res.src, res.table, res.lists, res.n, sel, B, G, P, sd, int(epoch), out, idx, res.err))
     return (out, idx) if return_idx else out
 
 

@@ -9,9 +9,9 @@ import torch
 
 from . import _lib
 
-_FWD_H3 = __import__("os").environ.get("FACL_FWD_H3", "1") != "0"
+_FWD_H3 = _lib.env_on("FACL_FWD_H3")
 # eval mode through the ONE-kernel path (csrc/sa_eval.hip); FACL_EVAL_FUSED=0: the training passes with folded constants (A/B)
-_EVAL_FUSED = __import__("os").environ.get("FACL_EVAL_FUSED", "1") != "0"
+_EVAL_FUSED = _lib.env_on("FACL_EVAL_FUSED")
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 UNIT = 64
@@ -27,7 +27,7 @@ class _Workspace:
     def get(cls, device):
         key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
         if key not in cls._ws:
-            n = _lib.load_library().facl_ws_bytes()
+            n = _lib.call_size("facl_ws_bytes")
             cls._ws[key] = torch.empty(n, dtype=torch.uint8, device=device)
         if _lib.POISON:
             cls._ws[key].fill_(0xFF)                     # NaN bytes: every partial row a reduction reads must be rewritten
@@ -40,23 +40,18 @@ def _bn_finalize(sums, C, count, gamma, beta, running_mean, running_var, momentu
     `after`: the (5, C') constants of the layer in front.  The heavy passes apply that layer's ReLU as max(v, 0), which drops a
     NaN; a non-finite scale or shift there makes every statistic of this layer NaN instead (facl_bn_finalize_after), as the
     reference's are -- the same launch, nothing changes while the constants are finite."""
-    lib = _lib.load_library()
     bnc = _lib.empty((5, C), dtype=torch.float32, device=sums.device)
     prev, nprev = (None, 0) if after is None else (after[2], 2 * after.shape[1])       # rows 2..3: scale | shift, contiguous
-    _lib.check(lib.facl_bn_finalize_after(_lib.ptr(sums), C, float(count), _lib.ptr(gamma), _lib.ptr(beta), BN_EPS,
-                                          momentum, _lib.ptr(running_mean), _lib.ptr(running_var), _lib.ptr(bnc),
-                                          _lib.ptr(aamax), _lib.ptr(zamax), _lib.ptr(prev), nprev, _lib.stream()),
-               "facl_bn_finalize_after")
+    _lib.call("facl_bn_finalize_after", sums, C, float(count), gamma, beta, BN_EPS, momentum, running_mean, running_var, bnc,
+              aamax, zamax, prev, nprev)
     return bnc
 
 
 def act_amax_eval(y_rows, bnc, aamax):
     """Eval mode: running statistics say nothing about the data, so the activation maximum max relu(scale y + shift) is
     MEASURED (one streaming pass over the layer's raw output) into `aamax`."""
-    lib = _lib.load_library()
     R, C = y_rows.shape
-    _lib.check(lib.facl_rows_act_amax(_lib.ptr(y_rows), R, C, _lib.ptr(bnc[2]), _lib.ptr(bnc[3]), _lib.ptr(aamax), _lib.stream()),
-               "facl_rows_act_amax")
+    _lib.call("facl_rows_act_amax", y_rows, R, C, bnc[2], bnc[3], aamax)
 
 
 _FRAG_ORDER = {}
@@ -76,12 +71,9 @@ def _frag_channel_order(dev):
 def _bn_eval(C, gamma, beta, running_mean, running_var, after=None):
     """`after`: a float32 / int32 tensor the layer's input depends on; a non-finite word in it makes every constant NaN
     (facl_bn_eval_consts_after)."""
-    lib = _lib.load_library()
     bnc = _lib.empty((5, C), dtype=torch.float32, device=gamma.device)
-    _lib.check(lib.facl_bn_eval_consts_after(C, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean),
-                                             _lib.ptr(running_var), BN_EPS, _lib.ptr(bnc), _lib.ptr(after),
-                                             0 if after is None else after.numel(), _lib.stream()),
-               "facl_bn_eval_consts_after")
+    _lib.call("facl_bn_eval_consts_after", C, gamma, beta, running_mean, running_var, BN_EPS, bnc, after,
+              0 if after is None else after.numel())
     return bnc
 
 
@@ -109,7 +101,6 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
       * K | 64: every group is replicated 64/K times inside its unit.  Uniform replication leaves the batch mean,
         the biased variance, the max and (with P' = replicated count used consistently) every gradient unchanged;
         only the unbiased running-variance factor needs the true count."""
-    lib = _lib.load_library()
     _lib.require_cuda(x_rows)
     rep, R = 1, 1
     if K != UNIT:
@@ -128,7 +119,6 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         raise NotImplementedError("INPUT_FEATURE_NUM must be in %d..%d (got %d)" % (_lib.SA_D_MIN, _lib.SA_D_MAX, D))
     nunits = P // UNIT
     dev = x_rows.device
-    st = _lib.stream()
     ws = _Workspace.get(dev)
     f64 = dict(dtype=torch.float64, device=dev)
     count = float(P)
@@ -143,7 +133,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
     amax = _lib.amax_buffers(4, dev, zero=not training)
     if training:
         mom = _lib.empty(D + D * D, **f64)
-        _lib.check(lib.facl_sa_x_moments(_lib.ptr(x_rows), P, D, _lib.ptr(mom), _lib.ptr(ws), st), "facl_sa_x_moments")
+        _lib.call("facl_sa_x_moments", x_rows, P, D, mom, ws)
         ctx["mom_local"] = mom
         if reduce_fn is not None:
             mom = reduce_fn(mom.clone())
@@ -156,19 +146,17 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         # one single-wave launch (facl_sa_bn1_chain; bit-identical to facl_bn1_sums_from_moments + facl_bn_finalize + facl_sa_l1tab)
         bnc1 = _lib.empty((5, 64), dtype=torch.float32, device=dev)
         l1tab = _lib.empty((64, L1C), dtype=torch.float32, device=dev)
-        _lib.check(lib.facl_sa_bn1_chain(_lib.ptr(mom), count, D, _lib.ptr(W1), _lib.ptr(p["b1"]), _lib.ptr(p["g1"]), _lib.ptr(p["be1"]),
-                                         BN_EPS, BN_MOMENTUM, _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(sums1), _lib.ptr(bnc1),
-                                         _lib.ptr(amax[1]), _lib.ptr(l1tab), st), "facl_sa_bn1_chain")
+        _lib.call("facl_sa_bn1_chain", mom, count, D, W1, p["b1"], p["g1"], p["be1"], BN_EPS, BN_MOMENTUM, rm, rv, sums1, bnc1,
+                  amax[1], l1tab)
         if update_running and not direct:
             _running_update(bnc1, p["rm1"], p["rv1"], n_true)
         ctx["mom"] = mom
     else:
         bnc1 = _bn_eval(64, p["g1"], p["be1"], p["rm1"], p["rv1"])
         xa = amax[0]                                       # eval: the bound of a1 follows from max|x| (facl_sa_l1tab)
-        _lib.check(lib.facl_absmax(_lib.ptr(x_rows), x_rows.numel(), _lib.ptr(xa), st), "facl_absmax")
+        _lib.call("facl_absmax", x_rows, x_rows.numel(), xa)
         l1tab = _lib.empty((64, L1C), dtype=torch.float32, device=dev)
-        _lib.check(lib.facl_sa_l1tab(_lib.ptr(W1), _lib.ptr(p["b1"]), D, _lib.ptr(bnc1[2]), _lib.ptr(bnc1[3]),
-                                     _lib.ptr(l1tab), _lib.ptr(xa), _lib.ptr(amax[1]), st), "facl_sa_l1tab")
+        _lib.call("facl_sa_l1tab", W1, p["b1"], D, bnc1[2], bnc1[3], l1tab, xa, amax[1])
     if not training and not eval_backward and _EVAL_FUSED and precision in ("f32", "x3b") and _FWD_H3:
         # eval mode = the extraction path (extract_motion_feature.py:143-221): every BatchNorm is a constant affine, so the whole
         # block is ONE kernel per unit, x -> pooled, with nothing stored in between (csrc/sa_eval.hip)
@@ -176,17 +164,15 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         bnc3 = _bn_eval(256, p["g3"], p["be3"], p["rm3"], p["rv3"])
         pooled_u = _lib.empty((nunits, 256), dtype=torch.float32, device=dev)
         with _lib.timed("facl_sa_eval"):
-            _lib.check(lib.facl_sa_eval(_lib.ptr(x_rows), nunits, D, _lib.ptr(l1tab), _lib.ptr(W2), _lib.ptr(p["b2"]),
-                                        _lib.ptr(bnc2[2]), _lib.ptr(bnc2[3]), _lib.ptr(W3), _lib.ptr(p["b3"]), _lib.ptr(bnc3[2]),
-                                        _lib.ptr(bnc3[3]), _lib.ptr(pooled_u), _lib.ptr(amax[1]), st), "facl_sa_eval")
+            _lib.call("facl_sa_eval", x_rows, nunits, D, l1tab, W2, p["b2"], bnc2[2], bnc2[3], W3, p["b3"], bnc3[2], bnc3[3],
+                      pooled_u, amax[1])
         if R > 1:      # a group spans R units: BN + ReLU are monotone per channel, so the group's feature is the maximum of its units'
             pooled_u = pooled_u.view(nunits // R, R, 256).max(dim=1).values.contiguous()
         return pooled_u, {"amax": None, "nunits": nunits, "D": D, "R": R, "x_rows": x_rows}
     y2f = _lib.empty(nunits * UNIT * 64, dtype=torch.float32, device=dev)
     sums2 = _lib.empty((64, 2), **f64) if training else None
     with _lib.timed("facl_sa_fwd2"):
-        _lib.check(lib.facl_sa_fwd2(_lib.ptr(x_rows), nunits, D, _lib.ptr(l1tab), _lib.ptr(W2), _lib.ptr(p["b2"]),
-                                    _lib.ptr(y2f), _lib.ptr(sums2), _lib.ptr(ws), _lib.ptr(amax[1]), st), "facl_sa_fwd2")
+        _lib.call("facl_sa_fwd2", x_rows, nunits, D, l1tab, W2, p["b2"], y2f, sums2, ws, amax[1])
     if training:
         if reduce_fn is not None:
             reduce_fn(sums2)
@@ -201,8 +187,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         # per-float4 constants in that order
         lay = _frag_channel_order(dev)
         sc_l, sh_l = bnc2[2][lay].contiguous(), bnc2[3][lay].contiguous()
-        _lib.check(lib.facl_rows_act_amax(_lib.ptr(y2f), nunits, 4096, _lib.ptr(sc_l), _lib.ptr(sh_l), _lib.ptr(amax[2]), st),
-                   "facl_rows_act_amax")
+        _lib.call("facl_rows_act_amax", y2f, nunits, 4096, sc_l, sh_l, amax[2])
     sgn3 = p["g3"]                                                    # the kernels take sign(gamma3) themselves (sign(0) = +1)
     ymax = _lib.empty((nunits, 256), dtype=torch.float32, device=dev)
     arg = _lib.empty((nunits, 256), dtype=torch.uint8, device=dev)
@@ -210,12 +195,10 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
     with _lib.timed("facl_sa_fwd3"):
         # dense configuration: fp16-input 64->256 layer; "x3": the opt-in three-product variant (tail.precision)
         # "f32" / "x3b": the fp32-grade forward -- fp16x3 (csrc/common.h; FACL_FWD_H3=0 selects bf16x6 for A/B)
-        f32_fwd3 = lib.facl_sa_fwd3_h3 if _FWD_H3 else lib.facl_sa_fwd3
-        fwd3 = {"f32": f32_fwd3, "f16": lib.facl_sa_fwd3_f16, "x3": lib.facl_sa_fwd3_x3, "x3b": f32_fwd3}[precision]
-        extra = (_lib.ptr(amax[2]),) if fwd3 is lib.facl_sa_fwd3_h3 else ()
-        _lib.check(fwd3(_lib.ptr(y2f), nunits, _lib.ptr(bnc2[2]), _lib.ptr(bnc2[3]), _lib.ptr(W3),
-                                    _lib.ptr(p["b3"]), _lib.ptr(sgn3), _lib.ptr(ymax), _lib.ptr(arg), _lib.ptr(sums3),
-                                    _lib.ptr(ws), *extra, st), "facl_sa_fwd3")
+        f32_fwd3 = "facl_sa_fwd3_h3" if _FWD_H3 else "facl_sa_fwd3"
+        fwd3 = {"f32": f32_fwd3, "f16": "facl_sa_fwd3_f16", "x3": "facl_sa_fwd3_x3", "x3b": f32_fwd3}[precision]
+        extra = (amax[2],) if fwd3 == "facl_sa_fwd3_h3" else ()
+        _lib.call(fwd3, y2f, nunits, bnc2[2], bnc2[3], W3, p["b3"], sgn3, ymax, arg, sums3, ws, *extra)
     _lib.tap("sa_arg", arg)
     if training:
         if reduce_fn is not None:
@@ -234,8 +217,7 @@ def sa_mlp_forward(x_rows, p, training, reduce_fn=None, update_running=True, K=6
         ymax_g, rsel = ymax.view(ngroups, R, 256).max(dim=1)
         ymax_g = ymax_g.contiguous()
     pooled = _lib.empty((ngroups, 256), dtype=torch.float32, device=dev)
-    _lib.check(lib.facl_sa_pool(_lib.ptr(ymax_g), ngroups, 256, _lib.ptr(bnc3[2]), _lib.ptr(bnc3[3]), _lib.ptr(pooled),
-                                _lib.ptr(amax[3]), st), "facl_sa_pool")
+    _lib.call("facl_sa_pool", ymax_g, ngroups, 256, bnc3[2], bnc3[3], pooled, amax[3])
     if _lib.TAPS is not None and K == UNIT:          # tests only: the ReLU decisions of the three layers (tie-proof parity)
         xd, tb = x_rows.double(), l1tab.double()
         v = (tb[:, 0] * xd[:, :1] + tb[:, L1C - 4]).float().double()          # the kernels' sequential fp32 FMA chain
@@ -266,9 +248,7 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
     A forward in eval mode (``ctx["training"]`` False: BatchNorm frozen at its running statistics) runs the SAME heavy passes:
     every batch-statistic term reaches them through the tables G3 / h3 / bw2 only, which the frozen closed forms hand over
     without those terms; nothing is all-reduced, and b1, b2, b3 get real gradients."""
-    lib = _lib.load_library()
     dev = x_rows.device
-    st = _lib.stream()
     ws = _Workspace.get(dev)
     f64 = dict(dtype=torch.float64, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -278,14 +258,12 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
     W2 = p["W2"].reshape(64, 64)
     W3 = p["W3"].reshape(256, 64)
     dpooled = dpooled.contiguous()
-    ptr = _lib.ptr
 
     # ---- pass 0: sparse values + (dbeta3, dgamma3)
     ngroups, R = ctx["ngroups"], ctx["R"]
     coef = _lib.empty((ngroups, 256), **f32)
     sums0 = _lib.empty((256, 2), **f64)
-    _lib.check(lib.facl_sa_bwd0(ptr(dpooled), ptr(ctx["ymax"]), ngroups, ptr(bnc3), ptr(coef), ptr(sums0), ptr(ws), st),
-               "facl_sa_bwd0")
+    _lib.call("facl_sa_bwd0", dpooled, ctx["ymax"], ngroups, bnc3, coef, sums0, ws)
     if R > 1:                                    # route each group's sparse value to the unit that won the max
         cu = torch.zeros((ngroups, R, 256), **f32)
         cu.scatter_(1, ctx["rsel"].unsqueeze(1), coef.unsqueeze(1))
@@ -298,17 +276,15 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
         sums0 = reduce_fn(sums0.clone())
     G3, h3 = _lib.empty((64, 64), **f32), _lib.empty(64, **f32)
     if frozen:
-        _lib.check(lib.facl_sa_bwd_consts3_frozen(ptr(G3), ptr(h3), st), "facl_sa_bwd_consts3_frozen")
+        _lib.call("facl_sa_bwd_consts3_frozen", G3, h3)
     else:
-        _lib.check(lib.facl_sa_bwd_consts3(ptr(sums0), ptr(bnc3), ptr(W3), ptr(p["b3"]), P, ptr(G3), ptr(h3), st),
-                   "facl_sa_bwd_consts3")
+        _lib.call("facl_sa_bwd_consts3", sums0, bnc3, W3, p["b3"], P, G3, h3)
 
     # ---- pass 1: dz2 + (dbeta2, dgamma2)
     dz2f = _lib.empty_like(ctx["y2f"])
     sums1 = _lib.empty((64, 2), **f64)
     with _lib.timed("facl_sa_bwd1"):
-        _lib.check(lib.facl_sa_bwd1(ptr(ctx["y2f"]), nunits, ptr(bnc2), ptr(G3), ptr(h3), ptr(W3), ptr(coef),
-                                    ptr(ctx["arg"]), ptr(dz2f), ptr(sums1), ptr(ws), ptr(ctx["amax"][2]), st), "facl_sa_bwd1")
+        _lib.call("facl_sa_bwd1", ctx["y2f"], nunits, bnc2, G3, h3, W3, coef, ctx["arg"], dz2f, sums1, ws, ctx["amax"][2])
     sums1_l = sums1
     if reduce_fn is not None:
         sums1 = reduce_fn(sums1.clone())
@@ -317,18 +293,16 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
     # that pass 1 touched last are still in the memory-side cache (FACL_BWD2_REV=0: front to back)
     bw2 = _lib.empty((4, 64), **f32)
     if frozen:
-        _lib.check(lib.facl_sa_bwd_consts2_frozen(ptr(bnc2), ptr(bw2), st), "facl_sa_bwd_consts2_frozen")
+        _lib.call("facl_sa_bwd_consts2_frozen", bnc2, bw2)
     else:
-        _lib.check(lib.facl_sa_bwd_consts2(ptr(sums1), ptr(bnc2), P, ptr(bw2), st), "facl_sa_bwd_consts2")
+        _lib.call("facl_sa_bwd_consts2", sums1, bnc2, P, bw2)
     out2 = _lib.empty(_lib.sa_bwd2_out(D), **f64)
     with _lib.timed("facl_sa_bwd2"):
-        _lib.check(lib.facl_sa_bwd2(ptr(dz2f), ptr(ctx["y2f"]), ptr(x_rows), nunits, D, ptr(bw2), ptr(W2), ptr(ctx["l1tab"]),
-                                    ptr(out2), ptr(ws), ptr(ctx["amax"][1]), st), "facl_sa_bwd2")
+        _lib.call("facl_sa_bwd2", dz2f, ctx["y2f"], x_rows, nunits, D, bw2, W2, ctx["l1tab"], out2, ws, ctx["amax"][1])
     # ---- layer-3 weight gradient ingredients: sparse gather, Gram, sum a2
     out3 = _lib.empty(256 * 64 + 64 * 64 + 64, **f64)
     with _lib.timed("facl_sa_bwd_w3"):
-        _lib.check(lib.facl_sa_bwd_w3(ptr(ctx["y2f"]), nunits, ptr(bnc2), ptr(coef), ptr(ctx["arg"]), ptr(out3), ptr(ws),
-                                      ptr(ctx["amax"][2]), st), "facl_sa_bwd_w3")
+        _lib.call("facl_sa_bwd_w3", ctx["y2f"], nunits, bnc2, coef, ctx["arg"], out3, ws, ctx["amax"][2])
 
     g = {"W3": _lib.empty_like(p["W3"]), "g3": _lib.empty(256, **f32), "be3": _lib.empty(256, **f32),
          "W2": _lib.empty_like(p["W2"]), "g2": _lib.empty(64, **f32), "be2": _lib.empty(64, **f32),
@@ -337,18 +311,14 @@ def _sa_mlp_backward(ctx, dpooled, x_rows, p, reduce_fn=None):
          "b1": None, "b2": None, "b3": None}
     if frozen:                                   # ... and a real gradient behind a frozen one: sum dy = scale * dbeta
         g.update(b1=_lib.empty(64, **f32), b2=_lib.empty(64, **f32), b3=_lib.empty(256, **f32))
-        _lib.check(lib.facl_sa_bwd_final_frozen(ptr(out3), ptr(sums0), ptr(bnc3), ptr(out2), ptr(sums1), ptr(bnc2), ptr(bnc1),
-                                                ptr(W1), ptr(p["b1"]), D, ptr(g["W3"]), ptr(g["g3"]), ptr(g["be3"]), ptr(g["b3"]),
-                                                ptr(g["W2"]), ptr(g["g2"]), ptr(g["be2"]), ptr(g["b2"]), ptr(g["W1"]),
-                                                ptr(g["g1"]), ptr(g["be1"]), ptr(g["b1"]), st), "facl_sa_bwd_final_frozen")
+        _lib.call("facl_sa_bwd_final_frozen", out3, sums0, bnc3, out2, sums1, bnc2, bnc1, W1, p["b1"], D, g["W3"], g["g3"],
+                  g["be3"], g["b3"], g["W2"], g["g2"], g["be2"], g["b2"], g["W1"], g["g1"], g["be1"], g["b1"])
         return g
     R1_g = out2[4096:]                           # (sa_l1_cols(D), 64): rows x_0..x_{D-1}, sum dz1, zeros
     if reduce_fn is not None:
         R1_g = reduce_fn(R1_g.clone())
-    _lib.check(lib.facl_sa_bwd_final(ptr(out3), ptr(sums0), ptr(sums0_l), ptr(bnc3), ptr(W3), ptr(p["b3"]), ptr(out2),
-                                     ptr(sums1_l), ptr(R1_g), ptr(ctx["mom_local"]), ptr(bnc1), ptr(W1), ptr(p["b1"]),
-                                     D, P, ptr(g["W3"]), ptr(g["g3"]), ptr(g["be3"]), ptr(g["W2"]), ptr(g["g2"]),
-                                     ptr(g["be2"]), ptr(g["W1"]), ptr(g["g1"]), ptr(g["be1"]), st), "facl_sa_bwd_final")
+    _lib.call("facl_sa_bwd_final", out3, sums0, sums0_l, bnc3, W3, p["b3"], out2, sums1_l, R1_g, ctx["mom_local"], bnc1, W1,
+              p["b1"], D, P, g["W3"], g["g3"], g["be3"], g["W2"], g["g2"], g["be2"], g["W1"], g["g1"], g["be1"])
     return g
 
 

@@ -24,14 +24,12 @@ def shoot_infs(inp_tensor):
 def distributed_sinkhorn(Q, nmb_iters):
     """cn3d_model_conbag.py:391-406: Q (K prototypes, n samples) -> (n, K) float32; one HIP launch."""
     _lib.require_cuda(Q)
-    lib = _lib.load_library()
     with torch.no_grad():
         Qc = Q.detach().float().contiguous()
         R, C = Qc.shape
         scratch = _lib.empty(R * C + R, dtype=torch.float32, device=Q.device)
         out = _lib.empty((C, R), dtype=torch.float32, device=Q.device)
-        _lib.check(lib.facl_sinkhorn(_lib.ptr(Qc), R, C, int(nmb_iters), _lib.ptr(scratch), _lib.ptr(out), _lib.stream()),
-                   "facl_sinkhorn")
+        _lib.call("facl_sinkhorn", Qc, R, C, int(nmb_iters), scratch, out)
     return out
 
 
@@ -54,14 +52,12 @@ def KMeans(x, K=10, Niters=10, verbose=False):
     """cn3d_train_motion_GL.py:54-70.  Returns (labels (N,) int64, centroids (K, D)); the centroids are differentiable
     in x through the final scatter-mean, like the reference's."""
     _lib.require_cuda(x)
-    lib = _lib.load_library()
     xc = x.detach().float().contiguous()
     N, D = xc.shape
     labels = _lib.empty(N, dtype=torch.int32, device=x.device)
     cent = _lib.empty((K, D), dtype=torch.float32, device=x.device)
     counts = _lib.empty(K, dtype=torch.int32, device=x.device)
-    _lib.check(lib.facl_kmeans(_lib.ptr(xc), N, D, int(K), int(Niters), _lib.ptr(labels), _lib.ptr(cent), _lib.ptr(counts),
-                               _lib.stream()), "facl_kmeans")
+    _lib.call("facl_kmeans", xc, N, D, int(K), int(Niters), labels, cent, counts)
     return labels.long(), _SegmentMean.apply(x, labels, cent, counts)
 
 

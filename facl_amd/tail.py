@@ -5,7 +5,6 @@ fused bias / centre term / BN column statistics, dgrad, split-K wgrad); train-mo
 SyncBN hook), BN+ReLU apply, BN+ReLU+max over the S centroids without materialising the activation, and the
 matching backward passes are the row kernels of csrc/rows.hip.
 """
-import os
 import threading
 
 import torch
@@ -58,19 +57,9 @@ def backward_precision(p):
     return "x3" if p == "x3b" else p
 
 
-def _fn(lib, name, prec):
-    return getattr(lib, name + _SUFFIX[prec])
-
-
-def _env_on(name, default="1"):
-    """A/B switch from the environment: on unless set to 0."""
-    return os.environ.get(name, default) != "0"
-
-
 def gemm_fwd(a, W, bias, want_stats=False, centers=None, Wc=None, prec=None):
     """y = a W^T + bias [+ centers Wc^T] on the hand-written fp32 MFMA GEMM (csrc/gemm.hip); optional fused
     column (sum, sumsq) for the BatchNorm that follows."""
-    lib = _lib.load_library()
     M, K = a.shape
     N = W.shape[0]
     y = _lib.empty((M, N), dtype=torch.float32, device=a.device)
@@ -78,22 +67,19 @@ def gemm_fwd(a, W, bias, want_stats=False, centers=None, Wc=None, prec=None):
     ws = _Workspace.get(a.device)
     prec = current_precision() if prec is None else prec
     with _lib.timed("facl_gemm_fwd %dx%dx%d%s" % (M, K, N, _LABEL[prec])):
-        _lib.check(_fn(lib, "facl_gemm_fwd", prec)(_lib.ptr(a), M, K, _lib.ptr(W), W.stride(0), N, _lib.ptr(bias), None, None,
-                                     _lib.ptr(centers), _lib.ptr(Wc), 3 if Wc is not None else 0, _lib.ptr(y),
-                                     _lib.ptr(sums), _lib.ptr(ws), _lib.stream()), "facl_gemm_fwd")
+        _lib.call("facl_gemm_fwd" + _SUFFIX[prec], a, M, K, W, W.stride(0), N, bias, None, None, centers, Wc,
+                  3 if Wc is not None else 0, y, sums, ws)
     return y, sums
 
 
 def gemm_dgrad(dy, W, prec=None):
     """da = dy W   (W (N,K) row-major, possibly a column slice of a wider matrix)."""
-    lib = _lib.load_library()
     M, N = dy.shape
     K = W.shape[1]
     da = _lib.empty((M, K), dtype=torch.float32, device=dy.device)
     prec = current_precision() if prec is None else prec
     with _lib.timed("facl_gemm_dgrad %dx%dx%d%s" % (M, N, K, _LABEL[prec])):
-        _lib.check(_fn(lib, "facl_gemm_dgrad", prec)(_lib.ptr(dy), M, N, W.data_ptr(), W.stride(0), K, _lib.ptr(da), _lib.stream()),
-                   "facl_gemm_dgrad")
+        _lib.call("facl_gemm_dgrad" + _SUFFIX[prec], dy, M, N, W, W.stride(0), K, da)
     return da
 
 
@@ -106,24 +92,18 @@ def _wgrad_slices(M, N, K):
 def _wgrad_h3(dy, a, bnc, amax, amax_b, dW, slices, nz):
     """dW = dy^T a (with `bnc`: dy^T relu(bn(a))) in fp16x3 on the LDS-staged kernel.  False (nothing written) when the
     kernel does not serve the shape (FACL_E_CONFIG): the caller falls through to the bf16x6 kernels."""
-    lib = _lib.load_library()
     M, N = dy.shape
     K = a.shape[1]
     ps, pt = (bnc[2], bnc[3]) if bnc is not None else (None, None)
     with _lib.timed("facl_gemm_wgrad %dx%dx%d h3" % (M, N, K)):
-        rc = lib.facl_gemm_wgrad_h3(_lib.ptr(dy), _lib.ptr(a), M, N, K, a.stride(0), _lib.ptr(ps), _lib.ptr(pt), _lib.ptr(amax),
-                                    _lib.ptr(amax_b), _lib.ptr(dW), _lib.ptr(slices), nz, _lib.stream())
-    if rc == -4:
-        return False
-    _lib.check(rc, "facl_gemm_wgrad_h3")
-    return True
+        rc = _lib.call("facl_gemm_wgrad_h3", dy, a, M, N, K, a.stride(0), ps, pt, amax, amax_b, dW, slices, nz, accept=(_lib.E_CONFIG,))
+    return rc != _lib.E_CONFIG
 
 
 def gemm_wgrad(dy, a, prec=None, amax=None, amax_b=None):
     """dW = dy^T a, contraction over the rows split into slices (deterministic slice-order sum).  `amax` (the device-side
     max|dy| buffer of facl_rows_bwd_apply_amax) + `amax_b` (the bound of max|a| its forward GEMM used): fp16x3 arithmetic
     where the 128x128-tile kernel serves the shape."""
-    lib = _lib.load_library()
     M, N = dy.shape
     K = a.shape[1]
     nz = _wgrad_slices(M, N, K)
@@ -133,29 +113,25 @@ def gemm_wgrad(dy, a, prec=None, amax=None, amax_b=None):
     if amax is not None and amax_b is not None and prec == "f32" and _wgrad_h3(dy, a, None, amax, amax_b, dW, slices, nz):
         return dW
     with _lib.timed("facl_gemm_wgrad %dx%dx%d%s" % (M, N, K, _LABEL[prec])):
-        _lib.check(_fn(lib, "facl_gemm_wgrad", prec)(_lib.ptr(dy), _lib.ptr(a), M, N, K, a.stride(0), _lib.ptr(dW), _lib.ptr(slices), nz,
-                                       _lib.stream()), "facl_gemm_wgrad")
+        _lib.call("facl_gemm_wgrad" + _SUFFIX[prec], dy, a, M, N, K, a.stride(0), dW, slices, nz)
     return dW
 
 
 def _stats(y, ws):
-    lib = _lib.load_library()
     R, C = y.shape
     sums = _lib.empty((C, 2), dtype=torch.float64, device=y.device)
-    _lib.check(lib.facl_rows_stats(_lib.ptr(y), R, C, _lib.ptr(sums), _lib.ptr(ws), _lib.stream()), "facl_rows_stats")
+    _lib.call("facl_rows_stats", y, R, C, sums, ws)
     return sums
 
 
 def _bn_bwd_consts(sums, C, count, reduce_fn, sums_g=None):
     """(dbeta, dgamma) fp64 sums -> fp32 parameter gradients of THIS rank + kk (2,C) = SyncBN-reduced sums / P.
     `sums_g`: the already reduced sums (a caller that all-reduces several layers' sums at once); `reduce_fn` is then not called."""
-    lib = _lib.load_library()
     f32 = dict(dtype=torch.float32, device=sums.device)
     dbeta, dgamma, kk = _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty((2, C), **f32)
     if sums_g is None:
         sums_g = reduce_fn(sums.clone()) if reduce_fn is not None else sums
-    _lib.check(lib.facl_bn_bwd_consts(_lib.ptr(sums), _lib.ptr(sums_g), C, float(count), _lib.ptr(dbeta), _lib.ptr(dgamma),
-                                      _lib.ptr(kk), _lib.stream()), "facl_bn_bwd_consts")
+    _lib.call("facl_bn_bwd_consts", sums, sums_g, C, float(count), dbeta, dgamma, kk)
     return dbeta, dgamma, kk
 
 
@@ -167,11 +143,9 @@ def _bn_bwd_consts_mode(sums, bnc, C, count, reduce_fn, training):
     nothing is all-reduced (facl_bn_bwd_consts_frozen)."""
     if training:
         return _bn_bwd_consts(sums, C, count, reduce_fn) + (None,)
-    lib = _lib.load_library()
     f32 = dict(dtype=torch.float32, device=sums.device)
     dbeta, dgamma, dbias, kk = _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty((2, C), **f32)
-    _lib.check(lib.facl_bn_bwd_consts_frozen(_lib.ptr(sums), _lib.ptr(bnc), C, _lib.ptr(dbeta), _lib.ptr(dgamma), _lib.ptr(dbias),
-                                             _lib.ptr(kk), _lib.stream()), "facl_bn_bwd_consts_frozen")
+    _lib.call("facl_bn_bwd_consts_frozen", sums, bnc, C, dbeta, dgamma, dbias, kk)
     return dbeta, dgamma, kk, dbias
 
 
@@ -179,28 +153,23 @@ def _bn_relu_backward(da, y, bnc, count, reduce_fn, ws, sums=None, amax=None, tr
     """Backward of relu(bn(y)) over rows: column sums (unless the producer of `da` left them in `sums`) -> constants -> dense
     dy, which also raises `amax` (or None) to max|dy|.  Returns (dy, dgamma, dbeta, dbias); the parameter gradients stay local
     sums; dbias is None behind a train-mode BatchNorm (`_bn_bwd_consts_mode`)."""
-    lib = _lib.load_library()
     R, C = y.shape
     if sums is None:
         sums = _lib.empty((C, 2), dtype=torch.float64, device=y.device)
-        _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws),
-                                           _lib.stream()), "facl_rows_bwd_stats")
+        _lib.call("facl_rows_bwd_stats", da, y, R, C, bnc, sums, ws)
     dbeta, dgamma, kk, dbias = _bn_bwd_consts_mode(sums, bnc, C, count, reduce_fn, training)
     dy = _lib.empty_like(y)
-    _lib.check(lib.facl_rows_bwd_apply_amax(_lib.ptr(da), _lib.ptr(y), R, C, _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy),
-                                            _lib.ptr(amax), _lib.stream()), "facl_rows_bwd_apply_amax")
+    _lib.call("facl_rows_bwd_apply_amax", da, y, R, C, bnc, kk, dy, amax)
     return dy, dgamma, dbeta, dbias
 
 
 def _first_layer_wgrad(dy, h, centers, ws, prec, amax=None, amax_b=None):
     """dW (C, 3 + Cin) of the first per-centroid layer, whose input is torch.cat((centers, h), 1): the GEMM on h, the three
     centroid-xyz columns as one streaming pass over dy."""
-    lib = _lib.load_library()
     R, C = dy.shape
     dWh = gemm_wgrad(dy, h, prec=prec, amax=amax, amax_b=amax_b)
     dWc = _lib.empty((C, 3), dtype=torch.float64, device=dy.device)
-    _lib.check(lib.facl_rows_center_wgrad(_lib.ptr(dy), _lib.ptr(centers), R, C, _lib.ptr(dWc), _lib.ptr(ws), _lib.stream()),
-               "facl_rows_center_wgrad")
+    _lib.call("facl_rows_center_wgrad", dy, centers, R, C, dWc, ws)
     return torch.cat((dWc.float(), dWh), dim=1)
 
 
@@ -231,7 +200,6 @@ class _LinearBNReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, W, b, gamma, beta, bn, training, reduce_fn, centers=None):
         ctx.prec = current_precision()
-        lib = _lib.load_library()
         _lib.require_cuda(h)
         ws = _Workspace.get(h.device)
         h = h.contiguous()
@@ -246,8 +214,7 @@ class _LinearBNReLU(torch.autograd.Function):
         ctx.Wh = Wh
         R, C = y.shape
         a = _lib.empty_like(y)
-        _lib.check(lib.facl_rows_bn_relu(_lib.ptr(y), R, C, _lib.ptr(bnc[2]), _lib.ptr(bnc[3]), _lib.ptr(a),
-                                         _lib.stream()), "facl_rows_bn_relu")
+        _lib.call("facl_rows_bn_relu", y, R, C, bnc[2], bnc[3], a)
         _lib.tap_relu("relu_t%d" % (1 if centers is not None else 2), a=a)
         ctx.save_for_backward(h, W, y, bnc)
         ctx.count, ctx.reduce_fn, ctx.training = count, reduce_fn, training
@@ -271,7 +238,6 @@ class _LinearBNSegmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, W, b, gamma, beta, bn, training, reduce_fn, S):
         ctx.prec = current_precision()
-        lib = _lib.load_library()
         _lib.require_cuda(h)
         ws = _Workspace.get(h.device)
         h = h.contiguous()
@@ -289,21 +255,16 @@ class _LinearBNSegmax(torch.autograd.Function):
             sums = _lib.empty((C, 2), dtype=torch.float64, device=h.device) if training else None
             ymax = _lib.empty((M, C), dtype=torch.float32, device=h.device)
             with _lib.timed("facl_gemm_fwd %dx%dx%d%s" % (R, h.shape[1], C, _LABEL[ctx.prec])):
-                rc = _fn(lib, "facl_gemm_fwd_segmax", ctx.prec)(_lib.ptr(h), R, h.shape[1], _lib.ptr(W), W.stride(0), C, _lib.ptr(b),
-                                              _lib.ptr(sgn), _lib.ptr(y), _lib.ptr(sums), _lib.ptr(ymax), _lib.ptr(arg),
-                                              _lib.ptr(ws), _lib.stream())
-            if rc == 0:
+                rc = _lib.call("facl_gemm_fwd_segmax" + _SUFFIX[ctx.prec], h, R, h.shape[1], W, W.stride(0), C, b, sgn, y, sums, ymax,
+                               arg, ws, accept=(_lib.E_CONFIG,))
+            if rc != _lib.E_CONFIG:                          # FACL_E_CONFIG: too small for the fused kernel
                 fused = True
                 bnc, count = _forward_bn_consts(y, bn, training, reduce_fn, ws, sums)
-                _lib.check(lib.facl_sa_pool(_lib.ptr(ymax), M, C, _lib.ptr(bnc[2]), _lib.ptr(bnc[3]), _lib.ptr(xpre), None,
-                                            _lib.stream()), "facl_sa_pool")
-            elif rc != -4:                                   # FACL_E_CONFIG: too small for the fused kernel
-                _lib.check(rc, "facl_gemm_fwd_segmax")
+                _lib.call("facl_sa_pool", ymax, M, C, bnc[2], bnc[3], xpre, None)
         if not fused:
             y, sums = gemm_fwd(h, W, b, want_stats=training, prec=ctx.prec)
             bnc, count = _forward_bn_consts(y, bn, training, reduce_fn, ws, sums)
-            _lib.check(lib.facl_rows_segmax(_lib.ptr(y), M, S, C, _lib.ptr(bnc), _lib.ptr(xpre), _lib.ptr(arg),
-                                            _lib.stream()), "facl_rows_segmax")
+            _lib.call("facl_rows_segmax", y, M, S, C, bnc, xpre, arg)
         _lib.tap("seg_arg", arg)
         _lib.tap_relu("relu_t3", a=xpre)
         ctx.save_for_backward(h, W, y, bnc, xpre, arg)
@@ -314,7 +275,6 @@ class _LinearBNSegmax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dxpre, _darg):
         bp = backward_precision(ctx.prec)   # the backward GEMMs run in the arithmetic the forward recorded
-        lib = _lib.load_library()
         h, W, y, bnc, xpre, arg = ctx.saved_tensors
         ws = _Workspace.get(y.device)
         R, C = y.shape
@@ -322,14 +282,10 @@ class _LinearBNSegmax(torch.autograd.Function):
         M = R // S
         dxpre = dxpre.contiguous()
         sums = _lib.empty((C, 2), dtype=torch.float64, device=y.device)
-        _lib.check(lib.facl_segmax_bwd_stats(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(y), _lib.ptr(arg), M, S, C,
-                                             _lib.ptr(bnc), _lib.ptr(sums), _lib.ptr(ws), _lib.stream()),
-                   "facl_segmax_bwd_stats")
+        _lib.call("facl_segmax_bwd_stats", dxpre, xpre, y, arg, M, S, C, bnc, sums, ws)
         dbeta, dgamma, kk, db = _bn_bwd_consts_mode(sums, bnc, C, ctx.count, ctx.reduce_fn, ctx.training)   # parameter gradients stay local sums
         dy = _lib.empty_like(y)
-        _lib.check(lib.facl_segmax_bwd_apply(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(y), _lib.ptr(arg), M, S, C,
-                                             _lib.ptr(bnc), _lib.ptr(kk), _lib.ptr(dy), _lib.stream()),
-                   "facl_segmax_bwd_apply")
+        _lib.call("facl_segmax_bwd_apply", dxpre, xpre, y, arg, M, S, C, bnc, kk, dy)
         dW = gemm_wgrad(dy, h, prec=bp)
         dh = gemm_dgrad(dy, W, prec=bp)
         return dh, dW, db, dgamma, dbeta, None, None, None, None
@@ -360,7 +316,7 @@ class _Linear(torch.autograd.Function):
         return gemm_dgrad(dy, W, prec=bp), gemm_wgrad(dy, h, prec=bp), dy.sum(0)
 
 
-_FC_FUSED = _env_on("FACL_FC_FUSED")        # A/B switch: 0 = the single-segment kernels of rounds 2-4
+_FC_FUSED = _lib.env_on("FACL_FC_FUSED")        # A/B switch: 0 = the single-segment kernels of rounds 2-4
 
 
 class _FCHead(torch.autograd.Function):
@@ -384,7 +340,6 @@ class _FCHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_pre, G, W1, b1, gamma, beta, bn, W2, b2, training, reduce_fn):
         ctx.prec = current_precision()
-        lib = _lib.load_library()
         _lib.require_cuda(x_pre)
         ws = _Workspace.get(x_pre.device)
         x_pre = x_pre.contiguous()
@@ -392,7 +347,7 @@ class _FCHead(torch.autograd.Function):
         B = M // G
         h = _lib.empty((M + B, Cin), dtype=torch.float32, device=x_pre.device)
         arg = _lib.empty((B, Cin), dtype=torch.int32, device=x_pre.device)
-        _lib.check(lib.facl_viewmax_stack(_lib.ptr(x_pre), G, B, Cin, _lib.ptr(h), _lib.ptr(arg), _lib.stream()), "facl_viewmax_stack")
+        _lib.call("facl_viewmax_stack", x_pre, G, B, Cin, h, arg)
         _lib.tap("view_arg", arg)
         W1, W2 = W1.contiguous(), W2.contiguous()
         R, C = M + B, W1.shape[0]
@@ -411,17 +366,15 @@ class _FCHead(torch.autograd.Function):
             y = gemm_fwd(h, W1, b1, prec=ctx.prec)[0]
             if reduce_fn is not None:
                 sums2 = _lib.empty((2, C, 2), dtype=torch.float64, device=y.device)
-            _lib.check(lib.facl_fc_bn_stats(_lib.ptr(y), M, R, C, _lib.ptr(sums2), _lib.ptr(ws), _lib.stream()), "facl_fc_bn_stats")
+            _lib.call("facl_fc_bn_stats", y, M, R, C, sums2, ws)
             if reduce_fn is not None:
                 reduce_fn(sums2)                                 # ONE SyncBN all-reduce for the pair
             else:
                 part, na, nb = ws, M // 32, (B + 31) // 32
             a = _lib.empty_like(y)
             bnc2 = _lib.empty((2, 5, C), **f32)
-            _lib.check(lib.facl_fc_bn_apply(_lib.ptr(y), M, R, C, _lib.ptr(sums2), _lib.ptr(part), na, nb, counts[0], counts[1],
-                                            _lib.ptr(gamma.detach()), _lib.ptr(beta.detach()), BN_EPS, BN_MOMENTUM,
-                                            _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), _lib.ptr(bnc2), _lib.ptr(a),
-                                            _lib.stream()), "facl_fc_bn_apply")
+            _lib.call("facl_fc_bn_apply", y, M, R, C, sums2, part, na, nb, counts[0], counts[1], gamma.detach(), beta.detach(),
+                      BN_EPS, BN_MOMENTUM, bn.running_mean, bn.running_var, bnc2, a)
             bn.count_batch()
             bn.count_batch()
             bncs = [bnc2]                                        # one (2, 5, C) tensor: both segments' constants
@@ -434,8 +387,7 @@ class _FCHead(torch.autograd.Function):
                 # reference's order (view rows :228, clip rows :229: the running statistics are updated twice)
                 sums2 = _lib.empty((2, C, 2), dtype=torch.float64, device=y.device)
                 for i, (r0, r1) in enumerate(segs):
-                    _lib.check(lib.facl_rows_stats(_lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(sums2[i]), _lib.ptr(ws), _lib.stream()),
-                               "facl_rows_stats")
+                    _lib.call("facl_rows_stats", y[r0:r1], r1 - r0, C, sums2[i], ws)
                 world = 1
                 if reduce_fn is not None:
                     reduce_fn(sums2)
@@ -447,8 +399,7 @@ class _FCHead(torch.autograd.Function):
                     bn.count_batch()
                 else:
                     bnc, count = _forward_bn_consts(y[r0:r1], bn, False, None, ws)
-                _lib.check(lib.facl_rows_bn_relu(_lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(bnc[2]), _lib.ptr(bnc[3]),
-                                                 _lib.ptr(a[r0:r1]), _lib.stream()), "facl_rows_bn_relu")
+                _lib.call("facl_rows_bn_relu", y[r0:r1], r1 - r0, C, bnc[2], bnc[3], a[r0:r1])
                 bncs.append(bnc)
                 counts.append(count)
         _lib.tap_relu("relu_fc", a=a)
@@ -460,7 +411,6 @@ class _FCHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         bp = backward_precision(ctx.prec)   # the backward GEMMs run in the arithmetic the forward recorded
-        lib = _lib.load_library()
         h, W1, y, a, W2, arg, *bncs = ctx.saved_tensors
         bnc2 = bncs[0] if ctx.fused else None
         bnc_a, bnc_b = (bnc2[0], bnc2[1]) if ctx.fused else bncs
@@ -473,7 +423,7 @@ class _FCHead(torch.autograd.Function):
         dW2 = gemm_wgrad(dout, a, prec=bp)
         if dout.shape[1] % 4 == 0:
             db2 = _lib.empty(dout.shape[1], **f32)
-            _lib.check(lib.facl_col_sums(_lib.ptr(dout), R, dout.shape[1], _lib.ptr(db2), _lib.stream()), "facl_col_sums")
+            _lib.call("facl_col_sums", dout, R, dout.shape[1], db2)
         else:
             db2 = dout.sum(0)
         dact = gemm_dgrad(dout, W2, prec=bp)
@@ -483,19 +433,16 @@ class _FCHead(torch.autograd.Function):
             sums2 = sums2_g = None
             if ctx.reduce_fn is not None:
                 sums2 = _lib.empty((2, C, 2), dtype=torch.float64, device=y.device)
-            _lib.check(lib.facl_fc_bn_bwd_stats(_lib.ptr(dact), _lib.ptr(y), M, R, C, _lib.ptr(bnc2), _lib.ptr(sums2), _lib.ptr(ws),
-                                                _lib.stream()), "facl_fc_bn_bwd_stats")
+            _lib.call("facl_fc_bn_bwd_stats", dact, y, M, R, C, bnc2, sums2, ws)
             if ctx.reduce_fn is not None:
                 sums2_g = ctx.reduce_fn(sums2)                   # the local slice sums stay in the workspace
             dgamma, dbeta, kk2 = _lib.empty(C, **f32), _lib.empty(C, **f32), _lib.empty((2, 2, C), **f32)
-            _lib.check(lib.facl_fc_bn_bwd_apply(_lib.ptr(dact), _lib.ptr(y), M, R, C, _lib.ptr(bnc2), _lib.ptr(sums2_g), _lib.ptr(ws),
-                                                ctx.counts[0], ctx.counts[1], _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(kk2),
-                                                _lib.ptr(dy), _lib.stream()), "facl_fc_bn_bwd_apply")
+            _lib.call("facl_fc_bn_bwd_apply", dact, y, M, R, C, bnc2, sums2_g, ws, ctx.counts[0], ctx.counts[1], dgamma, dbeta,
+                      kk2, dy)
         else:
             sums2 = _lib.empty((2, C, 2), dtype=torch.float64, device=y.device)
             for i, ((r0, r1), bnc) in enumerate(zip(ctx.segs, (bnc_a, bnc_b))):
-                _lib.check(lib.facl_rows_bwd_stats(_lib.ptr(dact[r0:r1]), _lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(bnc),
-                                                   _lib.ptr(sums2[i]), _lib.ptr(ws), _lib.stream()), "facl_rows_bwd_stats")
+                _lib.call("facl_rows_bwd_stats", dact[r0:r1], y[r0:r1], r1 - r0, C, bnc, sums2[i], ws)
             frozen = not ctx.training                            # eval mode: both segments share the running statistics
             sums2_g = ctx.reduce_fn(sums2.clone()) if ctx.reduce_fn is not None and not frozen else sums2   # one all-reduce for the pair
             parts = []
@@ -504,8 +451,7 @@ class _FCHead(torch.autograd.Function):
                     part = _bn_bwd_consts_mode(sums2[i], bnc, C, count, None, False)
                 else:
                     part = _bn_bwd_consts(sums2[i], C, count, None, sums_g=sums2_g[i]) + (None,)
-                _lib.check(lib.facl_rows_bwd_apply(_lib.ptr(dact[r0:r1]), _lib.ptr(y[r0:r1]), r1 - r0, C, _lib.ptr(bnc),
-                                                   _lib.ptr(part[2]), _lib.ptr(dy[r0:r1]), _lib.stream()), "facl_rows_bwd_apply")
+                _lib.call("facl_rows_bwd_apply", dact[r0:r1], y[r0:r1], r1 - r0, C, bnc, part[2], dy[r0:r1])
                 parts.append(part)
             dgamma, dbeta = parts[0][1] + parts[1][1], parts[0][0] + parts[1][0]
             if frozen:
@@ -513,8 +459,7 @@ class _FCHead(torch.autograd.Function):
         dW1 = gemm_wgrad(dy, h, prec=bp)
         dh = gemm_dgrad(dy, W1, prec=bp)
         # dL/dx_pre = dh[:M] + (dh[M:] routed to the winning view's row of each (clip, channel))
-        _lib.check(lib.facl_viewmax_bwd_add(dh[M:].data_ptr(), _lib.ptr(arg), ctx.G, B, dh.shape[1], _lib.ptr(dh), _lib.stream()),
-                   "facl_viewmax_bwd_add")
+        _lib.call("facl_viewmax_bwd_add", dh[M:], arg, ctx.G, B, dh.shape[1], dh)
         # d(bias of the first Linear) is identically zero in front of a train-mode BN: None leaves it untouched
         return dh[:M], None, dW1, db1, dgamma, dbeta, None, dW2, db2, None, None
 
@@ -532,15 +477,13 @@ class _NormalizeMap(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Wm):
-        lib = _lib.load_library()
         _lib.require_cuda(x)
         x, Wm = x.contiguous(), Wm.contiguous()
         M, C = x.shape
         K = Wm.shape[0]
         xn = _lib.empty_like(x)
         code = _lib.empty((M, K), dtype=torch.float32, device=x.device)
-        _lib.check(lib.facl_normalize_map(_lib.ptr(x), M, C, _lib.ptr(Wm), K, _lib.ptr(xn), _lib.ptr(code), _lib.stream()),
-                   "facl_normalize_map")
+        _lib.call("facl_normalize_map", x, M, C, Wm, K, xn, code)
         ctx.save_for_backward(x, xn, Wm)
         return xn, code
 
@@ -565,25 +508,23 @@ class _ViewMax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_pre, G):
-        lib = _lib.load_library()
         _lib.require_cuda(x_pre)
         x_pre = x_pre.contiguous()
         B, C = x_pre.shape[0] // G, x_pre.shape[1]
         out = _lib.empty((B, C), dtype=torch.float32, device=x_pre.device)
         arg = _lib.empty((B, C), dtype=torch.int32, device=x_pre.device)
-        _lib.check(lib.facl_viewmax_fwd(_lib.ptr(x_pre), G, B, C, _lib.ptr(out), _lib.ptr(arg), _lib.stream()), "facl_viewmax_fwd")
+        _lib.call("facl_viewmax_fwd", x_pre, G, B, C, out, arg)
         ctx.save_for_backward(arg)
         ctx.G = G
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load_library()
         arg, = ctx.saved_tensors
         B, C = arg.shape
         dout = dout.contiguous()
         dx = _lib.empty((ctx.G * B, C), dtype=torch.float32, device=dout.device)
-        _lib.check(lib.facl_viewmax_bwd(_lib.ptr(dout), _lib.ptr(arg), ctx.G, B, C, _lib.ptr(dx), _lib.stream()), "facl_viewmax_bwd")
+        _lib.call("facl_viewmax_bwd", dout, arg, ctx.G, B, C, dx)
         return dx, None
 
 
@@ -606,14 +547,11 @@ def linear_bn_relu_segmax(h, affine, bn, training, S, reduce_fn=None):
 def rs_planes(W, transposed, centers_cols=None, half=False):
     """Fragment-ordered bf16 planes of a weight matrix view (rows x cols, any leading dimension) for facl_gemm_rs_fwd
     (transposed = False) / facl_gemm_rs_dgrad (True).  `centers_cols`: (N,3) view whose columns join as the centre k-step."""
-    lib = _lib.load_library()
     N, K = W.shape
-    nb = lib.facl_gemm_rs_planes_bytes(K if transposed else N, N if transposed else K, 0 if centers_cols is None else 1)
+    nb = _lib.call_size("facl_gemm_rs_planes_bytes", K if transposed else N, N if transposed else K, 0 if centers_cols is None else 1)
     planes = _lib.empty(nb, dtype=torch.uint8, device=W.device)
-    _lib.check(lib.facl_gemm_rs_planes(W.data_ptr(), W.stride(0), N, K, 1 if transposed else 0,
-                                       None if centers_cols is None else centers_cols.data_ptr(),
-                                       0 if centers_cols is None else centers_cols.stride(0), 1 if half else 0,
-                                       _lib.ptr(planes), _lib.stream()), "facl_gemm_rs_planes")
+    _lib.call("facl_gemm_rs_planes", W, W.stride(0), N, K, 1 if transposed else 0, centers_cols,
+              0 if centers_cols is None else centers_cols.stride(0), 1 if half else 0, planes)
     return planes
 
 
@@ -623,35 +561,31 @@ def rs_planes_multi(jobs, absmax=None):
     `absmax` = (tensor, amax row): the same launch raises the amax row to max|tensor| (the centroid coordinates)."""
     jobs = [(j + (False,))[:4] for j in jobs]
     import ctypes
-    lib = _lib.load_library()
     n = len(jobs)
     outs = []
     for W, tr, xc, _h in jobs:
         N, K = W.shape
-        nb = lib.facl_gemm_rs_planes_bytes(K if tr else N, N if tr else K, 0 if xc is None else 1)
+        nb = _lib.call_size("facl_gemm_rs_planes_bytes", K if tr else N, N if tr else K, 0 if xc is None else 1)
         outs.append(_lib.empty(nb, dtype=torch.uint8, device=W.device))
     vp, ip = ctypes.c_void_p * n, ctypes.c_int * n
-    _lib.check(lib.facl_gemm_rs_planes_multi(
-        n, vp(*[j[0].data_ptr() for j in jobs]), ip(*[j[0].stride(0) for j in jobs]), ip(*[j[0].shape[0] for j in jobs]),
-        ip(*[j[0].shape[1] for j in jobs]), ip(*[1 if j[1] else 0 for j in jobs]),
-        vp(*[None if j[2] is None else j[2].data_ptr() for j in jobs]),
-        ip(*[0 if j[2] is None else j[2].stride(0) for j in jobs]), ip(*[1 if j[3] else 0 for j in jobs]),
-        vp(*[o.data_ptr() for o in outs]), None if absmax is None else _lib.ptr(absmax[0]),
-        0 if absmax is None else absmax[0].numel(), None if absmax is None else _lib.ptr(absmax[1]), _lib.stream()),
-        "facl_gemm_rs_planes_multi")
+    _lib.call("facl_gemm_rs_planes_multi", n, vp(*[j[0].data_ptr() for j in jobs]), ip(*[j[0].stride(0) for j in jobs]),
+              ip(*[j[0].shape[0] for j in jobs]), ip(*[j[0].shape[1] for j in jobs]), ip(*[1 if j[1] else 0 for j in jobs]),
+              vp(*[None if j[2] is None else j[2].data_ptr() for j in jobs]),
+              ip(*[0 if j[2] is None else j[2].stride(0) for j in jobs]), ip(*[1 if j[3] else 0 for j in jobs]),
+              vp(*[o.data_ptr() for o in outs]), None if absmax is None else absmax[0],
+              0 if absmax is None else absmax[0].numel(), None if absmax is None else absmax[1])
     return outs
 
 
 # Forward arithmetic of the row-streamed GEMMs: fp16x3 (two fp16 planes of pre-scaled operands, three products: the same
 # fp32-GEMM accuracy at half the MFMA work, csrc/common.h) unless FACL_FWD_H3=0 selects bf16x6 (A/B, bit-identity tests)
-FWD_H3 = _env_on("FACL_FWD_H3")
+FWD_H3 = _lib.env_on("FACL_FWD_H3")
 # Backward arithmetic of the row-streamed dgrad / weight-gradient kernels: fp16x3 with the gradient operand's power-of-two
 # scale taken per launch from max|dy| (a device scalar its producer kernel maintains); FACL_BWD_H3=0: bf16x6
-BWD_H3 = _env_on("FACL_BWD_H3")
+BWD_H3 = _lib.env_on("FACL_BWD_H3")
 
 
 def _rs_fwd(a, planes, N, bias, pro, centers, want_stats, seg_sgn, ws, half=False, amax_a=None):
-    lib = _lib.load_library()
     M, K = a.shape
     y = _lib.empty((M, N), dtype=torch.float32, device=a.device)
     sums = _lib.empty((N, 2), dtype=torch.float64, device=a.device) if want_stats else None
@@ -661,13 +595,12 @@ def _rs_fwd(a, planes, N, bias, pro, centers, want_stats, seg_sgn, ws, half=Fals
         arg = _lib.empty((M // 64, N), dtype=torch.int32, device=a.device)
     ps, pt = (pro[2], pro[3]) if pro is not None else (None, None)
     with _lib.timed("facl_gemm_rs_fwd %dx%dx%d%s" % (M, K, N, " h3" if half else "")):
-        _lib.check(lib.facl_gemm_rs_fwd(_lib.ptr(a), M, K, _lib.ptr(planes), 1 if half else 0, _lib.ptr(amax_a), N, _lib.ptr(bias), _lib.ptr(ps), _lib.ptr(pt),
-                                        _lib.ptr(centers), _lib.ptr(y), _lib.ptr(sums), _lib.ptr(seg_sgn), _lib.ptr(ymax),
-                                        _lib.ptr(arg), _lib.ptr(ws), _lib.stream()), "facl_gemm_rs_fwd")
+        _lib.call("facl_gemm_rs_fwd", a, M, K, planes, 1 if half else 0, amax_a, N, bias, ps, pt, centers, y, sums, seg_sgn,
+                  ymax, arg, ws)
     return y, sums, ymax, arg
 
 
-_FUSE_BNSTATS = _env_on("FACL_RS_BNSTATS")   # A/B switch: 0 = separate facl_rows_bwd_stats pass
+_FUSE_BNSTATS = _lib.env_on("FACL_RS_BNSTATS")   # A/B switch: 0 = separate facl_rows_bwd_stats pass
 
 
 def _rs_dgrad(dy, W, prec, planes=None, bn_y=None, bn_c=None, ws=None, amax=None):
@@ -676,7 +609,6 @@ def _rs_dgrad(dy, W, prec, planes=None, bn_y=None, bn_c=None, ws=None, amax=None
     `amax` (the _lib.AMAX_WORDS int32 buffer holding the bits of max|dy|): fp16x3 arithmetic; `planes` must then be fp16x3 planes."""
     if prec != "f32":
         return gemm_dgrad(dy, W, prec=prec), None
-    lib = _lib.load_library()
     M, N = dy.shape
     K = W.shape[1]
     half = 0 if amax is None else 1
@@ -687,60 +619,50 @@ def _rs_dgrad(dy, W, prec, planes=None, bn_y=None, bn_c=None, ws=None, amax=None
     with _lib.timed("facl_gemm_rs_dgrad %dx%dx%d%s" % (M, N, K, " h3" if half else "")):
         if bn_y is not None and _FUSE_BNSTATS:
             sums = _lib.empty((K, 2), dtype=torch.float64, device=dy.device)
-            _lib.check(lib.facl_gemm_rs_dgrad_bnstats(_lib.ptr(dy), M, N, _lib.ptr(planes), half, _lib.ptr(amax), K, _lib.ptr(da),
-                                                      _lib.ptr(bn_y), _lib.ptr(bn_c), _lib.ptr(sums), _lib.ptr(ws), _lib.stream()),
-                       "facl_gemm_rs_dgrad_bnstats")
+            _lib.call("facl_gemm_rs_dgrad_bnstats", dy, M, N, planes, half, amax, K, da, bn_y, bn_c, sums, ws)
         else:
-            _lib.check(lib.facl_gemm_rs_dgrad(_lib.ptr(dy), M, N, _lib.ptr(planes), half, _lib.ptr(amax), K, _lib.ptr(da),
-                                              _lib.stream()), "facl_gemm_rs_dgrad")
+            _lib.call("facl_gemm_rs_dgrad", dy, M, N, planes, half, amax, K, da)
     return da, sums
 
 
-_WGRAD_RS = _env_on("FACL_WGRAD_RS")         # A/B switch
+_WGRAD_RS = _lib.env_on("FACL_WGRAD_RS")         # A/B switch
 
 
 def _wgrad_pro(dy, y, bnc, prec, amax=None, amax_b=None):
     """dW = dy^T relu(bn(y)) with the activation recomputed while staged; falls back to a materialised activation.
     `amax`: bits of max|dy|, `amax_b`: the bound of max relu(bn(y)) the forward used -> fp16x3 arithmetic where the
     register-streamed kernel serves the shape."""
-    lib = _lib.load_library()
     M, N = dy.shape
     K = y.shape[1]
     dW = _lib.empty((N, K), dtype=torch.float32, device=dy.device)
-    nzr = lib.facl_gemm_rs_wgrad_slices(M, N, K) if (prec == "f32" and _WGRAD_RS and y.is_contiguous()) else 0
+    nzr = _lib.call_size("facl_gemm_rs_wgrad_slices", M, N, K) if (prec == "f32" and _WGRAD_RS and y.is_contiguous()) else 0
     if nzr > 0:                                                         # the widest layer: register-streamed kernel
         slices = _lib.empty(nzr * N * K, dtype=torch.float32, device=dy.device)
         with _lib.timed("facl_gemm_rs_wgrad %dx%dx%d%s" % (M, N, K, "" if amax is None else " h3")):
-            _lib.check(lib.facl_gemm_rs_wgrad(_lib.ptr(dy), _lib.ptr(y), M, N, K, _lib.ptr(bnc[2]), _lib.ptr(bnc[3]),
-                                              _lib.ptr(amax), _lib.ptr(amax_b), _lib.ptr(dW), _lib.ptr(slices), _lib.stream()),
-                       "facl_gemm_rs_wgrad")
+            _lib.call("facl_gemm_rs_wgrad", dy, y, M, N, K, bnc[2], bnc[3], amax, amax_b, dW, slices)
         return dW
     nz = _wgrad_slices(M, N, K)
     slices = _lib.empty(nz * N * K, dtype=torch.float32, device=dy.device)
     # fp16x3 on the LDS-staged kernel (the narrower layers)
     if amax is not None and prec == "f32" and _wgrad_h3(dy, y, bnc, amax, amax_b, dW, slices, nz):
         return dW
-    fn = lib.facl_gemm_wgrad_pro_x3 if prec == "x3" else lib.facl_gemm_wgrad_pro
     with _lib.timed("facl_gemm_wgrad %dx%dx%d%s" % (M, N, K, _LABEL[prec])):
-        rc = fn(_lib.ptr(dy), _lib.ptr(y), M, N, K, y.stride(0), _lib.ptr(bnc[2]), _lib.ptr(bnc[3]), _lib.ptr(dW),
-                _lib.ptr(slices), nz, _lib.stream())
-    if rc == -4:                                                        # FACL_E_CONFIG: shape not served -> materialise a
+        rc = _lib.call("facl_gemm_wgrad_pro_x3" if prec == "x3" else "facl_gemm_wgrad_pro", dy, y, M, N, K, y.stride(0), bnc[2], bnc[3],
+                       dW, slices, nz, accept=(_lib.E_CONFIG,))
+    if rc == _lib.E_CONFIG:                                                      # FACL_E_CONFIG: shape not served -> materialise a
         a = _lib.empty_like(y)
-        _lib.check(lib.facl_rows_bn_relu(_lib.ptr(y), M, K, _lib.ptr(bnc[2]), _lib.ptr(bnc[3]), _lib.ptr(a), _lib.stream()),
-                   "facl_rows_bn_relu")
+        _lib.call("facl_rows_bn_relu", y, M, K, bnc[2], bnc[3], a)
         return gemm_wgrad(dy, a, prec=prec)
-    _lib.check(rc, "facl_gemm_wgrad_pro")
     return dW
 
 
 def net3dv3_supported(P, widths, S, prec):
     """True when the three per-centroid layers (cn3d_model_conbag.py:61-77) run on the row-streamed kernels."""
-    if not _env_on("FACL_TAIL_RS") or prec not in ("f32", "x3b") or S != 64 or P % 64:
+    if not _lib.env_on("FACL_TAIL_RS") or prec not in ("f32", "x3b") or S != 64 or P % 64:
         return False
-    lib = _lib.load_library()
     c0, c1, c2, c3 = widths
-    return all(lib.facl_gemm_rs_supported(P, k, n) == 1 for k, n in ((c0, c1), (c1, c2), (c2, c3))) and max(c1, c2) <= 512 \
-        and all(lib.facl_gemm_rs_supported(P, n, k) == 1 for k, n in ((c0, c1), (c1, c2), (c2, c3)))
+    return all(_lib.call_size("facl_gemm_rs_supported", P, k, n) == 1 for k, n in ((c0, c1), (c1, c2), (c2, c3))) and max(c1, c2) <= 512 \
+        and all(_lib.call_size("facl_gemm_rs_supported", P, n, k) == 1 for k, n in ((c0, c1), (c1, c2), (c2, c3)))
 
 
 class _Net3DV3(torch.autograd.Function):
@@ -753,7 +675,6 @@ class _Net3DV3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pooled, centers, S, training, reduce_fn, bns, pooled_amax, W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, g3, be3):
         ctx.prec = current_precision()
-        lib = _lib.load_library()
         _lib.require_cuda(pooled)
         ws = _Workspace.get(pooled.device)
         pooled, centers = pooled.contiguous(), centers.contiguous()
@@ -775,7 +696,7 @@ class _Net3DV3(torch.autograd.Function):
             a0 = pooled_amax
         else:
             a0 = amax[0]
-            _lib.check(lib.facl_absmax(_lib.ptr(pooled), pooled.numel(), _lib.ptr(a0), _lib.stream()), "facl_absmax")
+            _lib.call("facl_absmax", pooled, pooled.numel(), a0)
         pl = rs_planes_multi(jobs, absmax=(centers, a0))
         ctx.bwd_planes = pl[3:] if want_bwd else None
         ctx.bwd_h3 = want_bwd and BWD_H3
@@ -788,8 +709,7 @@ class _Net3DV3(torch.autograd.Function):
         bnc3, _ = _forward_bn_consts(y3, bns[2], training, reduce_fn, ws, sums3)
         M, C = P // S, W3.shape[0]
         xpre = _lib.empty((M, C), dtype=torch.float32, device=pooled.device)
-        _lib.check(lib.facl_sa_pool(_lib.ptr(ymax), M, C, _lib.ptr(bnc3[2]), _lib.ptr(bnc3[3]), _lib.ptr(xpre), None, _lib.stream()),
-                   "facl_sa_pool")
+        _lib.call("facl_sa_pool", ymax, M, C, bnc3[2], bnc3[3], xpre, None)
         _lib.tap("seg_arg", arg)
         _lib.tap_relu("relu_t1", y1, bnc1[2], bnc1[3])
         _lib.tap_relu("relu_t2", y2, bnc2[2], bnc2[3])
@@ -801,10 +721,8 @@ class _Net3DV3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dxpre):
         bp = backward_precision(ctx.prec)
-        lib = _lib.load_library()
         pooled, centers, W1, W2, W3, y1, y2, y3, bnc1, bnc2, bnc3, xpre, arg, ymax = ctx.saved_tensors
         ws = _Workspace.get(y1.device)
-        st = _lib.stream()
         P, S = y1.shape[0], ctx.S
         M = P // S
         f64 = dict(dtype=torch.float64, device=y1.device)
@@ -817,15 +735,12 @@ class _Net3DV3(torch.autograd.Function):
         # zeroed by the statistics launch in front of those kernels (no fill launch)
         h3 = ctx.bwd_h3 and bp == "f32"
         amax = _lib.empty((3, _lib.AMAX_WORDS), dtype=torch.int32, device=y1.device) if h3 else None
-        _lib.check(lib.facl_segmax_bwd_stats_ymax(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(ymax), M, C3, _lib.ptr(bnc3),
-                                                  _lib.ptr(sums), _lib.ptr(ws), _lib.ptr(amax), 3 * _lib.AMAX_WORDS if h3 else 0, st),
-                   "facl_segmax_bwd_stats")
+        _lib.call("facl_segmax_bwd_stats_ymax", dxpre, xpre, ymax, M, C3, bnc3, sums, ws, amax,
+                  3 * _lib.AMAX_WORDS if h3 else 0)
         dbe3, dga3, kk, db3 = _bn_bwd_consts_mode(sums, bnc3, C3, ctx.count, ctx.reduce_fn, ctx.training)
         dy = _lib.empty_like(y3)
         am = (lambda i: amax[i]) if h3 else (lambda i: None)
-        _lib.check(lib.facl_segmax_bwd_apply_amax(_lib.ptr(dxpre), _lib.ptr(xpre), _lib.ptr(y3), _lib.ptr(arg), M, S, C3,
-                                                  _lib.ptr(bnc3), _lib.ptr(kk), _lib.ptr(dy), _lib.ptr(am(0)), st),
-                   "facl_segmax_bwd_apply")
+        _lib.call("facl_segmax_bwd_apply_amax", dxpre, xpre, y3, arg, M, S, C3, bnc3, kk, dy, am(0))
         bpl = ctx.bwd_planes if ctx.bwd_planes is not None else (None, None, None)
         a0b, a1b, a2b = ctx.act_amax                       # the activation bounds the forward GEMMs used
         dW3 = _wgrad_pro(dy, y2, bnc2, bp, am(0), a2b)

@@ -33,10 +33,8 @@ def knn_radius_group(points, sample_num_level1, knn_K, ball_radius, want_idx=Fal
     xt = _lib.empty((M, S, K, D), dtype=torch.float32, device=pts.device)
     yt = _lib.empty((M, S, 3), dtype=torch.float32, device=pts.device)
     idx = _lib.empty((M, S, K), dtype=torch.int32, device=pts.device) if want_idx else None
-    lib = _lib.load_library()
     with _lib.timed("facl_group"):
-        _lib.check(lib.facl_group(_lib.ptr(pts), M, N, D, S, K, float(ball_radius), _lib.ptr(idx), _lib.ptr(xt),
-                                  _lib.ptr(yt), _lib.stream()), "facl_group")
+        _lib.call("facl_group", pts, M, N, D, S, K, float(ball_radius), idx, xt, yt)
     inputs_level1 = xt.permute(0, 3, 1, 2)                       # (M,D,S,K), utils_my.py:283
     inputs_level1_center = yt.view(M, 1, S, 3).transpose(1, 3)   # (M,3,S,1), utils_my.py:284
     if want_idx:
@@ -50,10 +48,8 @@ def _knn_radius_group_clips(clips, sample_num_level1, knn_K, ball_radius, want_i
     xt = _lib.empty((M, S, K, D), dtype=torch.float32, device=clips.device)
     yt = _lib.empty((M, S, 3), dtype=torch.float32, device=clips.device)
     idx = _lib.empty((M, S, K), dtype=torch.int32, device=clips.device) if want_idx else None
-    lib = _lib.load_library()
     with _lib.timed("facl_group"):
-        _lib.check(lib.facl_group_clips(_lib.ptr(clips), B, G, N, D, S, K, float(ball_radius), _lib.ptr(idx), _lib.ptr(xt),
-                                        _lib.ptr(yt), _lib.stream()), "facl_group_clips")
+        _lib.call("facl_group_clips", clips, B, G, N, D, S, K, float(ball_radius), idx, xt, yt)
     out = (xt.permute(0, 3, 1, 2), yt.view(M, 1, S, 3).transpose(1, 3))
     return out + (idx,) if want_idx else out
 
@@ -349,7 +345,6 @@ class _ContrastivePair(torch.autograd.Function):
     def forward(ctx, stacked, keys, order, G, clip_offset, mask_mode=0, queue=None, classes=None, class_positives=0.0):
         from . import tail as _tail
         from .sa_mlp import _Workspace
-        lib = _lib.load_library()
         _lib.require_cuda(stacked, keys)
         dev = stacked.device
         ws = _Workspace.get(dev)
@@ -380,19 +375,14 @@ class _ContrastivePair(torch.autograd.Function):
         if class_positives and classes is None:
             raise ValueError("class_positives needs mask 'class' and the class ids of the key clips")
         if queue is None and class_positives:
-            _lib.check(lib.facl_contrast_pair_sum_sup(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, _lib.ptr(classes),
-                                                      float(class_positives), _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32),
-                                                      _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_sum_sup")
+            _lib.call("facl_contrast_pair_sum_sup", sim, G, B, Bk, J, order, clip_offset, classes, float(class_positives), dsim,
+                      out, out32, ws)
             ctx.save_for_backward(stacked, keys, dsim)
         elif queue is None and classes is not None:
-            _lib.check(lib.facl_contrast_pair_sum_cls(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, _lib.ptr(classes),
-                                                      _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
-                       "facl_contrast_pair_sum_cls")
+            _lib.call("facl_contrast_pair_sum_cls", sim, G, B, Bk, J, order, clip_offset, classes, dsim, out, out32, ws)
             ctx.save_for_backward(stacked, keys, dsim)
         elif queue is None:
-            _lib.check(lib.facl_contrast_pair_sum_mask(_lib.ptr(sim), G, B, Bk, J, _lib.ptr(order), clip_offset, mask_mode,
-                                                       _lib.ptr(dsim), _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
-                       "facl_contrast_pair_sum_mask")
+            _lib.call("facl_contrast_pair_sum_mask", sim, G, B, Bk, J, order, clip_offset, mask_mode, dsim, out, out32, ws)
             ctx.save_for_backward(stacked, keys, dsim)
         else:
             if queue.C != C or queue.buf.device != dev:
@@ -403,20 +393,14 @@ class _ContrastivePair(torch.autograd.Function):
             sim_q = _tail.gemm_fwd(stacked, queue.buf, None, prec=ctx.prec)[0] if ctx.mfma_q else stacked @ queue.buf.t()
             dsim_q = _lib.empty_like(sim_q)
             if class_positives:
-                _lib.check(lib.facl_contrast_pair_queue_sup(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order),
-                                                            clip_offset, _lib.ptr(classes), _lib.ptr(queue.ids), _lib.ptr(queue.state),
-                                                            float(class_positives), _lib.ptr(dsim), _lib.ptr(dsim_q), _lib.ptr(out),
-                                                            _lib.ptr(out32), _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_queue_sup")
+                _lib.call("facl_contrast_pair_queue_sup", sim, sim_q, G, B, Bk, J, L, order, clip_offset, classes, queue.ids,
+                          queue.state, float(class_positives), dsim, dsim_q, out, out32, ws)
             elif classes is not None:
-                _lib.check(lib.facl_contrast_pair_queue_cls(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order),
-                                                            clip_offset, _lib.ptr(classes), _lib.ptr(queue.ids), _lib.ptr(queue.state),
-                                                            _lib.ptr(dsim), _lib.ptr(dsim_q), _lib.ptr(out), _lib.ptr(out32),
-                                                            _lib.ptr(ws), _lib.stream()), "facl_contrast_pair_queue_cls")
+                _lib.call("facl_contrast_pair_queue_cls", sim, sim_q, G, B, Bk, J, L, order, clip_offset, classes, queue.ids,
+                          queue.state, dsim, dsim_q, out, out32, ws)
             else:
-                _lib.check(lib.facl_contrast_pair_queue(_lib.ptr(sim), _lib.ptr(sim_q), G, B, Bk, J, L, _lib.ptr(order), clip_offset,
-                                                        mask_mode, _lib.ptr(queue.state), _lib.ptr(dsim), _lib.ptr(dsim_q),
-                                                        _lib.ptr(out), _lib.ptr(out32), _lib.ptr(ws), _lib.stream()),
-                           "facl_contrast_pair_queue")
+                _lib.call("facl_contrast_pair_queue", sim, sim_q, G, B, Bk, J, L, order, clip_offset, mask_mode, queue.state,
+                          dsim, dsim_q, out, out32, ws)
             ctx.save_for_backward(stacked, keys, dsim, dsim_q, queue.buf)
         ctx.GB = G * B
         ctx.set_materialize_grads(False)           # an unused loss output arrives as None, not as a freshly filled zero tensor
@@ -443,29 +427,23 @@ class _ContrastivePair(torch.autograd.Function):
         g_c = zero if g_c is None else g_c.contiguous().float()
         g_o = zero if g_o is None else g_o.contiguous().float()
         # rows [0, G*B) carry the circle loss, rows [G*B, (G+1)*B) the global loss: one scaling launch for both
-        lib = _lib.load_library()
         ds = _lib.empty_like(dsim)
         R, J = dsim.shape
-        _lib.check(lib.facl_scale_rows2(_lib.ptr(dsim), _lib.ptr(ds), ctx.GB, R, J, _lib.ptr(g_o), _lib.ptr(g_c), _lib.stream()),
-                   "facl_scale_rows2")
+        _lib.call("facl_scale_rows2", dsim, ds, ctx.GB, R, J, g_o, g_c)
         d_stacked = _tail.gemm_dgrad(ds, keys, prec=bp) if ctx.mfma else ds @ keys
         if ctx.queue:                              # the queue's columns: d stacked += dsim_q @ queue (the queue gets no gradient)
             dsim_q, qbuf = ctx.saved_tensors[3:]
             dq = _lib.empty_like(dsim_q)
-            _lib.check(lib.facl_scale_rows2(_lib.ptr(dsim_q), _lib.ptr(dq), ctx.GB, R, dsim_q.shape[1], _lib.ptr(g_o), _lib.ptr(g_c),
-                                            _lib.stream()), "facl_scale_rows2")
+            _lib.call("facl_scale_rows2", dsim_q, dq, ctx.GB, R, dsim_q.shape[1], g_o, g_c)
             d_stacked += _tail.gemm_dgrad(dq, qbuf, prec=bp) if ctx.mfma_q else dq @ qbuf
         if ctx.own_keys and ctx.mfma:
             # d keys = dsim^T @ stacked accumulated straight into the view rows of d stacked (the keys ARE those rows)
             M_, N_, K_ = ds.shape[0], ds.shape[1], stacked.shape[1]
             pc = {"f32": 0, "x3b": 0, "f16": 1, "x3": 2}[bp]
             with _lib.timed("facl_gemm_wgrad %dx%dx%d%s" % (M_, N_, K_, _tail._LABEL[bp])):
-                rc = lib.facl_gemm_wgrad_acc(_lib.ptr(ds), _lib.ptr(stacked), M_, N_, K_, stacked.stride(0), _lib.ptr(d_stacked), pc,
-                                             _lib.stream())
-            if rc == 0:
+                rc = _lib.call("facl_gemm_wgrad_acc", ds, stacked, M_, N_, K_, stacked.stride(0), d_stacked, pc, accept=(_lib.E_CONFIG,))
+            if rc != _lib.E_CONFIG:
                 return d_stacked, None, None, None, None, None, None, None, None
-            if rc != -4:
-                _lib.check(rc, "facl_gemm_wgrad_acc")
         d_keys = _tail.gemm_wgrad(ds, stacked, prec=bp) if ctx.mfma else ds.t() @ stacked
         if ctx.own_keys:
             d_stacked[:ctx.GB] += d_keys
@@ -479,7 +457,6 @@ class _LossRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, normalize, s):
-        lib = _lib.load_library()
         _lib.require_cuda(x)
         if x.dtype != torch.float32 or x.dim() != 2:
             raise TypeError("the loss row pass takes a 2-D float32 matrix")
@@ -487,8 +464,7 @@ class _LossRows(torch.autograd.Function):
         R, C = x.shape
         n = _lib.empty_like(x)
         inv = _lib.empty(R, dtype=torch.float32, device=x.device)
-        _lib.check(lib.facl_loss_rows_fwd(_lib.ptr(x), R, C, int(normalize), s, _lib.ptr(n), _lib.ptr(inv), _lib.stream()),
-                   "facl_loss_rows_fwd(R=%d, C=%d)" % (R, C))
+        _lib.call("facl_loss_rows_fwd", x, R, C, int(normalize), s, n, inv, detail="R=%d, C=%d" % (R, C))
         ctx.save_for_backward(n, inv)
         ctx.mode = (int(normalize), s)
         return n
@@ -497,12 +473,10 @@ class _LossRows(torch.autograd.Function):
     def backward(ctx, dn):
         n, inv = ctx.saved_tensors
         normalize, s = ctx.mode
-        lib = _lib.load_library()
         dn = dn.contiguous().float()
         dx = _lib.empty_like(n)
         R, C = n.shape
-        _lib.check(lib.facl_loss_rows_bwd(_lib.ptr(dn), _lib.ptr(n), _lib.ptr(inv), R, C, normalize, s, _lib.ptr(dx),
-                                          _lib.stream()), "facl_loss_rows_bwd(R=%d, C=%d)" % (R, C))
+        _lib.call("facl_loss_rows_bwd", dn, n, inv, R, C, normalize, s, dx, detail="R=%d, C=%d" % (R, C))
         return dx, None, None
 
 

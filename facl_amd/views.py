@@ -109,7 +109,6 @@ def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None, nu
         raise ValueError("the reference's stream defines %d views of %d points only; other sizes need the counter-based "
                          "draws (philox)" % (NUM_CROP, NUM_POINT))
     rng = np.random if rng is None else rng
-    lib = _lib.load_library()
     B = len(clips)
     dt = clips[0][0].dtype
     if dt not in (np.float32, np.float64):
@@ -138,9 +137,7 @@ def build_views(clips, rng=None, device="cuda", device_rng=None, philox=None, nu
         idx, noise, cs = _device_draws(clips, bases, device_rng, dev)
     out = _lib.empty((NUM_CROP * B, NUM_POINT, 4), dtype=torch.float32, device=dev)
     _lib.require_cuda(out)
-    fn = lib.facl_build_views_f32 if dt == np.float32 else lib.facl_build_views_f64
-    _lib.check(fn(_lib.ptr(src), src.shape[0], 8, _lib.ptr(idx), _lib.ptr(noise), _lib.ptr(cs), B, _lib.ptr(out),
-                  _lib.stream()), "facl_build_views")
+    _lib.call("facl_build_views_f32" if dt == np.float32 else "facl_build_views_f64", src, src.shape[0], 8, idx, noise, cs, B, out)
     return out
 
 
@@ -215,8 +212,7 @@ def _call_view_entry(stem, f64, recipe, seed, args):
     name = "facl_build_views_%s_%s_%s" % (stem, "gp" if recipe is None else "recipe", "f64" if f64 else "f32")
     keep, extra = ((), ()) if recipe is None else recipe_args(recipe)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.check(getattr(_lib.load_library(), name)(*args(seed - (1 << 64) if seed >= 1 << 63 else seed), *extra, _lib.stream()),
-               name)
+    _lib.call(name, *args(seed - (1 << 64) if seed >= 1 << 63 else seed), *extra)
     del keep
 
 
@@ -227,7 +223,6 @@ def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NU
     (B, G, P) source rows and the error word).  `recipe`: a facl_amd.philox.Recipe, None = the default (the _gp entry)."""
     check_view_size(num_crop, num_point)
     G, P = int(num_crop), int(num_point)
-    lib = _lib.load_library()
     dev = src.device
     B, rows = meta.shape[0], src.shape[0]
     lists = _lib.empty((2, rows), dtype=torch.int32, device=dev)
@@ -237,12 +232,8 @@ def build_views_philox(src, meta, dt, seed, epoch, return_idx=False, num_crop=NU
     idx = _lib.empty((B, G, P), dtype=torch.int32, device=dev) if return_idx else None
     _lib.require_cuda(out)
     f64 = dt == np.float64
-    rt = lib.facl_views_temporal_rows_f64 if f64 else lib.facl_views_temporal_rows_f32
-    _lib.check(rt(_lib.ptr(src), rows, 8, _lib.ptr(meta), B, _lib.ptr(lists), _lib.ptr(counts), _lib.ptr(err),
-                  _lib.stream()), "facl_views_temporal_rows")
-    _call_view_entry("philox", f64, recipe, seed, lambda sd: (
-        _lib.ptr(src), rows, 8, _lib.ptr(meta), _lib.ptr(lists), _lib.ptr(counts), sd, int(epoch), B, G, P, _lib.ptr(out),
-        _lib.ptr(idx)))
+    _lib.call("facl_views_temporal_rows_f64" if f64 else "facl_views_temporal_rows_f32", src, rows, 8, meta, B, lists, counts, err)
+    _call_view_entry("philox", f64, recipe, seed, lambda sd: (src, rows, 8, meta, lists, counts, sd, int(epoch), B, G, P, out, idx))
     return (out, idx, err) if return_idx else out
 
 

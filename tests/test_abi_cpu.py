@@ -34,7 +34,12 @@ def test_header_constants_match_the_python_binding():
     txt = open(os.path.join(ROOT, "include", "facl_hip.h")).read()
     m = re.search(r"#define\s+FACL_AMAX_WORDS\s+(\d+)", txt)
     assert m and int(m.group(1)) == _lib.AMAX_WORDS
-    common = open(os.path.join(ROOT, "facl_amd", "csrc", "common.h")).read()
+    # the refusal codes that facl_amd/_lib.py names (call's `accept`) and puts into its messages
+    codes = dict(re.findall(r"#define\s+FACL_E_(\w+)\s+\((-\d+)\)", txt))
+    assert {k: int(v) for k, v in codes.items()} == {"SHAPE": _lib.E_SHAPE, "NULL": _lib.E_NULL, "ALIGN": _lib.E_ALIGN,
+                                                     "CONFIG": _lib.E_CONFIG}
+    assert sorted(_lib._ERR) == sorted(int(v) for v in codes.values())
+    common =open(os.path.join(ROOT, "facl_amd", "csrc", "common.h")).read()
     slots = int(re.search(r"#define\s+FACL_AMAX_SLOTS\s+(\d+)", common).group(1))
     stride = int(re.search(r"#define\s+FACL_AMAX_STRIDE\s+(\d+)", common).group(1))
     assert slots * stride == _lib.AMAX_WORDS and stride * 4 == 128           # one 128-byte line per slot

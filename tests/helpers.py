@@ -53,6 +53,33 @@ def max_rel_rows(a, b):
     return float((num / den).max())
 
 
+def sa_params(sd, dev, dtype=None):
+    """The 18 tensors of net3DV_1 under the names facl_amd/sa_mlp.py uses (W1 .. rv3), on `dev`, fp32 unless `dtype`."""
+    import torch
+    m = {"W1": "net3DV_1.0.weight", "b1": "net3DV_1.0.bias", "g1": "net3DV_1.1.weight", "be1": "net3DV_1.1.bias",
+         "rm1": "net3DV_1.1.running_mean", "rv1": "net3DV_1.1.running_var",
+         "W2": "net3DV_1.3.weight", "b2": "net3DV_1.3.bias", "g2": "net3DV_1.4.weight", "be2": "net3DV_1.4.bias",
+         "rm2": "net3DV_1.4.running_mean", "rv2": "net3DV_1.4.running_var",
+         "W3": "net3DV_1.6.weight", "b3": "net3DV_1.6.bias", "g3": "net3DV_1.7.weight", "be3": "net3DV_1.7.bias",
+         "rm3": "net3DV_1.7.running_mean", "rv3": "net3DV_1.7.running_var"}
+    return {k: torch.as_tensor(sd[v]).to(dev).to(dtype or torch.float32).contiguous() for k, v in m.items()}
+
+
+def oracle_pooled(sd, xt_MDSK, training, dtype):
+    """net3DV_1 of the oracle (oracle/encoder.py), in `dtype`, on CPU."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import encoder as E
+    sd = {k: (torch.as_tensor(v).to(dtype) if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v).clone())
+          for k, v in sd.items()}
+    h = xt_MDSK.to(dtype)
+    with torch.no_grad():
+        for li in (0, 3, 6):
+            h = E._conv_bn_relu(sd, "net3DV_1", li, h, training)
+        pooled = F.max_pool2d(h, (1, h.shape[-1]), stride=1)
+    return pooled.squeeze(-1).permute(0, 2, 1).reshape(-1, 256), sd
+
+
 def synth_clip(seed, dt, P=900, Kp=300, R1=500, R2=200):
     """The four (rows, 8) clouds `__getitem__` loads for one video (cn3D_data_set.py:105-116), synthetic; the same
     formula as tools/make_goldens.py: synth_clip, whose arguments tests/golden/views.npz records in `cases`."""

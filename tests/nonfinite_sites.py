@@ -90,15 +90,15 @@ def _xt(x_rows, K):
 
 @functools.lru_cache(maxsize=None)
 def _sa_forward_reference(key, training):
-    from test_gpu_sa_mlp import _oracle_pooled
+    from helpers import oracle_pooled
     case = dict(key)
     x, sd = sa_inputs(case)
-    pooled, sd64 = _oracle_pooled(sd, _xt(x, case["K"]), training, torch.float64)
+    pooled, sd64 = oracle_pooled(sd, _xt(x, case["K"]), training, torch.float64)
     return {"pooled": pooled, "buffers": {k: sd64[v] for k, v in SA_BUFFERS.items()}}
 
 
 def sa_reference(case, training=True):
-    """{"pooled": (groups, 256) fp64, "buffers": {rm1..rv3: fp64 after the forward}} of _oracle_pooled on the case's inputs.
+    """{"pooled": (groups, 256) fp64, "buffers": {rm1..rv3: fp64 after the forward}} of oracle_pooled on the case's inputs.
     Computed once per case and shared; callers must not modify it."""
     return _sa_forward_reference(tuple(sorted(case.items())), training)
 

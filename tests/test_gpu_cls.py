@@ -7,15 +7,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from poison import poisoned_scratch  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _gather64(stacked, G, B):

@@ -1,7 +1,5 @@
 """Spherical k-means on the device (csrc/cluster.hip, facl_amd/cluster.py), the clustering entry and --class_ids cluster of the
 training entries.  References are fp64 NumPy restatements of the algorithm as facl_amd.cluster.kmeans documents it."""
-import contextlib
-import io
 import os
 import re
 from types import SimpleNamespace
@@ -10,17 +8,13 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poisoned_scratch  # noqa: F401
+from synth_tree import epoch_loss_text, run_train_entry, train_argv, write_tree
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 EPS24 = 2.0 ** -24
 GAP = 2e-6                                                   # REL_TOL of tests/test_gpu_knn.py x the largest |cosine| = 1
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _dev(a, dtype=None):
@@ -293,52 +287,17 @@ def test_cluster_eval_entry(tmp_path, capsys):
 
 
 # ---- 5: --class_ids cluster of the training entry ---------------------------------------------------------------------------------
-def _clip(seed, P):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25
-    return pts, r.rand(300, 8) - 0.5, r.rand(400, 8) - 0.5, r.rand(150, 8) - 0.5
-
-
-def _tree(root, n=24):
-    """n clips over 4 actions: cameras 2 / 3 (cross-view train) and 1 (test), listed under the training and extraction folders
-    (the tree of test_gpu_loss_class.py)."""
-    from facl_amd.dataset import clip_paths
-    for i in range(n):
-        nm = "S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4)
-        for p, a in zip(clip_paths(str(root), nm, "0"), _clip(200 + i, 600 + 7 * i)):
-            os.makedirs(os.path.dirname(p), exist_ok=True)
-            np.save(p, a)
-        os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-
-
 CLUSTER = ("--loss_mask", "class", "--class_ids", "cluster", "--clusters", "3", "--cluster_every", "1")
 
 
 def _run_entry(root, folder, *extra):
-    from facl_amd import cn3d_train_motion_GL as train
-    args = ["--synthetic", "0", "--data_root", str(root), "--dataset", "ntu120", "--INPUT_FEATURE_NUM", "4", "--batchSize", "4",
-            "--num_crop", "10", "--SAMPLE_NUM", "512", "--loss_normalize", "1", "--loss_temperature", "0.1", "--neg_queue", "8",
-            "--nepoch", "2", "--save_root_dir", str(folder)]
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        net = train.main(args + [str(a) for a in extra])
-    torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, out.getvalue()
-
-
-def _loss_text(out, epoch):
-    m = re.findall(r"epoch: %d loss mode is : 1 --loss: (\S+)" % epoch, out)
-    assert len(m) == 1, out
-    return m[0]
+    mode = ("--loss_normalize", "1", "--loss_temperature", "0.1", "--neg_queue", "8", "--nepoch", "2")
+    return run_train_entry(train_argv(root, folder, *extra, before_save=mode, features_first=True))
 
 
 def test_train_entry_with_cluster_ids(tmp_path):
     root = tmp_path / "d"
-    _tree(str(root))
+    write_tree(str(root))
     sd_a, out_a = _run_entry(root, tmp_path / "a", *CLUSTER)
     lines = re.findall(r"epoch: (\d+) clusters: 3 objective: (\S+) iters: (\d+) sizes min/median/max: (\d+)/(\S+)/(\d+) \| acc: (\S+) nmi: (\S+)",
                        out_a)
@@ -350,13 +309,13 @@ def test_train_entry_with_cluster_ids(tmp_path):
     # epoch 0: every id is unknown, the class mask is the exclude mask bit for bit
     sd_x, out_x = _run_entry(root, tmp_path / "x", "--loss_mask", "exclude")
     assert "clusters:" not in out_x
-    assert _loss_text(out_a, 0) == _loss_text(out_x, 0)
+    assert epoch_loss_text(out_a, 0) == epoch_loss_text(out_x, 0)
     # epoch 1: sixteen clips in three clusters put two cluster-mates into every batch of four, so the mask acts
     assert sd_a.keys() == sd_x.keys()
     assert any(not torch.equal(sd_a[k], sd_x[k]) for k in sd_a)
     # two identical runs give bit-identical weights and checkpoints
     sd_b, out_b = _run_entry(root, tmp_path / "b", *CLUSTER)
-    assert [_loss_text(out_b, e) for e in (0, 1)] == [_loss_text(out_a, e) for e in (0, 1)]
+    assert [epoch_loss_text(out_b, e) for e in (0, 1)] == [epoch_loss_text(out_a, e) for e in (0, 1)]
     assert re.findall(r"clusters: .*", out_b) == re.findall(r"clusters: .*", out_a)
     for k in sd_a:
         assert torch.equal(sd_a[k], sd_b[k]), k

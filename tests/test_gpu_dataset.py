@@ -1,35 +1,24 @@
 """The dataset on disk through the GPU: --view_rng numpy views from files equal the reference's __getitem__ (fixture
 tests/golden/dataset.npz), the counter-based philox views (csrc/views_philox.hip) equal their NumPy restatement
 (facl_amd/philox.py) fed through the NumPy-mode kernel, and the training / extraction / probe entries run on a small tree."""
+import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from helpers import load_golden
+from ranks import rank_env, run_ranks
+from synth_tree import train_argv, tree_clip, write_clip, write_tree
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ULP1 = np.spacing(np.float32(1.0))
 
 
-def _write_clip(root, name, clip, branch="0"):
-    from facl_amd.dataset import clip_paths
-    for p, a in zip(clip_paths(str(root), name, branch), clip):
-        os.makedirs(os.path.dirname(p), exist_ok=True)
-        np.save(p, a)
-
-
 def _clip(seed, P=900, Kp=300, R1=500, R2=200, dt=np.float64):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25                          # at least one non-zero row in each temporal channel
-    return tuple(a.astype(dt) for a in (pts, r.rand(Kp, 8) - 0.5, r.rand(R1, 8) - 0.5, r.rand(R2, 8) - 0.5))
+    return tree_clip(seed, P, Kp, R1, R2, dt)                # this module's default sizes
 
 
 @pytest.mark.parametrize("prefetch", [False, True])
@@ -38,7 +27,7 @@ def test_numpy_views_from_disk_equal_the_reference(tmp_path, prefetch):
     g = load_golden("dataset.npz")
     names = [str(n) for n in g["item_names"]]
     for i, n in enumerate(names):
-        _write_clip(tmp_path, n, [g[f"item{i}/cloud{k}"] for k in range(4)])
+        write_clip(tmp_path, n, [g[f"item{i}/cloud{k}"] for k in range(4)])
     index = ClipIndex.from_dir(str(tmp_path / "reslution" / "Resolution60" / "raw"), "ntu120")
     vids = np.array(index.select("view"))
     for s in (3, 11):
@@ -130,23 +119,11 @@ def test_philox_views_any_cloud_size_and_missing_temporal_rows():
 
 
 # ---- entries on a small tree -------------------------------------------------------------------------------------------------
-def _tree(root, n=24):
-    """n clips: cameras 2 / 3 (cross-view train) and 1 (test); listed under the training, extraction and probe folders."""
-    names = []
-    for i in range(n):
-        cam = (2, 3, 1)[i % 3]
-        names.append("S%03dC%03dP%03dR001A%03d" % (1 + i % 4, cam, 1 + i, 1 + (i // 3) % 4))   # every action in both splits
-    for i, nm in enumerate(names):
-        _write_clip(root, nm, _clip(200 + i, 600 + 7 * i, 300, 400, 150))
-        os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-        os.makedirs(os.path.join(root, "reslution", "Resolution10", "raw"), exist_ok=True)
-    return names
+_tree = functools.partial(write_tree, listed=("raw", "res10"))     # listed under the training, extraction and probe folders
 
 
 def _train_args(root, ck, *extra):
-    return ["--synthetic", "0", "--data_root", str(root), "--dataset", "ntu120", "--batchSize", "4", "--nepoch", "2",
-            "--num_crop", "10", "--SAMPLE_NUM", "512", "--INPUT_FEATURE_NUM", "4", "--save_root_dir", str(ck)] + list(extra)
+    return train_argv(root, ck, *extra, after_batch=("--nepoch", "2"))
 
 
 def test_disk_training_eager_and_graph(tmp_path):
@@ -213,10 +190,8 @@ def test_disk_extraction_and_probe(tmp_path):
     assert top1 == 100.0
 
 
-def _ddp_worker(rank, world, port, root, ck, q):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      FACL_DIST_BACKEND="gloo", LOCAL_RANK="0")
+def _ddp_worker(rank, world, port, q, root, ck):
+    rank_env(rank, world, port, FACL_DIST_BACKEND="gloo", LOCAL_RANK="0")
     import torch.distributed as dist
     from facl_amd import cn3d_train_motion_GL as train
     net = train.main(_train_args(root, ck + str(rank), "--nepoch", "1", "--graph", "0", "--view_rng", "philox"))
@@ -226,15 +201,7 @@ def _ddp_worker(rank, world, port, root, ck, q):
 
 
 def test_disk_training_two_ranks_run_equal_step_counts(tmp_path):
-    import torch.multiprocessing as mp
     _tree(tmp_path / "d", n=27)                               # 18 train clips: 2 steps of 4 per rank, 2 clips left over
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 29700 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=_ddp_worker, args=(r, 2, port, str(tmp_path / "d"), str(tmp_path / "ck"), q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=600) for _ in procs])
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_ddp_worker, 2, port, args=(str(tmp_path / "d"), str(tmp_path / "ck")), timeout=600)
     assert res == [(0, 2), (1, 2)]

@@ -3,50 +3,19 @@ the sharded step (SyncBN hooks inside the HIP passes, embeddings all-gather, fla
 equal the single-process step at the global batch."""
 import os
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from ranks import ROOT, rank_env, run_ranks
+from step_factory import dp_step, make_net, step_opt
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _opt(D, B, N):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                           sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B,
-                           pooling="concatenation", SAMPLE_NUM=N)
-
-
-def _run_step(clip, G, rank, world):
-    from facl_amd import dist as fdist
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from facl_amd.train_common import ContrastiveStep
-    from oracle.weights import formula_state_dict
-    B, _, N, D = clip.shape
-    opt = _opt(D, B, N)
-    net = PointNet_Plus(opt, gost=G)
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(D).items()})
-    net = net.cuda().train()
-    net.bn_reduce_fn = fdist.make_bn_reduce_fn()
-    optim = torch.optim.SGD(net.parameters(), lr=0.0)            # keep the parameters: we compare gradients
-    step = ContrastiveStep(net, optim, opt, G)
-    # two steps (lr = 0): the first gradient sync is synchronous and learns the buckets, the second one overlaps the
-    # tail bucket's all-reduce with the set-abstraction backward (facl_amd/dist.py: GradSync)
-    step(clip.cuda(), epoch=0, order=np.array([2, 0, 3, 1]))
-    loss, _, _ = step(clip.cuda(), epoch=0, order=np.array([2, 0, 3, 1]))
-    grads = {k: p.grad.detach().cpu().clone() for k, p in net.named_parameters() if p.grad is not None}
-    bufs = {k: v.detach().cpu().clone() for k, v in net.state_dict().items() if "running" in k}
-    return float(loss.item()), grads, bufs
 
 
 def _worker(rank, world, port, q, extra_env=None):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      FACL_DIST_BACKEND="gloo")
-    os.environ.update(extra_env or {})
+    rank_env(rank, world, port, FACL_DIST_BACKEND="gloo", **(extra_env or {}))
     import torch.distributed as dist
     from facl_amd import dist as fdist
     torch.cuda.set_device(0)
@@ -54,7 +23,7 @@ def _worker(rank, world, port, q, extra_env=None):
     torch.manual_seed(3)
     G, Bl, N, D = 4, 2, 512, 4
     full = torch.rand(Bl * world, G, N, D) - 0.5
-    loss, grads, bufs = _run_step(full[rank * Bl:(rank + 1) * Bl], G, rank, world)
+    loss, grads, bufs = dp_step(full[rank * Bl:(rank + 1) * Bl], G, rank, world)
     q.put((rank, loss, {k: v.numpy() for k, v in grads.items()}, {k: v.numpy() for k, v in bufs.items()}))
     dist.barrier()
     dist.destroy_process_group()
@@ -64,21 +33,14 @@ def _worker(rank, world, port, q, extra_env=None):
 def test_two_ranks_equal_single_process_global_batch(oneshot):
     """oneshot: the SyncBN reductions go through the OPT-IN peer-mailbox kernel (FACL_ONESHOT_SYNCBN=1, csrc/mailbox.hip: both
     ranks open each other's IPC handle on the one GPU) instead of the process group's all-reduce; same bounds."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 29600 + (os.getpid() % 2000) + (7 if oneshot else 0)
     env = {"FACL_ONESHOT_SYNCBN": "1"} if oneshot else {"FACL_ONESHOT_SYNCBN": "0"}
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, env)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker, 2, port, args=(env,), timeout=300)
     # single process, global batch
     torch.manual_seed(3)
     G, Bl, N, D = 4, 2, 512, 4
     full = torch.rand(Bl * 2, G, N, D) - 0.5
-    loss1, grads1, bufs1 = _run_step(full, G, 0, 1)
+    loss1, grads1, bufs1 = dp_step(full, G, 0, 1)
     loss2 = 0.5 * (res[0][1] + res[1][1])                         # mean of the per-rank (local-mean) losses
     print("loss 1-rank %.6f  2-rank %.6f" % (loss1, loss2))
     assert abs(loss1 - loss2) <= 1e-5 * abs(loss1)
@@ -93,11 +55,10 @@ def test_two_ranks_equal_single_process_global_batch(oneshot):
         assert np.allclose(res[0][3][k], b1.numpy(), rtol=2e-5, atol=1e-7), k
 
 
-def _worker_nccl1(port, q):
+def _worker_nccl1(rank, world, port, q):
     """Real RCCL backend with a 1-rank group: every collective of facl_amd/dist.py executes (fp64 all-reduce of the BN
     buffers, all-gather + reduce-scatter of the embeddings, flat gradient all-reduce) and must be the identity."""
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1")
+    rank_env(rank, world, port)
     import torch.distributed as dist
     from facl_amd import dist as fdist
     import facl_amd.train_common as TC
@@ -107,21 +68,16 @@ def _worker_nccl1(port, q):
     TC.fdist.is_distributed = fdist.is_distributed
     torch.manual_seed(3)
     full = torch.rand(4, 4, 512, 4) - 0.5
-    loss, grads, bufs = _run_step(full, 4, 0, 1)
+    loss, grads, bufs = dp_step(full, 4, 0, 1)
     q.put((loss, {k: v.numpy() for k, v in grads.items()}))
     dist.destroy_process_group()
 
 
 def test_rccl_backend_one_rank_group_is_identity():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_worker_nccl1, args=(29700 + (os.getpid() % 2000), q))
-    p.start()
-    loss_d, grads_d = q.get(timeout=300)
-    p.join(timeout=60)
+    (loss_d, grads_d), = run_ranks(_worker_nccl1, 1, 29700 + (os.getpid() % 2000), timeout=300)
     torch.manual_seed(3)
     full = torch.rand(4, 4, 512, 4) - 0.5
-    loss1, grads1, _ = _run_step(full, 4, 0, 1)
+    loss1, grads1, _ = dp_step(full, 4, 0, 1)
     assert abs(loss1 - loss_d) <= 1e-6 * abs(loss1)
     for k, g1 in grads1.items():
         g1 = g1.numpy()
@@ -131,9 +87,7 @@ def test_rccl_backend_one_rank_group_is_identity():
 def _worker_nccl2(rank, world, port, q):
     """One rank per DEVICE on the real RCCL backend: reduce-scatter backward of the embeddings all-gather (rank-major
     (R,G,B_l,C) chunks), fp64 SyncBN all-reduces, asynchronous tail-bucket gradient all-reduce."""
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    rank_env(rank, world, port, LOCAL_RANK=str(rank), HSA_ENABLE_IPC_MODE_LEGACY="0")
     os.environ.pop("FACL_DIST_BACKEND", None)
     import torch.distributed as dist
     from facl_amd import dist as fdist
@@ -143,7 +97,7 @@ def _worker_nccl2(rank, world, port, q):
     torch.manual_seed(3)
     G, Bl, N, D = 4, 2, 512, 4
     full = torch.rand(Bl * world, G, N, D) - 0.5
-    loss, grads, bufs = _run_step(full[rank * Bl:(rank + 1) * Bl], G, rank, world)
+    loss, grads, bufs = dp_step(full[rank * Bl:(rank + 1) * Bl], G, rank, world)
     q.put((rank, loss, {k: v.numpy() for k, v in grads.items()}, {k: v.numpy() for k, v in bufs.items()}))
     dist.barrier()
     dist.destroy_process_group()
@@ -154,19 +108,12 @@ def test_two_ranks_on_rccl_equal_single_process_global_batch():
     gloo rehearsal above covers the math there)."""
     if torch.cuda.device_count() < 2:
         pytest.skip("needs >= 2 GPUs (RCCL refuses two ranks on one device)")
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 29800 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=_worker_nccl2, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=600) for _ in procs], key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker_nccl2, 2, port, timeout=600)
     torch.manual_seed(3)
     G, Bl, N, D = 4, 2, 512, 4
     full = torch.rand(Bl * 2, G, N, D) - 0.5
-    loss1, grads1, bufs1 = _run_step(full, G, 0, 1)
+    loss1, grads1, bufs1 = dp_step(full, G, 0, 1)
     loss2 = 0.5 * (res[0][1] + res[1][1])
     assert abs(loss1 - loss2) <= 1e-5 * abs(loss1)
     gmax = max(float(np.linalg.norm(v.numpy())) for v in grads1.values())
@@ -249,19 +196,15 @@ def _run_graphed_vs_eager(clip, G):
     optimizer steps each on the same clips; returns (eager losses, graph losses, max relative parameter difference,
     number of graph segments, number of eager collectives between them)."""
     from facl_amd import dist as fdist
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
     from facl_amd.optim import FusedAdam
     from facl_amd.train_common import ContrastiveStep, GraphedStep
-    from oracle.weights import formula_state_dict
     B, _, N, D = clip.shape
-    opt = _opt(D, B, N)
+    opt = step_opt(D, B, N)
     order = np.array([2, 0, 3, 1])
     clips = [clip.cuda(), (clip * 0.9).cuda(), (clip * 1.1).cuda()]
     nets, losses = [], []
     for graphed in (False, True):
-        net = PointNet_Plus(opt, gost=G)
-        net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(D).items()})
-        net = net.cuda().train()
+        net = make_net(D, G, opt=opt, device="cuda").train()
         net.bn_reduce_fn = fdist.make_bn_reduce_fn()
         step = ContrastiveStep(net, FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6), opt, G)
         seg = None
@@ -288,8 +231,7 @@ def _run_graphed_vs_eager(clip, G):
 
 
 def _worker_graph(rank, world, port, q, backend):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    rank_env(rank, world, port)
     import torch.distributed as dist
     from facl_amd import dist as fdist
     import facl_amd.train_common as TC
@@ -323,15 +265,8 @@ def test_segmented_graph_step_equals_eager_step_under_data_parallelism(backend, 
     HIP graphs, the collectives run eagerly between them.  Three optimizer steps (FusedAdam) must give the eager step's
     losses and parameters -- on 2 gloo ranks sharing the GPU, and on the real RCCL backend with a forced 1-rank group (every
     RCCL call executes between graph replays, as it will with N > 1)."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 29900 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=_worker_graph, args=(r, world, port, q, backend)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=240) for _ in procs], key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker_graph, world, port, args=(backend,), timeout=240)
     for r in res:
         assert r[1] != "error", r[2]
     for rank, l_eager, l_graph, worst, n_graphs, n_coll in res:
@@ -342,15 +277,12 @@ def test_segmented_graph_step_equals_eager_step_under_data_parallelism(backend, 
         assert worst < 1e-4
 
 
-def _worker_full_graph(port, q):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", FACL_DP_GRAPH="full")
+def _worker_full_graph(rank, world, port, q):
+    rank_env(rank, world, port, FACL_DP_GRAPH="full")
     import torch.distributed as dist
     from facl_amd import dist as fdist
     import facl_amd.train_common as TC
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
     from facl_amd.optim import FusedAdam
-    from oracle.weights import formula_state_dict
     torch.cuda.set_device(0)
     dist.init_process_group("nccl", rank=0, world_size=1)
     fdist.is_distributed = lambda: True                          # force every collective on with a 1-rank RCCL group
@@ -362,11 +294,9 @@ def _worker_full_graph(port, q):
         order = np.array([2, 0, 3, 1])
         out = []
         for graphed in (False, True):
-            net = PointNet_Plus(_opt(D, B, N), gost=G)
-            net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(D).items()})
-            net = net.cuda().train()
+            net = make_net(D, G, opt=step_opt(D, B, N), device="cuda").train()
             net.bn_reduce_fn = fdist.make_bn_reduce_fn()
-            step = TC.ContrastiveStep(net, FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6), _opt(D, B, N), G)
+            step = TC.ContrastiveStep(net, FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6), step_opt(D, B, N), G)
             if graphed:
                 step = TC.GraphedStep(step, clips[0], G, restore=True)
                 assert step.segments is None and step.full_dp_graph
@@ -383,12 +313,7 @@ def test_optin_full_graph_capture_of_the_data_parallel_step():
     graph (torch's RCCL process group joins the stream capture) -- no cut, no eager collective.  On the real RCCL backend with
     a forced 1-rank group: three optimizer steps equal the eager sharded step (GraphedStep validated the replay against one
     eager step before handing it out)."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_worker_full_graph, args=(30100 + (os.getpid() % 2000), q))
-    p.start()
-    status, payload = q.get(timeout=300)
-    p.join(timeout=60)
+    (status, payload), = run_ranks(_worker_full_graph, 1, 30100 + (os.getpid() % 2000), timeout=300)
     assert status == "ok", payload
     eager, graph = payload
     print("eager", eager, "full graph", graph)
@@ -397,8 +322,7 @@ def test_optin_full_graph_capture_of_the_data_parallel_step():
 
 
 def _worker_mailbox(rank, world, port, q):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    rank_env(rank, world, port)
     import torch.distributed as dist
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -451,14 +375,6 @@ def test_oneshot_mailbox_allreduce_equals_rank_ordered_sum(world):
     handles exactly as peers on other devices would: 30 eager calls (sizes 1 .. 4608 doubles, values over five decades) and a
     captured graph replayed four times must equal the sum in RANK ORDER bit for bit on every rank; no time-out was raised.
     What this cannot show is cross-device visibility over xGMI: the path stays opt-in."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 31000 + (os.getpid() % 2000) + world
-    procs = [ctx.Process(target=_worker_mailbox, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=240) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker_mailbox, world, port, timeout=240, check_exit=True)
     assert res == [(r, True) for r in range(world)], res
-    assert all(p.exitcode == 0 for p in procs)

@@ -1,12 +1,12 @@
 """GPU parity of the whole encoder + losses + training step (through the reference-shaped host API)
 vs the reference goldens and the fp64 oracle."""
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 import torch
 
 from helpers import forward64, load_golden, max_rel_rows, rel_err, routing_taps
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import make_net, step_opt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -18,30 +18,6 @@ TOL = 1e-4          # north_star: fp32 features / loss within 1e-4 relative
 GTOL = 5e-3
 PRE_BN_BIAS = {"net3DV_1.0.bias", "net3DV_1.3.bias", "net3DV_1.6.bias", "net3DV_3.0.bias",
                "net3DV_3.3.bias", "net3DV_3.6.bias", "netR_FC.0.bias"}
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned): the partial-sum workspace and
-    every output / scratch tensor the host layer allocates are filled with NaN bytes before the launches, so a partial
-    row or output element left unwritten at a ragged shape fails the comparison instead of reading recycled memory."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
-
-
-def _opt(D, B, N=512):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                           sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B,
-                           pooling="concatenation", SAMPLE_NUM=N)
-
-
-def _model(D, B, G, neg=False):
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from oracle.weights import formula_state_dict
-    net = PointNet_Plus(_opt(D, B), gost=G)
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(D, neg_gamma=neg).items()})
-    return net.to(DEV)
 
 
 def _oracle_forward(g, D, neg, dtype):
@@ -81,11 +57,11 @@ def test_c1_golden_forward_loss_backward_adam(tag, D, neg):
     from facl_amd.utils_my import circle_contrast, global_contrast, group_points_3DV
     g = load_golden(f"c1_{tag}.npz")
     B, G, N, S, K, _ = [int(v) for v in g["meta"]]
-    opt = _opt(D, B)
+    opt = step_opt(D, B)
     pts = torch.from_numpy(g["points"]).to(DEV)
     xt, yt = group_points_3DV(pts, opt)
 
-    net = _model(D, B, G, neg).eval()
+    net = make_net(D, G, B, neg_gamma=neg).eval()
     with torch.no_grad():
         ev = net(xt, yt)
     for name, t in zip(("x", "code", "x_nor", "x_global"), ev):
@@ -93,7 +69,7 @@ def test_c1_golden_forward_loss_backward_adam(tag, D, neg):
         print(f"eval {name}: {e:.2e}")
         assert e < TOL, name
 
-    net = _model(D, B, G, neg).train()
+    net = make_net(D, G, B, neg_gamma=neg).train()
     optim = torch.optim.Adam(net.parameters(), lr=0.0003, betas=(0.5, 0.999), eps=1e-06)
     losses = []
     for it in range(3):
@@ -234,8 +210,8 @@ def test_step_vs_fp64_oracle_headline_shapes_small_batch():
     D, B, G, N, S, K = 4, 3, 4, 2048, 64, 64
     torch.manual_seed(5)
     clip = torch.rand(B, G, N, D) - 0.5
-    opt = _opt(D, B, N)
-    net = _model(D, B, G).train()
+    opt = step_opt(D, B, N)
+    net = make_net(D, G, B).train()
     optim = torch.optim.Adam(net.parameters(), lr=0.0003, betas=(0.5, 0.999), eps=1e-06)
     step = ContrastiveStep(net, optim, opt, G)
     order = np.array([2, 0, 3, 1])
@@ -267,7 +243,7 @@ def test_tiny_golden_K8_through_replication():
     from facl_amd.utils_my import knn_radius_group
     from oracle.weights import formula_state_dict
     g = load_golden("tiny.npz")
-    opt = _opt(4, 2, 128)
+    opt = step_opt(4, 2, 128)
     opt.sample_num_level1 = 16
     net = PointNet_Plus_fine(opt, gost=3, sample_num_level1=16, knn_K=8)
     net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(4).items()})
@@ -290,7 +266,7 @@ def test_other_K_forward_backward_vs_fp64_oracle(S, K):
     D, B, G, N = 4, 8, 3, 512
     torch.manual_seed(K)
     pts = torch.rand(G * B, N, D) - 0.5
-    opt = _opt(D, B, N)
+    opt = step_opt(D, B, N)
     net = PointNet_Plus_fine(opt, gost=G, sample_num_level1=S, knn_K=K)
     sdn = formula_state_dict(D)
     net.load_state_dict({k: torch.as_tensor(v) for k, v in sdn.items()})
@@ -343,9 +319,9 @@ def test_optin_precisions_vs_default_path(prec):
     order = np.random.RandomState(3).permutation(G)
 
     def run(p):
-        net = _model(D, B, G).train()
+        net = make_net(D, G, B).train()
         net.precision = p
-        step = ContrastiveStep(net, torch.optim.SGD(net.parameters(), lr=0.0), _opt(D, B, N), G)
+        step = ContrastiveStep(net, torch.optim.SGD(net.parameters(), lr=0.0), step_opt(D, B, N), G)
         loss, lc, lo = step(clip, epoch=0, order=order)
         torch.cuda.synchronize()
         grads = {k: q.grad.detach().double().clone() for k, q in net.named_parameters() if q.grad is not None}

@@ -1,11 +1,12 @@
 """End-to-end entries on the GPU: training entry -> checkpoint -> extraction entry, the HIP-graph
 replay of the step, and checkpoint compatibility with the reference's key names."""
 import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+from step_factory import step_opt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,9 +33,7 @@ def test_train_entry_checkpoint_then_extract(tmp_path):
     from facl_amd.extract_common import extract_batch, save_single_feature
     from facl_amd.cn3d_model_conbag import PointNet_Plus
     from oracle import encoder as E, grouping as OG
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=4, Num_Class=512, batchSize=3, pooling="concatenation",
-                          SAMPLE_NUM=512)
+    opt = step_opt(4, 3, 512)
     m = PointNet_Plus(opt, gost=4)
     m.load_state_dict(sd)
     m = m.to(DEV).eval()
@@ -106,9 +105,7 @@ def test_graph_replay_equals_eager():
     from facl_amd.train_common import ContrastiveStep, GraphedStep
     from oracle.weights import formula_state_dict
     D, B, G, N = 4, 2, 3, 512
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B, pooling="concatenation",
-                          SAMPLE_NUM=N)
+    opt = step_opt(D, B, N)
     torch.manual_seed(0)
     clips = [torch.rand(B, G, N, D, device=DEV) - 0.5 for _ in range(3)]
     orders = [np.array([1, 2, 0]), np.array([2, 0, 1]), np.array([0, 2, 1])]
@@ -143,9 +140,7 @@ def test_graph_replay_sees_learning_rate_changes_with_fused_adam():
     from facl_amd.train_common import ContrastiveStep, GraphedStep
     from oracle.weights import formula_state_dict
     D, B, G, N = 4, 2, 3, 512
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B, pooling="concatenation",
-                          SAMPLE_NUM=N)
+    opt = step_opt(D, B, N)
     torch.manual_seed(0)
     clips = [torch.rand(B, G, N, D, device=DEV) - 0.5 for _ in range(3)]
     order = np.array([1, 2, 0])

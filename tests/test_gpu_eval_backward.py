@@ -15,18 +15,14 @@ import torch.nn.functional as F
 
 from eval_grad_ref import BN_EPS, bn_eval, forward64_eval, routed_pool, routed_relu, shifted_running_stats
 from helpers import FUSED_ADAM_BETAS, adam64, forward64, max_rel_rows, routing_taps, snapshot
-from test_gpu_finetune import ADAM_TOL, CONFIGS, NCLS, TOL, _grouped, _labels, _make, _opt, _points, _tree
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import class_labels, grouped, make_finetune_step, points, step_opt
+from synth_tree import write_tree
+from test_gpu_finetune import ADAM_TOL, CONFIGS, NCLS, TOL
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 S = K = 64
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _gen(seed):
@@ -316,7 +312,7 @@ def test_eval_forward_with_grad_vs_no_grad(D, K_, groups):
 # ---- 2 + 3. the whole model in eval(), one frozen FineTuneStep ------------------------------------------------------------------
 def _reference_eval(c, sd, pts, labels, routing, dtype):
     B, G = c["B"], c["G"]
-    x_rows, centers = _grouped(c, pts)
+    x_rows, centers = grouped(c, pts)
     x, xg, _, q, ties = forward64_eval(x_rows, centers, sd, G, S, K, DEV, routing=routing, grad=True, dtype=dtype)
     feat = torch.cat((x, xg), dim=0).view(G + 1, B, 512).permute(1, 0, 2).reshape(B, (G + 1) * 512)
     logits = F.normalize(feat, p=2, dim=1) @ q["head.fc.weight"].t() + q["head.fc.bias"]
@@ -334,15 +330,15 @@ def test_frozen_step_vs_fp64(cfg):
     against fp64 Adam on the kernel's gradients; a second step from the restored state bit-identical to the first."""
     from facl_amd.finetune import FineTuneStep
     c = CONFIGS[cfg]
-    net, optim, _ = _make(c)
-    pts, labels = _points(c, 100), _labels(c, 1)
-    x_rows, centers = _grouped(c, pts)
+    net, optim, _ = make_finetune_step(c, NCLS)
+    pts, labels = points(c, 100), class_labels(c, 1, NCLS)
+    x_rows, centers = grouped(c, pts)
     sd0 = {k: v.detach().cpu() for k, v in net.state_dict().items()}
     with torch.no_grad():
         stats = forward64(x_rows, centers, sd0, c["G"], S, K, DEV)[2]
     net.load_state_dict(shifted_running_stats(sd0, stats))
     del stats, x_rows, centers
-    step = FineTuneStep(net, optim, _opt(c), c["G"], freeze_bn=True)
+    step = FineTuneStep(net, optim, step_opt(c["D"], c["B"], c["N"]), c["G"], freeze_bn=True)
     step.labels.copy_(labels)
     before = snapshot(net, optim)
     with routing_taps() as routing:
@@ -400,7 +396,7 @@ def test_frozen_step_vs_fp64(cfg):
 # ---- 5. the entry ------------------------------------------------------------------------------------------------------------
 def test_entry_freeze_bn(tmp_path, capsys):
     from facl_amd import finetune
-    _tree(str(tmp_path / "d"))
+    write_tree(str(tmp_path / "d"))
     common = ["--synthetic", "0", "--data_root", str(tmp_path / "d"), "--dataset", "ntu120", "--batchSize", "4",
               "--num_crop", "10", "--SAMPLE_NUM", "512", "--INPUT_FEATURE_NUM", "4", "--label_fraction", "0.5", "--num_class", "4"]
     finetune.main(common + ["--nepoch", "1", "--graph", "0", "--eval_every", "0", "--save_root_dir", str(tmp_path / "pre")])

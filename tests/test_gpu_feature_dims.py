@@ -8,24 +8,17 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import canon_groups_np, load_golden
+from helpers import canon_groups_np, load_golden, max_rel_rows, sa_params
+from poison import poisoned  # noqa: F401  (as the autouse fixtures of the modules whose tests are called below)
+from ranks import rank_env, run_ranks
+from step_factory import dp_step, make_net, step_opt
 
-import test_gpu_ddp as TDDP
-import test_gpu_encoder as TENC
 import test_gpu_sa_mlp as TSA
 import test_gpu_trajectory as TTRJ
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 WIDE = [5, 6, 7, 8]
-
-
-@pytest.fixture
-def poisoned():
-    """NaN-poisoned scratch, as the autouse fixtures of the modules whose tests are called below."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 # ---- 1. grouping ---------------------------------------------------------------------------------------------------------
@@ -172,7 +165,7 @@ def test_sa_ragged_unit_counts_wide(D, nunits, poisoned):
     torch.manual_seed(nunits + 100 * D)
     x_rows = ((torch.rand(nunits * K, D, device=DEV) - 0.5) * 0.8).contiguous()
     sd = formula_state_dict(D)
-    p = TSA._params(sd, DEV)
+    p = sa_params(sd, DEV)
     params = [p[k].clone().requires_grad_(True) for k in sa_mlp._PARAM_ORDER]
     state = {"buffers": {k: p[k] for k in ("rm1", "rv1", "rm2", "rv2", "rm3", "rv3")}, "training": True}
     pooled = sa_mlp.SAMLPFunction.apply(x_rows, state, *params)
@@ -186,7 +179,7 @@ def test_sa_ragged_unit_counts_wide(D, nunits, poisoned):
         h = torch.relu((y - mean) / torch.sqrt(var + 1e-5) * q[gk] + q[bek])
     h3 = h.view(nunits, K, 256)
     ref, ref_arg = h3.max(dim=1)
-    assert TSA.max_rel_rows(pooled.detach().cpu().numpy(), ref.detach().cpu().numpy()) < 5e-5
+    assert max_rel_rows(pooled.detach().cpu().numpy(), ref.detach().cpu().numpy()) < 5e-5
     my_arg = pooled.grad_fn.c["arg"].long()
     flips = int((my_arg != ref_arg).sum())
     assert flips <= max(2, 1e-4 * ref_arg.numel())
@@ -230,18 +223,17 @@ def test_c1_d8_golden_features(poisoned):
     """The model's eval- and training-mode features on the reference's D = 8 fixture: within the golden's own fp32 distance to
     the fp64 oracle + 1e-4 (as test_gpu_encoder.py does for d3 / d4)."""
     from facl_amd.utils_my import group_points_3DV
-    from helpers import max_rel_rows
     from oracle import encoder as E, grouping as OG
     from oracle.weights import formula_state_dict
     g = load_golden("c1_d8.npz")
     B, G, N, S, K, D = [int(v) for v in g["meta"]]
     assert D == 8
-    xt, yt = group_points_3DV(torch.from_numpy(g["points"]).to(DEV), TENC._opt(D, B))
+    xt, yt = group_points_3DV(torch.from_numpy(g["points"]).to(DEV), step_opt(D, B, 512))
     _, xo, yo = OG.group_points(g["points"], S, K, 0.06)
     xt64 = torch.from_numpy(xo).permute(0, 3, 1, 2).double()
     yt64 = torch.from_numpy(yo).view(G * B, 1, S, 3).transpose(1, 3).double()
     for mode in ("eval", "train"):
-        net = TENC._model(D, B, G)
+        net = make_net(D, G, B)
         net = net.eval() if mode == "eval" else net.train()
         with torch.no_grad():
             out = net(xt, yt) if mode == "eval" else net(xt, yt, 1)
@@ -276,9 +268,7 @@ def test_train_d8_checkpoint_then_extract(tmp_path):
     feats = ext.main(["--checkpoint", path, "--batchSize", "3", "--num_crop", "4", "--SAMPLE_NUM", "512",
                       "--INPUT_FEATURE_NUM", str(D), "--num_batches", "1", "--save_path", str(tmp_path / "f")])
     assert feats.shape == (3, 5 * 512) and np.isfinite(feats).all()
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=3, pooling="concatenation",
-                          SAMPLE_NUM=512)
+    opt = step_opt(D, 3, 512)
     m = PointNet_Plus(opt, gost=4)
     m.load_state_dict(sd)
     m = m.to(DEV).eval()
@@ -319,11 +309,7 @@ def test_dataset_entry_still_refuses_d8(tmp_path):
 
 # ---- 8. two ranks on one GPU at D = 8 ------------------------------------------------------------------------------------
 def _worker_d8(rank, world, port, q, extra_env=None):
-    import sys
-    sys.path.insert(0, TDDP.ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      FACL_DIST_BACKEND="gloo")
-    os.environ.update(extra_env or {})
+    rank_env(rank, world, port, FACL_DIST_BACKEND="gloo", **(extra_env or {}))
     import torch.distributed as dist
     from facl_amd import dist as fdist
     torch.cuda.set_device(0)
@@ -331,7 +317,7 @@ def _worker_d8(rank, world, port, q, extra_env=None):
     torch.manual_seed(3)
     G, Bl, N, D = 4, 2, 512, 8
     full = torch.rand(Bl * world, G, N, D) - 0.5
-    loss, grads, bufs = TDDP._run_step(full[rank * Bl:(rank + 1) * Bl], G, rank, world)
+    loss, grads, bufs = dp_step(full[rank * Bl:(rank + 1) * Bl], G, rank, world)
     q.put((rank, loss, {k: v.numpy() for k, v in grads.items()}, {k: v.numpy() for k, v in bufs.items()}))
     dist.barrier()
     dist.destroy_process_group()
@@ -339,21 +325,13 @@ def _worker_d8(rank, world, port, q, extra_env=None):
 
 @pytest.mark.parametrize("oneshot", [False, True])
 def test_two_ranks_d8_equal_single_process_global_batch(oneshot):
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 31700 + (os.getpid() % 2000) + (7 if oneshot else 0)
     env = {"FACL_ONESHOT_SYNCBN": "1" if oneshot else "0"}
-    procs = [ctx.Process(target=_worker_d8, args=(r, 2, port, q, env)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t[0])
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker_d8, 2, port, args=(env,), timeout=300)
     torch.manual_seed(3)
     G, Bl, N, D = 4, 2, 512, 8
     full = torch.rand(Bl * 2, G, N, D) - 0.5
-    loss1, grads1, bufs1 = TDDP._run_step(full, G, 0, 1)
+    loss1, grads1, bufs1 = dp_step(full, G, 0, 1)
     loss2 = 0.5 * (res[0][1] + res[1][1])
     assert abs(loss1 - loss2) <= 1e-5 * abs(loss1)
     gmax = max(float(np.linalg.norm(v.numpy())) for v in grads1.values())

@@ -3,20 +3,21 @@ with the kernel's discrete decisions pinned, then normalise -> Linear -> cross-e
 with changing labels / clouds / learning rate, and the entry end to end on a tiny dataset.
 The whole module runs on NaN-poisoned scratch."""
 import os
-from types import SimpleNamespace
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from helpers import FUSED_ADAM_BETAS, PRE_BN_BIAS, adam64, forward64, max_rel_rows, routing_taps, snapshot
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import class_labels, grouped, make_finetune_step, points
+from synth_tree import write_tree
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-4              # logits / loss / gradients: the one-step bound of the suite
 ADAM_TOL = 2e-6         # Adam on the kernel's own gradients
-S = K = 64
+S = K = 64             # step_factory's
 NCLS = 12
 
 CONFIGS = {
@@ -26,64 +27,11 @@ CONFIGS = {
 }
 
 
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
-
-
-def _opt(c):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=S,
-                           sample_num_level2=S, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                           pooling="concatenation", SAMPLE_NUM=c["N"])
-
-
-def _make(c, lr=3e-4):
-    """FineTuneNet with the formula encoder weights and a head drawn from a fixed seed + FusedAdam + FineTuneStep."""
-    from facl_amd.finetune import FineTuneNet, FineTuneStep
-    from facl_amd.optim import FusedAdam
-    from oracle.weights import formula_state_dict
-    opt = _opt(c)
-    torch.manual_seed(5)
-    net = FineTuneNet(opt, NCLS, gost=c["G"])
-    net.load_encoder_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    with torch.no_grad():                                # logits of order one (a head some way into its training), so that the
-        net.head.fc.weight.mul_(50.0)                    # loss depends visibly on the labels; a non-zero bias, so that its
-        net.head.fc.bias.normal_(0.0, 0.5)               # update is checked against values
-    net = net.to(DEV).train()
-    optim = FusedAdam(net.parameters(), lr=lr, betas=(0.5, 0.999), eps=1e-6)
-    return net, optim, FineTuneStep(net, optim, opt, c["G"])
-
-
-def _points(c, seed):
-    B, G, N, D = c["B"], c["G"], c["N"], c["D"]
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    shape = (G * B, N, D) if c["view_major"] else (B, G, N, D)
-    return torch.rand(shape, device=DEV, generator=gen) - 0.5
-
-
-def _labels(c, seed):
-    return torch.from_numpy(np.random.RandomState(seed).randint(0, NCLS, c["B"]).astype(np.int32)).to(DEV)
-
-
-def _grouped(c, points):
-    from facl_amd.utils_my import group_points_3DV, knn_radius_group
-    N, D = c["N"], c["D"]
-    vm = points if c["view_major"] else points.permute(1, 0, 2, 3).reshape(-1, N, D)
-    if N == 512:
-        xt, yt = group_points_3DV(vm.contiguous(), _opt(c))
-    else:
-        xt, yt = knn_radius_group(vm.contiguous(), S, K, 0.16)
-    return xt.permute(0, 2, 3, 1).reshape(-1, D), yt.permute(0, 2, 1, 3).reshape(-1, 3)
-
-
 def _reference(c, before, pts, labels, routing, other_labels=None):
     """The supervised step in torch fp64 from the state `before`: encoder (forward64, routed through the kernel's max-pool
     and ReLU decisions), the clip-major vector [x_view0 .. x_view(G-1), x_global], F.normalize, Linear, mean cross-entropy."""
     B, G = c["B"], c["G"]
-    x_rows, centers = _grouped(c, pts)
+    x_rows, centers = grouped(c, pts)
     x, xg, _, q, ties = forward64(x_rows, centers, before["net"], G, S, K, DEV, routing=routing, grad=True)
     feat = torch.cat((x, xg), dim=0).view(G + 1, B, 512).permute(1, 0, 2).reshape(B, (G + 1) * 512)
     logits = F.normalize(feat, p=2, dim=1) @ q["head.fc.weight"].t() + q["head.fc.bias"]
@@ -146,8 +94,8 @@ def _grads_params(net):
 @pytest.mark.parametrize("cfg", ["ragged", "view_major"])
 def test_one_step_vs_fp64(cfg):
     c = CONFIGS[cfg]
-    net, optim, step = _make(c)
-    pts, labels = _points(c, 100), _labels(c, 1)
+    net, optim, step = make_finetune_step(c, NCLS)
+    pts, labels = points(c, 100), class_labels(c, 1, NCLS)
     step.labels.copy_(labels)
     before = snapshot(net, optim)
     with routing_taps() as routing:
@@ -164,15 +112,15 @@ def test_graph_replay_follows_labels_clouds_and_lr():
     that state, whose loss must equal the replay's to the bit); the labels reach the replay."""
     from facl_amd.train_common import GraphedStep
     c = CONFIGS["ragged"]
-    net_g, opt_g, step_g = _make(c)
+    net_g, opt_g, step_g = make_finetune_step(c, NCLS)
     snap0 = snapshot(net_g, opt_g)
-    g = GraphedStep(step_g, _points(c, 99), c["G"], restore=True)
+    g = GraphedStep(step_g, points(c, 99), c["G"], restore=True)
     torch.cuda.synchronize()
     after0 = snapshot(net_g, opt_g)
     for k in snap0["net"]:
         assert torch.equal(snap0["net"][k], after0["net"][k]), k                # the three warm-up steps undone
-    net_t, opt_t, step_t = _make(c)
-    sched = [(_points(c, 200 + k), _labels(c, 10 + k), lr) for k, lr in enumerate((3e-4, 3e-4, 1e-3))]
+    net_t, opt_t, step_t = make_finetune_step(c, NCLS)
+    sched = [(points(c, 200 + k), class_labels(c, 10 + k, NCLS), lr) for k, lr in enumerate((3e-4, 3e-4, 1e-3))]
     assert not torch.equal(sched[0][1], sched[1][1])
     for k, (pts, labels, lr) in enumerate(sched):
         opt_g.param_groups[0]["lr"] = lr
@@ -197,33 +145,12 @@ def test_graph_replay_follows_labels_clouds_and_lr():
             assert abs(float(out[0]) - ref["loss_other"]) > 10 * TOL * abs(ref["loss"]), (float(out[0]), ref["loss_other"])
 
 
-# ---- the entry on a tiny dataset ---------------------------------------------------------------------------------------------
-def _clip(seed, P):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25
-    return pts, r.rand(300, 8) - 0.5, r.rand(400, 8) - 0.5, r.rand(150, 8) - 0.5
-
-
-def _tree(root, n=24):
-    """n clips over 4 actions: cameras 2 / 3 (cross-view train) and 1 (test), listed under the training and extraction folders."""
-    from facl_amd.dataset import clip_paths
-    for i in range(n):
-        nm = "S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4)
-        for p, a in zip(clip_paths(str(root), nm, "0"), _clip(200 + i, 600 + 7 * i)):
-            os.makedirs(os.path.dirname(p), exist_ok=True)
-            np.save(p, a)
-        os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-
-
+# ---- the entry on a tiny dataset (synth_tree.write_tree) ------------------------------------------------------------------------
 def test_entry_end_to_end(tmp_path, capsys):
     from facl_amd import finetune
     from facl_amd.cn3d_model_conbag import PointNet_Plus
     from facl_amd.linear_classify import Final_FC
-    _tree(str(tmp_path / "d"))
+    write_tree(str(tmp_path / "d"))
     runs = []
     for tag in ("a", "b"):
         ck = tmp_path / ("ck" + tag)

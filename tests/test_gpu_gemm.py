@@ -4,19 +4,11 @@ import pytest
 import torch
 
 from helpers import bn_consts as _bn_consts, clear_of_the_relu_edge as _clear_of_the_relu_edge, rel_err
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import step_opt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned): the partial-sum workspace and
-    every output / scratch tensor the host layer allocates are filled with NaN bytes before the launches, so a partial
-    row or output element left unwritten at a ragged shape fails the comparison instead of reading recycled memory."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _ws():
@@ -692,11 +684,9 @@ def test_eval_mode_net3dv3_propagates_a_nan_like_torch():
     """relu / max-pool of the row-streamed path must not swallow a NaN (fmaxf(NaN, 0) = 0; `v > best` skips NaN) --
     torch.relu and MaxPool2d propagate it.  One poisoned centroid row through net3DV_3 in eval mode: that cloud's x_pre is
     non-finite, every other cloud's is finite and unchanged."""
-    from types import SimpleNamespace
     from facl_amd.cn3d_model_conbag import PointNet_Plus
     from oracle.weights import formula_state_dict
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64, sample_num_level2=64,
-                          INPUT_FEATURE_NUM=4, Num_Class=512, batchSize=8, pooling="concatenation", SAMPLE_NUM=512)
+    opt = step_opt(4, 8, 512)
     net = PointNet_Plus(opt, gost=4)
     net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(4).items()})
     net = net.to(DEV).eval()

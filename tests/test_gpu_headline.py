@@ -2,23 +2,17 @@
 through the appearance stream's entry (configs[2]: D=4, appearance-style clouds) against a plain torch-fp64 evaluation
 of the same graph on the GPU (matmuls, train-mode BN with batch statistics, ReLU, max-pools, the reference's literal
 loss construction) -- independent of the HIP kernels and of the size the oracle's goldens pin (C1)."""
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from helpers import forward64, max_rel_rows, rel_err, routing_taps
+from step_factory import step_opt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-4          # north_star: fp32 features / loss within 1e-4 relative
-
-
-def _opt(D, B, N):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                           sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B,
-                           pooling="concatenation", SAMPLE_NUM=N)
 
 
 # prec "x3" / "x3b": the opt-in three-product arithmetic (facl_amd.tail.precision).  "x3b" (backward GEMMs only) must
@@ -34,7 +28,7 @@ def test_full_step_at_headline_size_vs_torch_fp64(stream, D, prec):
     gen = torch.Generator(device=DEV)
     gen.manual_seed(11)
     clip = (appearance_batch if stream == "appearance" else synthetic_batch)(B, G, N, D, torch.device(DEV), gen)
-    opt = _opt(D, B, N)
+    opt = step_opt(D, B, N)
     sd = formula_state_dict(D)
     net = PointNet_Plus(opt, gost=G)
     net.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})

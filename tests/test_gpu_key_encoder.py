@@ -3,7 +3,6 @@ the training step with a key encoder (eager and graph-replayed) and the training
 size of test_gpu_neg_queue.py with its mode and its bound TOL.  The whole module runs on NaN-poisoned scratch."""
 import os
 import re
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -11,17 +10,12 @@ import torch
 
 from chunk_cases import DEV, _banded, _bands_intact, _case, _ints, _ptrs
 from helpers import snapshot
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import make_contrastive_step, make_net, points
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4                           # test_gpu_neg_queue.py / test_gpu_trajectory.py: losses of one step
 U = 2.0 ** -24                       # unit roundoff of fp32
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 # ---- 1: the kernel ------------------------------------------------------------------------------------------------------------------
@@ -72,34 +66,6 @@ STEP_MODE = dict(loss_normalize=1, loss_temperature=0.1, loss_mask="exclude")
 KW = dict(normalize=True, temperature=0.1, mask="exclude")
 
 
-def _opt(c, **flags):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                           sample_num_level2=64, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                           pooling="concatenation", SAMPLE_NUM=c["N"], **flags)
-
-
-def _make_net(c):
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from oracle.weights import formula_state_dict
-    net = PointNet_Plus(_opt(c), gost=c["G"])
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    return net.to(DEV).train()
-
-
-def _make_step(c, **flags):
-    from facl_amd.optim import FusedAdam
-    from facl_amd.train_common import ContrastiveStep
-    net = _make_net(c)
-    optim = FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6)
-    return net, optim, ContrastiveStep(net, optim, _opt(c, **flags), c["G"])
-
-
-def _points(c, seed):
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    return torch.rand((c["B"], c["G"], c["N"], c["D"]), device=DEV, generator=gen) - 0.5
-
-
 def _mapped(x_global):
     from facl_amd.utils_my import loss_rows
     return loss_rows(x_global.detach().contiguous(), KW["normalize"], KW["temperature"]).clone()
@@ -126,10 +92,10 @@ def test_key_encoder_at_m0_is_the_plain_queue():
     orders = [r.permutation(G) for _ in range(4)]
     res = []
     for flags in (dict(key_encoder=1, key_momentum=0.0), {}):
-        net, optim, step = _make_step(c, neg_queue=6, **STEP_MODE, **flags)
+        net, optim, step = make_contrastive_step(c, neg_queue=6, **STEP_MODE, **flags)
         per_step = []
         for k, order in enumerate(orders):
-            out = [t.detach().clone() for t in step(_points(c, 100 + k), order=order)]
+            out = [t.detach().clone() for t in step(points(c, 100 + k), order=order)]
             torch.cuda.synchronize()
             per_step.append((out, _sd(net), step.queue.buf.clone(), step.queue.head_valid()))
             if flags:                                       # m = 0: the copy's parameters are the model's after every step
@@ -153,13 +119,13 @@ def test_key_encoder_three_eager_steps_at_m_half():
     B, G = c["B"], c["G"]
     r = np.random.RandomState(7)
     orders = [r.permutation(G) for _ in range(3)]
-    net, optim, step = _make_step(c, neg_queue=6, key_encoder=1, key_momentum=0.5, **STEP_MODE)
-    net0, optim0, step0 = _make_step(c, neg_queue=6, **STEP_MODE)        # the run without a key encoder (step 1 only)
-    third = _make_net(c)
+    net, optim, step = make_contrastive_step(c, neg_queue=6, key_encoder=1, key_momentum=0.5, **STEP_MODE)
+    net0, optim0, step0 = make_contrastive_step(c, neg_queue=6, **STEP_MODE)        # the run without a key encoder (step 1 only)
+    third = make_net(c["D"], c["G"], c["B"], c["N"]).train()
     init = _sd(net)
     k64 = [p.detach().double().clone() for p in net.parameters()]
     for k in range(3):
-        pts = _points(c, 100 + k)
+        pts = points(c, 100 + k)
         held = None if step.queue is None else step.queue.valid_rows().double()
         want_rows = None
         if step.key_encoder is not None:
@@ -229,14 +195,14 @@ def test_key_encoder_graph_replay():
     r = np.random.RandomState(7)
     orders = [r.permutation(G) for _ in range(4)]
     flags = dict(neg_queue=6, key_encoder=1, key_momentum=0.9, **STEP_MODE)
-    net_g, opt_g, step_g = _make_step(c, **flags)
-    g = GraphedStep(step_g, _points(c, 99), G, restore=True)
+    net_g, opt_g, step_g = make_contrastive_step(c, **flags)
+    g = GraphedStep(step_g, points(c, 99), G, restore=True)
     assert step_g.queue is not None and step_g.queue.head_valid() == (0, 0) and int((step_g.queue.buf != 0).sum()) == 0
     assert step_g.key_encoder is not None
     _assert_key_equals(step_g.key_encoder, _sd(net_g), [m.steps for m in net_g.modules() if hasattr(m, "count_batch")], "start")
-    net_t, opt_t, step_t = _make_step(c, **flags)
+    net_t, opt_t, step_t = make_contrastive_step(c, **flags)
     for k, order in enumerate(orders):
-        pts = _points(c, 100 + k)
+        pts = points(c, 100 + k)
         before = snapshot(net_g, opt_g)
         qsnap, ksnap = step_g.queue.snapshot(), step_g.key_encoder.snapshot()
         out_g = [t.detach().clone() for t in g(pts, order=order)]

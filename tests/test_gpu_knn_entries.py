@@ -1,48 +1,25 @@
 """The weighted-kNN training monitor (--knn_every) and the standalone entry (python -m facl_amd.knn_eval) on a small
-dataset tree written the way tests/test_gpu_dataset.py writes its own."""
+dataset tree (synth_tree.write_tree: 16 train clips, 8 test clips, four actions, every action in both splits)."""
 import os
 import re
 
-import numpy as np
 import pytest
 import torch
+
+from synth_tree import train_argv, write_tree
 
 pytestmark = pytest.mark.gpu
 KNN_K = "3"
 
 
-def _clip(seed, P):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25                          # at least one non-zero row in each temporal channel
-    return pts, r.rand(300, 8) - 0.5, r.rand(400, 8) - 0.5, r.rand(150, 8) - 0.5
-
-
-def _tree(root, n=24):
-    """n clips: cameras 2 / 3 (cross-view train: 16) and 1 (test: 8), four actions, every action in both splits."""
-    from facl_amd.dataset import clip_paths
-    names = ["S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4) for i in range(n)]
-    os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-    for i, nm in enumerate(names):
-        for p, a in zip(clip_paths(str(root), nm, "0"), _clip(200 + i, 600 + 7 * i)):
-            os.makedirs(os.path.dirname(p), exist_ok=True)
-            np.save(p, a)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-    return names
-
-
 def _train_args(root, ck, *extra):
-    return ["--synthetic", "0", "--data_root", str(root), "--dataset", "ntu120", "--batchSize", "4", "--nepoch", "2",
-            "--max_steps_per_epoch", "2", "--num_crop", "10", "--SAMPLE_NUM", "512", "--INPUT_FEATURE_NUM", "4",
-            "--knn_k", KNN_K, "--save_root_dir", str(ck)] + list(extra)
+    return train_argv(root, ck, *extra, after_batch=("--nepoch", "2", "--max_steps_per_epoch", "2"), before_save=("--knn_k", KNN_K))
 
 
 @pytest.fixture(scope="module")
 def tree(tmp_path_factory):
     root = tmp_path_factory.mktemp("knn_tree")
-    return root, _tree(root)
+    return root, write_tree(root)
 
 
 def _logged(out):

@@ -4,31 +4,23 @@ ring buffer (facl_queue_push_ids), utils_my.contrastive_losses_stacked(mask='cla
 graph-replayed) and the training entry with --resume.  The fp64 truth is built here from the contract: the full logits with the
 masked columns at -inf, an empty negative set contributing exactly 0.  Bounds: those of test_gpu_loss_modes.py and
 test_gpu_trajectory.py.  The whole module runs on NaN-poisoned scratch."""
-import contextlib
-import io
 import os
 import re
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from helpers import snapshot
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import make_contrastive_step, points
+from synth_tree import assert_same_state, run_train_entry, train_argv, write_tree
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LOSS_TOL, GRAD_TOL = 2e-6, 2e-5      # test_gpu_loss_modes.py
 TOL = 1e-4                           # test_gpu_trajectory.py: losses of one step
 NINF = float("-inf")
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """NaN-poisoned outputs and scratch (facl_amd._lib.poisoned): an element a launch leaves unwritten shows up as NaN."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _state(head, valid):
@@ -426,24 +418,7 @@ KW = dict(normalize=True, temperature=0.1)
 
 
 def _make_step(c, mask="class", **flags):
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from facl_amd.optim import FusedAdam
-    from facl_amd.train_common import ContrastiveStep
-    from oracle.weights import formula_state_dict
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                          pooling="concatenation", SAMPLE_NUM=c["N"], loss_normalize=1, loss_temperature=0.1, loss_mask=mask, **flags)
-    net = PointNet_Plus(opt, gost=c["G"])
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    net = net.to(DEV).train()
-    optim = FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6)
-    return net, optim, ContrastiveStep(net, optim, opt, c["G"])
-
-
-def _points(c, seed):
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    return torch.rand((c["B"], c["G"], c["N"], c["D"]), device=DEV, generator=gen) - 0.5
+    return make_contrastive_step(c, loss_normalize=1, loss_temperature=0.1, loss_mask=mask, **flags)
 
 
 def test_step_with_class_mask_vs_closed_form_and_graph_replay():
@@ -466,8 +441,8 @@ def test_step_with_class_mask_vs_closed_form_and_graph_replay():
     outs = []
     for k in range(2):
         assert net.training
-        out = [t.detach().clone() for t in step(_points(c, 100 + k), order=orders[k])]
-        outs.append([t.detach().clone() for t in step_x(_points(c, 100 + k), order=orders[k])])
+        out = [t.detach().clone() for t in step(points(c, 100 + k), order=orders[k])]
+        outs.append([t.detach().clone() for t in step_x(points(c, 100 + k), order=orders[k])])
         torch.cuda.synchronize()
         if k == 0:
             rows1 = loss_rows(net._stacked.detach(), True, 0.1)[G * B:].clone()
@@ -491,13 +466,13 @@ def test_step_with_class_mask_vs_closed_form_and_graph_replay():
     del net, optim, step, net_x, optim_x, step_x
 
     net_g, opt_g, step_g = _make_step(c, neg_queue=6)
-    g = GraphedStep(step_g, _points(c, 99), G, restore=True)
+    g = GraphedStep(step_g, points(c, 99), G, restore=True)
     assert step_g.queue.head_valid() == (0, 0) and int((step_g.queue.buf != 0).sum()) == 0 and step_g.queue.ids.tolist() == [-1] * 6
     net_t, opt_t, step_t = _make_step(c, neg_queue=6)
     vectors = [[0, 0, 1], [1, -1, 1], [2, 2, 2], [-1, 0, 0]]             # [2, 2, 2]: every negative of that step is a queue row
     want_ids = [-1] * 6
     for k, order in enumerate(orders):
-        pts = _points(c, 100 + k)
+        pts = points(c, 100 + k)
         before = snapshot(net_g, opt_g)
         qsnap = step_g.queue.snapshot()
         step_g.clip_classes.copy_(_i32(vectors[k]))
@@ -522,60 +497,16 @@ def test_step_with_class_mask_vs_closed_form_and_graph_replay():
 
 
 # ---- 8: the training entry on a tiny dataset ------------------------------------------------------------------------------------------
-def _clip(seed, P):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25
-    return pts, r.rand(300, 8) - 0.5, r.rand(400, 8) - 0.5, r.rand(150, 8) - 0.5
-
-
-def _tree(root, n=24):
-    """n clips over 4 actions: cameras 2 / 3 (cross-view train) and 1 (test), listed under the training and extraction folders
-    (the tree of test_gpu_finetune.py)."""
-    from facl_amd.dataset import clip_paths
-    for i in range(n):
-        nm = "S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4)
-        for p, a in zip(clip_paths(str(root), nm, "0"), _clip(200 + i, 600 + 7 * i)):
-            os.makedirs(os.path.dirname(p), exist_ok=True)
-            np.save(p, a)
-        os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-
-
 def _run_entry(root, folder, *extra):
-    from facl_amd import cn3d_train_motion_GL as train
-    args = ["--synthetic", "0", "--data_root", str(root), "--dataset", "ntu120", "--INPUT_FEATURE_NUM", "4", "--batchSize", "4",
-            "--num_crop", "10", "--SAMPLE_NUM", "512", "--loss_normalize", "1", "--loss_temperature", "0.1", "--loss_mask", "class",
-            "--label_fraction", "0.5", "--neg_queue", "8", "--save_state_every", "1", "--save_root_dir", str(folder)]
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        net = train.main(args + [str(a) for a in extra])
-    torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, out.getvalue()
-
-
-def _same(a, b, where):
-    assert type(a) is type(b), where
-    if torch.is_tensor(a):
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), where
-    elif isinstance(a, dict):
-        assert list(a) == list(b), where
-        for k in a:
-            _same(a[k], b[k], "%s.%s" % (where, k))
-    elif isinstance(a, list):
-        assert len(a) == len(b), where
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (where, i))
-    else:
-        assert a == b, (where, a, b)
+    mode = ("--loss_normalize", "1", "--loss_temperature", "0.1", "--loss_mask", "class", "--label_fraction", "0.5",
+            "--neg_queue", "8", "--save_state_every", "1")
+    return run_train_entry(train_argv(root, folder, *extra, before_save=mode, features_first=True))
 
 
 def test_train_entry_with_class_mask_and_resume(tmp_path):
     from facl_amd import train_state
     root = tmp_path / "d"
-    _tree(str(root))
+    write_tree(str(root))
     state = lambda d, e: train_state.load_state(os.path.join(str(d), "state_%d.pth" % e))
     sd_a, out_a = _run_entry(root, tmp_path / "a", "--nepoch", 2)
     assert "class mask: 8 of 16 train clips labelled, 4 classes" in out_a
@@ -589,19 +520,19 @@ def test_train_entry_with_class_mask_and_resume(tmp_path):
     assert (s1["flags"]["loss_mask"], s1["flags"]["label_fraction"], s1["flags"]["label_seed"]) == ("class", 0.5, 0)
     # two identical runs give identical checkpoints
     sd_b, out_b = _run_entry(root, tmp_path / "b", "--nepoch", 2)
-    _same(sd_a, sd_b, "model")
-    _same(state(tmp_path / "b", 1), s1, "state_1")
+    assert_same_state(sd_a, sd_b, "model")
+    assert_same_state(state(tmp_path / "b", 1), s1, "state_1")
     names =[n for n in os.listdir(str(tmp_path / "a")) if n.endswith("_0.pth") and not n.startswith("state_")]
     assert len(names) == 1
-    _same(torch.load(os.path.join(str(tmp_path / "a"), names[0]), map_location="cpu", weights_only=True),
+    assert_same_state(torch.load(os.path.join(str(tmp_path / "a"), names[0]), map_location="cpu", weights_only=True),
           torch.load(os.path.join(str(tmp_path / "b"), names[0]), map_location="cpu", weights_only=True), names[0])
     # stopped after epoch 0 and continued: the same state_1
     _run_entry(root, tmp_path / "c", "--nepoch", 1)
     assert not os.path.exists(os.path.join(str(tmp_path / "c"), "state_1.pth"))
     sd_c, out_c = _run_entry(root, tmp_path / "c", "--nepoch", 2, "--resume", "auto")
     assert "resumed from %s: epoch 1" % os.path.join(str(tmp_path / "c"), "state_0.pth") in out_c
-    _same(sd_c, sd_a, "model")
-    _same(state(tmp_path / "c", 1), s1, "state_1")
+    assert_same_state(sd_c, sd_a, "model")
+    assert_same_state(state(tmp_path / "c", 1), s1, "state_1")
     # a resumed run repeats the labelled fraction
     with pytest.raises(RuntimeError, match="label_fraction"):
         _run_entry(root, tmp_path / "c", "--nepoch", 2, "--resume", "auto", "--label_fraction", "1.0")

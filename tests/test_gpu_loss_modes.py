@@ -2,25 +2,18 @@
 pass, the two mask modes of the fused pair-loss kernels, utils_my.contrastive_losses_stacked, the training step (eager and
 graph-replayed) and the training entry.  The fp64 truth is the device-agnostic closed form of utils_my (held to materialised
 logits in test_loss_modes_cpu.py).  The whole module runs on NaN-poisoned scratch."""
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from helpers import snapshot
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import make_contrastive_step, points
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LOSS_TOL, GRAD_TOL = 2e-6, 2e-5      # test_gpu_tail.py::test_contrastive_pair_on_stacked_embeddings_vs_closed_form_fp64
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """NaN-poisoned outputs and scratch (facl_amd._lib.poisoned): an element a launch leaves unwritten shows up as NaN."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 # ---- 1: the row pass ----------------------------------------------------------------------------------------------------
@@ -288,27 +281,6 @@ STEP_MODE = dict(loss_normalize=1, loss_temperature=0.1, loss_mask="exclude")
 TOL = 1e-4                                                 # test_gpu_trajectory.py: losses of one step
 
 
-def _make_step(c, **flags):
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from facl_amd.optim import FusedAdam
-    from facl_amd.train_common import ContrastiveStep
-    from oracle.weights import formula_state_dict
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                          pooling="concatenation", SAMPLE_NUM=c["N"], **flags)
-    net = PointNet_Plus(opt, gost=c["G"])
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    net = net.to(DEV).train()
-    optim = FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6)
-    return net, optim, ContrastiveStep(net, optim, opt, c["G"])
-
-
-def _points(c, seed):
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    return torch.rand((c["B"], c["G"], c["N"], c["D"]), device=DEV, generator=gen) - 0.5
-
-
 def test_step_with_modes_vs_closed_form_and_graph_replay():
     """ContrastiveStep in mode (normalize, 0.1, exclude) at the ragged size: the first step's two losses against the fp64
     closed form on the HIP forward's own stacked embeddings (1e-4), and they differ from the default-mode losses; then three
@@ -321,9 +293,9 @@ def test_step_with_modes_vs_closed_form_and_graph_replay():
     r = np.random.RandomState(7)
     orders = [r.permutation(G) for _ in range(3)]
     kw = dict(normalize=True, temperature=0.1, mask="exclude")
-    net, optim, step = _make_step(c, **STEP_MODE)
+    net, optim, step = make_contrastive_step(c, **STEP_MODE)
     assert step.loss_mode == kw
-    loss, loss_c, loss_circle = step(_points(c, 100), order=orders[0])
+    loss, loss_c, loss_circle = step(points(c, 100), order=orders[0])
     torch.cuda.synchronize()
     loss, loss_c, loss_circle = loss.detach(), loss_c.detach(), loss_circle.detach()
     st = net._stacked.detach().double()
@@ -336,11 +308,11 @@ def test_step_with_modes_vs_closed_form_and_graph_replay():
     assert abs(rc - dc) > 1e-2 * abs(dc)                   # the mode reached the loss
     del net, optim, step
 
-    net_g, opt_g, step_g = _make_step(c, **STEP_MODE)
-    g = GraphedStep(step_g, _points(c, 99), G, restore=True)
-    net_t, opt_t, step_t = _make_step(c, **STEP_MODE)
+    net_g, opt_g, step_g = make_contrastive_step(c, **STEP_MODE)
+    g = GraphedStep(step_g, points(c, 99), G, restore=True)
+    net_t, opt_t, step_t = make_contrastive_step(c, **STEP_MODE)
     for k, order in enumerate(orders):
-        pts = _points(c, 100 + k)
+        pts = points(c, 100 + k)
         before = snapshot(net_g, opt_g)
         out_g = [t.detach().clone() for t in g(pts, order=order)]
         net_t.load_state_dict(before["net"])

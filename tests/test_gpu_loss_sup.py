@@ -15,17 +15,12 @@ import test_gpu_loss_class as base
 from helpers import snapshot
 from test_gpu_loss_class import (DEV, GRAD_TOL, LOSS_TOL, PAIR_SHAPES, QUEUE_CASES, TOL, _every_anchor_keeps_a_negative, _i32, _ids,
                                  _masks, _positive_cells, _rel, _sim, _state)
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import points
+from synth_tree import assert_same_state, write_tree
 
 pytestmark = pytest.mark.gpu
 WEIGHTS = [1.0, 0.25]
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """NaN-poisoned outputs and scratch (facl_amd._lib.poisoned): an element a launch leaves unwritten shows up as NaN."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 # ---- the truth on a similarity matrix -----------------------------------------------------------------------------------------
@@ -349,7 +344,7 @@ def test_step_with_class_positives_vs_closed_form_and_graph_replay():
     step.clip_classes.copy_(ids)
     for k in range(2):
         assert net.training
-        out = [t.detach().clone() for t in step(base._points(c, 100 + k), order=orders[k])]
+        out = [t.detach().clone() for t in step(points(c, 100 + k), order=orders[k])]
         torch.cuda.synchronize()
         if k == 0:
             rows1 = loss_rows(net._stacked.detach(), True, 0.1)[G * B:].clone()
@@ -371,13 +366,13 @@ def test_step_with_class_positives_vs_closed_form_and_graph_replay():
     del net, optim, step
 
     net_g, opt_g, step_g = base._make_step(c, neg_queue=6, class_positives=1.0)
-    g = GraphedStep(step_g, base._points(c, 99), G, restore=True)
+    g = GraphedStep(step_g, points(c, 99), G, restore=True)
     assert step_g.queue.head_valid() == (0, 0) and int((step_g.queue.buf != 0).sum()) == 0 and step_g.queue.ids.tolist() == [-1] * 6
     net_t, opt_t, step_t = base._make_step(c, neg_queue=6, class_positives=1.0)
     vectors = [[0, 0, 1], [1, -1, 1], [2, 2, 2], [-1, 0, 0]]             # [2, 2, 2]: no in-batch negative
     want_ids = [-1] * 6
     for k, order in enumerate(orders):
-        pts = base._points(c, 100 + k)
+        pts = points(c, 100 + k)
         before = snapshot(net_g, opt_g)
         qsnap = step_g.queue.snapshot()
         step_g.clip_classes.copy_(_i32(vectors[k]))
@@ -407,7 +402,7 @@ def test_train_entry_with_class_positives_and_resume(tmp_path):
     test_gpu_loss_class.py: a 2-epoch run and a 1-epoch run resumed with --resume auto end in the same state_1.pth."""
     from facl_amd import train_state
     root = tmp_path / "d"
-    base._tree(str(root))
+    write_tree(str(root))
     state = lambda d, e: train_state.load_state(os.path.join(str(d), "state_%d.pth" % e))
     run = lambda folder, *extra: base._run_entry(root, folder, "--class_positives", 1, *extra)
     sd_a, out_a = run(tmp_path / "a", "--nepoch", 2)
@@ -421,7 +416,7 @@ def test_train_entry_with_class_positives_and_resume(tmp_path):
     assert not os.path.exists(os.path.join(str(tmp_path / "c"), "state_1.pth"))
     sd_c, out_c = run(tmp_path / "c", "--nepoch", 2, "--resume", "auto")
     assert "resumed from %s: epoch 1" % os.path.join(str(tmp_path / "c"), "state_0.pth") in out_c
-    base._same(sd_c, sd_a, "model")
-    base._same(state(tmp_path / "c", 1), s1, "state_1")
+    assert_same_state(sd_c, sd_a, "model")
+    assert_same_state(state(tmp_path / "c", 1), s1, "state_1")
     with pytest.raises(RuntimeError, match="class_positives"):
         base._run_entry(root, tmp_path / "c", "--nepoch", 2, "--resume", "auto", "--class_positives", "0.5")

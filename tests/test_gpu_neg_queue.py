@@ -3,7 +3,6 @@
 training step (eager and graph-replayed) and the training entry.  The fp64 truth is the device-agnostic closed form of utils_my
 (held to materialised logits in test_neg_queue_cpu.py).  Bounds: those of test_gpu_loss_modes.py.  The whole module runs on
 NaN-poisoned scratch."""
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -11,19 +10,13 @@ import torch
 
 import neg_queue_paths
 from helpers import snapshot
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import make_contrastive_step, points
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LOSS_TOL, GRAD_TOL = 2e-6, 2e-5      # test_gpu_loss_modes.py
 TOL = 1e-4                           # test_gpu_trajectory.py: losses of one step
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """NaN-poisoned outputs and scratch (facl_amd._lib.poisoned): an element a launch leaves unwritten shows up as NaN."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _state(head, valid):
@@ -288,27 +281,6 @@ STEP_MODE = dict(loss_normalize=1, loss_temperature=0.1, loss_mask="exclude")
 KW = dict(normalize=True, temperature=0.1, mask="exclude")
 
 
-def _make_step(c, **flags):
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from facl_amd.optim import FusedAdam
-    from facl_amd.train_common import ContrastiveStep
-    from oracle.weights import formula_state_dict
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                          pooling="concatenation", SAMPLE_NUM=c["N"], **flags)
-    net = PointNet_Plus(opt, gost=c["G"])
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    net = net.to(DEV).train()
-    optim = FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6)
-    return net, optim, ContrastiveStep(net, optim, opt, c["G"])
-
-
-def _points(c, seed):
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    return torch.rand((c["B"], c["G"], c["N"], c["D"]), device=DEV, generator=gen) - 0.5
-
-
 def _key_rows(net, G, B):
     """The rows a step stores: x_global of the step's stacked output after the row map of the step's mode, in fp32."""
     from facl_amd.utils_my import loss_rows
@@ -321,11 +293,11 @@ def test_step_with_neg_queue_zero_is_bit_identical():
     orders = [np.random.RandomState(3).permutation(c["G"]) for _ in range(2)]
     res = []
     for flags in ({}, dict(neg_queue=0)):
-        net, optim, step = _make_step(c, **STEP_MODE, **flags)
+        net, optim, step = make_contrastive_step(c, **STEP_MODE, **flags)
         assert step.queue is None
         outs = []
         for k, order in enumerate(orders):
-            outs += [t.detach().clone() for t in step(_points(c, 100 + k), order=order)]
+            outs += [t.detach().clone() for t in step(points(c, 100 + k), order=order)]
         torch.cuda.synchronize()
         assert step.queue is None
         res.append(outs + [v.detach().clone() for v in net.state_dict().values()])
@@ -346,11 +318,11 @@ def test_step_with_queue_vs_closed_form_and_graph_replay():
     B, G = c["B"], c["G"]
     r = np.random.RandomState(7)
     orders = [r.permutation(G) for _ in range(4)]
-    net, optim, step = _make_step(c, neg_queue=6, **STEP_MODE)
+    net, optim, step = make_contrastive_step(c, neg_queue=6, **STEP_MODE)
     assert step.loss_mode == KW and step.neg_queue == 6 and step.queue is None
     pushed = []
     for k in range(3):
-        loss, loss_c, loss_circle = [t.detach().clone() for t in step(_points(c, 100 + k), order=orders[k])]
+        loss, loss_c, loss_circle = [t.detach().clone() for t in step(points(c, 100 + k), order=orders[k])]
         torch.cuda.synchronize()
         st = net._stacked.detach().double()
         rows = torch.cat(pushed[-2:][::-1]).double() if pushed else None     # what the queue held during this step
@@ -372,12 +344,12 @@ def test_step_with_queue_vs_closed_form_and_graph_replay():
     assert torch.equal(step.queue.buf, torch.cat((pushed[2], pushed[1])))
     del net, optim, step
 
-    net_g, opt_g, step_g = _make_step(c, neg_queue=6, **STEP_MODE)
-    g = GraphedStep(step_g, _points(c, 99), G, restore=True)
+    net_g, opt_g, step_g = make_contrastive_step(c, neg_queue=6, **STEP_MODE)
+    g = GraphedStep(step_g, points(c, 99), G, restore=True)
     assert step_g.queue is not None and step_g.queue.head_valid() == (0, 0) and int((step_g.queue.buf != 0).sum()) == 0
-    net_t, opt_t, step_t = _make_step(c, neg_queue=6, **STEP_MODE)
+    net_t, opt_t, step_t = make_contrastive_step(c, neg_queue=6, **STEP_MODE)
     for k, order in enumerate(orders):
-        pts = _points(c, 100 + k)
+        pts = points(c, 100 + k)
         before = snapshot(net_g, opt_g)
         qsnap = step_g.queue.snapshot()
         out_g = [t.detach().clone() for t in g(pts, order=order)]

@@ -10,17 +10,11 @@ import torch
 
 import nonfinite_sites as NS
 from helpers import max_rel_rows, rel_err
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import step_opt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """NaN-poisoned scratch (facl_amd._lib.poisoned), like the neighbouring modules."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _bad(t):
@@ -34,13 +28,13 @@ def _counts(name, got_bad, ref_bad):
 # ---- (a) the SA block, training mode -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", NS.SA_TRAIN_CASES, ids=NS.ids(NS.SA_TRAIN_CASES))
 def test_sa_training_forward_is_non_finite_where_the_reference_is(case):
-    """sa_mlp_forward(training=True) against _oracle_pooled in fp64: isfinite(pooled) and isfinite of the six running buffers
+    """sa_mlp_forward(training=True) against oracle_pooled in fp64: isfinite(pooled) and isfinite of the six running buffers
     equal the reference's, element for element; elements the reference keeps finite agree with it (5e-5 per row, the bound of
     test_sa_ragged_unit_counts at these unit counts; 2e-6 on the buffers, the bound of test_sa_forward_vs_oracle)."""
     from facl_amd import sa_mlp
-    from test_gpu_sa_mlp import _params
+    from helpers import sa_params
     x, sd = NS.sa_inputs(case)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     pooled, _ = sa_mlp.sa_mlp_forward(x.to(DEV), p, True, K=case["K"], precision=case["precision"])
     torch.cuda.synchronize()
     ref = NS.sa_reference(case, True)
@@ -69,7 +63,7 @@ def test_sa_training_forward_is_non_finite_where_the_reference_is(case):
 # ---- (b) the SA block, eval mode ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", NS.SA_EVAL_CASES, ids=NS.ids(NS.SA_EVAL_CASES))
 def test_sa_eval_forward_is_non_finite_where_the_reference_is(case):
-    """sa_mlp_forward(training=False) with a NaN / +inf coordinate against _oracle_pooled in fp64.
+    """sa_mlp_forward(training=False) with a NaN / +inf coordinate against oracle_pooled in fp64.
     Default fused path (csrc/sa_eval.hip): exactly the reference's groups hold a non-finite feature (the kernel poisons the whole
     group where the reference, for an inf, keeps the features whose ReLU closed: compared per group), every other group agrees
     with the reference (2e-5, the bound of test_sa_eval_one_kernel_vs_training_kernels_and_fp64).
@@ -77,9 +71,9 @@ def test_sa_eval_forward_is_non_finite_where_the_reference_is(case):
     operand maximum of x into the constants of the last layer -- every output is non-finite at least wherever the reference's is.
     A SUPERSET (all groups non-finite) is accepted there: an extraction that is loud in too many rows is still loud."""
     from facl_amd import sa_mlp
-    from test_gpu_sa_mlp import _params
+    from helpers import sa_params
     x, sd = NS.sa_inputs(case)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     path = case["path"]
     prec = path if path in ("x3", "f16") else "f32"
     assert sa_mlp._EVAL_FUSED and sa_mlp._FWD_H3
@@ -110,9 +104,9 @@ def test_sa_backward_spreads_a_non_finite_upstream_gradient(case):
     The conv biases in front of a train-mode BatchNorm have no gradient here by construction (None: the optimizer never touches
     them, so no value can enter them) where autograd returns a rounding-noise gradient that the value poisons; asserted as None."""
     from facl_amd import sa_mlp
-    from test_gpu_sa_mlp import _params
+    from helpers import sa_params
     x, sd = NS.sa_inputs(dict(case, site=None))
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     params = [p[k].clone().requires_grad_(True) for k in sa_mlp._PARAM_ORDER]
     state = dict(training=True, K=case["K"], buffers={k: p[k] for k in NS.SA_BUFFERS})
     pooled = sa_mlp.SAMLPFunction.apply(x.to(DEV), state, *params)
@@ -192,9 +186,7 @@ def test_step_returns_a_non_finite_loss_on_the_clip_that_holds_a_nan(mode):
     from facl_amd.train_common import ContrastiveStep, GraphedStep
     c = NS.STEP_SHAPE
     clips, sd, order = NS.step_inputs()
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                          pooling="concatenation", SAMPLE_NUM=c["N"])
+    opt = step_opt(c["D"], c["B"], c["N"])
     net = PointNet_Plus(opt, gost=c["G"])
     net.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
     net = net.to(DEV).train()

@@ -4,10 +4,8 @@ the training step (eager and graph-replayed), the default path against the direc
 the entries.  The kernel cases are those of chunk_cases.py, the step runs at test_gpu_key_encoder.py's `ragged` size and mode.  The whole
 module runs on NaN-poisoned scratch."""
 import contextlib
-import io
 import os
 import re
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -15,6 +13,9 @@ import torch
 
 from chunk_cases import CHUNK, DEV, _banded, _bands_intact, _case, _chunks, _ints, _ptrs
 from helpers import FUSED_ADAM_BETAS, snapshot
+from step_factory import make_contrastive_step, points
+from synth_tree import assert_same_state, run_train_entry
+from poison import poisoned_scratch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ADAM_TOL = 2e-6                      # test_gpu_trajectory.py / test_gpu_tail.py: Adam on given gradients, of max |.| per tensor
@@ -22,13 +23,6 @@ NORM_TOL = 2.0 ** -22                # the gradient norm: see test_grad_sqnorm_a
 B1, B2 = 0.5, 0.999
 f32 = lambda x: float(np.float32(x))
 LR, EPS, WD = f32(1e-3), f32(1e-6), f32(0.05)             # what the kernels hold: fp32 launch constants and an fp32 device lr
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _norm64(gs):
@@ -232,28 +226,8 @@ LR0 = f32(3e-4)
 RECIPE = dict(weight_decay=0.05, schedule="cosine", warmup_steps=2, decay_steps=6)
 
 
-def _opt(c, **flags):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                           sample_num_level2=64, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                           pooling="concatenation", SAMPLE_NUM=c["N"], **flags)
-
-
 def _make_step(c=RAGGED, **recipe):
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from facl_amd.optim import FusedAdam
-    from facl_amd.train_common import ContrastiveStep
-    from oracle.weights import formula_state_dict
-    net = PointNet_Plus(_opt(c), gost=c["G"])
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    net = net.to(DEV).train()
-    optim = FusedAdam(net.parameters(), lr=3e-4, betas=(0.5, 0.999), eps=1e-6, **recipe)
-    return net, optim, ContrastiveStep(net, optim, _opt(c, **STEP_MODE), c["G"])
-
-
-def _points(seed, c=RAGGED):
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    return torch.rand((c["B"], c["G"], c["N"], c["D"]), device=DEV, generator=gen) - 0.5
+    return make_contrastive_step(c, adam=recipe, **STEP_MODE)
 
 
 class _Calls:
@@ -292,7 +266,7 @@ def step_a():
     with _lib.poisoned():
         net, optim, step = _make_step()
         before = snapshot(net, optim)
-        step(_points(100), order=np.random.RandomState(7).permutation(RAGGED["G"]))
+        step(points(RAGGED, 100), order=np.random.RandomState(7).permutation(RAGGED["G"]))
         torch.cuda.synchronize()
         grads = {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}
         after = snapshot(net, optim)
@@ -307,7 +281,7 @@ def test_default_optimizer_is_the_direct_call_sequence(step_a, monkeypatch):
     net, optim, step = _make_step()
     assert not optim.recipe and optim._partial is None
     with _recorded(monkeypatch) as calls:
-        step(_points(100), order=np.random.RandomState(7).permutation(RAGGED["G"]))
+        step(points(RAGGED, 100), order=np.random.RandomState(7).permutation(RAGGED["G"]))
     torch.cuda.synchronize()
     assert calls.optimizer() == ["facl_adam_prep", "facl_adam_apply"]
     assert float(optim.clip_coef()) == 1.0 and float(optim.grad_norm()) == 0.0 and float(optim.current_lr()) == LR0
@@ -339,7 +313,7 @@ def test_step_with_clipping_decay_and_cosine(step_a, monkeypatch):
     net, optim, step = _make_step(max_grad_norm=0.5 * n64, **RECIPE)
     assert optim.recipe
     with _recorded(monkeypatch) as calls:
-        step(_points(100), order=np.random.RandomState(7).permutation(RAGGED["G"]))
+        step(points(RAGGED, 100), order=np.random.RandomState(7).permutation(RAGGED["G"]))
     torch.cuda.synchronize()
     assert calls.optimizer() == ["facl_grad_sqnorm", "facl_adam_prep_ex", "facl_adamw_apply"]
     named = dict(net.named_parameters())
@@ -390,12 +364,12 @@ def test_recipe_graph_replay_equals_eager(step_a):
     runs = []
     for graphed in (False, True):
         net, optim, step = _make_step(max_grad_norm=0.5 * n64, lr_min=1e-5, **RECIPE)
-        run = GraphedStep(step, _points(99), G, restore=True) if graphed else step
+        run = GraphedStep(step, points(RAGGED, 99), G, restore=True) if graphed else step
         if graphed:
             assert float(optim._step) == 0.0
         per_step = []
         for k in range(6):
-            out = [t.detach().clone() for t in run(_points(100 + k), order=orders[k])]
+            out = [t.detach().clone() for t in run(points(RAGGED, 100 + k), order=orders[k])]
             torch.cuda.synchronize()
             assert all(torch.isfinite(t).all() for t in out)
             snap = snapshot(net, optim)
@@ -429,28 +403,7 @@ LINE = r"epoch: %d loss mode is : 1 --loss: (\S+) \| clips/s: \S+ \| grad norm m
 
 
 def _run(folder, *extra):
-    from facl_amd import cn3d_train_motion_GL as train
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        net = train.main(ENTRY + ["--save_root_dir", str(folder)] + [str(a) for a in extra])
-    torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, out.getvalue()
-
-
-def _same(a, b, where):
-    assert type(a) is type(b), where
-    if torch.is_tensor(a):
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), where
-    elif isinstance(a, dict):
-        assert list(a) == list(b), where
-        for k in a:
-            _same(a[k], b[k], "%s.%s" % (where, k))
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), where
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (where, i))
-    else:
-        assert a == b, (where, a, b)
+    return run_train_entry(ENTRY + ["--save_root_dir", str(folder)] + [str(a) for a in extra])
 
 
 def test_train_entry_with_the_recipe_and_resume(tmp_path):
@@ -471,8 +424,8 @@ def test_train_entry_with_the_recipe_and_resume(tmp_path):
     sd_b, out_b = _run(b, "--nepoch", 2, "--resume", "auto")
     assert "resumed from %s: epoch 1" % os.path.join(str(b), "state_0.pth") in out_b
     assert re.search(LINE % 1, out_b) and not re.search(LINE % 0, out_b)
-    _same(sd_b, sd_a, "model")
-    _same(train_state.load_state(os.path.join(str(b), "state_1.pth")), state_a, "state_1")
+    assert_same_state(sd_b, sd_a, "model")
+    assert_same_state(train_state.load_state(os.path.join(str(b), "state_1.pth")), state_a, "state_1")
     assert re.search(LINE % 1, out_b).groups() == re.search(LINE % 1, out_a).groups()
     # another warm-up would not continue the trajectory
     args = list(ENTRY)

@@ -8,17 +8,13 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poisoned_scratch  # noqa: F401
+from synth_tree import clip_names, write_tree
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ULP = 2                 # top_p against fp64: the kernels work in fp64 and round once (tests/test_gpu_cls.py's convention)
 GAP = 1e-6              # least relative distance of consecutive ranks in the fp64 reference of the random cases
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 # ---- numpy fp64 reference ----------------------------------------------------------------------------------------------------
@@ -200,27 +196,6 @@ def test_first_flag_overwrites_then_adds():
 
 
 # ---- the entry on a tiny dataset ---------------------------------------------------------------------------------------------
-def _clip(seed, P):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25
-    return pts, r.rand(300, 8) - 0.5, r.rand(400, 8) - 0.5, r.rand(150, 8) - 0.5
-
-
-def _tree(root, n=24):
-    """n clips over 4 actions: cameras 2 / 3 (cross-view train) and 1 (test), listed under the training and extraction folders."""
-    from facl_amd.dataset import clip_paths
-    for i in range(n):
-        nm = "S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4)
-        for p, a in zip(clip_paths(str(root), nm, "0"), _clip(200 + i, 600 + 7 * i)):
-            os.makedirs(os.path.dirname(p), exist_ok=True)
-            np.save(p, a)
-        os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-
-
 VIEW_ARGS = ["--num_crop", "10", "--SAMPLE_NUM", "512", "--INPUT_FEATURE_NUM", "4"]
 
 
@@ -230,7 +205,7 @@ def trained(tmp_path_factory):
     from facl_amd import finetune
     root = tmp_path_factory.mktemp("predict")
     d, ck = str(root / "d"), str(root / "ck")
-    _tree(d)
+    write_tree(d)
     top1 = finetune.main(["--synthetic", "0", "--data_root", d, "--dataset", "ntu120", "--batchSize", "4", "--nepoch", "2",
                           "--save_root_dir", ck, "--eval_every", "1", "--label_fraction", "0.5", "--num_class", "4"] + VIEW_ARGS)
     return d, ck, top1
@@ -242,7 +217,7 @@ def _predict_args(d, ck, *more):
 
 
 def _test_names():
-    return sorted("S%03dC%03dP%03dR001A%03d" % (1 + i % 4, 1, 1 + i, 1 + (i // 3) % 4) for i in range(24) if i % 3 == 2)
+    return sorted(nm for i, nm in enumerate(clip_names(24)) if i % 3 == 2)
 
 
 def test_entry_equals_finetune_top1(trained, tmp_path, capsys):

@@ -1,9 +1,7 @@
 """The prototype contrastive term (csrc/proto.hip, facl_amd/proto.py, --proto_weight of the training entries)
 against an fp64 NumPy restatement of the formula, and its invariants: unknown and out-of-range ids, run-to-run and replayed
 bits, exact row scaling, and the training entry."""
-import contextlib
 import functools
-import io
 import os
 import re
 
@@ -11,15 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from poison import poisoned_scratch  # noqa: F401
+from synth_tree import epoch_loss_text, run_train_entry, train_argv, write_tree
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _dev(a, dtype=None):
@@ -245,47 +239,12 @@ def test_scaling_a_row_by_a_power_of_two():
 
 
 # ---- 6: the training entry --------------------------------------------------------------------------------------------------------
-def _clip(seed, P):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25
-    return pts, r.rand(300, 8) - 0.5, r.rand(400, 8) - 0.5, r.rand(150, 8) - 0.5
-
-
-def _tree(root, n=24):
-    """n clips over 4 actions: cameras 2 / 3 (cross-view train) and 1 (test), listed under the training and extraction folders
-    (the tree of test_gpu_cluster.py)."""
-    from facl_amd.dataset import clip_paths
-    for i in range(n):
-        nm = "S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4)
-        for p, a in zip(clip_paths(str(root), nm, "0"), _clip(200 + i, 600 + 7 * i)):
-            os.makedirs(os.path.dirname(p), exist_ok=True)
-            np.save(p, a)
-        os.makedirs(os.path.join(root, "raw"), exist_ok=True)
-        np.save(os.path.join(root, "raw", nm + ".npy"), np.zeros((1, 8)))
-
-
 CLUSTER = ("--loss_mask", "class", "--class_ids", "cluster", "--clusters", "3", "--cluster_every", "1")
 
 
 def _run_entry(root, folder, *extra):
-    from facl_amd import cn3d_train_motion_GL as train
-    args = ["--synthetic", "0", "--data_root", str(root), "--dataset", "ntu120", "--INPUT_FEATURE_NUM", "4", "--batchSize", "4",
-            "--num_crop", "10", "--SAMPLE_NUM", "512", "--loss_normalize", "1", "--loss_temperature", "0.1", "--neg_queue", "8",
-            "--nepoch", "2", "--save_root_dir", str(folder)]
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        net = train.main(args + [str(a) for a in extra])
-    torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, out.getvalue()
-
-
-def _loss_text(out, epoch):
-    m = re.findall(r"epoch: %d loss mode is : 1 --loss: (\S+)" % epoch, out)
-    assert len(m) == 1, out
-    return m[0]
+    mode = ("--loss_normalize", "1", "--loss_temperature", "0.1", "--neg_queue", "8", "--nepoch", "2")
+    return run_train_entry(train_argv(root, folder, *extra, before_save=mode, features_first=True))
 
 
 def _checkpoints(folder):
@@ -295,7 +254,7 @@ def _checkpoints(folder):
 
 def test_train_entry_with_prototypes(tmp_path):
     root = tmp_path / "d"
-    _tree(str(root))
+    write_tree(str(root))
     sd_p, out_p = _run_entry(root, tmp_path / "p", *CLUSTER, "--proto_weight", "1.0")
     lines = re.findall(r"epoch: (\d+) prototypes: 3 concentration min/mean/max: (\S+)/(\S+)/(\S+)", out_p)
     assert [l[0] for l in lines] == ["0", "1"], out_p
@@ -305,13 +264,13 @@ def test_train_entry_with_prototypes(tmp_path):
     sd_n, out_n = _run_entry(root, tmp_path / "n", *CLUSTER)
     assert "prototypes:" not in out_n
     # epoch 0: every id is unknown, the term is +0.0 and its gradient zero
-    assert _loss_text(out_p, 0) == _loss_text(out_n, 0)
+    assert epoch_loss_text(out_p, 0) == epoch_loss_text(out_n, 0)
     # epoch 1 trains against the prototypes of the first clustering
     assert sd_p.keys() == sd_n.keys()
     assert any(not torch.equal(sd_p[k], sd_n[k]) for k in sd_p)
     # two identical runs give bit-identical weights and checkpoint files
     sd_q, out_q = _run_entry(root, tmp_path / "q", *CLUSTER, "--proto_weight", "1.0")
-    assert [_loss_text(out_q, e) for e in (0, 1)] == [_loss_text(out_p, e) for e in (0, 1)]
+    assert [epoch_loss_text(out_q, e) for e in (0, 1)] == [epoch_loss_text(out_p, e) for e in (0, 1)]
     assert re.findall(r"prototypes: .*", out_q) == re.findall(r"prototypes: .*", out_p)
     for k in sd_p:
         assert torch.equal(sd_p[k], sd_q[k]), k
@@ -322,13 +281,13 @@ def test_train_entry_with_prototypes(tmp_path):
     # weight 0 is the run without the flag: every printed loss, every weight
     sd_0, out_0 = _run_entry(root, tmp_path / "z", *CLUSTER, "--proto_weight", "0")
     assert "prototypes:" not in out_0
-    assert [_loss_text(out_0, e) for e in (0, 1)] == [_loss_text(out_n, e) for e in (0, 1)]
+    assert [epoch_loss_text(out_0, e) for e in (0, 1)] == [epoch_loss_text(out_n, e) for e in (0, 1)]
     for k in sd_n:
         assert torch.equal(sd_n[k], sd_0[k]), k
     # the term is part of the captured step: the graphed run replays it against the static prototypes and walks the eager trajectory
     sd_g, out_g = _run_entry(root, tmp_path / "g", *CLUSTER, "--proto_weight", "1.0", "--graph", "1")
     assert "graph capture failed" not in out_g
-    assert [_loss_text(out_g, e) for e in (0, 1)] == [_loss_text(out_p, e) for e in (0, 1)]
+    assert [epoch_loss_text(out_g, e) for e in (0, 1)] == [epoch_loss_text(out_p, e) for e in (0, 1)]
     assert re.findall(r"prototypes: .*", out_g) == re.findall(r"prototypes: .*", out_p)
     for k in sd_p:
         assert torch.equal(sd_p[k], sd_g[k]), k

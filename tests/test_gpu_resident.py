@@ -1,49 +1,27 @@
 """The training split resident in device memory (facl_amd/resident.py, csrc/views_resident.hip): its views are the disk
 path's philox views bit for bit, selection is by index, the refusals do not fault the device, the ingest holds no second
 copy of the data and does not depend on its chunking, and the training entry reaches the same weights with --resident 1."""
+import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from ranks import rank_env, run_ranks
+from synth_tree import train_argv, tree_clip, write_clip, write_tree
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 2000
 
 
-def _write_clip(root, name, clip, branch="0"):
-    from facl_amd.dataset import clip_paths
-    for p, a in zip(clip_paths(str(root), name, branch), clip):
-        os.makedirs(os.path.dirname(p), exist_ok=True)
-        np.save(p, a)
-
-
 def _clip(seed, P=900, Kp=300, R1=500, R2=200, dt=np.float64):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25                          # at least one non-zero row in each temporal channel
-    return tuple(a.astype(dt) for a in (pts, r.rand(Kp, 8) - 0.5, r.rand(R1, 8) - 0.5, r.rand(R2, 8) - 0.5))
+    return tree_clip(seed, P, Kp, R1, R2, dt)                # this module's default sizes
 
 
-def _names(n):
-    return ["S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4) for i in range(n)]
-
-
-def _tree(root, n=24, dt=np.float64, scale=1, clips=None):
-    """n clips: cameras 2 / 3 (cross-view train) and 1 (test); every clip has its own row count in all four clouds.
-    `clips`: {i: clip} replaces clip i."""
-    names = _names(n)
-    for i, nm in enumerate(names):
-        c = (clips or {}).get(i) or _clip(200 + i, scale * (600 + 7 * i), scale * (300 + 3 * i), scale * (400 + 5 * i),
-                                          scale * (150 + i), dt=dt)
-        _write_clip(root, nm, c)
-        os.makedirs(os.path.join(root, "reslution", "Resolution10", "raw"), exist_ok=True)
-    return names
+# every clip has its own row count in all four clouds; `clips`: {i: clip} replaces clip i
+_tree = functools.partial(write_tree, scale=1, listed=("res10",))
 
 
 def _index(root):
@@ -148,7 +126,7 @@ def test_resident_refusals_do_not_fault_the_device(tmp_path):
             ResidentClips(index, str(tmp_path / "a"), "0", split, DEV, host_check=host_check)
     bad[0][:, 7] = 0.5
     bad[0][:, 4] = 0
-    _write_clip(tmp_path / "a", names[3], tuple(bad))
+    write_clip(tmp_path / "a", names[3], tuple(bad))
     with pytest.raises(ValueError, match=names[3] + ".*channel 4"):
         ResidentClips(index, str(tmp_path / "a"), "0", split, DEV, host_check=False, chunk_clips=1)
     # a selection outside the table: the error word, zero views for that clip, its neighbours untouched
@@ -170,12 +148,12 @@ def test_resident_refusals_do_not_fault_the_device(tmp_path):
         assert (idx[[0, 2, 3]] >= 0).all()
     res.err.zero_()
     # mixed dtypes: refused in the header pass; a bound below the need: refused before anything is allocated
-    _write_clip(tmp_path / "b", index.v_name(split[2]), _clip(9, dt=np.float32))
+    write_clip(tmp_path / "b", index.v_name(split[2]), _clip(9, dt=np.float32))
     before = torch.cuda.memory_allocated()
     with pytest.raises(ValueError, match="mixes float32 and float64"):
         ResidentClips(index, str(tmp_path / "b"), "0", split, DEV)
     assert torch.cuda.memory_allocated() == before
-    _write_clip(tmp_path / "b", index.v_name(split[2]), _clip(9))
+    write_clip(tmp_path / "b", index.v_name(split[2]), _clip(9))
     del res
     need = None
     from facl_amd.resident import header_pass, pool_bytes
@@ -227,8 +205,7 @@ def test_resident_chunking_is_invisible(tmp_path):
 
 
 def _train_args(root, ck, *extra):
-    return ["--synthetic", "0", "--data_root", str(root), "--dataset", "ntu120", "--batchSize", "4", "--nepoch", "2",
-            "--num_crop", "10", "--SAMPLE_NUM", "512", "--INPUT_FEATURE_NUM", "4", "--save_root_dir", str(ck)] + list(extra)
+    return train_argv(root, ck, *extra, after_batch=("--nepoch", "2"))
 
 
 @pytest.mark.parametrize("gflag", ["1", "0"])
@@ -264,10 +241,8 @@ def test_resident_entry_refuses_numpy_draws_and_synthetic_input(tmp_path):
                                "--resident_max_gb", "0.0001"))
 
 
-def _ddp_worker(rank, world, port, root, ck, q):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      FACL_DIST_BACKEND="gloo", LOCAL_RANK="0")
+def _ddp_worker(rank, world, port, q, root, ck):
+    rank_env(rank, world, port, FACL_DIST_BACKEND="gloo", LOCAL_RANK="0")
     import torch.distributed as dist
     from facl_amd import cn3d_train_motion_GL as train
     net = train.main(_train_args(root, ck + str(rank), "--nepoch", "1", "--graph", "0", "--view_rng", "philox",
@@ -278,15 +253,7 @@ def _ddp_worker(rank, world, port, root, ck, q):
 
 
 def test_resident_training_two_ranks_run_equal_step_counts(tmp_path):
-    import torch.multiprocessing as mp
     _tree(tmp_path / "d", n=27)                               # 18 train clips: 2 steps of 4 per rank, 2 clips left over
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 31700 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=_ddp_worker, args=(r, 2, port, str(tmp_path / "d"), str(tmp_path / "ck"), q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted([q.get(timeout=600) for _ in procs])
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_ddp_worker, 2, port, args=(str(tmp_path / "d"), str(tmp_path / "ck")), timeout=600)
     assert res == [(0, 2), (1, 2)]

@@ -11,11 +11,13 @@ import io
 import os
 import re
 import shutil
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
+
+from step_factory import step_opt
+from synth_tree import assert_same_state, run_train_entry, write_tree
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,33 +29,12 @@ BASE = ["--synthetic", "1", "--batchSize", "4", "--num_crop", "4", "--SAMPLE_NUM
 
 def _run(folder, *extra, base=BASE):
     """One run of the motion entry into `folder`: (the returned model's state_dict on the CPU, what it printed)."""
-    from facl_amd import cn3d_train_motion_GL as train
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        net = train.main(list(base) + ["--save_root_dir", str(folder)] + [str(a) for a in extra])
-    torch.cuda.synchronize()
-    return {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, out.getvalue()
+    return run_train_entry(list(base) + ["--save_root_dir", str(folder)] + [str(a) for a in extra])
 
 
 def _losses(printed):
     """{epoch: the mean loss as printed}"""
     return {int(e): v for e, v in re.findall(r"epoch: (\d+) loss mode is : 1 --loss: (\S+)", printed)}
-
-
-def _same(a, b, where):
-    assert type(a) is type(b), where
-    if torch.is_tensor(a):
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), where
-    elif isinstance(a, dict):
-        assert list(a) == list(b), where
-        for k in a:
-            _same(a[k], b[k], "%s.%s" % (where, k))
-    elif isinstance(a, list):
-        assert len(a) == len(b), where
-        for i, (x, y) in enumerate(zip(a, b)):
-            _same(x, y, "%s[%d]" % (where, i))
-    else:
-        assert a == b, (where, a, b)
 
 
 def _state(folder, epoch):
@@ -63,8 +44,8 @@ def _state(folder, epoch):
 
 def _assert_run_equals(got, want, got_dir, want_dir, epochs=(2, 3), last=3):
     (sd_g, out_g), (sd_w, out_w) = got, want
-    _same(sd_g, sd_w, "model")
-    _same(_state(got_dir, last), _state(want_dir, last), "state_%d" % last)
+    assert_same_state(sd_g, sd_w, "model")
+    assert_same_state(_state(got_dir, last), _state(want_dir, last), "state_%d" % last)
     lg, lw = _losses(out_g), _losses(out_w)
     assert all(np.isfinite(float(lw[e])) for e in epochs)
     assert {e: lg[e] for e in epochs} == {e: lw[e] for e in epochs}, (lg, lw)
@@ -108,7 +89,7 @@ def test_control_two_plain_runs_are_bit_identical(run_a, tmp_path):
     got = _run(tmp_path, "--nepoch", 4, "--graph", 1)
     _assert_run_equals(got, run_a[0], tmp_path, run_a[1], epochs=(0, 1, 2, 3))
     for e in range(3):
-        _same(_state(tmp_path, e), _state(run_a[1], e), "state_%d" % e)
+        assert_same_state(_state(tmp_path, e), _state(run_a[1], e), "state_%d" % e)
 
 
 @pytest.mark.parametrize("graph_b,graph_c", [(1, 1), (0, 0), (1, 0), (0, 1)])
@@ -121,7 +102,7 @@ def test_resumed_equals_uninterrupted(run_a, runs_b, tmp_path, graph_b, graph_c)
     assert sorted(_losses(got[1])) == [2, 3]                                   # epochs 0 and 1 are not run again
     assert sorted(n for n in os.listdir(str(tmp_path)) if n.startswith("state_")) == ["state_2.pth", "state_3.pth"]
     _assert_run_equals(got, run_a[0], tmp_path, run_a[1])
-    _same(_state(tmp_path, 2), _state(run_a[1], 2), "state_2")
+    assert_same_state(_state(tmp_path, 2), _state(run_a[1], 2), "state_2")
 
 
 def test_resume_auto(run_a, runs_b, tmp_path):
@@ -155,9 +136,7 @@ def test_swav_state_round_trips_through_the_step():
     from facl_amd.train_common import ContrastiveStep
     from oracle.weights import formula_state_dict
     D, B, G, N = 4, 4, 4, 512
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B, pooling="concatenation",
-                          SAMPLE_NUM=N)
+    opt = step_opt(D, B, N)
     gen = torch.Generator(device=DEV)
     gen.manual_seed(3)
     points = [torch.rand((B, G, N, D), device=DEV, generator=gen) - 0.5 for _ in range(4)]
@@ -199,46 +178,14 @@ def test_swav_state_round_trips_through_the_step():
         for a, b in zip(g, w):
             assert torch.isfinite(a).all() and torch.equal(a, b), (k, float(a), float(b))
     assert torch.equal(step_c.swav_state.queue, step_a.swav_state.queue) and step_c.swav_state.filled == step_a.swav_state.filled
-    _same(train_state.to_cpu(dict(net_c.state_dict())), train_state.to_cpu(dict(net_a.state_dict())), "model")
+    assert_same_state(train_state.to_cpu(dict(net_c.state_dict())), train_state.to_cpu(dict(net_a.state_dict())), "model")
 
 
-# ---- clips on disk (the tree of tests/test_gpu_resident.py) --------------------------------------------------------------
-def _write_clip(root, name, clip, branch="0"):
-    from facl_amd.dataset import clip_paths
-    for p, a in zip(clip_paths(str(root), name, branch), clip):
-        os.makedirs(os.path.dirname(p), exist_ok=True)
-        np.save(p, a)
-
-
-def _clip(seed, P=900, Kp=300, R1=500, R2=200, dt=np.float64):
-    r = np.random.RandomState(seed)
-    pts = r.rand(P, 8) - 0.5
-    pts[r.rand(P) < 0.3, 4] = 0
-    pts[r.rand(P) < 0.5, 7] = 0
-    pts[0, 4] = pts[0, 7] = 0.25                          # at least one non-zero row in each temporal channel
-    return tuple(a.astype(dt) for a in (pts, r.rand(Kp, 8) - 0.5, r.rand(R1, 8) - 0.5, r.rand(R2, 8) - 0.5))
-
-
-def _names(n):
-    return ["S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4) for i in range(n)]
-
-
-def _tree(root, n=24, dt=np.float64, scale=1, clips=None):
-    """n clips: cameras 2 / 3 (cross-view train) and 1 (test); every clip has its own row count in all four clouds.
-    `clips`: {i: clip} replaces clip i."""
-    names = _names(n)
-    for i, nm in enumerate(names):
-        c = (clips or {}).get(i) or _clip(200 + i, scale * (600 + 7 * i), scale * (300 + 3 * i), scale * (400 + 5 * i),
-                                          scale * (150 + i), dt=dt)
-        _write_clip(root, nm, c)
-        os.makedirs(os.path.join(root, "reslution", "Resolution10", "raw"), exist_ok=True)
-    return names
-
-
+# ---- clips on disk (the tree of tests/test_gpu_resident.py: every clip has its own row count in all four clouds) ----------
 @pytest.fixture(scope="module")
 def disk_tree(tmp_path_factory):
     root = tmp_path_factory.mktemp("tree")
-    _tree(str(root))
+    write_tree(str(root), scale=1, listed=("res10",))
     return root
 
 

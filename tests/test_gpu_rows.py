@@ -5,20 +5,12 @@ import pytest
 import torch
 
 from helpers import bn_consts, clear_of_the_relu_edge
+from poison import poisoned_scratch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 E_ALIGN = -3
 U32, U64 = 2.0 ** -24, 2.0 ** -52
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """NaN-poisoned scratch (facl_amd._lib.poisoned), as in test_gpu_tail.py: an output element or partial-sum row left
-    unwritten at a ragged shape fails the comparison."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 def _env():

@@ -4,43 +4,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import load_golden, max_rel_rows, rel_err, routing_taps
+from helpers import load_golden, max_rel_rows, oracle_pooled, rel_err, routing_taps, sa_params
+from poison import poisoned_scratch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned): the partial-sum workspace and
-    every output / scratch tensor the host layer allocates are filled with NaN bytes before the launches, so a partial
-    row or output element left unwritten at a ragged shape fails the comparison instead of reading recycled memory."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
-
-
-def _params(sd, dev, dtype=torch.float32):
-    m = {"W1": "net3DV_1.0.weight", "b1": "net3DV_1.0.bias", "g1": "net3DV_1.1.weight", "be1": "net3DV_1.1.bias",
-         "rm1": "net3DV_1.1.running_mean", "rv1": "net3DV_1.1.running_var",
-         "W2": "net3DV_1.3.weight", "b2": "net3DV_1.3.bias", "g2": "net3DV_1.4.weight", "be2": "net3DV_1.4.bias",
-         "rm2": "net3DV_1.4.running_mean", "rv2": "net3DV_1.4.running_var",
-         "W3": "net3DV_1.6.weight", "b3": "net3DV_1.6.bias", "g3": "net3DV_1.7.weight", "be3": "net3DV_1.7.bias",
-         "rm3": "net3DV_1.7.running_mean", "rv3": "net3DV_1.7.running_var"}
-    return {k: torch.as_tensor(sd[v]).to(dev).to(dtype).contiguous() for k, v in m.items()}
-
-
-def _oracle_pooled(sd, xt_MDSK, training, dtype):
-    """net3DV_1 of the oracle (oracle/encoder.py), in `dtype`, on CPU."""
-    from oracle import encoder as E
-    sd = {k: (torch.as_tensor(v).to(dtype) if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v).clone())
-          for k, v in sd.items()}
-    h = xt_MDSK.to(dtype)
-    with torch.no_grad():
-        for li in (0, 3, 6):
-            h = E._conv_bn_relu(sd, "net3DV_1", li, h, training)
-        pooled = F.max_pool2d(h, (1, h.shape[-1]), stride=1)
-    return pooled.squeeze(-1).permute(0, 2, 1).reshape(-1, 256), sd
 
 
 @pytest.mark.parametrize("D,neg,training", [(4, False, True), (3, False, True), (4, True, True), (4, False, False),
@@ -53,12 +21,12 @@ def test_sa_forward_vs_oracle(D, neg, training):
     pts = (torch.rand(M, N, D) - 0.5)
     xt, yt = utils_my.knn_radius_group(pts.to(DEV), S, K, 0.06)
     sd = formula_state_dict(D, neg_gamma=neg)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     x_rows = xt.permute(0, 2, 3, 1).reshape(-1, D)
     assert x_rows.is_contiguous()
     pooled, ctx = sa_mlp.sa_mlp_forward(x_rows, p, training)
-    ref64, sd64 = _oracle_pooled(sd, xt.cpu(), training, torch.float64)
-    ref32, sd32 = _oracle_pooled(sd, xt.cpu(), training, torch.float32)
+    ref64, sd64 = oracle_pooled(sd, xt.cpu(), training, torch.float64)
+    ref32, sd32 = oracle_pooled(sd, xt.cpu(), training, torch.float32)
     e_mine = max_rel_rows(pooled.cpu().numpy(), ref64.numpy())
     e_t32 = max_rel_rows(ref32.numpy(), ref64.numpy())
     print(f"pooled: mine-vs-fp64 {e_mine:.2e}   torch-fp32-vs-fp64 {e_t32:.2e}")
@@ -84,7 +52,7 @@ def test_sa_eval_one_kernel_vs_training_kernels_and_fp64(D, neg, K):
     pts = (torch.rand(M, N, D) - 0.5)
     xt, yt = utils_my.knn_radius_group(pts.to(DEV), S, K, 0.1)
     sd = formula_state_dict(D, neg_gamma=neg)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     x_rows = xt.permute(0, 2, 3, 1).reshape(-1, D).contiguous()
     assert sa_mlp._EVAL_FUSED
     fused, _ = sa_mlp.sa_mlp_forward(x_rows, p, False, K=K)
@@ -93,7 +61,7 @@ def test_sa_eval_one_kernel_vs_training_kernels_and_fp64(D, neg, K):
         unfused, _ = sa_mlp.sa_mlp_forward(x_rows, p, False, K=K)
     finally:
         sa_mlp._EVAL_FUSED = True
-    ref64, _ = _oracle_pooled(sd, xt.cpu(), False, torch.float64)
+    ref64, _ = oracle_pooled(sd, xt.cpu(), False, torch.float64)
     e_f, e_u = max_rel_rows(fused.cpu().numpy(), ref64.numpy()), max_rel_rows(unfused.cpu().numpy(), ref64.numpy())
     print(f"one kernel vs fp64 {e_f:.2e}   training passes with folded constants vs fp64 {e_u:.2e}")
     assert fused.shape == unfused.shape == (M * S, 256)
@@ -123,7 +91,7 @@ def test_fp16x3_activation_bounds_are_rigorous_and_scale_free(scale_x, gscale):
     for li in (1, 4, 7):                                               # BatchNorm weights / biases of the three layers
         sd[f"net3DV_1.{li}.weight"] = np.asarray(sd[f"net3DV_1.{li}.weight"]) * np.float32(gscale)
         sd[f"net3DV_1.{li}.bias"] = np.asarray(sd[f"net3DV_1.{li}.bias"]) * np.float32(gscale)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     x_rows = xt.permute(0, 2, 3, 1).reshape(-1, D).contiguous()
     pooled, ctx = sa_mlp.sa_mlp_forward(x_rows, p, True, update_running=False)
     am = ctx["amax"].view(torch.float32)[:, ::32]                     # the 64 slots of each buffer (the words between them are unused)
@@ -153,7 +121,7 @@ def test_sa_forward_c1_golden():
     g = load_golden("c1_d4.npz")
     pts = torch.from_numpy(g["points"]).to(DEV)
     xt, yt = utils_my.knn_radius_group(pts, 64, 64, 0.06)
-    p = _params(formula_state_dict(4), DEV)
+    p = sa_params(formula_state_dict(4), DEV)
     pooled, _ = sa_mlp.sa_mlp_forward(xt.permute(0, 2, 3, 1).reshape(-1, 4), p, True)
     mine = pooled.view(32, 64, 256).cpu().numpy()[::4]
     assert max_rel_rows(mine, g["train_pooled"]) < 1e-4
@@ -170,7 +138,7 @@ def test_sa_backward_vs_oracle_fp64(D, neg):
     pts = (torch.rand(M, N, D) - 0.5)
     xt, yt = utils_my.knn_radius_group(pts.to(DEV), S, K, 0.06)
     sd = formula_state_dict(D, neg_gamma=neg)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     x_rows = xt.permute(0, 2, 3, 1).reshape(-1, D)
     names = sa_mlp._PARAM_ORDER
     params = [p[k].clone().requires_grad_(True) for k in names]
@@ -240,7 +208,7 @@ def test_sa_other_K_kernel_level(S, K):
     pts = (torch.rand(M, N, D) - 0.5)
     xt, yt = utils_my.knn_radius_group(pts.to(DEV), S, K, 0.1)
     sd = formula_state_dict(D)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     x_rows = xt.permute(0, 2, 3, 1).reshape(-1, D)
     names = sa_mlp._PARAM_ORDER
     params = [p[k].clone().requires_grad_(True) for k in names]
@@ -285,7 +253,7 @@ def test_sa_headline_size_forward_backward_vs_torch_fp64():
     xt, _ = utils_my.knn_radius_group(pts, S, K, 0.16)
     del pts
     sd = formula_state_dict(D)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     x_rows = xt.permute(0, 2, 3, 1).reshape(-1, D).contiguous()                   # (P, D), P = M*S*K
     del xt
     params = [p[k].clone().requires_grad_(True) for k in sa_mlp._PARAM_ORDER]
@@ -385,7 +353,7 @@ def test_sa_ragged_unit_counts(nunits):
     torch.manual_seed(nunits)
     x_rows = ((torch.rand(nunits * K, D, device=DEV) - 0.5) * 0.8).contiguous()
     sd = formula_state_dict(D)
-    p = _params(sd, DEV)
+    p = sa_params(sd, DEV)
     params = [p[k].clone().requires_grad_(True) for k in sa_mlp._PARAM_ORDER]
     state = {"buffers": {k: p[k] for k in ("rm1", "rv1", "rm2", "rv2", "rm3", "rv3")}, "training": True}
     pooled = sa_mlp.SAMLPFunction.apply(x_rows, state, *params)

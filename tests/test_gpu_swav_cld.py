@@ -1,11 +1,10 @@
 """the optional SwAV (sinkhorn) and CLD (k-means) loss terms vs oracle/swav_cld.py and the reference fixture."""
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 import torch
 
 from helpers import load_golden
+from step_factory import step_opt
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -111,9 +110,7 @@ def test_training_step_with_both_terms_runs_and_changes_the_loss():
     from facl_amd.train_common import ContrastiveStep
     from oracle.weights import formula_state_dict
     D, B, G, N = 4, 4, 6, 512
-    opt = SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=64,
-                          sample_num_level2=64, INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B, pooling="concatenation",
-                          SAMPLE_NUM=N)
+    opt = step_opt(D, B, N)
     torch.manual_seed(1)
     clip = (torch.rand(B, G, N, D) - 0.5).to(DEV)
     losses = []

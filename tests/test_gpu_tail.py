@@ -4,19 +4,10 @@ import pytest
 import torch
 
 from helpers import FUSED_ADAM_BETAS, load_golden
+from poison import poisoned_scratch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned): the partial-sum workspace and
-    every output / scratch tensor the host layer allocates are filled with NaN bytes before the launches, so a partial
-    row or output element left unwritten at a ragged shape fails the comparison instead of reading recycled memory."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
 
 
 @pytest.mark.parametrize("G,B,C", [(10, 4, 1024), (24, 32, 1024), (3, 5, 8), (1, 7, 16)])

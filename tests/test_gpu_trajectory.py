@@ -6,13 +6,14 @@ host-side num_batches_tracked, and whatever a graph replay reuses.  The four ste
 left over from the previous step is wrong for the next one: the input scale drops 4x, then rises 16x, the learning rate
 changes twice and the circle-loss order changes.  The whole module runs on NaN-poisoned scratch."""
 import io
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
 from helpers import FUSED_ADAM_BETAS, PRE_BN_BIAS, SA_T_BN, adam64, forward64, max_rel_rows, reference_step64, rel_err, routing_taps, snapshot
+from poison import poisoned_scratch  # noqa: F401
+from step_factory import grouped, make_contrastive_step, points
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -38,41 +39,9 @@ CONFIGS = {
 SCHEDULE = [(1.0, 3e-4, 0), (2.0 ** -2, 3e-4, 1), (2.0 ** 2, 1e-3, 2), (1.0, 3e-5, 0)]
 
 
-@pytest.fixture(autouse=True)
-def _poisoned_scratch():
-    """Every test of this module runs with NaN-poisoned scratch (facl_amd._lib.poisoned); a captured graph captures the
-    poison fills too, so every replay starts from NaN scratch."""
-    from facl_amd import _lib
-    with _lib.poisoned():
-        yield
-
-
-def _opt(c):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius=0.16, ball_radius2=0.25, sample_num_level1=S,
-                           sample_num_level2=S, INPUT_FEATURE_NUM=c["D"], Num_Class=512, batchSize=c["B"],
-                           pooling="concatenation", SAMPLE_NUM=c["N"])
-
-
 def _make(c):
     """Model with the formula weights + FusedAdam (the optimizer of the training entries) + ContrastiveStep."""
-    from facl_amd.cn3d_model_conbag import PointNet_Plus
-    from facl_amd.optim import FusedAdam
-    from facl_amd.train_common import ContrastiveStep
-    from oracle.weights import formula_state_dict
-    opt = _opt(c)
-    net = PointNet_Plus(opt, gost=c["G"])
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in formula_state_dict(c["D"]).items()})
-    net = net.to(DEV).train()
-    optim = FusedAdam(net.parameters(), lr=SCHEDULE[0][1], betas=(0.5, 0.999), eps=1e-6)
-    return net, optim, ContrastiveStep(net, optim, opt, c["G"])
-
-
-def _points(c, seed, scale=1.0):
-    B, G, N, D = c["B"], c["G"], c["N"], c["D"]
-    gen = torch.Generator(device=DEV)
-    gen.manual_seed(seed)
-    shape = (G * B, N, D) if c["view_major"] else (B, G, N, D)
-    return (torch.rand(shape, device=DEV, generator=gen) - 0.5) * scale
+    return make_contrastive_step(c, lr=SCHEDULE[0][1])
 
 
 def _schedule(c):
@@ -80,20 +49,7 @@ def _schedule(c):
     r = np.random.RandomState(7)
     perms = [r.permutation(c["G"]) for _ in range(3)]
     assert len({tuple(p) for p in perms}) == 3
-    return [(_points(c, 100 + k, sc), lr, perms[o]) for k, (sc, lr, o) in enumerate(SCHEDULE)]
-
-
-def _grouped(c, points):
-    """Grouped rows (P,D) and centres (M*S,3) of `points` through the grouping the step itself uses (bit-exact to the
-    reference: test_gpu_grouping.py), from the view-major rows."""
-    from facl_amd.utils_my import group_points_3DV, knn_radius_group
-    N, D = c["N"], c["D"]
-    vm = points if c["view_major"] else points.permute(1, 0, 2, 3).reshape(-1, N, D)
-    if N == 512:
-        xt, yt = group_points_3DV(vm.contiguous(), _opt(c))
-    else:
-        xt, yt = knn_radius_group(vm.contiguous(), S, K, 0.16)
-    return xt.permute(0, 2, 3, 1).reshape(-1, D), yt.permute(0, 2, 1, 3).reshape(-1, 3)
+    return [(points(c, 100 + k, sc), lr, perms[o]) for k, (sc, lr, o) in enumerate(SCHEDULE)]
 
 
 def _state(net, optim, out):
@@ -160,7 +116,7 @@ def _step_vs_fp64(c, tag, before, after, pts, order, routing, x, xg, losses, gra
     B, G = c["B"], c["G"]
     k = tag[-1]
     b1, b2 = FUSED_ADAM_BETAS
-    x_rows, centers = _grouped(c, pts)
+    x_rows, centers = grouped(c, pts)
     ref = reference_step64(before, x_rows, centers, G, B, S, K, order, routing, betas=FUSED_ADAM_BETAS)
     loss, loss_c, loss_circle = (float(v.detach()) for v in losses)
     rl = lambda a, b: abs(a - b) / abs(b)
@@ -262,7 +218,7 @@ def _graph_vs_eager_twin(c, tag, check=None):
     from facl_amd.train_common import GraphedStep
     net_g, opt_g, step_g = _make(c)
     snap0 = snapshot(net_g, opt_g)
-    g = GraphedStep(step_g, _points(c, 99), c["G"], restore=True)
+    g = GraphedStep(step_g, points(c, 99), c["G"], restore=True)
     torch.cuda.synchronize()
     _assert_same_state(snapshot(net_g, opt_g), snap0, (tag, "restore=True"))      # the three warm-up steps undone
     net_t, opt_t, step_t = _make(c)
@@ -320,7 +276,7 @@ def test_graph_replay_at_headline_size():
 
     def check(k, before, after, rg, pts, order, net_g, routing):
         stacked = net_g._stacked.detach()                  # the replay's (M + B, 512) embeddings (graph pool)
-        x_rows, centers = _grouped(c, pts)
+        x_rows, centers = grouped(c, pts)
         ref = reference_step64(before, x_rows, centers, G, B, S, K, order, None, backward=False)
         e_x = max_rel_rows(stacked[:M].cpu().numpy(), ref["x"].cpu().numpy())
         e_xg = max_rel_rows(stacked[M:].cpu().numpy(), ref["xg"].cpu().numpy())
@@ -349,7 +305,7 @@ def test_resume_from_state_dicts_continues_the_trajectory():
     from facl_amd.train_common import GraphedStep
     c = CONFIGS["ref_default"]
     net_g, opt_g, step_g = _make(c)
-    g = GraphedStep(step_g, _points(c, 99), c["G"], restore=True)
+    g = GraphedStep(step_g, points(c, 99), c["G"], restore=True)
     sched = _schedule(c)
     for pts, lr, order in sched[:2]:
         opt_g.param_groups[0]["lr"] = lr

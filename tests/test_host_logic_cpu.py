@@ -1,22 +1,15 @@
 """CPU tests of the host-side mirror: model container (state_dict contract, initialisation), the loss
 functions (pure tensor algebra, device-agnostic), LR schedule, and the world_size-2 gloo path."""
 import os
-import sys
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 from helpers import load_golden
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _opt(D=4, B=4):
-    return SimpleNamespace(temperal_num=3, knn_K=64, ball_radius2=0.25, sample_num_level1=64, sample_num_level2=64,
-                           INPUT_FEATURE_NUM=D, Num_Class=512, batchSize=B, pooling="concatenation", SAMPLE_NUM=512)
+from ranks import rank_env, run_ranks
+from step_factory import step_opt
 
 
 @pytest.mark.parametrize("D", [3, 4])
@@ -26,7 +19,7 @@ def test_state_dict_contract_and_seeded_init(D):
     from oracle.weights import state_dict_shapes
     g = load_golden("init.npz")
     torch.manual_seed(1)
-    net = PointNet_Plus(_opt(D))
+    net = PointNet_Plus(step_opt(D, 4))
     sd = net.state_dict()
     want = state_dict_shapes(D)
     assert list(sd.keys()) == [k for k, _ in want]
@@ -45,14 +38,14 @@ def test_state_dict_contract_and_seeded_init(D):
 
 def test_fine_variant_and_ctor_errors():
     from facl_amd.cn3d_model_conbag import PointNet_Plus, PointNet_Plus_fine
-    net = PointNet_Plus_fine(_opt(), gost=8, sample_num_level1=64, knn_K=64)
-    assert set(net.state_dict().keys()) == set(PointNet_Plus(_opt()).state_dict().keys())
-    bad = _opt()
+    net = PointNet_Plus_fine(step_opt(4, 4), gost=8, sample_num_level1=64, knn_K=64)
+    assert set(net.state_dict().keys()) == set(PointNet_Plus(step_opt(4, 4)).state_dict().keys())
+    bad = step_opt(4, 4)
     bad.pooling = "vlad"
     with pytest.raises(AttributeError):          # reference: dim_out only exists for 'concatenation' (:40-41)
         PointNet_Plus(bad)
     with pytest.raises(RuntimeError):            # no CPU path
-        PointNet_Plus(_opt())(torch.zeros(10, 4, 64, 64), torch.zeros(10, 3, 64, 1))
+        PointNet_Plus(step_opt(4, 4))(torch.zeros(10, 4, 64, 64), torch.zeros(10, 3, 64, 1))
 
 
 @pytest.mark.parametrize("tag", ["d4", "d3", "d4_neg"])
@@ -103,8 +96,7 @@ def test_train_entry_flags_match_reference_defaults():
 
 # ---- world_size = 2 over gloo: sharded losses + all-gather == single process at the global batch ----
 def _worker(rank, world, port, q):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    rank_env(rank, world, port)
     import torch.distributed as dist
     from facl_amd import dist as fdist
     from facl_amd.utils_my import circle_contrast, global_contrast
@@ -149,23 +141,14 @@ def _worker(rank, world, port, q):
 
 
 def test_world_size_2_gloo_sharded_loss_equals_global():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 29500 + (os.getpid() % 2000)
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=120) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker, 2, port, timeout=120)
     assert sorted(res) == [(0, True), (1, True)]
 
 
 # ---- failure protocol of the segmented graph capture (facl_amd/dist.py: GraphSegments votes), 2 gloo ranks, no GPU ----
 def _worker_capture_protocol(rank, world, port, q, fail_rank, fail_cut, ncoll):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      FACL_DIST_BACKEND="gloo", FACL_DIST_TIMEOUT_S="30")
+    rank_env(rank, world, port, FACL_DIST_BACKEND="gloo", FACL_DIST_TIMEOUT_S="30")
     if fail_rank is not None:
         os.environ["FACL_TEST_CAPTURE_FAIL"] = "%d:%d" % (fail_rank, fail_cut)
     import torch.distributed as dist
@@ -213,15 +196,8 @@ def _worker_capture_protocol(rank, world, port, q, fail_rank, fail_cut, ncoll):
 def test_capture_failure_on_one_rank_is_agreed_on_by_all_ranks(fail_rank, fail_cut, ncoll):
     """a capture that fails on ONE rank after k collectives must take EVERY rank out of the capture at the same
     collective (then all continue eagerly together) -- never one rank eager against others replaying."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
     port = 29400 + (os.getpid() % 2000) + (0 if fail_rank is None else 7 * (fail_rank + 1) + fail_cut)
-    procs = [ctx.Process(target=_worker_capture_protocol, args=(r, 2, port, q, fail_rank, fail_cut, ncoll)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = sorted(q.get(timeout=120) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    res = run_ranks(_worker_capture_protocol, 2, port, args=(fail_rank, fail_cut, ncoll), timeout=120)
     expect = "captured" if fail_rank is None else "failed"
     assert [r[1] for r in res] == [expect, expect], res
     assert res[0][2] == res[1][2] == (ncoll if fail_rank is None else fail_cut), res     # same number of collectives issued

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from synth_tree import clip_names, write_clip
+
 
 def _clip(seed, sizes, dt=np.float64):
     r = np.random.RandomState(seed)
@@ -14,26 +16,15 @@ def _clip(seed, sizes, dt=np.float64):
     return tuple(a.astype(dt) for a in arrs)
 
 
-def _write_clip(root, name, clip, branch="0"):
-    from facl_amd.dataset import clip_paths
-    for p, a in zip(clip_paths(str(root), name, branch), clip):
-        os.makedirs(os.path.dirname(p), exist_ok=True)
-        np.save(p, a)
-
-
-def _names(n):
-    return ["S%03dC%03dP%03dR001A%03d" % (1 + i % 4, (2, 3, 1)[i % 3], 1 + i, 1 + (i // 3) % 4) for i in range(n)]
-
-
 def _sizes(i):
     return (600 + 7 * i, 300 + 3 * i, 400 + 5 * i, 150 + i)
 
 
 def _tree(root, n=9, dt=np.float64):
     from facl_amd.dataset import ClipIndex
-    names = _names(n)
+    names = clip_names(n)
     for i, nm in enumerate(names):
-        _write_clip(root, nm, _clip(i, _sizes(i), dt))
+        write_clip(root, nm, _clip(i, _sizes(i), dt))
     return ClipIndex.from_dir(os.path.join(str(root), "reslution", "Resolution60", "raw"), "ntu120")
 
 
@@ -44,7 +35,7 @@ def test_header_pass_and_table_give_exact_totals_and_offsets(tmp_path):
     assert len(split) == 6
     rows, dt = R.header_pass(index, str(tmp_path), "0", split)
     assert dt == np.float64 and rows.dtype == np.int64
-    want = np.array([_sizes(_names(9).index(index.names[v][:20])) for v in split], dtype=np.int64)
+    want = np.array([_sizes(clip_names(9).index(index.names[v][:20])) for v in split], dtype=np.int64)
     np.testing.assert_array_equal(rows, want)
     table, rows_total, rows0_total = R.build_table(rows, split)
     assert table.dtype == np.int64 and table.shape == (6, R.REC)
@@ -92,17 +83,17 @@ def test_header_pass_refuses_what_load_clip_refuses(tmp_path):
     index = _tree(tmp_path / "a", n=6)
     split = index.select("view")
     nm = index.v_name(split[1])
-    _write_clip(tmp_path / "a", nm, _clip(50, (10, 10, 10, 10), np.float32))
+    write_clip(tmp_path / "a", nm, _clip(50, (10, 10, 10, 10), np.float32))
     with pytest.raises(ValueError, match="mixes float32 and float64.*" + nm):
         R.header_pass(index, str(tmp_path / "a"), "0", split)
     c = list(_clip(51, (10, 10, 10, 10)))
     c[2] = c[2][:, :7]
-    _write_clip(tmp_path / "a", nm, c)
+    write_clip(tmp_path / "a", nm, c)
     with pytest.raises(ValueError, match=nm + ".*rows, >=8"):
         R.header_pass(index, str(tmp_path / "a"), "0", split)
     c = list(_clip(52, (10, 10, 10, 10)))
     c[1] = c[1].astype(np.float32)
-    _write_clip(tmp_path / "a", nm, c)
+    write_clip(tmp_path / "a", nm, c)
     with pytest.raises(ValueError, match="share one dtype"):
         R.header_pass(index, str(tmp_path / "a"), "0", split)
     with pytest.raises(ValueError, match="3-D"):

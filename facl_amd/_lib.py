@@ -151,6 +151,9 @@ SIGNATURES = {
     "facl_grad_sqnorm": [c_i, c_p, c_p, c_p, c_s],
     "facl_adam_prep_ex": [c_p, c_p, c_f, c_f, c_p, c_i, c_d, c_i, c_i, c_i, c_d, c_p, c_s],
     "facl_adamw_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_s],
+    "facl_tensor_sqnorms": [c_i, c_p, c_p, c_p, c_p, c_p, c_s],
+    "facl_sgd_prep": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_i, c_i, c_i, c_d, c_d, c_d, c_p, c_p, c_s],
+    "facl_sgd_apply": [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_s],
     "facl_mailbox_bytes": [c_i, c_i],
     "facl_mailbox_alloc": [c_l, c_p, c_p],
     "facl_mailbox_open": [c_p, c_p],
@@ -266,7 +269,8 @@ VIEW_POS_MAX = 12          # FACL_VIEW_POS_MAX: positions of a round at most
 VIEW_NSTRENGTH = 6         # FACL_VIEW_NSTRENGTH: jitter_sigma, jitter_clip, rot_range, scale_lo, scale_hi, tilt_angle
 VIEW_TABLE_COLS = 8        # FACL_VIEW_TABLE_COLS: int32 words per position of facl_view_recipe_table
 
-# include/facl_hip.h: the chunk table of the optimizer entries (facl_adam_apply, facl_ema_apply, facl_grad_sqnorm, facl_adamw_apply)
+# include/facl_hip.h: the chunk table of the optimizer entries (facl_adam_apply, facl_ema_apply, facl_grad_sqnorm, facl_adamw_apply,
+# facl_tensor_sqnorms, facl_sgd_apply)
 ADAM_MAX_TENSORS = 64      # FACL_ADAM_MAX_TENSORS: tensors per launch at most
 ADAM_CHUNK = 2048          # FACL_ADAM_CHUNK: elements per workgroup; facl_grad_sqnorm writes one partial per chunk
 

@@ -4,7 +4,7 @@
 // modes (facl_amd/optim.py: weight_decay, max_grad_norm, schedule; off by default -- the first three entries are then
 // the whole step).  torch's fused multi-tensor kernel walks 64 K-element chunks: 2.36 M parameters are 36 workgroups (47 us on
 // 256 CUs); here a workgroup takes FACL_ADAM_CHUNK = 2048 elements (~1150 workgroups, HBM-bound: 7 x 9.4 MB per Adam step).
-// What the four chunked kernels share is stated once:
+// What the chunked kernels share is stated once:
 //   ChunkTable<NP>  NP columns of tensor pointers, the element counts and the first chunk of every tensor, BY VALUE in the kernel
 //                   arguments (no device-side table to keep coherent; a HIP graph bakes the pointers at capture time, when the
 //                   gradient buffers of the captured step are fixed); chunk_table() checks the caller's host arrays and fills it
@@ -21,6 +21,12 @@
 //                      lr_t = warm-up x (host lr | cosine) from the step counter; consts = (lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t),
 //                      lr_t, c, norm)
 //   facl_adamw_apply: g' = c g; p *= 1 - lr_t wd on flagged tensors (torch.optim.AdamW's order); then facl_adam_apply's update on g'
+// SGD with momentum and LARS (facl_amd/optim.py: FusedSGD) are a second update rule on the same table, walk, sums
+// and device-side step / rate / clip / schedule:
+//   facl_tensor_sqnorms: facl_grad_sqnorm on two columns in one pass, partial_p[chunk] = sum p^2, partial_g[chunk] = sum g^2  -- LARS
+//   facl_sgd_prep: step += 1; lr_t, c, norm as facl_adam_prep_ex; consts = (lr_t, 0, lr_t, c, norm); under LARS the trust ratio of
+//                  every tensor from the partials of its own chunks: eta |p| / (c |g| + wd |p|) on the flagged tensors, else 1
+//   facl_sgd_apply: d = (c g + wd p on flagged tensors) * trust; buf = mu buf + d; p -= lr_t (buf | d + mu buf under Nesterov)
 #include "common.h"
 #include <math.h>
 #include <stdint.h>
@@ -36,6 +42,17 @@ struct ChunkTable {
 struct AdamWTable {
     ChunkTable<4> t;
     unsigned char decay[FACL_ADAM_MAX_TENSORS];   // 1: the tensor is weight-decayed
+};
+
+struct SgdTable {
+    ChunkTable<3> t;
+    unsigned char mask[FACL_ADAM_MAX_TENSORS];    // 1: the tensor is weight-decayed and, under LARS, adapted
+};
+
+struct SgdPrefix {                                // what facl_sgd_prep needs of the chunk table, BY VALUE like the table itself
+    int chunk0[FACL_ADAM_MAX_TENSORS + 1];
+    unsigned char mask[FACL_ADAM_MAX_TENSORS];
+    int nt;                                       // 0: plain SGD, no trust ratio is formed
 };
 
 namespace {
@@ -217,6 +234,18 @@ __global__ __launch_bounds__(256) void k_grad_sqnorm(ChunkTable<1> tb, double* _
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
+// The learning rate of step tt (1-based) in fp64: the warm-up factor min(1, tt / W) times the host's rate lr0 or the half cosine
+// from lr0 at tt = W down to lr_min at tt = T.  The one evaluation of both preps (facl_amd.optim.lr_at_step is its host form).
+__device__ __forceinline__ double scheduled_lr(double lr0, double tt, int cosine, int W, int T, double lr_min) {
+    const double warm = W > 0 ? fmin(1.0, tt / (double)W) : 1.0;
+    double lr_s = lr0;
+    if (cosine) {
+        const double tp = fmax(tt - (double)W, 0.0), Tp = (double)(T - W);
+        lr_s = lr_min + (lr0 - lr_min) * 0.5 * (1.0 + cos(M_PI * fmin(tp, Tp) / Tp));
+    }
+    return warm * lr_s;
+}
+
 // One workgroup of 256 threads.  consts = (lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t), lr_t, c, norm); np == 0: no clipping, c = 1 exactly.
 // A non-finite norm goes the way it goes in torch.nn.utils.clip_grad_norm_: inf gives c = 0 (and 0 * inf = NaN in the update),
 // NaN gives c = NaN (the comparison of the clamp is false).
@@ -229,14 +258,8 @@ __global__ __launch_bounds__(256) void k_adam_prep_ex(const float* __restrict__ 
     s = wg256_sum_f64(s, red);
     if (threadIdx.x != 0) return;
     double bc1, bc2;
-    const double tt = (double)adam_advance(step, b1, b2, bc1, bc2), lr0 = (double)lr[0];
-    const double warm = W > 0 ? fmin(1.0, tt / (double)W) : 1.0;
-    double lr_s = lr0;
-    if (cosine) {
-        const double tp = fmax(tt - (double)W, 0.0), Tp = (double)(T - W);
-        lr_s = lr_min + (lr0 - lr_min) * 0.5 * (1.0 + cos(M_PI * fmin(tp, Tp) / Tp));
-    }
-    const double lr_t = warm * lr_s;
+    const double tt = (double)adam_advance(step, b1, b2, bc1, bc2);
+    const double lr_t = scheduled_lr((double)lr[0], tt, cosine, W, T, lr_min);
     double norm = 0.0, c = 1.0;
     if (np > 0) {
         norm = sqrt(s);
@@ -248,6 +271,106 @@ __global__ __launch_bounds__(256) void k_adam_prep_ex(const float* __restrict__ 
     consts[2] = (float)lr_t;
     consts[3] = (float)c;
     consts[4] = (float)norm;
+}
+
+// k_grad_sqnorm on two columns in one pass: partial_p[chunk] = sum of p^2, partial_g[chunk] = sum of g^2, each with k_grad_sqnorm's
+// own additions in its own order, so partial_g holds the bits that kernel writes.  The walk issues the two float4 of both
+// columns, four 16-byte loads per thread, before the first square.
+__global__ __launch_bounds__(256) void k_tensor_sqnorms(ChunkTable<2> tb, double* __restrict__ partial_p,
+                                                        double* __restrict__ partial_g) {
+    __shared__ double red[2][4];
+    const Chunk ck = chunk_of(tb);
+    float* const col[2] = {tb.col[0][ck.t], tb.col[1][ck.t]};                     // p, g
+    double sp = 0.0, sg = 0.0;
+    chunk_walk<0>(col, ck, [&](float (&x)[2][4], int E) {
+        double qp = (double)x[0][0] * (double)x[0][0], qg = (double)x[1][0] * (double)x[1][0];
+        for (int e = 1; e < E; ++e) {
+            qp += (double)x[0][e] * (double)x[0][e];
+            qg += (double)x[1][e] * (double)x[1][e];
+        }
+        sp += qp;
+        sg += qg;
+    });
+    sp = wg256_sum_f64(sp, red[0]);
+    sg = wg256_sum_f64(sg, red[1]);
+    if (threadIdx.x == 0) {
+        partial_p[blockIdx.x] = sp;
+        partial_g[blockIdx.x] = sg;
+    }
+}
+
+// One workgroup of 256 threads.  consts = (lr_t, 0, lr_t, c, norm): slots 2..4 as k_adam_prep_ex writes them, by the same
+// operations in the same order (the sum of the partials included).  px.nt > 0 (LARS): wave w takes the tensors w, w + 4, ...;
+// its lanes add the tensor's partials lane-strided, then the butterfly: one fixed order.  The clip coefficient enters |g| as
+// the fp32 value that k_sgd_apply multiplies the gradient by.
+__global__ __launch_bounds__(256) void k_sgd_prep(const float* __restrict__ lr, float* __restrict__ step,
+                                                  const double* __restrict__ partial_g, const double* __restrict__ partial_p,
+                                                  int np, SgdPrefix px, double max_norm, int clip_on, int cosine, int W, int T,
+                                                  double lr_min, double eta, double wd, float* __restrict__ consts,
+                                                  float* __restrict__ trust) {
+    __shared__ double red[4];
+    __shared__ float clip;
+    double s = 0.0;
+    if (clip_on)
+        for (int i = threadIdx.x; i < np; i += 256) s += partial_g[i];
+    s = wg256_sum_f64(s, red);
+    if (threadIdx.x == 0) {
+        const float t = step[0] + 1.f;
+        step[0] = t;
+        const double lr_t = scheduled_lr((double)lr[0], (double)t, cosine, W, T, lr_min);
+        double norm = 0.0, c = 1.0;
+        if (clip_on) {
+            norm = sqrt(s);
+            c = max_norm / (norm + 1e-6);
+            if (c > 1.0) c = 1.0;
+        }
+        consts[0] = (float)lr_t;
+        consts[1] = 0.f;
+        consts[2] = (float)lr_t;
+        consts[3] = (float)c;
+        consts[4] = (float)norm;
+        clip = (float)c;
+    }
+    if (px.nt == 0) return;                                   // uniform: plain SGD
+    __syncthreads();
+    const double c = (double)clip;
+    const int lane = threadIdx.x & 63;
+    for (int i = threadIdx.x >> 6; i < px.nt; i += 4) {
+        double sp = 0.0, sg = 0.0;
+        for (int k = px.chunk0[i] + lane; k < px.chunk0[i + 1]; k += 64) {
+            sp += partial_p[k];
+            sg += partial_g[k];
+        }
+        sp = wave_sum_f64(sp);
+        sg = wave_sum_f64(sg);
+        if (lane == 0) {
+            const double wn = sqrt(sp), gn = c * sqrt(sg);
+            // a NaN norm fails the comparisons: ratio 1, and the NaN reaches the parameters through the gradient itself
+            trust[i] = (px.mask[i] && wn > 0.0 && gn > 0.0) ? (float)(eta * wn / (gn + wd * wn)) : 1.f;
+        }
+    }
+}
+
+// d = c g (+ wd p on the flagged tensors), times the tensor's trust ratio; buf = mu buf + d; p -= lr_t (buf, or d + mu buf under
+// Nesterov): torch.optim.SGD(momentum = mu, dampening = 0) in its operation order, one rounding per operation (the build has
+// -ffp-contract=off).  c == 1.0f and q == 1.0f multiply exactly, so plain SGD pays nothing for the recipe's slots.
+__global__ __launch_bounds__(256) void k_sgd_apply(SgdTable ts, const float* __restrict__ consts, const float* __restrict__ trust,
+                                                   float mu, float wd, int nesterov) {
+    const float lr_t = consts[2], c = consts[3];              // read while the search runs
+    const Chunk ck = chunk_of(ts.t);
+    const float q = trust ? trust[ck.t] : 1.f;
+    const bool decay = ts.mask[ck.t];
+    float* const col[3] = {ts.t.col[1][ck.t], ts.t.col[2][ck.t], ts.t.col[0][ck.t]};          // g, buf, p
+    chunk_walk<0b110>(col, ck, [&](float (&x)[3][4], int E) {
+        for (int e = 0; e < E; ++e) {
+            const float gc = x[0][e] * c, p = x[2][e];
+            float d = decay ? gc + wd * p : gc;
+            d = d * q;
+            const float buf = mu * x[1][e] + d;
+            x[1][e] = buf;
+            x[2][e] = p - lr_t * (nesterov ? d + mu * buf : buf);
+        }
+    });
 }
 
 }  // namespace
@@ -313,5 +436,66 @@ extern "C" int facl_adamw_apply(int nt, float* const* p, const float* const* g, 
     if (chunks < 0) return chunks;
     for (int i = 0; i < nt; ++i) tw.decay[i] = decay[i] ? 1 : 0;
     hipLaunchKernelGGL(k_adamw_apply, dim3(chunks), dim3(256), 0, (hipStream_t)stream, tw, consts, b1, b2, eps, wd);
+    return facl_launch_status();
+}
+
+// p / g: HOST arrays of nt device pointers; n: HOST array of element counts; partial_p / partial_g: DEVICE arrays of one double
+// per chunk, every entry written
+extern "C" int facl_tensor_sqnorms(int nt, const float* const* p, const float* const* g, const int* n, double* partial_p,
+                                   double* partial_g, void* stream) {
+    if (!partial_p || !partial_g) return FACL_E_NULL;
+    ChunkTable<2> tb;
+    const int chunks = chunk_table(tb, nt, {p, g}, n);
+    if (chunks < 0) return chunks;
+    hipLaunchKernelGGL(k_tensor_sqnorms, dim3(chunks), dim3(256), 0, (hipStream_t)stream, tb, partial_p, partial_g);
+    return facl_launch_status();
+}
+
+// partial_p != NULL: LARS; then n (HOST, nt element counts) and mask (HOST, nt flags) describe the tensors whose partials the two
+// arrays hold, npartial is their chunk count, and trust (DEVICE, nt floats) is written.  partial_p == NULL: nt, n, mask, eta, wd
+// and trust are not read.
+extern "C" int facl_sgd_prep(const float* lr, float* step, const double* partial_g, const double* partial_p, int npartial, int nt,
+                             const int* n, const int* mask, double max_norm, int clip_on, int schedule, int warmup_steps,
+                             int decay_steps, double lr_min, double eta, double wd, float* consts, float* trust, void* stream) {
+    if (!lr || !step || !consts) return FACL_E_NULL;
+    if (!partial_g && (clip_on || partial_p)) return FACL_E_NULL;
+    if (partial_p && (!n || !mask || !trust)) return FACL_E_NULL;
+    if (npartial < 0 || (clip_on && !(max_norm > 0.0))) return FACL_E_SHAPE;                   // NaN included
+    if (schedule != FACL_LR_STEP && schedule != FACL_LR_COSINE) return FACL_E_SHAPE;
+    if (warmup_steps < 0 || !(lr_min >= 0.0)) return FACL_E_SHAPE;
+    if (schedule == FACL_LR_COSINE && decay_steps <= warmup_steps) return FACL_E_SHAPE;
+    SgdPrefix px;
+    px.nt = 0;
+    if (partial_p) {
+        if (!(eta >= 0.0) || !(wd >= 0.0)) return FACL_E_SHAPE;
+        if (nt < 1 || nt > FACL_ADAM_MAX_TENSORS) return FACL_E_SHAPE;
+        int chunks = 0;
+        for (int i = 0; i < nt; ++i) {
+            if (n[i] < 1) return FACL_E_SHAPE;
+            px.chunk0[i] = chunks;
+            px.mask[i] = mask[i] ? 1 : 0;
+            chunks += (n[i] + FACL_ADAM_CHUNK - 1) / FACL_ADAM_CHUNK;
+        }
+        px.chunk0[nt] = chunks;
+        if (chunks != npartial) return FACL_E_SHAPE;          // the partials are those of these tensors
+        px.nt = nt;
+    }
+    hipLaunchKernelGGL(k_sgd_prep, dim3(1), dim3(256), 0, (hipStream_t)stream, lr, step, partial_g, partial_p, npartial, px,
+                       max_norm, clip_on ? 1 : 0, schedule == FACL_LR_COSINE ? 1 : 0, warmup_steps, decay_steps, lr_min, eta, wd,
+                       consts, trust);
+    return facl_launch_status();
+}
+
+// p / g / buf: HOST arrays of nt device pointers (parameter, gradient, momentum buffer); n, mask: HOST arrays of element counts
+// and flags; consts: facl_sgd_prep's; trust: its ratios, or NULL = 1 for every tensor
+extern "C" int facl_sgd_apply(int nt, float* const* p, const float* const* g, float* const* buf, const int* n, const int* mask,
+                              const float* consts, const float* trust, float mu, float wd, int nesterov, void* stream) {
+    if (!mask || !consts) return FACL_E_NULL;
+    if (!(mu >= 0.f && mu < 1.f) || !(wd >= 0.f)) return FACL_E_SHAPE;                         // NaN included
+    SgdTable ts;
+    const int chunks = chunk_table(ts.t, nt, {p, g, buf}, n);
+    if (chunks < 0) return chunks;
+    for (int i = 0; i < nt; ++i) ts.mask[i] = mask[i] ? 1 : 0;
+    hipLaunchKernelGGL(k_sgd_apply, dim3(chunks), dim3(256), 0, (hipStream_t)stream, ts, consts, trust, mu, wd, nesterov ? 1 : 0);
     return facl_launch_status();
 }

@@ -18,6 +18,7 @@ from .cls_head import ClipClassifier
 from .extract_common import ordered_views
 from .train_common import TrainBatches, eval_mode, setup_run, synthetic_batch, train_epochs
 from .train_flags import check_finetune_flags, check_finetune_train_flags, finetune_parser, optim_recipe, view_recipe  # noqa: F401
+from .train_flags import describe_optimizer, finetune_train_parser, make_optimizer
 from .train_step import GroupedStep
 
 HEAD_PREFIX = "head."
@@ -127,7 +128,7 @@ def evaluate(netR, step, opt, device):
 
 def main(args=None):
     """Returns the last test top-1 (%), or None when no evaluation ran."""
-    opt = finetune_parser().parse_args(args)
+    opt = finetune_train_parser().parse_args(args)
     print(opt)
     check_finetune_train_flags(opt)
     if opt.synthetic != 1:
@@ -151,9 +152,9 @@ def main(args=None):
     source = TrainBatches(opt, device, 0, 1, subset=labelled, too_few="the labelled subset has %(clips)d clips: fewer than "
                           "one batch of %(batch)d") if opt.synthetic == 0 else None
     steps_per_epoch = opt.steps_per_epoch if source is None else source.steps
-    from .optim import FusedAdam
-    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06,
-                          **optim_recipe(opt, steps_per_epoch))
+    optimizer = make_optimizer(opt, netR.parameters(), steps_per_epoch)
+    if describe_optimizer(opt):
+        print(describe_optimizer(opt))
     step = FineTuneStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder), freeze_bn=bool(opt.freeze_bn))
     if opt.freeze_bn:
         opt.graph = 0                                    # no capture of a step whose model is in eval()

@@ -165,3 +165,131 @@ class FusedAdam:
             self.state[p]["exp_avg_sq"].copy_(s["exp_avg_sq"])
             self._step.fill_(float(s["step"]))
         self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]
+
+
+class FusedSGD:
+    """SGD with momentum, and LARS, as ONE update launch over all parameter tensors (csrc/adam.hip).
+
+    ``torch.optim.SGD(params, lr, momentum, dampening=0, nesterov=...)`` with L2 ``weight_decay`` on the tensors of ``decay_mask``
+    only; ``lars=True`` multiplies every masked tensor's decayed gradient by its trust ratio ``lars_eta |p| / (|g| + wd |p|)`` in
+    front of the momentum (You et al.'s layer-wise rate as SimCLR applies it: one mask keeps biases and BatchNorm out of both the
+    decay and the adaptation).  The surface is FusedAdam's: the step counter and the rate live on the device, ``max_grad_norm``
+    and the schedule are evaluated there by the same expressions, ``sync_lr()`` carries a host change to a replayed graph.
+    Launches per step: facl_sgd_prep + facl_sgd_apply, with facl_grad_sqnorm in front when clipping and facl_tensor_sqnorms in
+    front under LARS (its gradient partials serve the clip too).  Parameters without a gradient are skipped."""
+    MAX_TENSORS = _lib.ADAM_MAX_TENSORS
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, nesterov=False, weight_decay=0.0, decay_mask=None, lars=False,
+                 lars_eta=1e-3, max_grad_norm=0.0, schedule="step", warmup_steps=0, decay_steps=0, lr_min=0.0):
+        """`decay_mask`: one bool per tensor of `params` (True: `weight_decay` and, under `lars`, the trust ratio apply), or None
+        = the tensors with ndim >= 2.  `max_grad_norm` 0 = no clipping."""
+        params = list(params)
+        if decay_mask is None:
+            decay_mask = [p.ndim >= 2 for p in params]
+        decay_mask = [bool(d) for d in decay_mask]
+        if len(decay_mask) != len(params):
+            raise ValueError("decay_mask has %d entries for %d tensors" % (len(decay_mask), len(params)))
+        self.params = [p for p in params if p.requires_grad]
+        if not self.params:
+            raise ValueError("optimizer got an empty parameter list")
+        if len(self.params) > self.MAX_TENSORS:
+            raise ValueError("FusedSGD handles at most %d tensors per step" % self.MAX_TENSORS)
+        for p in self.params:
+            _lib.require_cuda(p)
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise TypeError("FusedSGD needs contiguous float32 CUDA parameters")
+        momentum, weight_decay, lars_eta = float(momentum), float(weight_decay), float(lars_eta)
+        max_grad_norm, lr_min = float(max_grad_norm), float(lr_min)
+        warmup_steps, decay_steps = int(warmup_steps), int(decay_steps)
+        if not 0.0 <= momentum < 1.0:                                              # NaN fails both comparisons
+            raise ValueError("momentum must be in [0, 1) (got %r)" % momentum)
+        if not weight_decay >= 0.0 or math.isinf(weight_decay):
+            raise ValueError("weight_decay must be finite and >= 0 (got %r)" % weight_decay)
+        if not lars_eta >= 0.0 or math.isinf(lars_eta) or (lars and not lars_eta > 0.0):
+            raise ValueError("lars_eta must be finite and %s (got %r)" % ("> 0 under lars" if lars else ">= 0", lars_eta))
+        if not max_grad_norm >= 0.0:
+            raise ValueError("max_grad_norm must be >= 0, 0 = off (got %r)" % max_grad_norm)
+        if schedule not in SCHEDULES:
+            raise ValueError("schedule must be one of %s (got %r)" % (sorted(SCHEDULES), schedule))
+        if warmup_steps < 0:
+            raise ValueError("warmup_steps must be >= 0 (got %d)" % warmup_steps)
+        if not lr_min >= 0.0 or math.isinf(lr_min):
+            raise ValueError("lr_min must be finite and >= 0 (got %r)" % lr_min)
+        if schedule == "cosine" and decay_steps <= warmup_steps:
+            raise ValueError("cosine needs decay_steps > warmup_steps (got %d, %d)" % (decay_steps, warmup_steps))
+        dev = self.params[0].device
+        self.momentum, self.nesterov, self.weight_decay = momentum, bool(nesterov), weight_decay
+        self.lars, self.lars_eta, self.max_grad_norm = bool(lars), lars_eta, max_grad_norm
+        self.schedule, self.warmup_steps, self.decay_steps, self.lr_min = schedule, warmup_steps, decay_steps, lr_min
+        self._decay = {p: d for p, d in zip(params, decay_mask) if p.requires_grad}
+        self.param_groups = [{"lr": float(lr), "momentum": momentum, "dampening": 0, "weight_decay": weight_decay,
+                              "nesterov": self.nesterov, "params": self.params}]
+        self._lr_host = None
+        self._lr = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._step = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._consts = torch.tensor([0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float32, device=dev)     # (lr_t, 0, lr_t, c, norm)
+        self._trust = torch.ones(len(self.params), dtype=torch.float32, device=dev)
+        chunks = sum((p.numel() + CHUNK - 1) // CHUNK for p in self.params)      # one fp64 partial per 2048-element chunk
+        self._partial_g = torch.zeros(chunks, dtype=torch.float64, device=dev) if (max_grad_norm or lars) else None
+        self._partial_p = torch.zeros(chunks, dtype=torch.float64, device=dev) if lars else None
+        self.state = {p: {"momentum_buffer": torch.zeros_like(p)} for p in self.params}
+
+    zero_grad = FusedAdam.zero_grad
+    sync_lr = FusedAdam.sync_lr
+    grad_norm = FusedAdam.grad_norm
+    clip_coef = FusedAdam.clip_coef
+
+    def current_lr(self):
+        """The learning rate the last step applied (a 0-dimensional device view)."""
+        return self._consts[2]
+
+    def trust_ratios(self):
+        """A device view of one float per tensor of the last step, in its order (the parameters that had a gradient): LARS's
+        trust ratio, 1 on the unmasked tensors and on those whose weight or gradient norm is 0; all 1 for plain SGD."""
+        return self._trust[:len(self.last_mask)] if self.last_mask else self._trust
+
+    last_mask = ()                                            # the mask flags of the last step's tensors, in its order
+
+    @torch.no_grad()
+    def step(self):
+        self.sync_lr()
+        act = [p for p in self.params if p.grad is not None]
+        if not act:
+            return
+        nt = len(act)
+        self.last_mask = [bool(self._decay[p]) for p in act]
+        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in act]
+        P, G = _lib.ptr_array(act), _lib.ptr_array(grads)
+        B = _lib.ptr_array([self.state[p]["momentum_buffer"] for p in act])
+        N = _lib.int_array([p.numel() for p in act])
+        D = _lib.int_array([self._decay[p] for p in act])
+        clip = bool(self.max_grad_norm)
+        npartial = sum((p.numel() + CHUNK - 1) // CHUNK for p in act) if (clip or self.lars) else 0
+        if self.lars:
+            _lib.call("facl_tensor_sqnorms", nt, P, G, N, self._partial_p, self._partial_g)
+        elif clip:
+            _lib.call("facl_grad_sqnorm", nt, G, N, self._partial_g)
+        trust = self._trust if self.lars else None
+        _lib.call("facl_sgd_prep", self._lr, self._step, self._partial_g, self._partial_p, npartial, nt, N, D,
+                  self.max_grad_norm, int(clip), SCHEDULES[self.schedule], self.warmup_steps, self.decay_steps, self.lr_min,
+                  self.lars_eta, self.weight_decay, self._consts, trust)
+        _lib.call("facl_sgd_apply", nt, P, G, B, N, D, self._consts, trust, self.momentum, self.weight_decay, int(self.nesterov))
+
+    def state_dict(self):
+        """torch.optim.SGD's layout (momentum_buffer by parameter index; lr, momentum, dampening 0, weight_decay, nesterov in the
+        group) plus a `step` per entry, from which the device-side schedule continues."""
+        step = self._step.detach().clone().cpu()[0]
+        return {"state": {i: {"step": step.clone(), "momentum_buffer": self.state[p]["momentum_buffer"]}
+                          for i, p in enumerate(self.params)},
+                "param_groups": [{"lr": self.param_groups[0]["lr"], "momentum": self.momentum, "dampening": 0,
+                                  "weight_decay": self.weight_decay, "nesterov": self.nesterov,
+                                  "params": list(range(len(self.params)))}]}
+
+    def load_state_dict(self, sd):
+        for i, p in enumerate(self.params):
+            s = sd["state"].get(i)
+            if s is None:
+                continue
+            self.state[p]["momentum_buffer"].copy_(s["momentum_buffer"])
+            self._step.fill_(float(s["step"]))
+        self.param_groups[0]["lr"] = sd["param_groups"][0]["lr"]

@@ -15,7 +15,8 @@ from . import dist as fdist
 from .train_flags import (OPTIM_FLAGS, VIEW_RECIPE_DEFAULTS, VIEW_RECIPE_FLAGS, _check_cosine_span, add_view_recipe_flags,  # noqa: F401
                           build_parser, check_class_mask_flags, check_cluster_id_flags, check_key_flags, check_knn_flags,
                           check_loss_flags, check_optim_flags, check_proto_flags, check_queue_flags, check_resident_flags,
-                          check_state_flags, check_train_flags, check_view_flags, optim_recipe, view_recipe, with_defaults)
+                          check_sgd_flags, check_state_flags, check_train_flags, check_view_flags, describe_optimizer,
+                          make_optimizer, optim_recipe, optimizer_flags, train_parser, view_recipe, with_defaults)
 from .train_step import ContrastiveStep, GraphCaptureFailed, GraphedStep, TrainStep, group_views  # noqa: F401
 
 
@@ -305,11 +306,21 @@ def check_finite_loss(lv, epoch, i):
         raise FloatingPointError("non-finite loss %r at epoch %d, iteration %d" % (lv, epoch, i))
 
 
+def trust_ratio_tail(optimizer):
+    """' | trust ratio min/median/max: a/b/c' over the tensors that LARS adapted in the last step (read after a synchronisation)."""
+    r = optimizer.trust_ratios().cpu()
+    r = r[torch.tensor(optimizer.last_mask, dtype=torch.bool)]
+    if not r.numel():
+        return ' | trust ratio min/median/max: -/-/-'
+    return ' | trust ratio min/median/max: %.4g/%.4g/%.4g' % (float(r.min()), float(r.median()), float(r.max()))
+
+
 def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, after_step=None, start_epoch=0, end_of_epoch=None):
     """The epoch loop of the training entries under StepLR(`lr_step`, 0.7).  `source`: the TrainBatches of --synthetic 0, else
     None (--steps_per_epoch steps).  The entries differ in `next_batch(disk, epoch, i)` -> the step's input (`disk`: the epoch's
     iterator of `source`, or None), `after_step(what the step returned)` and `after_epoch(epoch, mean_loss, clips_per_s)` --
-    with --clip_grad_norm on it gets a fourth argument, the ' | grad norm ...' tail of the epoch line.  Under --lr_schedule cosine
+    with --clip_grad_norm on or under --optim lars it gets a fourth argument, the ' | grad norm ...' / ' | trust ratio ...' tail of
+    the epoch line.  Under --lr_schedule cosine
     the optimizer keeps the base rate and its device-side schedule does the rest.
     `start_epoch`: the first epoch run (a resumed run's).  `end_of_epoch(epoch)`: called last in every epoch, when the epoch's
     producer thread has stopped, so that the view generator's state is the one the next epoch starts from."""
@@ -317,6 +328,7 @@ def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, aft
     run_step = step
     recipe = with_defaults(opt)                          # a namespace from before the recipe flags: the reference's StepLR
     cosine, max_norm = recipe.lr_schedule == "cosine", float(recipe.clip_grad_norm)
+    lars = optimizer_flags(opt).optim == "lars"
     for epoch in range(start_epoch, opt.nepoch):
         for net in step.encoders():                      # MoCo's convention: the key copy normalises with batch statistics too
             net.train()
@@ -345,6 +357,8 @@ def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, aft
         extra = ()
         if max_norm:
             extra = (' | grad norm mean/max: %.4g/%.4g, clipped %d/%d steps' % (sum(norms) / steps, max(norms), clipped, steps),)
+        if lars:                                         # the last step's ratios of the adapted tensors: one read per epoch
+            extra = (''.join(extra) + trust_ratio_tail(step.optimizer),)
         after_epoch(epoch, loss_sigma / steps, opt.batchSize * steps * world / (time.time() - t0), *extra)
         if end_of_epoch is not None:
             end_of_epoch(epoch)
@@ -352,7 +366,7 @@ def train_epochs(opt, step, source, world, lr_step, next_batch, after_epoch, aft
 
 def run(default_branch, ckpt_pattern, args=None):
     # ---- flags (everything here raises before the device is touched)
-    opt = build_parser(default_branch).parse_args(args)
+    opt = train_parser(default_branch).parse_args(args)
     print(opt)
     check_train_flags(opt)
     recipe = view_recipe(opt)
@@ -377,8 +391,10 @@ def run(default_branch, ckpt_pattern, args=None):
     steps = opt.steps_per_epoch if source is None else source.steps
     # cn3d_train_motion_GL.py:180: the same update as torch.optim.Adam, all tensors in one HIP launch (facl_amd/optim.py); the
     # recipe flags (all off by default) add decay, clipping and the device-side schedule, which counts in steps of an epoch
-    from .optim import FusedAdam
-    optimizer = FusedAdam(netR.parameters(), lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06, **optim_recipe(opt, steps))
+    # --optim sgd / lars: FusedSGD on the same kernels' table, with the same clipping and schedule
+    optimizer = make_optimizer(opt, netR.parameters(), steps)
+    if rank == 0 and describe_optimizer(opt):
+        print(describe_optimizer(opt))
     step = ContrastiveStep(netR, optimizer, opt, num_crop, opt.group_radius, bool(opt.fps_reorder), opt.swa_if, opt.cld_if)
     gen = torch.Generator(device=device)
     gen.manual_seed(1000 + rank)

@@ -182,6 +182,38 @@ def add_view_recipe_flags(p):
                    help='NEW (--view_rng philox): tilt_neg / tilt_pos turn about y by -/+ pi * this (literal 0.25 at :723)')
 
 
+def add_optimizer_flags(p):
+    """--optim and the four flags of SGD / LARS (facl_amd.optim.FusedSGD), the training entries' own: build_parser is
+    also the parser of the extraction and prediction entries, which have no optimizer.  The reference's --momentum and
+    --weight_decay stay parsed and unread; where `p` has them their help says so."""
+    p.add_argument('--optim', type=str, default='adam', choices=('adam', 'sgd', 'lars'),
+                   help='NEW (one rank for sgd / lars): adam = the reference\'s Adam; sgd = SGD with momentum; lars = SGD with '
+                        'momentum on layer-wise adapted gradients (facl_amd.optim.FusedSGD); --clip_grad_norm and the schedule '
+                        'flags apply to all three')
+    p.add_argument('--sgd_momentum', type=float, default=0.9, help='NEW (--optim sgd / lars): the momentum, 0 <= m < 1')
+    p.add_argument('--sgd_nesterov', type=int, default=0, choices=(0, 1), help='NEW (--optim sgd / lars): 1 = Nesterov momentum')
+    p.add_argument('--sgd_weight_decay', type=float, default=0.0,
+                   help='NEW (--optim sgd / lars): L2 weight decay on every weight matrix and convolution kernel; biases and '
+                        'BatchNorm gamma / beta are not decayed')
+    p.add_argument('--lars_eta', type=float, default=0.001,
+                   help='NEW (--optim lars): the trust coefficient of eta |w| / (|g| + wd |w|), on the tensors that are decayed')
+    unread = {"momentum": "--sgd_momentum", "weight_decay": "--sgd_weight_decay"}
+    for a in p._actions:
+        if a.dest in unread:
+            a.help += "; parsed and never read, as in the reference: %s is the live one" % unread[a.dest]
+    return p
+
+
+def train_parser(default_branch):
+    """The parser of the two pre-training entries: build_parser's flags and the optimizer's."""
+    return add_optimizer_flags(build_parser(default_branch))
+
+
+def finetune_train_parser():
+    """The parser of the fine-tuning entry: finetune_parser's flags and the optimizer's."""
+    return add_optimizer_flags(finetune_parser())
+
+
 def finetune_parser():
     p = build_parser('0')
     p.description = "Supervised fine-tuning"
@@ -201,6 +233,8 @@ FLAG_DEFAULTS = vars(finetune_parser().parse_args([]))         # build_parser's 
 VIEW_RECIPE_FLAGS = ("view_kinds", "jitter_sigma", "jitter_clip", "rot_range", "scale_lo", "scale_hi", "tilt_angle")
 VIEW_RECIPE_DEFAULTS = tuple(FLAG_DEFAULTS[k] for k in VIEW_RECIPE_FLAGS)   # = ("reference",) + facl_amd.philox.DEFAULT_STRENGTHS
 OPTIM_FLAGS = ("adamw_decay", "clip_grad_norm", "lr_schedule", "warmup_steps", "lr_decay_epochs", "lr_min")
+SGD_FLAGS = ("sgd_momentum", "sgd_nesterov", "sgd_weight_decay", "lars_eta")        # read under --optim sgd / lars only
+OPTIMIZER_FLAG_DEFAULTS = vars(add_optimizer_flags(argparse.ArgumentParser()).parse_args([]))   # --optim and the four
 
 
 def with_defaults(opt):
@@ -211,6 +245,12 @@ def with_defaults(opt):
 def env_world_size():
     """The launcher's WORLD_SIZE (torch.distributed.run); 1 without a launcher."""
     return int(os.environ.get("WORLD_SIZE", "1"))
+
+
+def optimizer_flags(opt):
+    """A new namespace of --optim and the four SGD flags: `opt`'s value where it has the name (a namespace of build_parser or a
+    bare one has none), else the parser's default, Adam."""
+    return argparse.Namespace(**{k: getattr(opt, k, d) for k, d in OPTIMIZER_FLAG_DEFAULTS.items()})
 
 
 def one_rank_only(flag, clause, world=None):
@@ -444,6 +484,34 @@ def check_optim_flags(opt, world=None):
             one_rank_only("--%s %s" % (name, getattr(opt, name)), ": the optimizer recipe has never run data-parallel", world)
 
 
+def check_sgd_flags(opt, world=None):
+    """--optim sgd / lars: one rank; --sgd_momentum in [0, 1), --sgd_weight_decay and --lars_eta finite and >= 0, eta > 0 under lars;
+    --adamw_decay is Adam's decay and is refused.  --optim adam: the four flags stay at their defaults.  Raises before the device
+    is touched (`world` None: the launcher's WORLD_SIZE); namespaces without the flags hold the defaults."""
+    o = optimizer_flags(opt)
+    adamw_decay = with_defaults(opt).adamw_decay
+    if o.optim == "adam":
+        for name in SGD_FLAGS:
+            if getattr(o, name) != OPTIMIZER_FLAG_DEFAULTS[name]:
+                raise RuntimeError("--%s %s belongs to --optim sgd / lars (got --optim adam, which does not read it)"
+                                   % (name, getattr(o, name)))
+        return
+    if o.optim not in ("sgd", "lars"):
+        raise RuntimeError("--optim must be adam, sgd or lars (got %r)" % (o.optim,))
+    one_rank_only("--optim %s" % o.optim, ": the optimizer has never run data-parallel", world)
+    if adamw_decay:
+        raise RuntimeError("--adamw_decay %r is the decoupled decay of --optim adam: --optim %s takes --sgd_weight_decay"
+                           % (adamw_decay, o.optim))
+    if not 0.0 <= o.sgd_momentum < 1.0:                      # NaN fails both comparisons
+        raise RuntimeError("--sgd_momentum must be in [0, 1) (got %r)" % o.sgd_momentum)
+    for name in ("sgd_weight_decay", "lars_eta"):
+        v = getattr(o, name)
+        if not 0.0 <= v < float("inf"):
+            raise RuntimeError("--%s must be finite and >= 0 (got %r)" % (name, v))
+    if o.optim == "lars" and not o.lars_eta > 0.0:
+        raise RuntimeError("--optim lars needs --lars_eta > 0 (got %r): at 0 no masked tensor would move" % o.lars_eta)
+
+
 def optim_recipe(opt, steps):
     """FusedAdam's keyword arguments for the recipe flags; `steps`: optimizer steps per epoch (T = --lr_decay_epochs x steps)."""
     kw = dict(weight_decay=opt.adamw_decay, max_grad_norm=opt.clip_grad_norm, schedule=opt.lr_schedule,
@@ -453,13 +521,36 @@ def optim_recipe(opt, steps):
     return kw
 
 
+def describe_optimizer(opt):
+    """The entries' line about an optimizer other than Adam; None under --optim adam."""
+    o = optimizer_flags(opt)
+    if o.optim == "adam":
+        return None
+    return "optimizer: %s momentum %g nesterov %d weight decay %g%s" % (
+        o.optim, o.sgd_momentum, o.sgd_nesterov, o.sgd_weight_decay, " eta %g" % o.lars_eta if o.optim == "lars" else "")
+
+
+def make_optimizer(opt, params, steps):
+    """The optimizer of the training entries for --optim: FusedAdam as cn3d_train_motion_GL.py:180 sets it (lr, betas (0.5, 0.999),
+    eps 1e-6) with the recipe flags, or FusedSGD (plain / LARS) with the same clipping and schedule.  `steps`: optimizer steps per
+    epoch.  A namespace without --optim gets Adam."""
+    from .optim import FusedAdam, FusedSGD
+    o = optimizer_flags(opt)
+    kw = optim_recipe(opt, steps)
+    if o.optim == "adam":
+        return FusedAdam(params, lr=opt.learning_rate, betas=(0.5, 0.999), eps=1e-06, **kw)
+    kw.pop("weight_decay")                                   # --adamw_decay: refused with these (check_sgd_flags)
+    return FusedSGD(params, lr=opt.learning_rate, momentum=o.sgd_momentum, nesterov=bool(o.sgd_nesterov),
+                    weight_decay=o.sgd_weight_decay, lars=o.optim == "lars", lars_eta=o.lars_eta, **kw)
+
+
 def check_train_flags(opt, world=None):
     """Every check of the pre-training entries; a run with two mistakes reports the first in this order: the data (resident clips,
     views), the monitor, the loss (modes, class mask and ids, prototypes), its queue and key encoder, state files, the optimizer."""
     check_resident_flags(opt)
     check_view_flags(opt)
     for check in (check_knn_flags, check_loss_flags, check_class_mask_flags, check_proto_flags, check_queue_flags,
-                  check_key_flags, check_state_flags, check_optim_flags):
+                  check_key_flags, check_state_flags, check_optim_flags, check_sgd_flags):
         check(opt, world)
 
 
@@ -509,3 +600,4 @@ def check_finetune_train_flags(opt, world=None):
     check_resident_flags(opt)
     check_view_flags(opt)
     check_optim_flags(opt, world=1)
+    check_sgd_flags(opt, world=1)

@@ -21,16 +21,21 @@ TRAJECTORY_FLAGS = ("batchSize", "num_crop", "SAMPLE_NUM", "INPUT_FEATURE_NUM", 
                     "Num_Class", "swa_if", "cld_if", "loss_normalize", "loss_temperature", "loss_mask", "neg_queue", "key_encoder",
                     "key_momentum", "adamw_decay", "clip_grad_norm", "lr_schedule", "warmup_steps", "lr_decay_epochs", "lr_min",
                     "view_kinds", "jitter_sigma", "jitter_clip", "rot_range", "scale_lo", "scale_hi", "tilt_angle",
-                    "label_fraction", "label_seed", "class_positives")
+                    "label_fraction", "label_seed", "class_positives",
+                    "optim", "sgd_momentum", "sgd_nesterov", "sgd_weight_decay", "lars_eta")
 
 # the optimizer-recipe flags and the view-recipe flags came after the first states were written: a state without them ran with
 # the recipe off / with the reference's ten views at its strengths, which is what these defaults (the parser's) say; so did the
 # labelled fraction of the class-aware loss mask (every label, seed 0: the mask itself did not exist) and the weight of
-# class-mates as extra positives (0: off).  Every other flag must be in the file.
+# class-mates as extra positives (0: off).  Every other flag must be in the file, but for OPTIMIZER_FLAG_DEFAULTS below.
 LATER_FLAG_DEFAULTS = {"adamw_decay": 0.0, "clip_grad_norm": 0.0, "lr_schedule": "step", "warmup_steps": 0, "lr_decay_epochs": 0,
                        "lr_min": 0.0, "view_kinds": "reference", "jitter_sigma": 0.01, "jitter_clip": 0.05, "rot_range": 0.8,
                        "scale_lo": 0.5, "scale_hi": 1.5, "tilt_angle": 0.25, "label_fraction": 1.0, "label_seed": 0,
                        "class_positives": 0.0}
+
+# --optim and the four flags of SGD / LARS (the training entries' own parser, train_flags.add_optimizer_flags): a state without
+# them was an Adam run, and a namespace without them (build_parser's: the extraction entries share it) is one too
+OPTIMIZER_FLAG_DEFAULTS = {"optim": "adam", "sgd_momentum": 0.9, "sgd_nesterov": 0, "sgd_weight_decay": 0.0, "lars_eta": 0.001}
 
 _STATE_NAME = re.compile(r"^state_(\d+)\.pth$")
 
@@ -55,8 +60,13 @@ def to_cpu(obj):
     return obj
 
 
+def flag_of(opt, k):
+    """The value of trajectory flag `k` in the namespace `opt`; the optimizer's flags read as Adam's where `opt` has none."""
+    return getattr(opt, k, OPTIMIZER_FLAG_DEFAULTS[k]) if k in OPTIMIZER_FLAG_DEFAULTS else getattr(opt, k)
+
+
 def flags_of(opt):
-    return {k: getattr(opt, k) for k in TRAJECTORY_FLAGS}
+    return {k: flag_of(opt, k) for k in TRAJECTORY_FLAGS}
 
 
 # ---- generators ----------------------------------------------------------------------------------------------------------
@@ -145,10 +155,11 @@ def load_state(path):
     if state["format"] != FORMAT:
         raise RuntimeError("%s has state format %r; this code reads format %d" % (path, state["format"], FORMAT))
     missing = [k for k in KEYS if k not in state] + ["rng." + k for k in RNG_KEYS if k not in state.get("rng", {})] \
-        + ["flags." + k for k in TRAJECTORY_FLAGS if k not in state.get("flags", {}) and k not in LATER_FLAG_DEFAULTS]
+        + ["flags." + k for k in TRAJECTORY_FLAGS if k not in state.get("flags", {}) and k not in LATER_FLAG_DEFAULTS
+           and k not in OPTIMIZER_FLAG_DEFAULTS]
     if missing:
         raise RuntimeError("%s lacks %s" % (path, ", ".join(missing)))
-    for k, v in LATER_FLAG_DEFAULTS.items():
+    for k, v in list(LATER_FLAG_DEFAULTS.items()) + list(OPTIMIZER_FLAG_DEFAULTS.items()):
         state["flags"].setdefault(k, v)
     return state
 
@@ -181,8 +192,8 @@ def prune(folder, keep):
 def check_compatible(saved_flags, opt):
     """Every option that determines the trajectory must equal the saved run's; anything else (nepoch, save_root_dir, log_file,
     graph, prefetch, resident, knn_*, main_gpu, workers, the state flags themselves) may differ."""
-    differ = ["--%s %r (the state: %r)" % (k, getattr(opt, k), saved_flags[k]) for k in TRAJECTORY_FLAGS
-              if saved_flags[k] != getattr(opt, k)]
+    differ = ["--%s %r (the state: %r)" % (k, flag_of(opt, k), saved_flags[k]) for k in TRAJECTORY_FLAGS
+              if saved_flags[k] != flag_of(opt, k)]
     if differ:
         raise RuntimeError("the state was written by a run with other options, which would not continue its trajectory: "
                            + "; ".join(differ))

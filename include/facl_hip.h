@@ -584,7 +584,8 @@ int facl_mailbox_allreduce(const double* in, double* out, int n, int n_max, void
  * counter live on the device so that a captured HIP graph advances them by itself.
  * facl_adam_apply: ALL parameter tensors in one launch.  p / g / m / v are HOST arrays of nt <= 64 device pointers
  * (parameter, gradient, exp_avg, exp_avg_sq), n their element counts.
- * The chunk table, shared by facl_adam_apply, facl_ema_apply, facl_grad_sqnorm and facl_adamw_apply: the entry copies its nt <=
+ * The chunk table, shared by facl_adam_apply, facl_ema_apply, facl_grad_sqnorm, facl_adamw_apply and the SGD entries below
+ * (facl_tensor_sqnorms, facl_sgd_apply): the entry copies its nt <=
  * FACL_ADAM_MAX_TENSORS pointers and counts into the kernel arguments, where they travel by value (a captured graph bakes
  * them), and cuts every tensor into chunks of FACL_ADAM_CHUNK elements, one 256-thread workgroup each, the chunks of tensor 0
  * first: sum_i ceil(n[i] / FACL_ADAM_CHUNK) workgroups.  A chunk is walked 16 bytes per lane where n[i] % 4 == 0 and every
@@ -632,6 +633,42 @@ int facl_adam_prep_ex(const float* lr, float* step, float b1, float b2, const do
                       int schedule, int warmup_steps, int decay_steps, double lr_min, float* consts, void* stream);
 int facl_adamw_apply(int nt, float* const* p, const float* const* g, float* const* m, float* const* v, const int* n,
                      const int* decay, const float* consts, float b1, float b2, float eps, float wd, void* stream);
+
+/* ---- SGD with momentum and LARS on the optimizer's chunk table (facl_amd/optim.py: FusedSGD) -------------------
+ * The step is [facl_grad_sqnorm when clipping | facl_tensor_sqnorms under LARS] -> facl_sgd_prep -> facl_sgd_apply; plain SGD
+ * is the last two.  The table, its walk and its refusals are facl_adam_apply's.
+ * facl_tensor_sqnorms: partial_p[chunk] = sum of p^2 and partial_g[chunk] = sum of g^2 over the chunk, in ONE pass over both
+ *   columns, in the chunk table's order; DEVICE arrays of sum_i ceil(n[i] / FACL_ADAM_CHUNK) doubles each, every entry written.
+ *   The arithmetic is facl_grad_sqnorm's (widened to fp64 before the square, one fixed order, no atomic): partial_g holds the
+ *   bits facl_grad_sqnorm writes for the same gradients.  p and g are only read.
+ * facl_sgd_prep: one workgroup.  step[0] += 1; lr_t, c and norm by facl_adam_prep_ex's own operations (clip_on != 0: norm =
+ *   sqrt(partial_g[0] + ... + partial_g[npartial - 1]), c = min(1, max_norm / (norm + 1e-6)); clip_on == 0: c = 1 exactly,
+ *   norm = 0, max_norm is not read); consts (5 floats) = (lr_t, 0, lr_t, c, norm): slots 2, 3, 4 as facl_adam_prep_ex's.
+ *   partial_p != NULL (LARS): n and mask are HOST arrays of nt <= 64 element counts and flags, copied into the kernel
+ *   arguments as a prefix table of chunks (a captured graph bakes it); npartial must be their chunk count.  For tensor i, over
+ *   its own chunks in one fixed order and in fp64, wn = sqrt(sum partial_p), gn = c * sqrt(sum partial_g), with c the fp32 value
+ *   of consts[3] that facl_sgd_apply multiplies by, and
+ *     trust[i] = (mask[i] && wn > 0 && gn > 0) ? eta * wn / (gn + wd * wn) : 1      rounded once to fp32
+ *   (a NaN norm fails the comparisons and gives 1: the NaN reaches the parameters through the gradient itself).
+ *   partial_p == NULL (plain SGD): nt, n, mask, eta, wd and trust are not read and trust is not written.
+ * facl_sgd_apply: p / g / buf are HOST arrays of nt <= 64 device pointers (parameter, gradient, momentum buffer), n their
+ *   element counts, mask HOST flags, trust facl_sgd_prep's ratios or NULL (q = 1).  Per element in fp32, one rounding per
+ *   operation, in this order:
+ *     gc = g * c;  d = mask[t] ? gc + wd * p : gc;  d = d * q;  buf = mu * buf + d;  p = p - lr_t * (nesterov ? d + mu * buf : buf)
+ *   torch.optim.SGD(momentum = mu, dampening = 0, nesterov) with L2 decay on the flagged tensors; with c == 1 and q == 1 the two
+ *   products are exact, and mu = 0, wd = 0 gives p - lr_t * g to the bit.  g is only read.
+ * Refusals, all before the launch: a NULL array or entry: FACL_E_NULL (trust of facl_sgd_apply may be NULL; partial_p may be
+ * NULL, and then n, mask and trust of facl_sgd_prep too; partial_g only when clip_on == 0 and partial_p == NULL); nt outside
+ * 1..64, an n[i] < 1, mu outside [0, 1), wd, eta or lr_min negative, max_norm not positive when clipping (NaN included in
+ * each), npartial < 0 or, under LARS, not the chunk count of n, warmup_steps < 0, a schedule other than the two, decay_steps <=
+ * warmup_steps under FACL_LR_COSINE: FACL_E_SHAPE. */
+int facl_tensor_sqnorms(int nt, const float* const* p, const float* const* g, const int* n, double* partial_p,
+                        double* partial_g, void* stream);
+int facl_sgd_prep(const float* lr, float* step, const double* partial_g, const double* partial_p, int npartial, int nt,
+                  const int* n, const int* mask, double max_norm, int clip_on, int schedule, int warmup_steps, int decay_steps,
+                  double lr_min, double eta, double wd, float* consts, float* trust, void* stream);
+int facl_sgd_apply(int nt, float* const* p, const float* const* g, float* const* buf, const int* n, const int* mask,
+                   const float* consts, const float* trust, float mu, float wd, int nesterov, void* stream);
 
 /* ---- optional loss terms of the training loop (switched off in the shipped loop) ----------------------
  * facl_sinkhorn: distributed_sinkhorn + shoot_infs (cn3d_model_conbag.py:391-425).  Q (R,C) = exp(scores)^T, R prototypes
